@@ -2,6 +2,7 @@
 """bench.py -- reconstructed 128x128 slices/sec @ T=1000 of the cDDPM reverse-diffusion path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--size S] [--no-cpu] [--no-alt] [--no-profile]
+                    [--dump-outputs DIR]
         (N > 1 without RANK in the environment: starts the N ranks itself -- the torchrun line below as a child process --
          and relays rank 0's JSON line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -21,6 +22,12 @@ plus the head of the next chain.
     value [slices/s] = n_gpus * B * (K * 50 / 1000) / seconds        (max over ranks, barrier + synchronize both sides)
 Untimed before it: W segments of warm-up. Untimed after it: a short pass with per-kernel HIP events (roofline), the
 small-batch line, the alternative arithmetic paths and the CPU baseline (rank 0, one GPU only).
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the timed path handed its caller, as DIR/<name>.npy (float32):
+`x`, the chain state after the last timed segment (world*B x 1 x S x S: the gathered tensor under torchrun; after K = 20 the
+reconstructions x_0), or `residual_maps` for --workload residual. Over 64 MB in all, every array keeps a fixed, seeded sample
+of its slices (sorted indices drawn by numpy's default_rng(0)). Weights, x_T, the context and z_t are seeded, so the same
+arguments give the same inputs on every run and two builds can be compared output for output.
 
 Extra objects on the JSON line:
   roofline      dominant kernel = the fused 3x3 convolution (conv_x6.hip: conv_split_kernel<9,8,2,true> and the
@@ -155,6 +162,28 @@ def run_chain(eng, synth, x, n_rev, slice0):
         eng.reverse_range_(x, T_TOTAL - 1, T_TOTAL - n, seed=3, slice0=slice0)
         done += n
     return x
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every device tensor in `arrays` as out_dir/<name>.npy in float32. Over `limit` bytes in all, each array
+    keeps the same fraction of its leading (slice) axis, a sorted sample drawn by default_rng(0). Returns what was written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy()
+        rows = None
+        if total > limit:
+            keep = max(1, a.shape[0] * limit // total)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = {"shape": list(a.shape), "dtype": "float32", "sampled_rows": None if rows is None else int(len(rows))}
+    return written
 
 
 def training_rate(torch, dev, synth, B=16, S=128, steps=3, precision=32):
@@ -305,6 +334,8 @@ def residual_workload(args, torch, dev, rank, world, dist, result_fd):
                       "conv_family": CONV_MODE, "arithmetic": ARITH, "result_shape": list(res.shape), "finite_and_in_unit_range": ok,
                       "residual_mean": float(res.mean().item()),
                       "checksum_first_last": [float(res[0].double().sum().item()), float(res[-1].double().sum().item())]}}
+    if args.dump_outputs and rank == 0:
+        out["config"]["outputs_dumped"] = dump_outputs(args.dump_outputs, {"residual_maps": res})
     eng.close()
     if rank == 0:
         os.write(result_fd, (json.dumps(out) + "\n").encode())
@@ -329,8 +360,12 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-alt", action="store_true", help="skip the alternative-arithmetic children and the small-batch line")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP event pass (no roofline object)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the timed path returned as DIR/<name>.npy (float32, <= 64 MB in all)")
     ap.add_argument("--alt-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     plan = launch_plan(args.gpus, sys.argv[1:], os.environ)
     if plan is not None:
@@ -409,6 +444,9 @@ def main():
     finite = bool(torch.isfinite(x).all().item())
     complete = (n_rev % T_TOTAL == 0)
     in_range = bool(((x >= 0) & (x <= 1)).all().item()) if complete else None
+    dumped = None
+    if args.dump_outputs and rank == 0:                 # what the timed path returned: the gathered tensor under torchrun
+        dumped = dump_outputs(args.dump_outputs, {"x": gathered if dist is not None else x})
 
     value = world * B * (n_rev / T_TOTAL) / elapsed
     s_per_rev = elapsed / n_rev
@@ -435,6 +473,8 @@ def main():
                    "executed_tflops_fp32_equivalent": flop_step * EXECUTED_FRACTION / s_per_rev / 1e12,
                    "hbm_frac_fused_model": (BYTES_PER_SLICE_STEP_128 * (S / 128.0) ** 2 * B + 0.1755e9) / s_per_rev / (PEAK_HBM_TBPS * 1e12)},
     }
+    if dumped is not None:
+        out["config"]["outputs_dumped"] = dumped
 
     # ---- per-kernel-class HIP events: a second, short pass outside the timed region
     if not args.no_profile:

@@ -6,8 +6,8 @@ config_name="config.yaml")`, reference run.py:20-56) composes the config and ins
 Neither package is in this image, so this module composes the few files that fix the UNet shape with
 PyYAML: configs/config.yaml defaults -> configs/model/DDPM_2D.yaml, configs/datamodule/IXI.yaml, then the
 experiment overlay (`# @package _global_`), then `key=value` overrides; `${datamodule.cfg.x}`
-interpolations are resolved. It reads the reference's YAML files where they lie (path given by the caller):
-no config text is copied into this repository.
+interpolations are resolved. It reads the reference's YAML files where they lie (path given by the caller);
+tests/golden/configs is a reduced fixture of that tree for the tests.
 """
 from __future__ import annotations
 

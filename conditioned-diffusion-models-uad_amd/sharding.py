@@ -44,8 +44,9 @@ def reconstruct_sharded(n_slices: int, shape_hw: Tuple[int, int], reconstruct_ch
         parts.append(out)
     if parts:
         mine = torch.cat(parts, dim=0)
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    else:       # an empty block still joins the collective: on the device the process group's backend works on
+        on_gpu = dist.get_backend(group) == "nccl" if dist.is_initialized() else torch.cuda.is_available()
+        dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
         mine = torch.empty((0, 1, H, W), dtype=torch.float32, device=dev)
     if world == 1 or gather == "none":
         return mine

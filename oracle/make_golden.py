@@ -17,6 +17,8 @@ import os
 import sys
 import time
 
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")     # the MKL code path tests/conftest.py pins: the same bits on any x86 host
+
 import numpy as np
 import torch
 
@@ -72,7 +74,7 @@ def main():
         return
     os.makedirs(GOLD, exist_ok=True)
     torch.manual_seed(0)
-    manifest = {"torch": torch.__version__, "threads": torch.get_num_threads(), "cases": {}}
+    manifest = {"torch": torch.__version__, "threads": torch.get_num_threads(), "mkl_cbwr": os.environ.get("MKL_CBWR"), "cases": {}}
 
     sd_np = synth.synth_state_dict(SEED_W)
     sd = O.to_torch_sd(sd_np)

@@ -15,6 +15,8 @@ import json
 import os
 import sys
 
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")     # the MKL code path tests/conftest.py pins: the same bits on any x86 host
+
 import numpy as np
 import torch
 

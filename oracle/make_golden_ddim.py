@@ -16,6 +16,8 @@ import os
 import sys
 import types
 
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")     # the MKL code path tests/conftest.py pins: the same bits on any x86 host
+
 import numpy as np
 import torch
 

@@ -4,6 +4,11 @@ import importlib
 import os
 import sys
 
+# The golden vectors were written with MKL on its COMPATIBLE code path (MANIFEST.json "mkl_cbwr"). Left to itself MKL picks a
+# branch per CPU vendor and ISA, and its exp / sin / cos differ between them by an ulp, which the timestep embedding turns into
+# 3e-5; pinned, Intel and AMD hosts compute the same bits. Set before torch (and with it MKL) is loaded.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 import numpy as np
 import pytest
 

@@ -56,6 +56,30 @@ def test_train_step_bench_shares_the_plan():
     assert "launch_plan(a.gpus" in src and src.index("launch_plan(a.gpus") < src.index("import torch\n")
 
 
+def test_bench_refuses_zero_timed_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and r.stdout.strip() == ""
+
+
+def test_dump_outputs_writes_float32_and_samples_a_fixed_subset(tmp_path):
+    import numpy as np
+    import torch
+    a = torch.arange(40 * 8, dtype=torch.float64).reshape(40, 2, 2, 2)
+    b = -torch.arange(40 * 4, dtype=torch.float32).reshape(40, 1, 2, 2)
+    full = bench.dump_outputs(str(tmp_path / "full"), {"a": a, "b": b})
+    assert full["a"] == {"shape": [40, 2, 2, 2], "dtype": "float32", "sampled_rows": None}
+    got = np.load(tmp_path / "full" / "a.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a.float().numpy())
+    limit = (40 * 8 + 40 * 4) * 4 // 4                       # a quarter of what the two arrays hold
+    cut = [bench.dump_outputs(str(tmp_path / d), {"a": a, "b": b}, limit=limit) for d in ("s1", "s2")]
+    assert cut[0] == cut[1] and cut[0]["a"]["sampled_rows"] == cut[0]["b"]["sampled_rows"] == 10
+    sa, sb = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s1" / "b.npy")
+    assert sa.nbytes + sb.nbytes <= limit
+    rows = sa[:, 0, 0, 0].astype(np.int64) // 8                  # row i of `a` starts with 8 * i
+    assert np.all(np.diff(rows) > 0) and np.array_equal(sb[:, 0, 0, 0], -4.0 * rows)     # sorted, the same rows in both arrays
+    assert np.array_equal(sa, np.load(tmp_path / "s2" / "a.npy"))                       # the same sample on every run
+
+
 @pytest.mark.gpu
 def test_bench_under_the_launcher_runs_the_rccl_path():
     """the driver's N > 1 command line with N = 1 (one GPU on the box): init_process_group('nccl'), the all_gather inside the

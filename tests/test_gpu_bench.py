@@ -39,6 +39,29 @@ def test_bench_contract():
     assert "alt_paths" not in cfg and "small_batch" not in cfg      # --no-alt
 
 
+def test_bench_dump_outputs_are_the_same_on_every_run(tmp_path):
+    """--dump-outputs DIR: the chain state the timed segments leave (B x 1 x S x S, float32), identical for two runs with the same
+    arguments; --steps sets how many segments that is (1 vs 2 give different states)"""
+    import numpy as np
+    dumps = []
+    for tag, steps in (("a", "2"), ("b", "2"), ("c", "1")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "1", "--batch", "4", "--size", "32",
+                            "--no-cpu", "--no-alt", "--no-profile", "--dump-outputs", str(tmp_path / tag)],
+                           capture_output=True, text=True, timeout=600, env=dict(os.environ))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out["steps"] == int(steps) and out["config"]["reverse_steps_timed"] == 50 * int(steps)
+        assert out["config"]["outputs_dumped"] == {"x": {"shape": [4, 1, 32, 32], "dtype": "float32", "sampled_rows": None}}
+        assert sorted(os.listdir(tmp_path / tag)) == ["x.npy"]
+        dumps.append(np.load(tmp_path / tag / "x.npy"))
+    a, b, c = dumps
+    assert a.dtype == np.float32 and a.shape == (4, 1, 32, 32) and np.isfinite(a).all()
+    assert np.array_equal(a, b)
+    assert not np.array_equal(a, c)
+
+
 def test_bench_complete_reconstruction_small():
     """K = 20 segments = ONE complete reconstruction (a single cddpm_reverse(t_start = 1000)); here at B = 2, 32x32 so
     that the test stays short; also exercises the small-batch line and one alternative-arithmetic child"""

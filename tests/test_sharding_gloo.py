@@ -25,10 +25,12 @@ def _fake_reco(slice0, count, H=8, W=12):
     return (idx * 0.5 + torch.arange(H * W, dtype=torch.float32).reshape(1, 1, H, W) * 1e-3).contiguous()
 
 
-def _worker(rank, world, port, n_slices, chunk, mode, q):
+def _worker(rank, world, port, n_slices, chunk, mode, q, gpu_visible=False):
     import importlib
     import sys
     sys.path.insert(0, ROOT)
+    if gpu_visible:         # as on a GPU box: a visible device must not pull a gloo (host) collective onto it
+        torch.cuda.is_available = lambda: True
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     sh = importlib.import_module(PKG_NAME + ".sharding")
@@ -47,10 +49,20 @@ def _worker(rank, world, port, n_slices, chunk, mode, q):
 
 @pytest.mark.parametrize("n_slices,chunk,mode", [(8, 3, "all"), (7, 2, "all"), (5, 64, "root"), (1, 4, "all")])
 def test_two_rank_shard_and_gather(n_slices, chunk, mode):
+    _two_rank_shard_and_gather(n_slices, chunk, mode)
+
+
+def test_an_empty_block_stays_on_the_host_with_a_gpu_visible():
+    """1 slice over 2 ranks: rank 1's block is empty, and its placeholder for the gloo collective is a host tensor even when a GPU is
+    visible (the process group's backend decides, not the machine)"""
+    _two_rank_shard_and_gather(1, 4, "all", gpu_visible=True)
+
+
+def _two_rank_shard_and_gather(n_slices, chunk, mode, gpu_visible=False):
     world, port = 2, _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n_slices, chunk, mode, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, n_slices, chunk, mode, q, gpu_visible)) for r in range(world)]
     for p in procs:
         p.start()
     res = {}
