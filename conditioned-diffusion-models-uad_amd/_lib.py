@@ -68,8 +68,6 @@ SYMBOLS = {
     "cddpm_op_conv": (_i, [_vp, _fp, _i, _fp, _i, _fp, _i, _i, _fp, _fp, _i, _i, _fp, _i, _fp, _i, _i, _i, _vp]),
     "cddpm_op_conv_skip": (_i, [_vp, _fp, _i, _fp, _i, _fp, _fp, _i, _fp, _i, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_conv_gn": (_i, [_vp, _fp, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _vp]),
-    "cddpm_op_conv_bench": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_double),
-                                 C.POINTER(_u64)]),
     "cddpm_op_gn_coef": (_i, [_vp, _fp, _i, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _vp]),
     "cddpm_op_attention": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_encoder_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),

@@ -33,22 +33,20 @@ def lib_is_current() -> bool:
     return all(os.path.getmtime(d) <= t for d in deps if os.path.exists(d))
 
 
-def build_lib(force: bool = False, verbose: bool = False, defines=(), tag: str = "", conv_src: str = "") -> str:
-    """defines/tag: experimental A/B builds, e.g. defines=["CDDPM_STAMPS"], tag="stamps" -> libcddpm_hip_stamps.so
-    (loaded through the CDDPM_LIB environment variable by tools/conv_ab.py); the product build has neither."""
+def build_lib(force: bool = False, verbose: bool = False, tag: str = "") -> str:
+    """tag: a side-by-side build, e.g. tag="base" -> libcddpm_hip_base.so (loaded through the CDDPM_LIB environment variable by
+    tools/conv_ab.py); the product build has none."""
     lib_out = LIB if not tag else LIB.replace(".so", f"_{tag}.so")
     if not force and not tag and lib_is_current():
         return LIB
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + [f"-D{d}" for d in defines]
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
     objs = []
 
     def compile_one(src):
         obj = os.path.join(OBJ, src.replace(".hip", f"{('_' + tag) if tag else ''}.o"))
-        # A/B of older conv kernels: an alternative file replaces conv_x6.hip if its name starts with conv_x6, else conv_mfma.hip
-        swap = "conv_x6.hip" if os.path.basename(conv_src).startswith("conv_x6") else "conv_mfma.hip"
-        path = conv_src if (conv_src and src == swap) else os.path.join(CSRC, src)
+        path = os.path.join(CSRC, src)
         deps = [path, os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "conv_split.h"),
                 os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "cddpm.h"), os.path.abspath(__file__)]
         stamp = obj + ".flags"          # an object is reused when it is newer than its inputs and was built with the same flags

@@ -197,8 +197,7 @@ double conv_bytes(const ConvArgs& a) {
 // as it is computed on handles of the same maximum geometry (sharded runs: the same engine configuration on every rank).
 constexpr int KSPLIT_PLANE_FLOATS = 256 * 256 * 128;      // S * workgroups <= 256, a workgroup's tile <= 256 x 128 outputs
 int plan_ksplit(const cddpm_ctx* h, const ConvArgs& a, short* kbound) {
-    static const bool off = [] { const char* e = getenv("CDDPM_KSPLIT"); return e && e[0] == '0'; }();
-    if (off || conv_mode() != 2 || h->cur_H <= 0) return 1;
+    if (conv_mode() != 2 || h->cur_H <= 0) return 1;
     const bool up2 = (a.taps == 4);
     const int Hm = (int)((long long)a.H * h->d.max_h / h->cur_H), Wm = (int)((long long)a.W * h->d.max_w / h->cur_W);
     const int gh = up2 ? Hm / 2 : Hm, gw = up2 ? Wm / 2 : Wm;
@@ -259,7 +258,7 @@ int conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s) {
     }
     // large-batch plan: 256-cout workgroups where the handle's maximum geometry still fills the chip with them (a property of the
     // handle like S above, never of the call)
-    a.nb2 = ((h->nb2_now || conv_nb2_env() == 2) && conv_nb2_ok(a.Cout, conv_workgroups_at_max(h, a), 1, 0)) ? 1 : 0;
+    a.nb2 = ((h->nb2_now || conv_nb2_env() == 2) && conv_nb2_ok(a.Cout, conv_workgroups_at_max(h, a), 1)) ? 1 : 0;
     const int nrec = (a.taps == 4) ? conv_stat_records_up2(a.H, a.W) : conv_stat_records(a.H, a.W);
     if (a.stats) {
         // a statically sized buffer against a shape-derived count: refuse to launch rather than write past the end
@@ -1402,7 +1401,7 @@ int cddpm_op_conv_packed(cddpm_handle h, const float* src0, int C0, const float*
     a.hi_only = train_precision() == 16 ? 1 : 0;
     // the training operators plan per call, and DO take the 256-cout workgroups wherever the call fills the chip with them: a gradient's
     // accuracy need (2e-5 of float64 autograd; SGD noise far above that) is not the 1000-step chain's, and +9...12 % per layer is
-    a.nb2 = (conv_nb2_env() >= 1 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, a.hi_only)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() >= 1 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
     Prof prof_(h, a.taps == 1 ? PC_CONV1 : PC_CONV3, conv_flops(a), conv_bytes(a), (hipStream_t)stream);
     launch_conv(a, (hipStream_t)stream);
     HIPCHECK(h, hipGetLastError());
@@ -1457,7 +1456,7 @@ int cddpm_op_conv(cddpm_handle h, const float* src0, int C0, const float* src1, 
     a.coef = coef_dev; a.silu = silu; a.wpk = dw; a.bias = db; a.res = res_dev; a.res_up = res_upsample;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = folded ? 4 : taps;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, a.hi_only)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
     launch_conv(a, s);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(s));
@@ -1493,7 +1492,7 @@ int cddpm_op_conv_skip(cddpm_handle h, const float* src0, int C0, const float* c
     a.skip0 = skip_dev; a.S0 = S0; a.skip_wpk = dws;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = 9;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, a.hi_only)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
     launch_conv(a, s);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(s));
@@ -1528,86 +1527,12 @@ int cddpm_op_conv_gn(cddpm_handle h, const float* src0, int C0, const float* w_h
     a.src0 = src0; a.C0 = C0; a.srcH = H; a.srcW = W; a.wpk = dw; a.bias = db; a.stats = rec;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = 9;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, a.hi_only)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
     launch_conv(a, s);
     launch_gn_finalize(rec, Cout, nrec, nullptr, 0, 0, B, H * W, g, bt, nullptr, nullptr, 0, 0, nullptr, nullptr, coef_dev, s);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(s));
     for (void* p : {(void*)dw, (void*)db, (void*)g, (void*)bt, (void*)rec}) (void)hipFree(p);
-    return 0;
-}
-
-int cddpm_op_conv_bench(cddpm_handle h, int C0, int C1, int Cout, int ksize, int B, int H, int W, int use_coef, int silu,
-                        int upsample, int res_mode, int skipC, int iters, double* ms_out, uint64_t* stamps_out) {
-    if (!h) return -1;
-    const int Cin = C0 + C1, taps = ksize * ksize;
-    if ((ksize != 1 && ksize != 3) || C0 % 32 || C1 % 32 || Cin <= 0 || Cout % 128 || skipC % 32)
-        return fail(h, "cddpm_op_conv_bench: unsupported shape");
-    HIPCHECK(h, hipSetDevice(h->device));
-    hipStream_t s = nullptr;
-    const int sh = upsample ? H / 2 : H, sw = upsample ? W / 2 : W;
-    const size_t n0 = (size_t)B * sh * sw * C0, n1 = (size_t)B * sh * sw * C1, nout = (size_t)B * H * W * Cout;
-    const size_t nsk = (size_t)B * H * W * skipC;
-    const size_t nres = res_mode == 2 ? nout / 4 : nout;
-    float *x0 = nullptr, *x1 = nullptr, *out = nullptr, *res = nullptr, *sk = nullptr, *w = nullptr, *ws = nullptr, *cf = nullptr, *bs = nullptr;
-    unsigned long long* stamps = nullptr;
-    auto alloc_fill = [&](float** p, size_t n, uint32_t stream_id, float scale) -> int {
-        if (!n) return 0;
-        const size_t n4 = (n + 3) / 4 * 4;
-        if (hipMalloc((void**)p, n4 * sizeof(float)) != hipSuccess) return -1;
-        if (getenv("CDDPM_BENCH_ZERO")) { (void)hipMemsetAsync(*p, 0, n4 * sizeof(float), s); return 0; }   // DVFS check: zeros vs random
-        launch_noise_fill(*p, 1234, stream_id, 0, 0, 1, (int)n4, s);
-        (void)scale;
-        return 0;
-    };
-    int rc = 0;
-    rc |= alloc_fill(&x0, n0, 1, 1.f); rc |= alloc_fill(&x1, n1, 2, 1.f); rc |= alloc_fill(&sk, nsk, 3, 1.f);
-    // weights: random host values through the packer of the active kernel family (fp32 image or 16-bit split image)
-    const int bench_wexp = (conv_mode() == 2) ? 18 : 0;
-    auto pack_upload = [&](float** p, int cin, int tp, uint64_t seed) -> int {
-        if (!cin) return 0;
-        std::vector<float> hwt((size_t)Cout * cin * tp);
-        uint64_t st = seed;
-        for (float& v : hwt) { st = st * 6364136223846793005ull + 1442695040888963407ull; v = ((int64_t)(st >> 33) - (1ll << 30)) * (0.05f / (1ll << 30)); }
-        std::vector<float> pk(packed_conv_floats(Cout, cin, tp));
-        pack_conv_weights(hwt.data(), Cout, cin, tp, pk.data(), bench_wexp);      // |w| < 0.05 -> 2^18 keeps it below 2^14
-        if (hipMalloc((void**)p, pk.size() * sizeof(float)) != hipSuccess) return -1;
-        return hipMemcpy(*p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-    };
-    rc |= pack_upload(&w, Cin, taps, 4); rc |= pack_upload(&ws, skipC, 1, 5); rc |= alloc_fill(&cf, (size_t)3 * B * Cin, 6, 1.f);
-    rc |= alloc_fill(&bs, Cout, 7, 1.f);
-    if (res_mode) rc |= alloc_fill(&res, nres, 8, 1.f);
-    if (hipMalloc((void**)&out, nout * sizeof(float)) != hipSuccess) rc = -1;
-    if (hipMalloc((void**)&stamps, 64 * sizeof(unsigned long long)) != hipSuccess) rc = -1;
-    if (rc) return fail(h, "cddpm_op_conv_bench: allocation failed");
-    HIPCHECK(h, hipMemset(stamps, 0, 64 * sizeof(unsigned long long)));
-    ConvArgs a;
-    zero_conv_args(a);
-    a.src0 = x0; a.C0 = C0; a.src1 = x1; a.C1 = C1; a.srcH = sh; a.srcW = sw; a.upsample = upsample;
-    a.coef = use_coef ? cf : nullptr; a.silu = silu; a.wpk = w; a.bias = bs; a.res = res; a.res_up = (res_mode == 2);
-    a.out = out; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = taps;
-    a.skip0 = sk; a.S0 = skipC; a.skip_wpk = ws;
-    a.wscale_inv = ldexpf(1.0f, -bench_wexp);
-    a.stamps = nullptr;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, 0)) ? 1 : 0;      // the A/B tool forces it
-    hipEvent_t e0, e1;
-    HIPCHECK(h, hipEventCreate(&e0));
-    HIPCHECK(h, hipEventCreate(&e1));
-    launch_conv(a, s);   // warm-up
-    a.stamps = stamps_out ? stamps : nullptr;
-    HIPCHECK(h, hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) launch_conv(a, s);
-    HIPCHECK(h, hipEventRecord(e1, s));
-    HIPCHECK(h, hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHECK(h, hipEventElapsedTime(&ms, e0, e1));
-    if (ms_out) *ms_out = ms / iters;
-    if (stamps_out) HIPCHECK(h, hipMemcpy(stamps_out, stamps, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHECK(h, hipGetLastError());
-    for (void* p : {(void*)x0, (void*)x1, (void*)out, (void*)res, (void*)sk, (void*)w, (void*)ws, (void*)cf, (void*)bs, (void*)stamps})
-        if (p) (void)hipFree(p);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return 0;
 }
 
@@ -1664,7 +1589,7 @@ int cddpm_op_conv_dgrad(cddpm_handle h, const float* dy_dev, int Cout, const flo
     a.src0 = dy_dev; a.C0 = Cout; a.srcH = H; a.srcW = W; a.wpk = dw; a.bias = db;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = dx_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cin; a.taps = taps;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, a.hi_only)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
     launch_conv(a, s);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(s));
@@ -1689,10 +1614,9 @@ int cddpm_op_conv_wgrad(cddpm_handle h, const float* x0_dev, int C0, const float
                         int upsample, const float* dy_dev, int Cout, int ksize, float* dw_dev, float* db_dev, int B, int H, int W,
                         void* stream) {
     if (!h) return -1;
-    const bool f32k = wgrad_mode() == 0;      // the fp32-MFMA family walks 4-row tiles and 64-channel chunks of a 1x1 kernel
-    const int Cin = C0 + C1, taps = ksize * ksize, ck = (ksize == 3 || !f32k) ? 32 : 64;
-    if ((ksize != 1 && ksize != 3) || C0 <= 0 || C1 < 0 || Cin % ck || (C1 > 0 && C0 % ck) || Cout <= 0 || Cout % 64 || H < 1 ||
-        (f32k && (H < 4 || H % 4)) || W < 1 || B < 1 || (C1 > 0 && !x1_dev) || (upsample && (C1 > 0 || (W & 1) || (H & 1))))
+    const int Cin = C0 + C1, taps = ksize * ksize;
+    if ((ksize != 1 && ksize != 3) || C0 <= 0 || C1 < 0 || Cin % 32 || (C1 > 0 && C0 % 32) || Cout <= 0 || Cout % 64 || H < 1 ||
+        W < 1 || B < 1 || (C1 > 0 && !x1_dev) || (upsample && (C1 > 0 || (W & 1) || (H & 1))))
         return fail(h, "cddpm_op_conv_wgrad: unsupported shape (k %d, C0 %d, C1 %d, Cout %d, H %d)", ksize, C0, C1, Cout, H);
     if (!x0_dev || !dy_dev || !dw_dev) return fail(h, "cddpm_op_conv_wgrad: NULL argument");
     hipStream_t s = (hipStream_t)stream;
@@ -1717,18 +1641,10 @@ int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const floa
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(h, hipSetDevice(h->device));
     Prof prof_(h, PC_ATTN, 0.0, 0.0, (hipStream_t)stream);
-    static const bool gemm_form = [] { const char* e = getenv("CDDPM_ATTN_BWD"); return e && !strcmp(e, "gemm"); }();
     OpScratch sc(h, s);
-    if (gemm_form) {
-        const size_t nn = (size_t)B * (C / 64) * N * N;
-        float *p = sc.n<float>(nn), *dp = sc.n<float>(nn);
-        SCRATCH_CHECK(sc)
-        launch_attention_backward(qkv_dev, da_dev, dqkv_dev, p, dp, B, N, C, s);
-    } else {
-        float* stats = sc.n<float>((size_t)B * (C / 64) * N * 2);
-        SCRATCH_CHECK(sc)
-        launch_attention_backward_flash(qkv_dev, da_dev, dqkv_dev, stats, B, N, C, s);
-    }
+    float* stats = sc.n<float>((size_t)B * (C / 64) * N * 2);
+    SCRATCH_CHECK(sc)
+    launch_attention_backward_flash(qkv_dev, da_dev, dqkv_dev, stats, B, N, C, s);
     HIPCHECK(h, hipGetLastError());
     return 0;
 }

@@ -19,21 +19,12 @@
 // Each lane fetches 4 consecutive channels per ds_read_b128 and feeds them to 4 successive MFMAs; the K order
 // inside a 8-channel group is therefore {c, c+4} pairs -- identical for A and B, so the sum is unchanged.
 #include "kernels.h"
-#include <cstdlib>
 #include <vector>
 
 namespace cddpm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float v4f __attribute__((ext_vector_type(4)));   // native vector: stays in registers (HIP's float4 struct arrays may not)
-
-#ifdef CDDPM_STAMPS
-// phase accounting for diagnostic builds: 0 prologue, 1 patch stage (barrier + transform + ds_write), 2 weight stage
-// (ds_write + prefetch issue + barrier), 3 MFMA compute, 4 chunk fold, 5 epilogue
-#define STAMP(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_[i] += now_ - last_; last_ = now_; }
-#else
-#define STAMP(i)
-#endif
 
 __device__ __forceinline__ float silu_f(float v) {
     // v * sigmoid(v). exp(-v) = 2^t with t = -v log2(e) carried as (t, tl): the rounding error of the product is
@@ -48,14 +39,11 @@ __device__ __forceinline__ float silu_f(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
-// NWV = waves per workgroup: 4 -> each wave owns 64 pixels x 64 couts (2 x 2 MFMA tiles), 2 workgroups per CU;
-//                            8 -> each wave owns 64 pixels x 32 couts (2 x 1 MFMA tiles), 2 workgroups per CU = 4 waves
-//                                 per SIMD: with four MFMA streams per SIMD the matrix pipe stays fed while some
-//                                 waves stage, wait at the per-tap barrier or run their epilogue.
-template <int TAPS, int NWV>
-__global__ __launch_bounds__(64 * NWV, NWV / 2) void conv_mfma_kernel(const ConvArgs a) {
-    constexpr int THREADS = 64 * NWV;
-    constexpr int NT = 8 / NWV;                 // 32-cout MFMA tiles per wave: 2 | 1
+// 4 waves per workgroup, each owns 64 pixels x 64 couts (2 x 2 MFMA tiles); 2 workgroups per CU
+template <int TAPS>
+__global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
+    constexpr int THREADS = 256;
+    constexpr int NT = 2;                       // 32-cout MFMA tiles per wave
     // TAPS == 4 is the folded form of "nearest x2 upsample -> 3x3 conv": an output pixel (2y+a, 2x+b) sees only
     // 2 x 2 distinct source pixels, so each of the four parity classes (a, b) is a 2x2-tap convolution of the
     // LOW-resolution input with pre-summed weights (pack_conv_weights_up2): 4/9 of the multiplies, same result up to
@@ -65,8 +53,8 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void conv_mfma_kernel(const Conv
     constexpr int PW = UP2 ? 33 : 32 + 2 * PAD;     // patch width  (pixels)
     constexpr int PH = UP2 ? 5 : 4 + 2 * PAD;       // patch height (pixels)
     constexpr int NPIX = PW * PH;                   // 204 | 128 | 165
-    constexpr int NK = (NPIX * 8 + THREADS - 1) / THREADS;  // v4f patch entries per thread: 7 | 4 (4 waves), 4 | 2 (8 waves)
-    constexpr int WK = 1024 / THREADS;          // v4f of a weight slab per thread: 4 | 2
+    constexpr int NK = (NPIX * 8 + THREADS - 1) / THREADS;  // v4f patch entries per thread: 7 | 4 | 6
+    constexpr int WK = 1024 / THREADS;          // v4f of a weight slab per thread
 
     extern __shared__ v4f lds[];
     v4f* ldsA = lds;                // NPIX * 8 v4f
@@ -75,15 +63,10 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void conv_mfma_kernel(const Conv
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-#ifdef CDDPM_STAMPS
-    unsigned long long st_[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-    const unsigned long long t0c_ = last_, t0r_ = __builtin_amdgcn_s_memrealtime();   // in-kernel clock = dc / dr * 100 MHz
-#endif
     const int li = lane & 31;
     const int lh = lane >> 5;
     const int wm = wave & 1;    // pixel rows {0,1} | {2,3}
-    const int wn = wave >> 1;   // cout block of 32 * NT within the 128
+    const int wn = wave >> 1;   // cout half (64) of the 128
 
     const int ncb = a.Cout >> 7;
     // tile grid: the output image, or (UP2) the low-resolution grid of one parity class
@@ -255,13 +238,11 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void conv_mfma_kernel(const Conv
         }
     }
     int buf = 0;
-    STAMP(0)
     for (int chunk = 0; chunk < nch; ++chunk) {
         const bool main_seg = chunk < nch_main;
         const int ntap = main_seg ? TAPS : 1;
         __syncthreads();   // every wave is done reading the previous patch
         store_act(chunk);
-        STAMP(1)
         for (int t = 0; t < ntap; ++t) {
 #pragma unroll
             for (int i = 0; i < WK; ++i) ldsW[buf * 1024 + tid + THREADS * i] = wreg[i];
@@ -271,10 +252,8 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void conv_mfma_kernel(const Conv
             for (int i = 0; i < WK; ++i) wreg[i] = pn[tid + THREADS * i];
             if (last_tap && chunk + 1 < nch) load_act(chunk + 1);
             __syncthreads();
-            STAMP(2)
             compute(main_seg ? t : (TAPS / 2), buf);   // skip segment: centre tap
             buf ^= 1;
-            STAMP(3)
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -284,7 +263,6 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void conv_mfma_kernel(const Conv
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
             }
-        STAMP(4)
     }
 
     __syncthreads();   // every wave is done with the patch / weight buffers before they become transpose space
@@ -358,50 +336,28 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void conv_mfma_kernel(const Conv
             __builtin_amdgcn_wave_barrier();
         }
     }
-#ifdef CDDPM_STAMPS
-    STAMP(5)
-    if (a.stamps && lane == 0) {
-        for (int i = 0; i < 6; ++i) atomicAdd(&a.stamps[wave * 8 + i], st_[i]);
-        if (wave == 0) {
-            atomicAdd(&a.stamps[40], __builtin_amdgcn_s_memtime() - t0c_);
-            atomicAdd(&a.stamps[41], __builtin_amdgcn_s_memrealtime() - t0r_);
-        }
-    }
-#endif
 }
 
 void launch_conv(const ConvArgs& a, hipStream_t stream) {
     if (conv_mode() != 0) { launch_conv_split(a, stream); return; }
-    // 4 waves (64 x 64 per wave, 2 waves per SIMD) is the default; CDDPM_CONV_WAVES=8 selects the 8-wave split
-    // (64 x 32 per wave, 4 waves per SIMD), which measures the same throughput (tools/conv_ab.py, profiles/)
-    static const int nwv = [] { const char* e = getenv("CDDPM_CONV_WAVES"); return (e && e[0] == '8') ? 8 : 4; }();
     const bool up2 = (a.taps == 4);
     const int gh = up2 ? a.H / 2 : a.H, gw = up2 ? a.W / 2 : a.W;
     const int tilesX = (gw + 31) / 32, tilesY = (gh + 3) / 4;
     const unsigned grid = (unsigned)(a.B * (up2 ? 4 : 1) * tilesX * tilesY * (a.Cout / 128));
-    // patch + 2 weight slabs + coefficient cache; the epilogue reuses the space as NWV private 8-KB transpose regions
+    // patch + 2 weight slabs + coefficient cache; the epilogue reuses the space as 4 private 8-KB transpose regions
     const size_t coef_lds = a.coef ? (size_t)3 * (a.C0 + a.C1) * sizeof(float) : 0;
     const size_t need9 = (size_t)(6 * 34 * 8 + 2048) * 16 + coef_lds, need1 = (size_t)(4 * 32 * 8 + 2048) * 16 + coef_lds;
     const size_t need4 = (size_t)(5 * 33 * 8 + 2048) * 16 + coef_lds;
     static bool attr = false;
     if (!attr) {   // > 64 KB of dynamic LDS needs the opt-in; 80 KB still leaves two workgroups per CU
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<9, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<9, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         attr = true;
     }
-    if (up2) {
-        hipLaunchKernelGGL((conv_mfma_kernel<4, 4>), dim3(grid), dim3(256), need4, stream, a);
-    } else if (nwv == 8) {
-        const size_t tr = 8 * 2048 * sizeof(float);
-        if (a.taps == 9) hipLaunchKernelGGL((conv_mfma_kernel<9, 8>), dim3(grid), dim3(512), need9 > tr ? need9 : tr, stream, a);
-        else hipLaunchKernelGGL((conv_mfma_kernel<1, 8>), dim3(grid), dim3(512), need1 > tr ? need1 : tr, stream, a);
-    } else {
-        if (a.taps == 9) hipLaunchKernelGGL((conv_mfma_kernel<9, 4>), dim3(grid), dim3(256), need9, stream, a);
-        else hipLaunchKernelGGL((conv_mfma_kernel<1, 4>), dim3(grid), dim3(256), need1, stream, a);
-    }
+    if (up2) hipLaunchKernelGGL((conv_mfma_kernel<4>), dim3(grid), dim3(256), need4, stream, a);
+    else if (a.taps == 9) hipLaunchKernelGGL((conv_mfma_kernel<9>), dim3(grid), dim3(256), need9, stream, a);
+    else hipLaunchKernelGGL((conv_mfma_kernel<1>), dim3(grid), dim3(256), need1, stream, a);
 }
 
 size_t packed_conv_floats(int Cout, int Cin, int taps) {

@@ -42,34 +42,9 @@
 
 namespace cddpm {
 
-#if defined(CDDPM_STAMPS_EPI)
-// accounting of the fixed per-workgroup cost (tools/conv_ab.py, AB_EPI=1): 0 prologue (kernel start .. first chunk), 1 main loop,
-// 2 residual requests, 3 the barrier in front of the epilogue, 4 / 6 transpose of cout half 0 / 1 through LDS, 5 / 7 its stores + statistics
-#define STAMP(i)
-#define FSTAMP(i)
-#define ESTAMP(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_[i] += now_ - last_; last_ = now_; }
-#elif defined(CDDPM_STAMPS_FINE)
-// finer accounting of the LDS-DMA main loop (tools/conv_ab.py, AB_FINE=1): 0 wait for the chunk's first weight stage and patch
-// registers (vmcnt), 1 the barrier behind it, 2 patch transform + store, 3 the barrier behind it, 4 wait for the next weight stage at
-// the end of a stage (vmcnt), 5 the barrier behind it, 6 request issue + MFMA compute + fold, 7 prologue + epilogue
-#define STAMP(i)
-#define FSTAMP(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_[i] += now_ - last_; last_ = now_; }
-#define ESTAMP(i)
-#elif defined(CDDPM_STAMPS)
-// phase accounting for diagnostic builds: 0 prologue, 1 patch stage (barrier + transform + split + ds_write), 2 weight
-// stage (ds_write + prefetch issue + barrier), 3 MFMA compute, 4 fold, 5 epilogue
-#define STAMP(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_[i] += now_ - last_; last_ = now_; }
-#define FSTAMP(i)
-#define ESTAMP(i)
-#else
-#define STAMP(i)
-#define FSTAMP(i)
-#define ESTAMP(i)
-#endif
-
-// M16X: the fp16 form on v_mfma_f32_16x16x32_f16 (one MFMA spans a tap's whole 32-channel chunk; 16 tiles of 16 x 16 per
-// wave) instead of 32x32x16: the same cycle count, but the chip holds a higher clock on this shape -- the default of the
-// fp16 form (the 32x32x16 instances stay for CDDPM_M16=0); half as many accumulate roundings per product.
+// The fp16 form (NS = 2) runs on v_mfma_f32_16x16x32_f16 (one MFMA spans a tap's whole 32-channel chunk; 16 tiles of 16 x 16 per
+// wave), the bf16 form on 32x32x16. For fp16 both shapes take the same cycle count, but the chip holds a higher clock on 16x16x32
+// (MI355X_MICROARCH.md, DVFS give-back item 7: 3-9 % faster on every layer shape); half as many accumulate roundings per product.
 // HI1: multiply the hi terms only (plain fp16 operands, fp32 accumulation: the training operators under CDDPM_TRAIN_PRECISION=16); its own
 // instantiation, so that the reconstruction path's kernel is unchanged by it
 // NB: cout blocks of 128 per workgroup. NB = 2 (16 x 16 form, LDS-DMA loop only; a.nb2): the workgroup's tile is 256 pixels x 256 couts,
@@ -78,9 +53,10 @@ namespace cddpm {
 // registers `acc` and `tot` take at NB = 1, so the three-level accumulation becomes two-level: every MFMA accumulates into the output's
 // one long-lived chain (rounding noise of a K = 4608 dot product 7.6e-7 of rms(C) instead of 1.9e-7; the reference's CPU fmaf chain:
 // 1.2e-6 -- tools/ubench/bf16_split_accuracy.hip, rows "h3" / "h3 fold96" / "cpu fma32").
-template <int TAPS, int ROWS, int NS, bool M16X = false, bool HI1 = false, int NB = 1>
+static constexpr int ROWS = 8;      // image rows of a workgroup's pixel tile (x 32 columns), two per wave
+template <int TAPS, int NS, bool HI1 = false, int NB = 1>
 __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a) {
-    static_assert(NB == 1 || (NB == 2 && M16X && NS == 2 && TAPS != 1), "two cout blocks per workgroup: 16 x 16 fp16 form, LDS-DMA loop (3x3 and folded 2x2) only");
+    static_assert(NB == 1 || (NB == 2 && NS == 2 && TAPS != 1), "two cout blocks per workgroup: 16 x 16 fp16 form, LDS-DMA loop (3x3 and folded 2x2) only");
     typedef typename SplitT<NS>::v8 frag;
     constexpr int SP = 4 * NS;                          // 16-B slots per pixel / per cout row
     constexpr int THREADS = 64 * ROWS;
@@ -91,16 +67,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     constexpr int PH = UP2 ? ROWS + 1 : ROWS + 2 * PAD; // patch height (pixels)
     constexpr int NPIX = PW * PH;                       // 340 | 256 | 297 at ROWS = 8
     constexpr int NK = (NPIX * 8 + THREADS - 1) / THREADS;   // 16-B (4-channel) patch entries per thread: 6 | 4 | 5
-#ifndef CDDPM_X6_FOLD
-#define CDDPM_X6_FOLD 3
-#endif
-#ifndef CDDPM_GLDS
-#define CDDPM_GLDS 1
-#endif
-// (the timing-only ablation builds of rounds 1-2 -- NOBARRIER / NOFOLD / NOFRAG / NODMA, wrong results by construction -- are no longer
-// switches of this file: tools/ubench/conv_x6_ablation_switches.patch re-creates them for tools/conv_ab.py)
-#define LOOP_BARRIER() __syncthreads()
-    constexpr int FOLD = (TAPS == 9) ? CDDPM_X6_FOLD : (TAPS == 4 ? 2 : 1);   // taps per accumulation group
+    constexpr int FOLD = (TAPS == 9) ? 3 : (TAPS == 4 ? 2 : 1);   // taps per accumulation group: one row of taps
     constexpr int WSLOTS = 128 * SP;                    // 16-B slots of a weight slab
     // taps per weight stage: the fp16 form stages a whole row of taps (3 of the 3x3, 2 of the folded 2x2) per workgroup
     // barrier -- one barrier (and one burst of fragment reads behind it) per 72 MFMAs of a wave instead of per 24, and the
@@ -118,11 +85,6 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-#if defined(CDDPM_STAMPS) || defined(CDDPM_STAMPS_FINE) || defined(CDDPM_STAMPS_EPI)
-    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-    const unsigned long long t0c_ = last_, t0r_ = __builtin_amdgcn_s_memrealtime();
-#endif
     const int li = lane & 31;
     const int lh = lane >> 5;
     const int wm = wave % (ROWS / 2);   // pixel rows {2 wm, 2 wm + 1} of the tile
@@ -137,9 +99,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     // tiles instead: the cout blocks of one tile and the tiles above / below it (shared halo rows) then run on one XCD at
     // about the same time, and the second reader of a patch row finds it in that L2.
     int bid = blockIdx.x;
-#ifndef CDDPM_NO_XCD_REMAP
     if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-#endif
     const int cb = bid % ncbw;
     bid /= ncbw;
     // split-K (small batches, cddpm_api.hip::conv_launch): this workgroup multiplies the chunks kbound[ks] .. kbound[ks + 1] only
@@ -170,7 +130,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     //             slot bit 2; the patch width is even, so column and pixel parity agree): a tap's row shift ky is then a
     //             plain address offset and the fragment addresses are computed once per kernel, not once per tap.
     // Both are conflict-free for every tap; with the weights' swizzle the 16x16 reads took 7 LDS cycles instead of 4.
-    constexpr bool M16S = M16X && (NS == 2);
+    constexpr bool M16 = (NS == 2);      // the 16 x 16 form
     auto swz16 = [](int pc) -> int { return (2 * ((pc >> 1) & 3)) ^ (4 * (pc & 1)); };
     auto slot_a = [](int row, int sp, int u) -> int {      // (not the 16x16 form)
         if (NS == 3) return row * 12 + 4 * sp + (u ^ ((row >> 2) & 3));
@@ -193,7 +153,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     for (int k = 0; k < NK; ++k) {
         const int q = (tid >> 3) + (THREADS / 8) * k;
         const int pr = q / PW, pc = q - pr * PW;
-        if constexpr (M16S) colswz |= (unsigned)swz16(pc) << (3 * k);
+        if constexpr (M16) colswz |= (unsigned)swz16(pc) << (3 * k);
         const int y = UP2 ? (y0 + pr + pa - 1) : (y0 + pr - PAD), x = UP2 ? (x0 + pc + pb - 1) : (x0 + pc - PAD);
         const bool valid = (q < NPIX) && (y >= 0) && (y < gridH) && (x >= 0) && (x < gridW);
         const int sy = (!UP2 && a.upsample) ? (y >> 1) : y, sx = (!UP2 && a.upsample) ? (x >> 1) : x;
@@ -205,7 +165,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     const v4f* wskip = reinterpret_cast<const v4f*>(a.skip_wpk) + (size_t)(NB * cb) * nch_skip * WSLOTS;
     const size_t wmain_blk = (size_t)nch_main * TAPS * WSLOTS, wskip_blk = (size_t)nch_skip * WSLOTS;    // next cout block of the image
 
-    v4f wreg[TPS * WK];
+    v4f wreg[WK];                       // (TPS == 1 loop) the next weight slab
     v4f areg[NK];
     const bool have_coef = (a.coef != nullptr);
 
@@ -277,7 +237,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 // 4 channels = half a slot: slot u = c4 >> 1 of each split, half c4 & 1
 #pragma unroll
                 for (int sp = 0; sp < (HI1 ? 1 : NS); ++sp) {        // (hi-only products never read the mid plane: it is neither computed nor stored)
-                    const int sl = M16S ? (q * 8 + ((4 * sp + (c4 >> 1)) ^ (int)((colswz >> (3 * k)) & 7u))) : slot_a(q, sp, c4 >> 1);
+                    const int sl = M16 ? (q * 8 + ((4 * sp + (c4 >> 1)) ^ (int)((colswz >> (3 * k)) & 7u))) : slot_a(q, sp, c4 >> 1);
                     dst[sl * 2 + (c4 & 1)] = __builtin_bit_cast(v2f, sreg[k][sp]);
                 }
             }
@@ -285,7 +245,6 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     };
     auto store_act = [&](int chunk) { transform_act(chunk); write_act(); };
 
-    constexpr bool M16 = M16X && (NS == 2);
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x16 acc[2][2], tot[2][2];            // 32 x 32 form: [pixel row][cout 32-tile]
     f32x4 acc16[NB][4][4], tot16[4][4];     // 16 x 16 form: [cout block][pixel 16-group][cout 16-group]  (only one of the two sets is live; NB = 2: no tot16)
@@ -452,13 +411,11 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         }
     }
     int buf = 0;
-    STAMP(0)
     for (int chunk = 0; chunk < nch; ++chunk) {
         const bool main_seg = chunk < nch_main;
         const int ntap = main_seg ? TAPS : 1;
         __syncthreads();   // every wave is done reading the previous patch
         store_act(chunk);
-        STAMP(1)
         for (int t = 0; t < ntap; ++t) {
 #pragma unroll
             for (int i = 0; i < WK; ++i) ldsW[buf * WSLOTS + tid + THREADS * i] = wreg[i];
@@ -468,22 +425,17 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             for (int i = 0; i < WK; ++i) wreg[i] = pn[tid + THREADS * i];
             if (last_tap && chunk + 1 < nch) load_act(chunk + 1);
             __syncthreads();
-            STAMP(2)
             // accumulation in three levels: an MFMA sums 16 products, `acc` collects FOLD taps of a 32-channel chunk
             // (<= 96 products per chain), `tot` sums those groups. The rounding noise of an fp32 chain grows with the
             // magnitude of its partial sums, so short chains folded into a long-lived total keep it near the
             // storage-rounding level (tools/ubench/bf16_split_accuracy.hip, tools/chain_noise.py).
             compute(std::integral_constant<int, 0>{}, main_seg ? t : (TAPS / 2), 0, !main_seg, ldsW + buf * WSLOTS, (t % FOLD) == 0);   // skip segment: centre tap (16x16 form: 1x1 convolutions only get here)
             buf ^= 1;
-            STAMP(3)
-            if ((t % FOLD) == FOLD - 1 || last_tap) {
-                fold_acc();
-                STAMP(4)
-            }
+            if ((t % FOLD) == FOLD - 1 || last_tap) fold_acc();
         }
     }
 
-    } else if constexpr (CDDPM_GLDS != 0) {
+    } else {
     // ---- main loop, weights by LDS-DMA: a stage (TPS taps of one 32-channel chunk, 48 KB) is copied global -> LDS by
     //      global_load_lds_dwordx4 while the previous stage is multiplied -- the packed image IS the LDS image, so the copy is
     //      lane-linear; no weight registers, no ds_write pass. One barrier per stage, behind a vmcnt(0) that retires the copy.
@@ -521,43 +473,16 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             ldsC[i] = *reinterpret_cast<const v4f*>(a.coef + pl * plane + (size_t)b * Cin + 4 * cq);
         }
     }
-#ifndef CDDPM_TRANSFORM_AFTER_BARRIER
     if (have_coef) __syncthreads();     // the coefficient cache is read by transform_act in FRONT of the first chunk barrier
-#endif
     int buf = 0;
-#ifdef CDDPM_STAGGER_SLEEP
-    // A/B switch (tools/conv_ab.py): the two waves of a SIMD (w and w + 4) run the same program between the same barriers;
-    // waves 4-7 start every stage 64 * CDDPM_STAGGER_SLEEP cycles late so that their fragment reads fall behind their partner's
-    // (MI355X_MICROARCH.md, Two waves per SIMD, item 9). Results unchanged.
-    const bool late = __builtin_amdgcn_readfirstlane(wave) >= 4;
-#define STAGGER() { if (late) __builtin_amdgcn_s_sleep(CDDPM_STAGGER_SLEEP); }
-#else
-#define STAGGER()
-#endif
-    STAMP(0)
     for (int chunk = kc0; chunk < kc1; ++chunk) {
         const bool main_seg = chunk < nch_main;
         const int nst = main_seg ? TAPS / TPS : 1;       // stages of this chunk
-        FSTAMP(chunk == kc0 ? 7 : 6)
-        if (chunk == kc0) { ESTAMP(0) }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this chunk's first weight stage (and its patch registers) have landed
-        FSTAMP(0)
-#ifndef CDDPM_TRANSFORM_AFTER_BARRIER
         transform_act(chunk);   // registers only: in front of the barrier, where the early waves would otherwise wait
-        FSTAMP(2)
-        LOOP_BARRIER();   // the stage has landed in every wave, and every wave is done reading the previous patch
-        FSTAMP(1)
+        __syncthreads();   // the stage has landed in every wave, and every wave is done reading the previous patch
         write_act();
-#else
-        LOOP_BARRIER();   // ... in every wave, and every wave is done reading the previous patch
-        FSTAMP(1)
-        store_act(chunk);
-#endif
-        FSTAMP(2)
-        LOOP_BARRIER();
-        FSTAMP(3)
-        STAGGER();
-        STAMP(1)
+        __syncthreads();
         if constexpr (NB == 1) {
         for (int st = 0; st < nst; ++st) {
             const int ntaps = nsl_cur;                    // taps of this stage
@@ -569,7 +494,6 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 const v4f* pn = last_st ? wstage(chunk + 1, 0, 0, nsl_next) : wstage(chunk, 0, st + 1, nsl_next);
                 dma_stage(pn, nsl_next, buf ^ 1);
             }
-            STAMP(2)
 #pragma unroll
             for (int tt = 0; tt < TPS; ++tt)
                 if (tt < ntaps) {
@@ -578,18 +502,10 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 }
             buf ^= 1;
             nsl_cur = nsl_next;
-            STAMP(3)
-            if (((st + 1) * TPS) % FOLD == 0 || last_st) {
-                fold_acc();
-                STAMP(4)
-            }
+            if (((st + 1) * TPS) % FOLD == 0 || last_st) fold_acc();
             if (!last_st) {
-                FSTAMP(6)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                FSTAMP(4)
-                LOOP_BARRIER();   // the next stage has landed in every wave; this stage's buffer is free
-                FSTAMP(5)
-                STAGGER();
+                __syncthreads();   // the next stage has landed in every wave; this stage's buffer is free
             }
         }
         } else {
@@ -607,7 +523,6 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                                             : (st == nst - 1 ? wstage(chunk, HB + 1, 0, nsl_next) : wstage(chunk, HB, st + 1, nsl_next));
                     dma_stage(pn, nsl_next, buf ^ 1);
                 }
-                STAMP(2)
 #pragma unroll
                 for (int tt = 0; tt < TPS; ++tt)
                     if (tt < ntaps) {
@@ -617,18 +532,10 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     }
                 buf ^= 1;
                 nsl_cur = nsl_next;
-                STAMP(3)
-                if (((st + 1) * TPS) % FOLD == 0 || st == nst - 1) {
-                    fold_acc();
-                    STAMP(4)
-                }
+                if (((st + 1) * TPS) % FOLD == 0 || st == nst - 1) fold_acc();
                 if (!last_st) {
-                    FSTAMP(6)
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    FSTAMP(4)
-                    LOOP_BARRIER();   // the next stage has landed in every wave; this stage's buffer is free
-                    FSTAMP(5)
-                    STAGGER();
+                    __syncthreads();   // the next stage has landed in every wave; this stage's buffer is free
                 }
             }
         };
@@ -637,90 +544,11 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         }
     }
 
-    } else {
-    // ---- main loop: weight stages (TPS taps of one 32-channel chunk) double-buffered in LDS and prefetched through
-    //      registers one stage ahead; the next chunk's patch is fetched into registers behind the last stage's MFMAs.
-    // stage pointer / slab count; past the end it wraps to stage 0 so that the prefetch stays unconditional
-    auto wstage = [&](int chunk, int st, int& nsl) -> const v4f* {
-        if (chunk >= nch) { chunk = 0; st = 0; }
-        if (chunk < nch_main) { nsl = TPS; return wmain + ((size_t)chunk * TAPS + st * TPS) * WSLOTS; }
-        nsl = 1;
-        return wskip + (size_t)(chunk - nch_main) * WSLOTS;
-    };
-    auto get_stage = [&](const v4f* p, int nsl) {        // global -> registers (nsl slabs of this stage)
-#pragma unroll
-        for (int sl = 0; sl < TPS; ++sl)
-            if (TPS == 1 || sl < nsl) {
-#pragma unroll
-                for (int i = 0; i < WK; ++i) wreg[sl * WK + i] = p[sl * WSLOTS + tid + THREADS * i];
-            }
-    };
-    auto put_stage = [&](int buf, int nsl) {             // registers -> LDS
-#pragma unroll
-        for (int sl = 0; sl < TPS; ++sl)
-            if (TPS == 1 || sl < nsl) {
-#pragma unroll
-                for (int i = 0; i < WK; ++i) ldsW[buf * WSTAGE + sl * WSLOTS + tid + THREADS * i] = wreg[sl * WK + i];
-            }
-    };
-    int nsl_cur = 0;
-    {
-        const v4f* p0 = wstage(0, 0, nsl_cur);
-        get_stage(p0, nsl_cur);
-    }
-    load_act(0);
-    if (have_coef) {
-        const int nq = Cin >> 2;
-        const size_t plane = (size_t)a.B * Cin;
-        for (int i = tid; i < 3 * nq; i += THREADS) {
-            const int pl = i / nq, cq = i - pl * nq;
-            ldsC[i] = *reinterpret_cast<const v4f*>(a.coef + pl * plane + (size_t)b * Cin + 4 * cq);
-        }
-    }
-    int buf = 0;
-    STAMP(0)
-    for (int chunk = 0; chunk < nch; ++chunk) {
-        const bool main_seg = chunk < nch_main;
-        const int nst = main_seg ? TAPS / TPS : 1;       // stages of this chunk
-        __syncthreads();   // every wave is done reading the previous patch
-        store_act(chunk);
-        STAMP(1)
-        for (int st = 0; st < nst; ++st) {
-            put_stage(buf, nsl_cur);
-            const int ntaps = nsl_cur;                    // taps of this stage
-            const bool last_st = (st == nst - 1);
-            int nsl_next = 0;
-            const v4f* pn = last_st ? wstage(chunk + 1, 0, nsl_next) : wstage(chunk, st + 1, nsl_next);
-            get_stage(pn, nsl_next);
-            nsl_cur = nsl_next;
-            if (last_st && chunk + 1 < nch) load_act(chunk + 1);
-            __syncthreads();
-            STAMP(2)
-            // accumulation in three levels: an MFMA sums 16 products, `acc` collects FOLD taps of a 32-channel chunk
-            // (<= 96 products per chain), `tot` sums those groups. The rounding noise of an fp32 chain grows with the
-            // magnitude of its partial sums, so short chains folded into a long-lived total keep it near the
-            // storage-rounding level (tools/ubench/bf16_split_accuracy.hip, tools/chain_noise.py).
-#pragma unroll
-            for (int tt = 0; tt < TPS; ++tt)
-                if (TPS == 1 || tt < ntaps) {
-                    const int t = st * TPS + tt;                                  // tap index inside the chunk
-                    compute(std::integral_constant<int, 0>{}, main_seg ? t : (TAPS / 2), tt, !main_seg, ldsW + buf * WSTAGE + tt * WSLOTS, (t % FOLD) == 0);   // skip segment: centre tap
-                }
-            buf ^= 1;
-            STAMP(3)
-            if (((st + 1) * TPS) % FOLD == 0 || last_st) {
-                fold_acc();
-                STAMP(4)
-            }
-        }
-    }
-
     }
 
     // residual tile of this wave (16 x 16 B per lane): requested here, in one go, so that the loads fly while the waves
     // meet at the barrier and transpose; the accumulator / fragment registers are dead by now. (Loading each batch right
     // before its add exposed the global latency four times per wave: 12 % of the kernel on the +residual layers.)
-    ESTAMP(1)
     // the epilogue handles 2 NB quarter-tiles q = 2 hb + nt (cout block hb of the workgroup, 32-cout half nt of the wave's 64): the
     // residual of quarter q sits in buffer q & 1, requested two quarters ahead (q = 0, 1 here, q + 2 when quarter q's registers are free)
     v4f rsd_all[2][2][4];
@@ -746,16 +574,11 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     };
     load_rsd(0);
     load_rsd(1);
-    ESTAMP(2)
     __syncthreads();   // every wave is done with the patch / weight buffers before they become transpose space
-    ESTAMP(3)
     // ---- epilogue: as conv_mfma.hip -- each wave transposes its 64 x 64 tile through a private 8-KB LDS region so
     //      that every lane moves 16 B; bias, residual and the GroupNorm statistics of the output are applied here.
     {
-#ifndef CDDPM_TRS16
-#define CDDPM_TRS16 36
-#endif
-        constexpr int TRS = M16 ? CDDPM_TRS16 : 32;                            // row stride of the transpose region (36: conflict-free for the 16 x 16 C layout)
+        constexpr int TRS = M16 ? 36 : 32;                            // row stride of the transpose region (36: conflict-free for the 16 x 16 C layout)
         float* tr = reinterpret_cast<float*>(lds) + wave * (64 * TRS);   // [64 pixels][32 channels]
         const int cq = lane & 7;
         const int prow = lane >> 3;
@@ -783,7 +606,6 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                         tr[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = tot[mt][nt][r];
             }
             __builtin_amdgcn_wave_barrier();
-            if (nt == 0) { ESTAMP(4) } else { ESTAMP(6) }
             const v4f bias = a.bias ? *reinterpret_cast<const v4f*>(a.bias + co) : v4f{0.f, 0.f, 0.f, 0.f};
             const float wsc = (NS == 2) ? a.wscale_inv : 1.0f;      // fp16 weights were pre-scaled by a power of two
             v4f ssum = v4f{0.f, 0.f, 0.f, 0.f}, ssq = ssum;
@@ -828,20 +650,8 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 }
             }
             __builtin_amdgcn_wave_barrier();
-            if (nt == 0) { ESTAMP(5) } else { ESTAMP(7) }
         }
     }
-#if defined(CDDPM_STAMPS) || defined(CDDPM_STAMPS_FINE) || defined(CDDPM_STAMPS_EPI)
-    STAMP(5)
-    FSTAMP(7)
-    if (a.stamps && lane == 0 && wave < 4) {
-        for (int i = 0; i < 8; ++i) atomicAdd(&a.stamps[wave * 8 + i], st_[i]);
-        if (wave == 0) {
-            atomicAdd(&a.stamps[40], __builtin_amdgcn_s_memtime() - t0c_);
-            atomicAdd(&a.stamps[41], __builtin_amdgcn_s_memrealtime() - t0r_);
-        }
-    }
-#endif
 }
 
 int conv_mode() {
@@ -854,41 +664,33 @@ int conv_mode() {
     return mode;
 }
 
-template <int NS, int ROWS>
+template <int NS>
 static void launch_split(const ConvArgs& a, hipStream_t stream) {
     const bool up2 = (a.taps == 4);
     const int gh = up2 ? a.H / 2 : a.H, gw = up2 ? a.W / 2 : a.W;
     const int tilesX = (gw + 31) / 32, tilesY = (gh + ROWS - 1) / ROWS;
     // a.nb2 (set by the caller's plan: conv_nb2_ok): 256 couts per workgroup, the chunk's patch produced once for both cout blocks
-    static const int m16_env = [] { const char* e = getenv("CDDPM_M16"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-    const bool m16 = (NS == 2) && (m16_env != 0);
-    const bool nb2 = (NS == 2) && m16 && a.nb2 && a.ksplit <= 1 && (a.Cout % 256) == 0 && a.taps != 1;
+    const bool nb2 = (NS == 2) && a.nb2 && a.ksplit <= 1 && (a.Cout % 256) == 0 && a.taps != 1;
     const unsigned grid = (unsigned)(a.B * (up2 ? 4 : 1) * tilesX * tilesY * (a.Cout / (nb2 ? 256 : 128)) * (a.ksplit > 1 ? a.ksplit : 1));
     const size_t coef_lds = a.coef ? (size_t)3 * (a.C0 + a.C1) * sizeof(float) : 0;
-    auto need = [&](int npix) {
-        const int tps = (NS == 2) ? (a.taps == 9 ? 3 : (a.taps == 4 ? 2 : 1)) : 1;     // taps per weight stage (kernel: TPS)
-        const size_t main = (size_t)(npix + 2 * tps * 128) * (4 * NS) * 16 + coef_lds;
-        const size_t tr = (size_t)ROWS * 64 * 36 * sizeof(float);   // epilogue transpose regions alias the buffers (stride <= 36)
-        return main > tr ? main : tr;
-    };
-    // MFMA shape of the fp16 form: 16x16x32 (CDDPM_M16=0 forces 32x32x16). The chip holds a higher clock on it
-    // (MI355X_MICROARCH.md, DVFS give-back item 7): 3-9 % faster on every layer shape, at the same cycle count.
+    const int npix = (a.taps == 9) ? (ROWS + 2) * 34 : (up2 ? (ROWS + 1) * 33 : ROWS * 32);     // patch pixels (kernel: NPIX)
+    const int tps = (NS == 2) ? (a.taps == 9 ? 3 : (up2 ? 2 : 1)) : 1;                             // taps per weight stage (kernel: TPS)
+    const size_t main = (size_t)(npix + 2 * tps * 128) * (4 * NS) * 16 + coef_lds;
+    const size_t tr = (size_t)ROWS * 64 * 36 * sizeof(float);   // epilogue transpose regions alias the buffers (stride <= 36)
+    const size_t lds = main > tr ? main : tr;
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, ROWS, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, ROWS, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<1, ROWS, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<1, ROWS, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, ROWS, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, ROWS, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<1, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if constexpr (NS == 2) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, ROWS, NS, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<1, ROWS, NS, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, ROWS, NS, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, ROWS, NS, true, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, ROWS, NS, true, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, ROWS, NS, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, ROWS, NS, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<1, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         }
         attr = true;
     }
@@ -896,26 +698,22 @@ static void launch_split(const ConvArgs& a, hipStream_t stream) {
     if constexpr (NS == 2) {
         if (nb2) {
             if (a.hi_only) {       // plain fp16 operands (the training operators under precision 16)
-                if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, ROWS, NS, true, true, 2>), g, blk, need((ROWS + 2) * 34), stream, a);
-                else hipLaunchKernelGGL((conv_split_kernel<4, ROWS, NS, true, true, 2>), g, blk, need((ROWS + 1) * 33), stream, a);
-            } else if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, ROWS, NS, true, false, 2>), g, blk, need((ROWS + 2) * 34), stream, a);
-            else hipLaunchKernelGGL((conv_split_kernel<4, ROWS, NS, true, false, 2>), g, blk, need((ROWS + 1) * 33), stream, a);
+                if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS, true, 2>), g, blk, lds, stream, a);
+                else hipLaunchKernelGGL((conv_split_kernel<4, NS, true, 2>), g, blk, lds, stream, a);
+            } else if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS, false, 2>), g, blk, lds, stream, a);
+            else hipLaunchKernelGGL((conv_split_kernel<4, NS, false, 2>), g, blk, lds, stream, a);
+            return;
+        }
+        if (a.hi_only) {
+            if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS, true>), g, blk, lds, stream, a);
+            else if (a.taps == 1) hipLaunchKernelGGL((conv_split_kernel<1, NS, true>), g, blk, lds, stream, a);
+            else hipLaunchKernelGGL((conv_split_kernel<4, NS, true>), g, blk, lds, stream, a);
             return;
         }
     }
-    if (a.taps == 9) {
-        if (m16 && a.hi_only) hipLaunchKernelGGL((conv_split_kernel<9, ROWS, NS, true, true>), g, blk, need((ROWS + 2) * 34), stream, a);
-        else if (m16) hipLaunchKernelGGL((conv_split_kernel<9, ROWS, NS, true>), g, blk, need((ROWS + 2) * 34), stream, a);
-        else     hipLaunchKernelGGL((conv_split_kernel<9, ROWS, NS>), g, blk, need((ROWS + 2) * 34), stream, a);
-    } else if (a.taps == 1) {
-        if (m16 && a.hi_only) hipLaunchKernelGGL((conv_split_kernel<1, ROWS, NS, true, true>), g, blk, need(ROWS * 32), stream, a);
-        else if (m16) hipLaunchKernelGGL((conv_split_kernel<1, ROWS, NS, true>), g, blk, need(ROWS * 32), stream, a);
-        else     hipLaunchKernelGGL((conv_split_kernel<1, ROWS, NS>), g, blk, need(ROWS * 32), stream, a);
-    } else {
-        if (m16 && a.hi_only) hipLaunchKernelGGL((conv_split_kernel<4, ROWS, NS, true, true>), g, blk, need((ROWS + 1) * 33), stream, a);
-        else if (m16) hipLaunchKernelGGL((conv_split_kernel<4, ROWS, NS, true>), g, blk, need((ROWS + 1) * 33), stream, a);
-        else     hipLaunchKernelGGL((conv_split_kernel<4, ROWS, NS>), g, blk, need((ROWS + 1) * 33), stream, a);
-    }
+    if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS>), g, blk, lds, stream, a);
+    else if (a.taps == 1) hipLaunchKernelGGL((conv_split_kernel<1, NS>), g, blk, lds, stream, a);
+    else hipLaunchKernelGGL((conv_split_kernel<4, NS>), g, blk, lds, stream, a);
 }
 
 // May a launch use 256-cout workgroups (ConvArgs::nb2)? Feasibility only -- WHEN it is used is the caller's plan (cddpm_api.hip: the
@@ -928,16 +726,14 @@ int conv_nb2_env() {
     static const int v = [] { const char* e = getenv("CDDPM_NB2"); return (e && e[0] == '0') ? 0 : (e && !strcmp(e, "force")) ? 2 : 1; }();
     return v;
 }
-bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit, int hi_only) {
-    static const bool m16 = [] { const char* e = getenv("CDDPM_M16"); return !(e && e[0] == '0'); }();
+bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit) {
     const int on = conv_nb2_env();
-    (void)hi_only;       // both operand forms have the 256-cout instantiation
-    return on && m16 && conv_mode() == 2 && ksplit <= 1 && (Cout % 256) == 0 && (on == 2 || workgroups128 >= 512);
+    return on && conv_mode() == 2 && ksplit <= 1 && (Cout % 256) == 0 && (on == 2 || workgroups128 >= 512);
 }
 
 void launch_conv_split(const ConvArgs& a, hipStream_t stream) {
-    if (conv_mode() == 1) launch_split<3, 8>(a, stream);
-    else launch_split<2, 8>(a, stream);
+    if (conv_mode() == 1) launch_split<3>(a, stream);
+    else launch_split<2>(a, stream);
 }
 
 // ---- host side: 16-bit round-to-nearest-even conversions and the splits

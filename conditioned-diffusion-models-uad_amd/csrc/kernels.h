@@ -31,7 +31,6 @@ struct ConvArgs {
     // used for ResBlock skip_connection convs: out += conv1x1(skip0|skip1) (bias folded by the caller)
     const float* skip0; const float* skip1; int S0, S1;   // NHWC at the OUTPUT resolution
     const float* skip_wpk;
-    unsigned long long* stamps;   // diagnostic builds (-DCDDPM_STAMPS) only: per-wave phase cycle sums, else nullptr
     // optional GroupNorm statistics of the OUTPUT tensor, produced by the epilogue: fp32 records
     // [B][nrec = 2 * tilesX * tilesY][Cout][2] = per-channel (sum, sum of squares) over the 64 pixels a wave owns
     float* stats;
@@ -41,15 +40,15 @@ struct ConvArgs {
     // of `out` ([ksplit][B][H][W][Cout]; the caller passes no bias / residual / stats) and launch_conv_reduce combines the planes.
     int ksplit;
     short kbound[CDDPM_MAX_KSPLIT + 1];
-    // fp16-split family, 16 x 16 form only: 1 = multiply the hi terms only (plain fp16 operands, fp32 accumulation -- the arithmetic of the
+    // fp16-split family only: 1 = multiply the hi terms only (plain fp16 operands, fp32 accumulation -- the arithmetic of the
     // reference trainer's `precision: 16`; a third of the MFMAs). Set by the training operators under CDDPM_TRAIN_PRECISION=16, never by
     // the reconstruction path.
     int hi_only;
-    // fp16-split family, 16 x 16 form, unsplit K: 1 = workgroups of 256 pixels x 256 couts (two cout blocks per workgroup sharing the
+    // fp16-split family, unsplit K: 1 = workgroups of 256 pixels x 256 couts (two cout blocks per workgroup sharing the
     // chunk's transformed patch; two-level accumulation, see conv_x6.hip). Decided by the caller with conv_nb2_ok.
     int nb2;
 };
-bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit, int hi_only);
+bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit);
 int conv_nb2_env();      // CDDPM_NB2: 0 never, 1 by plan (default), 2 forced
 // out[b][p][c] = ((plane 0 + plane 1) + ...) + bias[c] + residual, in this fixed order; optional GroupNorm statistics records of
 // `out`: one record per 64 consecutive pixels, [B][ceil(HW / 64)][Cout][2]
@@ -169,20 +168,17 @@ void launch_simplex(unsigned short* out, long long seed, int B, int H, int W, in
 void launch_gn_bwd_planes(const float* rec, int nrec, const float* gamma, const float* beta, const float* film, int B, int C, int HW,
                           float* planes, hipStream_t stream);
 // conv wgrad (3x3 pad 1, or 1x1): dw [Cout][Cin][k][k] (PyTorch layout), db [Cout] or nullptr; input = cat[x0 (C0), x1 (C1)];
-// part: scratch of conv_wgrad_parts() * Cout * Cin * taps floats. Cin multiple of 32 (3x3) / 64 (1x1), C0 of 64, Cout of 64, H of 4
+// part: scratch of conv_wgrad_parts() * Cout * Cin * taps floats. Cin (and C0 when C1 > 0) multiple of 32, Cout of 64
 int train_precision();                 // 32 (default) or 16: see train_kernels.hip
 int set_train_precision(int bits);    // returns the previous value
-int wgrad_mode();      // CDDPM_WGRAD: 2 = h3 (default), 1 = h1, 0 = f32
 int conv_wgrad_parts(int B, int H, int W, int Cin, int Cout, int taps);
 size_t conv_wgrad_image_units(int B, int H, int W, int Cin, int Cout, int taps);   // 16-byte units of `images` (0: not used by this call)
 void launch_conv_wgrad(const float* x0, int C0, const float* x1, int C1, const float* coef, int silu, int up, const float* dy, int B, int H,
                        int W, int Cout, int taps, float* part, int P, void* images, float* dw, float* db, hipStream_t stream);
 void launch_bias_grad(const float* dy, long long npix, int C, float* db, double* scratch /* 512 * C doubles */, hipStream_t stream);
-// QKVAttention backward: qkv [B][N][3C] (q | k | v), da [B][N][C] -> dqkv [B][N][3C]; p, dp: scratch [B * C / 64][N][N] floats each
-// flash-style (default): stats = B * heads * N * 2 floats of scratch; the GEMM form below (CDDPM_ATTN_BWD=gemm) materialises p, dp [B heads][N][N]
+// QKVAttention backward (attention.hip, flash-style): qkv [B][N][3C] (q | k | v), da [B][N][C] -> dqkv [B][N][3C];
+// stats = B * heads * N * 2 floats of scratch
 void launch_attention_backward_flash(const float* qkv, const float* da, float* dqkv, float* stats, int B, int N, int C, hipStream_t stream);
-void launch_attention_backward(const float* qkv, const float* da, float* dqkv, float* p, float* dp, int B, int N, int C,
-                               hipStream_t stream);
 // backward of y = [SiLU](x) W^T + b: x [M][K], W [N][K], dy [M][N] -> dW [N][K], db [N] (or nullptr), dx [M][K] (or nullptr);
 // a_scratch [M][K] when silu_in
 size_t linear_backward_scratch_floats(int M, int N, int K, int silu_in);      // floats of a_scratch

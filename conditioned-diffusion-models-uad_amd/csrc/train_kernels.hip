@@ -15,8 +15,8 @@
 //       dx = r_g (du g' - m1 - x^ m2)
 //   Two passes over (x, da): gn_bwd_partial_kernel (per-channel S1, S2 over pixel splits, fp64 inside) and gn_bwd_apply_kernel
 //   (elementwise dx), with gn_bwd_finalize_kernel (tiny) in between. The statistics (mu, r) are an input: the forward's.
-// * conv wgrad (below): a pixel-contraction GEMM on the fp32 MFMA with the activation recomputed while staging.
-// Further down: the weight-gradient families, the batched fp32 GEMM and the linear backward, resampling backward, the one-channel
+// * conv wgrad (below): a pixel-contraction GEMM on the 16-bit matrix pipe (fp16 operand terms) with the activation recomputed while
+//   staging. Further down: the batched fp32 GEMM and the linear backward, resampling backward, the one-channel
 // convolutions' gradients, the loss, Adam. (Attention backward: attention.hip; the encoder: encoder_train.hip; sequencing: training.py.)
 #include <atomic>
 #include "kernels.h"
@@ -241,17 +241,8 @@ void launch_gn_silu_backward(const float* x, const float* x1, int C0, float* dx1
 // ------------------------------------------------------------------------------------------------------------------
 // conv wgrad: dW[co][ci][ky][kx] = sum_{b,y,x} dy[b,y,x,co] * a[b, y + ky - 1, x + kx - 1, ci],  a = act(GroupNorm(x)) recomputed
 // from the conv's input x and the forward's coefficient planes while staging (the activated tensor was never stored).
-//
-// GEMM view: M = Cout, N = 32 input channels x 9 taps, K = pixels. The contraction runs over PIXELS, and both operands are NHWC
-// ([pixel][channel]); the fp32 MFMA v_mfma_f32_32x32x2_f32 takes ONE float per lane for each operand -- lanes 0..31 the 32 rows /
-// columns at k = 0, lanes 32..63 at k = 1 -- so a fragment is one ds_read_b32 of 32 consecutive channels of one pixel (conflict
-// free), a tap is a row offset in the patch, and no transposed image of either tensor is needed; products are exact fp32 (the
-// gradients then carry fp32 accuracy like autograd's; config 5's bf16 autocast can later use the 16-bit pipe the way the forward
-// split kernels do).
-// Workgroup = 4 waves = (32-channel block of the 64 output channels) x (taps 0..4 | 5..8); it walks a contiguous range of
-// 4 x 32-pixel tiles: per tile the dy tile [128 px][64 co] and the activated patch [6 x 34 px][32 ci] go to LDS (59 KB: two
-// workgroups per CU), 64 k-steps of 2 pixels, chains folded per tile into a running total (the three-level accumulation of the
-// forward kernels). P workgroups per (co block, ci chunk) write P partial tiles; wgrad_reduce_kernel adds them in fixed order.
+// GEMM view: M = Cout, N = input channels x taps, K = pixels. P workgroups per (co block, ci chunk) write P partial tiles;
+// conv_wgrad_reduce_kernel adds them in fixed order.
 // ------------------------------------------------------------------------------------------------------------------
 typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -269,109 +260,8 @@ struct WgradArgs {
 
 __device__ __forceinline__ float silu_t(float v) { return v * sigmoid_t(v); }
 
-// TAPS = 9: 3x3, padding 1, 32 input channels per workgroup, wave = (co 32-block, taps 0..4 | 5..8)
-// TAPS = 1: 1x1 (skip_connection, qkv, proj_out), 64 input channels per workgroup, wave = (co 32-block, ci 32-block)
-template <int TAPS>
-__global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
-    constexpr int TR = 4;                                   // tile rows
-    constexpr int PAD = (TAPS == 9) ? 1 : 0;
-    constexpr int PW = 32 + 2 * PAD, PH = TR + 2 * PAD, NPIX = PW * PH;
-    constexpr int CK = (TAPS == 9) ? 32 : 64;               // input channels per workgroup
-    constexpr int NT = (TAPS == 9) ? 5 : 1;                 // accumulators per wave
-    __shared__ float dys[TR * 32 * 64];                     // [128 px][64 co]
-    __shared__ float xs[NPIX * CK];                         // [204 px][32 ci] | [128 px][64 ci]
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int cw = wave & 1, tg = wave >> 1;                // co 32-block; tap group | ci 32-block (wave-uniform)
-    const int Cin = a.C0 + a.C1;
-    const int nchunk = Cin / CK, ncb = a.Cout >> 6;
-    int bid = blockIdx.x;
-    const int chunk = bid % nchunk; bid /= nchunk;
-    const int cb = bid % ncb;
-    const int p = bid / ncb;
-    const int tilesX = (a.W + 31) >> 5, tilesY = a.H / TR;
-    const int ntile = a.B * tilesY * tilesX;
-    const int t0 = (int)((long long)ntile * p / a.P), t1 = (int)((long long)ntile * (p + 1) / a.P);
-    const int tapbase = (TAPS == 9) ? tg * 5 : 0, ntap = (TAPS == 9) ? (tg ? 4 : 5) : 1;
-    // source tensor of this chunk (a chunk never straddles the two sources: C0 is a multiple of 64)
-    const int ch0 = chunk * CK;
-    const float* xsrc = (ch0 < a.C0) ? a.x0 : a.x1;
-    const int Cs = (ch0 < a.C0) ? a.C0 : a.C1, cs0 = (ch0 < a.C0) ? ch0 : ch0 - a.C0;
-    wg_f32x16 acc[NT], tot[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; tot[i][r] = 0.f; }
-    const int li = lane & 31, lh = lane >> 5;
-    for (int tile = t0; tile < t1; ++tile) {
-        const int tx = tile % tilesX, ty = (tile / tilesX) % tilesY, b = tile / (tilesX * tilesY);
-        const int y0 = ty * TR, x0 = tx * 32;
-        __syncthreads();                          // the previous tile's fragments have been read
-        // dy tile: 128 px x 64 co = 2048 float4
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = tid + 256 * i, q = e >> 4, c4 = e & 15;
-            const int y = y0 + (q >> 5), x = x0 + (q & 31);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (x < a.W) v = *reinterpret_cast<const float4*>(a.dy + ((size_t)(b * a.H + y) * a.W + x) * a.Cout + cb * 64 + 4 * c4);
-            *reinterpret_cast<float4*>(dys + q * 64 + 4 * c4) = v;
-        }
-        // activated patch: NPIX px x CK ci
-        for (int e = tid; e < NPIX * (CK / 4); e += 256) {
-            const int q = e / (CK / 4), c4 = e % (CK / 4);
-            const int pr = q / PW, pc = q - pr * PW;
-            const int y = y0 + pr - PAD, x = x0 + pc - PAD;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
-                const size_t sp = a.up ? ((size_t)(b * (a.H >> 1) + (y >> 1)) * (a.W >> 1) + (x >> 1)) : ((size_t)(b * a.H + y) * a.W + x);
-                v = *reinterpret_cast<const float4*>(xsrc + sp * Cs + cs0 + 4 * c4);
-                if (a.coef) {
-                    const size_t pl = (size_t)a.B * Cin, bc = (size_t)b * Cin + ch0 + 4 * c4;
-                    const float4 m = *reinterpret_cast<const float4*>(a.coef + bc), g = *reinterpret_cast<const float4*>(a.coef + pl + bc);
-                    const float4 d = *reinterpret_cast<const float4*>(a.coef + 2 * pl + bc);
-                    v.x = (v.x - m.x) * g.x + d.x; v.y = (v.y - m.y) * g.y + d.y; v.z = (v.z - m.z) * g.z + d.z; v.w = (v.w - m.w) * g.w + d.w;
-                }
-                if (a.silu) { v.x = silu_t(v.x); v.y = silu_t(v.y); v.z = silu_t(v.z); v.w = silu_t(v.w); }
-            }
-            *reinterpret_cast<float4*>(xs + q * CK + 4 * c4) = v;
-        }
-        __syncthreads();
-        // 64 k-steps of two pixels (x, x + 1 of one row); A = dy[px][co], B = act[px + tap][ci]
-#pragma unroll 4
-        for (int k = 0; k < 64; ++k) {
-            const int py = k >> 4, pxx = (k & 15) * 2 + lh;
-            const float av = dys[(py * 32 + pxx) * 64 + cw * 32 + li];
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                if (i < ntap) {
-                    const int t = tapbase + i, ky = (TAPS == 9) ? t / 3 : 0, kx = (TAPS == 9) ? t - 3 * ky : 0;
-                    const float bv = xs[((py + ky) * PW + pxx + kx) * CK + ((TAPS == 9) ? 0 : tg * 32) + li];
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            tot[i] += acc[i];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        }
-    }
-    // partial tile: [64 co][TAPS][CK ci]; D row = co = (r & 3) + 8 (r >> 2) + 4 lh, column = ci = li
-    float* o = a.part + ((((size_t)p * ncb + cb) * nchunk + chunk) * 64) * TAPS * CK;
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-        if (i < ntap) {
-            const int t = tapbase + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = cw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                o[((size_t)co * TAPS + t) * CK + ((TAPS == 9) ? 0 : tg * 32) + li] = tot[i][r];
-            }
-        }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// conv wgrad on the 16-bit matrix pipe (the default): the same contraction, products formed like the forward kernel's -- both operands
+// conv wgrad on the 16-bit matrix pipe: the same contraction, products formed like the forward kernel's -- both operands
 // split into NS fp16 terms (NS = 2: hi . hi + hi . mid + mid . hi, fp32-grade; NS = 1: plain fp16 operands with fp32 accumulation,
 // the arithmetic of the reference trainer's `precision: 16`), v_mfma_f32_16x16x32_f16.
 //
@@ -755,8 +645,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_img_kernel(const WgradImgAr
                     o[((size_t)(cw * 32 + i * 16 + 4 * g + e) * TAPS + t) * CK + (cj * NJ + j) * 16 + r] = acc[i][j][t][e];
 }
 
-// convolution weight-gradient family: CDDPM_WGRAD = h3 (default: fp16 two-term split, fp32-grade), h1 (plain fp16 operands), f32 (the
-// fp32-MFMA kernel above)
 // training arithmetic of the process: 32 = fp32-grade (two-term fp16 splits), 16 = plain fp16 operands with fp32 accumulation (the reference
 // trainer's `precision: 16`). Initial value from CDDPM_TRAIN_PRECISION, changed by cddpm_set_train_precision (the DDPM_2D mirror passes the
 // Trainer's precision).
@@ -774,14 +662,6 @@ int set_train_precision(int bits) {
     const int prev = train_precision();
     g_train_precision.store(bits == 16 ? 16 : 32, std::memory_order_relaxed);
     return prev;
-}
-int wgrad_mode() {
-    static const int forced = [] {
-        const char* e = getenv("CDDPM_WGRAD");
-        return !e ? -1 : !strcmp(e, "f32") ? 0 : !strcmp(e, "h1") ? 1 : 2;
-    }();
-    if (forced >= 0) return forced;
-    return train_precision() == 16 ? 1 : 2;         // precision 16: plain fp16 operands everywhere in the training step
 }
 
 // dW[co][ci][t] (PyTorch layout) = sum over the P partial tiles in the order of p
@@ -877,12 +757,11 @@ static void bias_grad_run(const float* dy, long long npix, int C, float* db, dou
 
 int conv_wgrad_parts(int B, int H, int W, int Cin, int Cout, int taps) {
     // enough workgroups for two per CU, at most one tile each, at least 1
-    // mirrors launch_conv_wgrad's choice of kernel: the split families tile (8 samples) x (2 x 8 pixels); chunks of 32 input channels
-    // (3x3, and the single-pass 1x1 fallback) or 64 (1x1 over images, and the fp32 family's 1x1)
-    const bool f32k = wgrad_mode() == 0;
-    const bool img = !f32k && (taps == 9 || Cin % 64 == 0);
-    const int ntile = !f32k ? ((B + 7) / 8) * ((H + 1) / 2) * ((W + 7) / 8) : B * (H / 4) * ((W + 31) / 32);
-    const int per = (Cout / 64) * (Cin / ((taps == 9 || (!f32k && !img)) ? 32 : 64));
+    // mirrors launch_conv_wgrad's choice of kernel: tiles of (8 samples) x (2 x 8 pixels); chunks of 32 input channels (3x3, and the
+    // single-pass 1x1 fallback) or 64 (1x1 over images)
+    const bool img = (taps == 9 || Cin % 64 == 0);
+    const int ntile = ((B + 7) / 8) * ((H + 1) / 2) * ((W + 7) / 8);
+    const int per = (Cout / 64) * (Cin / ((taps == 9 || !img) ? 32 : 64));
     int P = (512 + per - 1) / per;
     if (P > ntile) P = ntile;
     if (P > 64) P = 64;
@@ -893,12 +772,11 @@ int conv_wgrad_parts(int B, int H, int W, int Cin, int Cout, int taps) {
 
 // scratch of the two-pass 3x3 family beyond the partial tiles: the two k-images, in 16-byte units (0: this call does not use them)
 size_t conv_wgrad_image_units(int B, int H, int W, int Cin, int Cout, int taps) {
-    const int mode = wgrad_mode();
-    if (mode == 0 || (taps == 1 && Cin % 64)) return 0;
+    if (taps == 1 && Cin % 64) return 0;
     // + the bias gradient's partial rows written by the dy image pass: [(HW / 8 rounded up) * G][Cout] floats
     const size_t bias_rows = (size_t)((H * W + 7) / 8) * ((B + 7) / 8);
     const size_t bias_units = ((bias_rows + (bias_rows + 127) / 128) * Cout + 3) / 4;       // + the second-level partial rows behind them
-    return (size_t)(mode == 2 ? 2 : 1) * ((B + 7) / 8) * (size_t)(Cin + Cout) * H * W + bias_units;
+    return (size_t)(train_precision() == 16 ? 1 : 2) * ((B + 7) / 8) * (size_t)(Cin + Cout) * H * W + bias_units;
 }
 
 void launch_conv_wgrad(const float* x0, int C0, const float* x1, int C1, const float* coef, int silu, int up, const float* dy, int B, int H,
@@ -906,12 +784,12 @@ void launch_conv_wgrad(const float* x0, int C0, const float* x1, int C1, const f
     WgradArgs a;
     a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.coef = coef; a.silu = silu; a.up = up; a.dy = dy; a.B = B; a.H = H; a.W = W; a.Cout = Cout;
     a.part = part; a.P = P;
-    const int Cin = C0 + C1, mode = wgrad_mode();
+    const int Cin = C0 + C1;
+    const int NS = train_precision() == 16 ? 1 : 2;     // fp16 terms per operand: plain fp16 (precision 16) or the two-term split
     const int G = (B + 7) / 8;
     int CK = 32;
-    if (mode != 0 && (taps == 9 || Cin % 64 == 0)) {
+    if (taps == 9 || Cin % 64 == 0) {
         // pass 1: the two k-images; pass 2: the GEMM over them
-        const int NS = mode == 2 ? 2 : 1;
         uint4* aimg = static_cast<uint4*>(images);
         uint4* dimg = aimg + (size_t)NS * G * Cin * H * W;
         ImageArgs ia;
@@ -937,14 +815,9 @@ void launch_conv_wgrad(const float* x0, int C0, const float* x1, int C1, const f
             if (NS == 2) hipLaunchKernelGGL((conv_wgrad_img_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, w);
             else         hipLaunchKernelGGL((conv_wgrad_img_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, w);
         }
-    } else if (mode == 0) {
-        CK = taps == 9 ? 32 : 64;
-        const unsigned grid = (unsigned)(P * (Cout / 64) * (Cin / CK));
-        if (taps == 9) hipLaunchKernelGGL(conv_wgrad_kernel<9>, dim3(grid), dim3(256), 0, stream, a);
-        else           hipLaunchKernelGGL(conv_wgrad_kernel<1>, dim3(grid), dim3(256), 0, stream, a);
     } else {
         const unsigned grid = (unsigned)(P * (Cout / 64) * (Cin / 32));
-        if (mode == 1) hipLaunchKernelGGL((conv_wgrad_x_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, a, G);
+        if (NS == 1) hipLaunchKernelGGL((conv_wgrad_x_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, a, G);
         else           hipLaunchKernelGGL((conv_wgrad_x_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, a, G);
     }
     const long long n = (long long)Cout * Cin * taps;
@@ -957,8 +830,7 @@ void launch_conv_wgrad(const float* x0, int C0, const float* x1, int C1, const f
 
 // ------------------------------------------------------------------------------------------------------------------
 // Batched fp32 GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 products): C[z] = alpha * op(A[z]) . op(B[z]), arbitrary M, N, K and
-// strides, two-level batch index z = (z0, z1). Used by the attention backward (five N x N x 64 products per head) and by the
-// backward of the embedding linears. 64 x 64 tiles, 4 waves (2 x 2 of 32 x 32), K steps of 32 through k-major LDS tiles
+// strides, two-level batch index z = (z0, z1). Used by the backward of the embedding linears. 64 x 64 tiles, 4 waves (2 x 2 of 32 x 32), K steps of 32 through k-major LDS tiles
 // (operand fragment = one ds_read_b32 of 32 consecutive rows / columns at one k). Correctness-first: these products are < 2 % of a
 // training step's FLOPs.
 // ------------------------------------------------------------------------------------------------------------------
@@ -1022,84 +894,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs g) {
 
 void launch_gemm_f32(const GemmArgs& g, int nz, hipStream_t stream) {
     hipLaunchKernelGGL(gemm_f32_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64, nz), dim3(256), 0, stream, g);
-}
-
-// row softmax in place: one workgroup per row of an [rows][n] matrix
-__global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ s, int n) {
-    __shared__ float red[256];
-    float* row = s + (size_t)blockIdx.x * n;
-    const int tid = threadIdx.x;
-    float mx = -3.0e38f;
-    for (int i = tid; i < n; i += 256) mx = fmaxf(mx, row[i]);
-    red[tid] = mx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
-    mx = red[0];
-    __syncthreads();
-    float sum = 0.f;
-    for (int i = tid; i < n; i += 256) { const float e = __expf(row[i] - mx); row[i] = e; sum += e; }
-    red[tid] = sum;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-    const float inv = 1.0f / red[0];
-    for (int i = tid; i < n; i += 256) row[i] *= inv;
-}
-
-// dS = P o (dP - rowsum(dP o P)) in place of dP: one workgroup per row
-__global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const float* __restrict__ p, float* __restrict__ dp, int n) {
-    __shared__ float red[256];
-    const float* pr = p + (size_t)blockIdx.x * n;
-    float* dr = dp + (size_t)blockIdx.x * n;
-    const int tid = threadIdx.x;
-    float d = 0.f;
-    for (int i = tid; i < n; i += 256) d += pr[i] * dr[i];
-    red[tid] = d;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-    d = red[0];
-    for (int i = tid; i < n; i += 256) dr[i] = pr[i] * (dr[i] - d);
-}
-
-// QKVAttention backward (src/models/modules/OpenAI_Unet.py:457-476, new attention order): qkv NHWC [B][N][3C] = (q | k | v), heads =
-// contiguous groups of 64 channels; w = softmax((q s)^T (k s)), s = 64^-1/4; a = w v. Given da [B][N][C] writes dqkv [B][N][3C].
-// p, dp: scratch [B * heads][N][N] each (the probabilities are recomputed, not stored by the forward).
-void launch_attention_backward(const float* qkv, const float* da, float* dqkv, float* p, float* dp, int B, int N, int C,
-                               hipStream_t stream) {
-    const int heads = C / 64, nz = B * heads;
-    const long long row = 3LL * C, NN = (long long)N * N;
-    GemmArgs g;
-    g.nz1 = heads;
-    // S = Q K^T / 8
-    g.A = qkv; g.lda = row; g.transA = 0; g.sA0 = (long long)N * row; g.sA1 = 64;
-    g.B = qkv + C; g.ldb = row; g.transB = 1; g.sB0 = (long long)N * row; g.sB1 = 64;
-    g.C = p; g.ldc = N; g.sC0 = heads * NN; g.sC1 = NN;
-    g.M = N; g.N = N; g.K = 64; g.alpha = 0.125f;
-    launch_gemm_f32(g, nz, stream);
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((long long)nz * N)), dim3(256), 0, stream, p, N);
-    // dV = P^T dA
-    g.A = p; g.lda = N; g.transA = 1; g.sA0 = heads * NN; g.sA1 = NN;
-    g.B = da; g.ldb = C; g.transB = 0; g.sB0 = (long long)N * C; g.sB1 = 64;
-    g.C = dqkv + 2 * C; g.ldc = row; g.sC0 = (long long)N * row; g.sC1 = 64;
-    g.M = N; g.N = 64; g.K = N; g.alpha = 1.0f;
-    launch_gemm_f32(g, nz, stream);
-    // dP = dA V^T
-    g.A = da; g.lda = C; g.transA = 0; g.sA0 = (long long)N * C; g.sA1 = 64;
-    g.B = qkv + 2 * C; g.ldb = row; g.transB = 1; g.sB0 = (long long)N * row; g.sB1 = 64;
-    g.C = dp; g.ldc = N; g.sC0 = heads * NN; g.sC1 = NN;
-    g.M = N; g.N = N; g.K = 64; g.alpha = 1.0f;
-    launch_gemm_f32(g, nz, stream);
-    hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((unsigned)((long long)nz * N)), dim3(256), 0, stream, p, dp, N);
-    // dQ = dS K / 8
-    g.A = dp; g.lda = N; g.transA = 0; g.sA0 = heads * NN; g.sA1 = NN;
-    g.B = qkv + C; g.ldb = row; g.transB = 0; g.sB0 = (long long)N * row; g.sB1 = 64;
-    g.C = dqkv; g.ldc = row; g.sC0 = (long long)N * row; g.sC1 = 64;
-    g.M = N; g.N = 64; g.K = N; g.alpha = 0.125f;
-    launch_gemm_f32(g, nz, stream);
-    // dK = dS^T Q / 8
-    g.A = dp; g.lda = N; g.transA = 1;
-    g.B = qkv; g.ldb = row; g.transB = 0; g.sB0 = (long long)N * row; g.sB1 = 64;
-    g.C = dqkv + C;
-    launch_gemm_f32(g, nz, stream);
 }
 
 // y = act(x) W^T + b (torch.nn.Linear, optional SiLU on the input: emb_layers = Sequential(SiLU, Linear), OpenAI_Unet.py:201-207):

@@ -274,7 +274,7 @@ class CddpmEngine:
         return x
 
     def set_accumulation_switch(self, t_switch: int):
-        """reverse steps t >= t_switch use the faster two-level-accumulation convolution plan (include/cddpm.h); default 200"""
+        """reverse steps t >= t_switch use the faster two-level-accumulation convolution plan (include/cddpm.h); default off (2^30)"""
         self._ck(self.lib.cddpm_set_accumulation_switch(self._h, int(t_switch)), "cddpm_set_accumulation_switch")
 
     def set_clip_denoised(self, on: bool):

@@ -13,6 +13,15 @@
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream); all work is
  *     enqueued on it, nothing synchronises with the host inside forward/reverse calls.
  *   - one handle per device; a handle is not thread-safe.
+ *
+ * Environment variables the library reads
+ *   - CDDPM_CONV: convolution family and packed weight format. h3 or unset = fp16 two-term split (default), x6 = bf16
+ *     three-term split, f32 = fp32 MFMA (see cddpm_pack_conv_weights).
+ *   - CDDPM_NB2: 256-cout workgroups of the default family. Unset = where the plan takes them (cddpm_set_accumulation_switch,
+ *     cddpm_op_conv_packed); 0 = never; force = wherever the kernel can, in every entry point and at any geometry.
+ *   - CDDPM_GRAPH: 1 = cddpm_reverse / cddpm_reverse_range (>= 5 steps, not while profiling) replay each step as a captured
+ *     hipGraph instead of launching its kernels: bit-identical, not faster.
+ *   - CDDPM_TRAIN_PRECISION: 16 = initial training arithmetic plain fp16 operands; unset = 32 (cddpm_set_train_precision).
  */
 #ifndef CDDPM_H
 #define CDDPM_H
@@ -115,7 +124,8 @@ int cddpm_reverse(cddpm_handle h, float* img_inout_dev, const float* noise_dev, 
  *   rms        6.95e-6  8.02e-6  9.08e-6  1.09e-5  1.02e-5        (the reference against itself: 1.02e-4 / 5.6e-6)
  * -- the extra rounding noise of ANY part of the chain survives to the end (there is no late switch step that hides it), which is why
  * the default keeps three-level accumulation on every step. A function of t alone: a slice's bits do not depend on its batch.
- * Single forwards (cddpm_unet_forward, cddpm_ddim_step, the training operators) always use the three-level kernel. */
+ * Single forwards (cddpm_unet_forward, cddpm_ddim_step) use the three-level kernel. cddpm_op_conv_packed plans per call instead: it
+ * takes the 256-cout form wherever the call itself has >= 512 workgroups of the 128-cout form (CDDPM_NB2=0 disables it). */
 int cddpm_set_accumulation_switch(cddpm_handle h, int t_switch);
 
 /* `clip_denoised` of p_sample / ddim_sample (src/models/modules/cond_DDPM.py:433, :467): on (the reference's default, and the
@@ -228,14 +238,6 @@ int cddpm_op_conv_gn(cddpm_handle h, const float* src0_dev, int C0, const float*
                      const float* gamma_host, const float* beta_host, float* out_dev, float* coef_dev, int B, int H, int W,
                      void* stream);
 
-/* micro-benchmark of the fused conv kernel on device-generated N(0,1) data (no result check): average ms per
- * launch over `iters` launches; res_mode 0 none, 1 same resolution, 2 half resolution; skipC = channels of a fused
- * 1x1 skip_connection segment (0 = none). stamps_out (64 x uint64, may be NULL) receives per-wave phase cycle sums
- * in diagnostic builds (-DCDDPM_STAMPS), zeros otherwise. */
-int cddpm_op_conv_bench(cddpm_handle h, int C0, int C1, int Cout, int ksize, int B, int H, int W, int use_coef,
-                        int silu, int upsample, int res_mode, int skipC, int iters, double* ms_out,
-                        uint64_t* stamps_out);
-
 /* standalone GroupNorm(32) statistics + coefficient kernel pair: coef_dev [3][B][C] (mean, a, d) with
  * a = rstd*gamma*(1+scale), d = beta*(1+scale)+shift; film_dev = [B][2C] (scale | shift) or NULL. */
 int cddpm_op_gn_coef(cddpm_handle h, const float* src0_dev, int C0, const float* src1_dev, int C1,
@@ -269,18 +271,18 @@ int cddpm_op_conv_dgrad(cddpm_handle h, const float* dy_dev, int Cout, const flo
 /* dL/d(weight), dL/d(bias) of y = Conv2d(k in {1,3}, padding k/2) applied to a = act(cat[x0, x1]) with act(v) = silu?((v - mean) *
  * a + d) as in cddpm_op_conv (coef_dev [3][B][C0 + C1] or NULL): dw_dev [Cout,Cin,k,k] (PyTorch layout) = sum over batch and pixels of
  * dy (x) a, db_dev [Cout] = sum of dy (may be NULL). x0_dev [B,H,W,C0], x1_dev [B,H,W,C1] or NULL (C1 = 0), dy_dev [B,H,W,Cout];
- * C0 + C1 a multiple of 32, C0 of 32 when C1 > 0, Cout of 64 (the CDDPM_WGRAD=f32 family: 64 for k = 1, C0 of 64, H of 4). upsample != 0:
+ * C0 + C1 a multiple of 32, C0 of 32 when C1 > 0, Cout of 64. upsample != 0:
  * the conv input is the nearest x2 upsampling of act(x0) (up ResBlocks, OpenAI_Unet.py:289-293): x0_dev is [B,H/2,W/2,C0], H and W even.
- * Arithmetic (environment CDDPM_WGRAD): h3 (default) products from two-term fp16 splits of both operands on v_mfma_f32_16x16x32_f16,
- * fp32 accumulation -- the forward kernel's arithmetic; h1 plain fp16 operands; f32 v_mfma_f32_32x32x2_f32. */
+ * Arithmetic (cddpm_set_train_precision): 32 = products from two-term fp16 splits of both operands on v_mfma_f32_16x16x32_f16, fp32
+ * accumulation -- the forward kernel's arithmetic; 16 = plain fp16 operands. */
 int cddpm_op_conv_wgrad(cddpm_handle h, const float* x0_dev, int C0, const float* x1_dev, int C1, const float* coef_dev, int silu,
                         int upsample, const float* dy_dev, int Cout, int ksize, float* dw_dev, float* db_dev, int B, int H, int W,
                         void* stream);
 /* db_dev[C] = sum over the npix rows of dy_dev [npix][C] (bias gradient of a convolution) */
 int cddpm_op_bias_grad(cddpm_handle h, const float* dy_dev, int64_t npix, int C, float* db_dev, void* stream);
 /* backward of the attention core QKVAttention (src/models/modules/OpenAI_Unet.py:457-476): qkv_dev [B,N,3C] (q | k | v, heads of 64
- * channels), da_dev [B,N,C] = dL/d(output) -> dqkv_dev [B,N,3C]. The probabilities are recomputed (2 x B x C/64 x N x N floats of
- * scratch are allocated for the call). */
+ * channels), da_dev [B,N,C] = dL/d(output) -> dqkv_dev [B,N,3C]. The probabilities are recomputed (flash-style: B x C/64 x N x 2
+ * floats of scratch for the row statistics). */
 int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
                                 void* stream);
 /* backward of torch.nn.Linear behind an optional SiLU, y = [SiLU](x) W^T + b (emb_layers / time_embed / label_emb,
@@ -349,7 +351,7 @@ int cddpm_op_adam_guarded(cddpm_handle h, float* p_dev, const float* g_dev, floa
  * (4 * cddpm_packed_conv_bytes(Cout, Cin, 4) bytes; the class sums can reach 4 max|w|). Bit-identical to the host packer for the same
  * exponent. Default convolution family only.
  * Environment CDDPM_TRAIN_PRECISION=16 (read once per process): cddpm_op_conv_packed multiplies plain fp16 operands (the hi terms of the
- * images only, fp32 accumulation) and cddpm_op_conv_wgrad defaults to its h1 family -- the arithmetic of the reference trainer's precision 16.
+ * images only, fp32 accumulation) and so does cddpm_op_conv_wgrad -- the arithmetic of the reference trainer's precision 16.
  * The reconstruction entry points (cddpm_reverse, cddpm_unet_forward, ...) are not affected.
  * cddpm_op_conv_packed: cddpm_op_conv / cddpm_op_conv_skip on such images: out = conv_k(act(cat[src0, src1])) [+ conv1x1(skip)] + bias
  * [+ res]; bias_dev NULL = none; skip_dev NULL = no skip segment (its image shares scale_exp); folded_up: src0 is at H/2 x W/2. */

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""A/B micro-benchmark of the fused conv kernel across library builds (guide rule: compare variants on one
-device, random data). Build variants in the container first:
-    python tools/conv_ab.py --build base: stamps:CDDPM_STAMPS accsilu:CDDPM_ACCURATE_SILU
-then on the GPU box:
-    python tools/conv_ab.py --run base stamps accsilu
-Each variant runs in its own process (CDDPM_LIB selects the .so); shapes are the UNet's layers at B=64."""
-import ctypes as C
+"""Interleaved A/B timing of the fused convolution (default fp16-split family) across library builds, on one device with random
+data. Build a side-by-side library in the container first, e.g. build.build_lib(tag="base") -> csrc/libcddpm_hip_base.so, then on
+the GPU box:
+    python tools/conv_ab.py --run base prod prod+nb1 prod+nb2
+A variant is LIB[+OPT]: LIB = "prod" (csrc/libcddpm_hip.so) or a tag; OPT nb1 / nb2 = CDDPM_NB2=0 / force (256-cout workgroups off /
+wherever the kernel can). Each variant runs in its own process (CDDPM_LIB selects the .so) through the product entry points:
+cddpm_op_pack_conv once, then cddpm_op_conv_packed timed between events. Shapes are the UNet's layers at B=64 (AB_BATCH)."""
 import importlib
 import json
 import os
@@ -32,108 +32,75 @@ SHAPES = [
     ("conv 256>256 @32", 256, 0, 256, 3, 32, 32, 1, 1, 0, 0, 0),
     ("cat conv1 384>128 @128", 256, 128, 128, 3, 128, 128, 1, 1, 0, 0, 0),
 ]
-PHASES = ["prologue", "patch stage", "weight stage", "mfma compute", "chunk fold", "epilogue"]
-FINE = ["chunk: wait vmcnt", "chunk: barrier A", "patch transform+store", "chunk: barrier B", "stage end: wait vmcnt", "stage end: barrier",
-        "issue + MFMA + fold", "prologue + epilogue"]
-EPI = ["prologue", "main loop", "residual requests", "barrier", "transpose 0", "stores+stats 0", "transpose 1", "stores+stats 1"]
-PHASES8 = ["prologue", "chunk barrier", "patch store", "weight store", "stage barrier", "compute", "fold", "epilogue"]
 
 
 def child(B, iters):
+    import torch
     lib = importlib.import_module(PKG + "._lib").load_library()
     eng = importlib.import_module(PKG + ".engine")
     e = eng.CddpmEngine(timesteps=10, max_batch=1, max_h=32, max_w=32)
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device="cuda").manual_seed(1234)
+    rnd = lambda *shape, scale=1.0: torch.randn(*shape, device="cuda", generator=g) * scale
+    p = lambda t: None if t is None else t.data_ptr()
+
+    def pack(Cout, Cin, k, mode, wexp):
+        w = rnd(Cout, Cin, k, k, scale=0.01)        # w * 2^wexp (and the folded class sums) stay far inside the fp16 range
+        taps = 4 if mode == 2 else k * k
+        img = torch.empty(lib.cddpm_packed_conv_bytes(Cout, Cin, taps) * (4 if mode == 2 else 1), dtype=torch.uint8, device="cuda")
+        assert lib.cddpm_op_pack_conv(e._h, p(w), Cout, Cin, k, mode, wexp, p(img), s) == 0, lib.cddpm_last_error(e._h)
+        return img
+
     out = []
     for (name, C0, C1, Cout, k, H, W, coef, silu, up, res, sk) in SHAPES:
-        ms = C.c_double()
-        st = (C.c_uint64 * 64)()
-        rc = lib.cddpm_op_conv_bench(e._h, C0, C1, Cout, k, B, H, W, coef, silu, up, res, sk, iters, C.byref(ms), st)
-        assert rc == 0, lib.cddpm_last_error(e._h)
-        flops = 2.0 * B * H * W * Cout * ((C0 + C1) * k * k + sk)
-        row = {"shape": name, "ms": ms.value, "tflops": flops / ms.value / 1e9}
-        tot = [sum(st[w * 8 + i] for w in range(4)) for i in range(6)]
-        if st[41]:
-            row["clock_GHz"] = round(st[40] / st[41] * 0.1, 3)
-        if os.environ.get("CDDPM_CONV_WS") == "1" and sum(st[:4]):
-            row["ws_cycles"] = {"matrix work": int(st[0]), "matrix barrier": int(st[1]), "staging work": int(st[2]), "staging barrier": int(st[3])}
-        if sum(st[48:56]) and sum(st[:8]):
-            tt = [st[i] for i in range(8)]
-            names = ("c:mfma k0", "c:frag reads k1", "c:patch entry", "c:mfma k1", "s:fold", "s:weight write", "s:requests", "s:frag prefetch")
-            row["pp_fine"] = {k: round(v / max(1, sum(tt)), 3) for k, v in zip(names, tt)}
-        if sum(st[48:56]):
-            for g in (0, 1):
-                tt = [st[48 + 4 * g + i] for i in range(4)]
-                row["pp_group%d" % g] = {k: round(v / max(1, sum(tt)), 3) for k, v in zip(("compute", "staging", "wait after compute", "wait after staging"), tt)}
-        if os.environ.get("AB_EPI") and sum(st[:32]):
-            tt = [sum(st[w * 8 + i] for w in range(4)) for i in range(8)]
-            row["fine"] = {p: round(t / max(1, sum(tt)), 4) for p, t in zip(EPI, tt)}
-        elif os.environ.get("AB_FINE") and sum(st[:32]):
-            tt = [sum(st[w * 8 + i] for w in range(4)) for i in range(8)]
-            row["fine"] = {p: round(t / max(1, sum(tt)), 4) for p, t in zip(FINE, tt)}
-        elif os.environ.get("AB_PHASES8") and sum(st[:16]):
-            for wv in (0, 1):
-                tt = [st[wv * 8 + i] for i in range(8)]
-                row["wave%d" % (wv * 4)] = {p: round(t / max(1, sum(tt)), 3) for p, t in zip(PHASES8, tt)}
-        elif sum(tot):
-            row["phase_share"] = {p: round(t / sum(tot), 4) for p, t in zip(PHASES, tot)}
-        out.append(row)
+        h, w = (H // 2, W // 2) if up else (H, W)
+        wexp = 16
+        x0, x1 = rnd(B, h, w, C0), (rnd(B, h, w, C1) if C1 else None)
+        cf = rnd(3, B, C0 + C1) if coef else None
+        img = pack(Cout, C0 + C1, k, 2 if up else 0, wexp)
+        skip, skimg = (rnd(B, H, W, sk), pack(Cout, sk, 1, 0, wexp)) if sk else (None, None)
+        bias, r = rnd(Cout), (rnd(B, H, W, Cout) if res else None)
+        y = torch.empty(B, H, W, Cout, device="cuda")
+        run = lambda: lib.cddpm_op_conv_packed(e._h, p(x0), C0, p(x1), C1, p(cf), silu, up, p(img), wexp, p(bias), Cout, k, p(r), 0,
+                                               p(skip), sk, None, 0, p(skimg), p(y), None, B, H, W, s)
+        assert run() == 0, lib.cddpm_last_error(e._h)        # warm-up
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            run()
+        e1.record()
+        e1.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        flops = 2.0 * B * H * W * Cout * ((C0 + C1) * k * k + sk)        # nominal: the folded upsample multiplies 4/9 of it
+        out.append({"shape": name, "ms": ms, "tflops": flops / ms / 1e9})
+    e.close()
     print(json.dumps(out))
 
 
 def main():
-    if sys.argv[1] == "--build":
-        b = importlib.import_module(PKG + ".build")
-        for spec in sys.argv[2:]:
-            tag, _, rest = spec.partition(":")
-            defs, _, src = rest.partition("@")          # tag:DEF1,DEF2@path/to/alternative_conv_mfma.hip
-            print(b.build_lib(force=True, defines=[d for d in defs.split(",") if d], tag=tag, conv_src=src))
-    elif sys.argv[1] == "--child":
+    if sys.argv[1] == "--child":
         child(int(sys.argv[2]), int(sys.argv[3]))
-    elif sys.argv[1] == "--run":
-        B = int(os.environ.get("AB_BATCH", "64"))
-        rounds = int(os.environ.get("AB_ROUNDS", "2"))
-        res = {}
-        for r in range(rounds):          # interleaved rounds
-            for tag in sys.argv[2:]:
-                lib, _, opt = tag.partition("+")          # "cur+ws": library cur with CDDPM_CONV_WS=1
-                env = dict(os.environ, CDDPM_LIB=os.path.join(CSRC, "libcddpm_hip.so" if lib == "prod" else f"libcddpm_hip_{lib}.so"))
-                if opt in ("nb1", "nb2"):          # 256-cout workgroups (conv_x6.hip, NB = 2) off / on wherever the kernel can
-                    env["CDDPM_NB2"] = "0" if opt == "nb1" else "force"
-                if opt == "ws":
-                    env["CDDPM_CONV_WS"] = "1"
-                if opt in ("f32", "x6", "h3"):
-                    env["CDDPM_CONV"] = opt
-                if opt == "pp":
-                    env["CDDPM_CONV_PP"] = "1"
-                if opt in ("m16", "m32"):
-                    env["CDDPM_M16"] = "1" if opt == "m16" else "0"
-                if opt == "r4":
-                    env["CDDPM_ROWS"] = "4"
-                if opt == "zero":
-                    env["CDDPM_BENCH_ZERO"] = "1"
-                if opt in ("w4", "w8"):
-                    env["CDDPM_CONV_WAVES"] = opt[1]
-                o = subprocess.run([sys.executable, __file__, "--child", str(B), "5"], env=env, capture_output=True, text=True)
-                if o.returncode != 0:
-                    print(tag, "FAILED", o.stderr[-2000:])
-                    continue
-                res.setdefault(tag, []).append(json.loads(o.stdout.strip().splitlines()[-1]))
-        for i, shp in enumerate(SHAPES):
-            print(shp[0])
-            for tag, runs in res.items():
-                ms = [r[i]["ms"] for r in runs]
-                tf = [r[i]["tflops"] for r in runs]
-                line = f"   {tag:10s} ms min {min(ms):8.3f} med {sorted(ms)[len(ms) // 2]:8.3f}  TF max {max(tf):6.1f}"
-                if "phase_share" in runs[0][i]:
-                    line += "  " + json.dumps(runs[0][i]["phase_share"])
-                if "clock_GHz" in runs[0][i]:
-                    line += f"  clock {runs[0][i]['clock_GHz']} GHz"
-                for wk in ("fine", "wave0", "wave4", "pp_group0", "pp_group1", "pp_fine"):
-                    if wk in runs[0][i]:
-                        line += "\n        " + wk + " " + json.dumps(runs[0][i][wk])
-                if "ws_cycles" in runs[0][i]:
-                    line += "  " + json.dumps(runs[0][i]["ws_cycles"])
-                print(line)
+        return
+    assert sys.argv[1] == "--run", __doc__
+    B = int(os.environ.get("AB_BATCH", "64"))
+    rounds = int(os.environ.get("AB_ROUNDS", "2"))
+    res = {}
+    for _ in range(rounds):          # interleaved rounds
+        for tag in sys.argv[2:]:
+            lib, _, opt = tag.partition("+")
+            env = dict(os.environ, CDDPM_LIB=os.path.join(CSRC, "libcddpm_hip.so" if lib == "prod" else f"libcddpm_hip_{lib}.so"))
+            if opt:
+                env["CDDPM_NB2"] = {"nb1": "0", "nb2": "force"}[opt]
+            o = subprocess.run([sys.executable, __file__, "--child", str(B), "5"], env=env, capture_output=True, text=True)
+            if o.returncode != 0:          # stop: nothing more is started on a device a child may have left faulted
+                sys.exit(f"{tag} FAILED (exit {o.returncode}):\n{o.stderr[-2000:]}")
+            res.setdefault(tag, []).append(json.loads(o.stdout.strip().splitlines()[-1]))
+    for i, shp in enumerate(SHAPES):
+        print(shp[0])
+        for tag, runs in res.items():
+            ms = [r[i]["ms"] for r in runs]
+            tf = [r[i]["tflops"] for r in runs]
+            print(f"   {tag:10s} ms min {min(ms):8.3f} med {sorted(ms)[len(ms) // 2]:8.3f}  TF max {max(tf):6.1f}")
 
 
 if __name__ == "__main__":
