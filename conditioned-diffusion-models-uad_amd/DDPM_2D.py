@@ -20,6 +20,8 @@ nn.Module / a plain attribute dict when not.
 """
 from __future__ import annotations
 
+import warnings
+
 import torch
 import torch.nn as nn
 
@@ -89,7 +91,19 @@ def load_pretrained_encoder(encoder, encoder_path):
     return encoder.load_state_dict(rewrite_pretrained_encoder_keys(ckpt["state_dict"]), strict=False)
 
 
+def _to_cpu(state):
+    """a checkpoint entry with its tensors on the host (nested dicts included)"""
+    if torch.is_tensor(state):
+        return state.cpu()
+    if isinstance(state, dict):
+        return {k: _to_cpu(v) for k, v in state.items()}
+    return state
+
+
 class DDPM_2D(_Base):
+    SCALER_CHECK_EVERY = 50      # training steps between two read-backs of the loss scaler's consecutive skips
+    SCALER_STALL_SKIPS = 30      # that many skips in a row: warn once
+
     def __init__(self, cfg, prefix=None, encoder=None):
         super().__init__()
         if isinstance(cfg, dict) and not isinstance(cfg, AttrDict):
@@ -377,16 +391,54 @@ class DDPM_2D(_Base):
 
     def on_save_checkpoint(self, checkpoint):
         """Lightning hook: `configure_optimizers` returns a torch Adam that is never stepped (manual optimisation on the HIP operators), so
-        the checkpoint's `optimizer_states` is empty; the real Adam state (m, v, step count -- what the reference's checkpoints carry in
-        `optimizer_states`) goes under its own key"""
+        the checkpoint's `optimizer_states` is empty; the real Adam state (m, v, step count, the dynamic loss scaler -- what the
+        reference's checkpoints carry in `optimizer_states` and `native_amp_scaling_state`) goes under its own key"""
         st = self.hip_optimizer_state()
         if st is not None:
-            checkpoint["hip_optimizer_state"] = {k: {kk: (vv.cpu() if torch.is_tensor(vv) else vv) for kk, vv in v.items()} for k, v in st.items()}
+            checkpoint["hip_optimizer_state"] = {k: _to_cpu(v) for k, v in st.items()}
 
     def on_load_checkpoint(self, checkpoint):
+        """restores hip_optimizer_state; a checkpoint without it but with Lightning 1.5's native AMP scaler state (a reference checkpoint
+        trained at precision 16: `native_amp_scaling_state` = GradScaler.state_dict()) seeds the loss scale and growth tracker of the
+        dynamic loss scaling, applied when a precision-16 step turns it on"""
         st = checkpoint.get("hip_optimizer_state")
         if st is not None:
             self.load_hip_optimizer_state({k: dict(v) for k, v in st.items()})
+        elif checkpoint.get("native_amp_scaling_state"):
+            from .training import loss_scaling_from_grad_scaler
+            self._pending_amp_scaler = loss_scaling_from_grad_scaler(checkpoint["native_amp_scaling_state"])
+
+    def _loss_scaling(self, trainer, bits):
+        """precision 16 (plain fp16 operands) trains under a dynamic loss scale, as Lightning's native AMP does with a GradScaler; at 32
+        nothing changes. A seed from a reference checkpoint (on_load_checkpoint) restarts the scaler from its scale and growth tracker."""
+        if bits != 16:
+            return
+        seed = getattr(self, "_pending_amp_scaler", None)
+        self._pending_amp_scaler = None
+        if seed is not None or not trainer.loss_scaling:
+            trainer.enable_loss_scaling(**(seed or {}))
+
+    def _watch_loss_scale(self, trainer):
+        """logs the loss scale and the skipped steps (device tensors: no read-back here) and, every SCALER_CHECK_EVERY steps, reads the
+        consecutive skips once: SCALER_STALL_SKIPS of them in a row mean the gradients are non-finite whatever the scale (a NaN input, a
+        diverged run) -- one RuntimeWarning instead of a run that silently stops learning"""
+        if hasattr(self, "log") and _Base is not nn.Module:
+            try:
+                self.log(f"{self.prefix}train/loss_scale", trainer.scaler[:1].view(torch.float32)[0].clone(), on_step=True, on_epoch=False)
+                self.log(f"{self.prefix}train/skipped_steps", trainer._ctrl()[3].float(), on_step=True, on_epoch=False)
+            except Exception:
+                pass
+        self._scaler_steps = getattr(self, "_scaler_steps", 0) + 1
+        if self._scaler_steps % self.SCALER_CHECK_EVERY:
+            return
+        skips = trainer.consecutive_skips
+        if skips < self.SCALER_STALL_SKIPS:
+            self._scaler_warned = False
+        elif not getattr(self, "_scaler_warned", False):
+            self._scaler_warned = True
+            warnings.warn(f"{skips} training steps in a row were skipped for non-finite gradients (loss scale now "
+                          f"{trainer.loss_scale:g}): the gradients are not finite at any scale -- a NaN / inf input or a diverged run?",
+                          RuntimeWarning, stacklevel=2)
 
     def _train_precision(self):
         """the Trainer's `precision` (the reference trains with 16: configs/trainer/default.yaml:7) or cfg.precision; None = leave the
@@ -410,13 +462,13 @@ class DDPM_2D(_Base):
         frozen feature extractor (`hip_trainer(...).dcond` holds dL/d(context) for whoever trains it)."""
         from . import training as _training
         prec = self._train_precision()
-        if prec is not None:
-            _training.set_precision(prec)
+        bits = _training.set_precision(prec) if prec is not None else _training.get_precision()
         vol = batch["vol"]
         input = vol["data"].squeeze(-1).float()              # torchio's DATA key is the string "data"
         dev = input.device
         trainer = self.hip_trainer(dev)
         self._alias_unet()                 # the module's parameters must still BE the trainer's (a .cpu() / load_state_dict in between?)
+        self._loss_scaling(trainer, bits)
         enc_trainer = self.hip_encoder_trainer(dev) if _cfg_get(self.cfg, "condition", True) else None
         if enc_trainer is not None:
             self._alias_encoder()
@@ -433,6 +485,8 @@ class DDPM_2D(_Base):
                                        buffers={k: getattr(d, k) for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
                                                                            "p2_loss_weight")})
         d.model._hip.invalidate()
+        if trainer.loss_scaling:
+            self._watch_loss_scale(trainer)
         if enc_trainer is not None:
             self._enc_core._key = None                    # the inference encoder re-reads the updated weights and running statistics
             for name, buf in self._enc_core.named_buffers():

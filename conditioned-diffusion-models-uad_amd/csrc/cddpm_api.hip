@@ -1736,7 +1736,13 @@ int cddpm_op_head_dgrad(cddpm_handle h, const float* dout_dev, const float* w9_d
 int cddpm_op_loss(cddpm_handle h, const float* out_dev, const float* target_dev, const float* w_b_dev, int l2, int B, int HW, float grad_scale,
                   float* dout_dev, float* loss_b_dev, void* stream) {
     OP_PROLOGUE(out_dev && target_dev && dout_dev && loss_b_dev && B > 0 && HW > 0, "cddpm_op_loss: bad arguments")
-    launch_loss(out_dev, target_dev, w_b_dev, l2, B, HW, grad_scale, dout_dev, loss_b_dev, s);
+    launch_loss(out_dev, target_dev, w_b_dev, l2, B, HW, grad_scale, nullptr, dout_dev, loss_b_dev, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_loss_scaled(cddpm_handle h, const float* out_dev, const float* target_dev, const float* w_b_dev, int l2, int B, int HW,
+                         const int32_t* scaler_dev, float* dout_dev, float* loss_b_dev, void* stream) {
+    OP_PROLOGUE(out_dev && target_dev && scaler_dev && dout_dev && loss_b_dev && B > 0 && HW > 0, "cddpm_op_loss_scaled: bad arguments")
+    launch_loss(out_dev, target_dev, w_b_dev, l2, B, HW, 0.0f, scaler_dev, dout_dev, loss_b_dev, s);
     OP_EPILOGUE()
 }
 int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
@@ -1767,7 +1773,26 @@ int cddpm_op_adam_guarded(cddpm_handle h, float* p_dev, const float* g_dev, floa
                           float beta2, float eps, float grad_unscale, const int32_t* ctrl_dev, void* stream) {
     OP_PROLOGUE(p_dev && g_dev && m_dev && v_dev && ctrl_dev && n > 0, "cddpm_op_adam_guarded: bad arguments")
     OP_CLASS(PC_OPT, 0.0)
-    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, grad_unscale, ctrl_dev, s);
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, grad_unscale, ctrl_dev, nullptr, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_adam_scaled(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1,
+                         float beta2, float eps, float extra_unscale, const int32_t* ctrl_dev, const int32_t* scaler_dev, void* stream) {
+    OP_PROLOGUE(p_dev && g_dev && m_dev && v_dev && ctrl_dev && scaler_dev && n > 0, "cddpm_op_adam_scaled: bad arguments")
+    OP_CLASS(PC_OPT, 0.0)
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, extra_unscale, ctrl_dev, scaler_dev, s);
+    OP_EPILOGUE()
+}
+static bool power_of_two(float x) {
+    int e;
+    return std::isfinite(x) && x > 0.0f && std::frexp(x, &e) == 0.5f;
+}
+int cddpm_op_scaler_update(cddpm_handle h, const int32_t* ctrl_dev, int32_t* scaler_dev, float growth, float backoff, int interval,
+                           void* stream) {
+    OP_PROLOGUE(ctrl_dev && scaler_dev && power_of_two(growth) && growth > 1.0f && power_of_two(backoff) && backoff < 1.0f && interval >= 1,
+                "cddpm_op_scaler_update: bad arguments (growth > 1 and backoff < 1 powers of two, interval >= 1)")
+    OP_CLASS(PC_OPT, 0.0)
+    launch_scaler_update(ctrl_dev, scaler_dev, growth, backoff, interval, s);
     OP_EPILOGUE()
 }
 

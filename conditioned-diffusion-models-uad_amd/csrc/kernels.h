@@ -191,14 +191,18 @@ void launch_add_inplace(float* a, const float* b, long long n, hipStream_t strea
 void launch_chan_image_corr(const float* T, const float* coef, int silu, const float* simg, int sign, int B, int H, int W, int C,
                             double* part, float* dw, hipStream_t stream);
 void launch_head_dgrad(const float* dout, const float* w9, float* dact, int B, int H, int W, int C, hipStream_t stream);
-void launch_loss(const float* out, const float* target, const float* w_b, int l2, int B, int HW, float grad_scale, float* dout, float* loss_b,
-                 hipStream_t stream);
+// scaler: nullptr = loss scale `grad_scale`; else the device loss scale (bits of scaler[0], see launch_scaler_update)
+void launch_loss(const float* out, const float* target, const float* w_b, int l2, int B, int HW, float grad_scale, const int* scaler, float* dout,
+                 float* loss_b, hipStream_t stream);
 void launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step, float grad_unscale,
                  hipStream_t stream);
 void launch_grad_check(const float* g, long long n, int* ctrl, hipStream_t stream);
 void launch_guard_commit(int* ctrl, float b1, float b2, hipStream_t stream);
+// scaler: nullptr = gradient g * grad_unscale; else g * grad_unscale / (the device loss scale)
 void launch_adam_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float grad_unscale,
-                         const int* ctrl, hipStream_t stream);
+                         const int* ctrl, const int* scaler, hipStream_t stream);
+// scaler = int32[4] {bits of the loss scale, growth tracker, consecutive skips, -}: torch._amp_update_scale_ from ctrl's skip decision
+void launch_scaler_update(const int* ctrl, int* scaler, float growth, float backoff, int interval, hipStream_t stream);
 void launch_gn_silu_backward(const float* x, const float* x1 /* second source of a concatenated input or nullptr */, int C0, float* dx1,
                              const float* da, const float* planes, const float* gamma, const float* beta,
                              const float* film, int silu, int B, int C, int HW, int nsplit, double* part, float* out_bc, float* dx,

@@ -1143,13 +1143,16 @@ void launch_head_dgrad(const float* dout, const float* w9, float* dact, int B, i
 }
 
 // loss of p_losses (cond_DDPM.py:636-645): per-sample mean of |out - target| (l1) or (out - target)^2 (l2), times p2_loss_weight[t_b],
-// mean over the batch; writes dL/d(out) and the B per-sample terms (their mean is the loss)
+// mean over the batch; writes dL/d(out) and the B per-sample terms (their mean is the loss). The loss scale is `grad_scale`, or, when
+// `scaler` is given, the device loss scale scaler[0] (bits of an fp32; see scaler_update_kernel)
 __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out, const float* __restrict__ target, const float* __restrict__ w_b,
-                                                   int l2, int B, int HW, float grad_scale, float* __restrict__ dout, float* __restrict__ loss_b) {
+                                                   int l2, int B, int HW, float grad_scale, const int* __restrict__ scaler,
+                                                   float* __restrict__ dout, float* __restrict__ loss_b) {
     __shared__ double red[256];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float wb = w_b ? w_b[b] : 1.0f;
-    const float gscale = grad_scale * wb / ((float)B * (float)HW);
+    const float scale = scaler ? reinterpret_cast<const float*>(scaler)[0] : grad_scale;
+    const float gscale = scale * wb / ((float)B * (float)HW);
     double s = 0;
     for (int p = tid; p < HW; p += 256) {
         const float d = out[(size_t)b * HW + p] - target[(size_t)b * HW + p];
@@ -1164,9 +1167,9 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out
 void launch_bias_grad(const float* dy, long long npix, int C, float* db, double* scratch /* 512 * C doubles */, hipStream_t stream) {
     bias_grad_run(dy, npix, C, db, scratch, bias_grad_chunks(npix, C, (size_t)1024 * C), stream);
 }
-void launch_loss(const float* out, const float* target, const float* w_b, int l2, int B, int HW, float grad_scale, float* dout, float* loss_b,
-                 hipStream_t stream) {
-    hipLaunchKernelGGL(loss_kernel, dim3(B), dim3(256), 0, stream, out, target, w_b, l2, B, HW, grad_scale, dout, loss_b);
+void launch_loss(const float* out, const float* target, const float* w_b, int l2, int B, int HW, float grad_scale, const int* scaler, float* dout,
+                 float* loss_b, hipStream_t stream) {
+    hipLaunchKernelGGL(loss_kernel, dim3(B), dim3(256), 0, stream, out, target, w_b, l2, B, HW, grad_scale, scaler, dout, loss_b);
 }
 
 // Adam (torch.optim.Adam defaults of DDPM_2D.configure_optimizers, DDPM_2D.py:305-306: lr 1e-4, betas (0.9, 0.999), eps 1e-8, no weight
@@ -1189,8 +1192,8 @@ void launch_adam(float* p, const float* g, float* m, float* v, long long n, floa
 }
 
 // ---- guarded update: a non-finite gradient (an fp16 operand overflow in the precision-16 arithmetic, a diverging loss) must not reach the
-// parameters or Adam's moments -- what torch's GradScaler does for the reference trainer (`precision: 16`, configs/trainer/default.yaml:7):
-// the step is skipped and the optimizer's step count does not advance. All on the device, no read-back: ctrl = int32[8] =
+// parameters or Adam's moments: the step is skipped and the optimizer's step count does not advance (the skip half of torch's GradScaler;
+// the scale half is scaler_update_kernel). All on the device, no read-back: ctrl = int32[8] =
 // {non-finite flag, step, skip this update, updates skipped so far, bits of 1 - beta1^step, bits of 1 - beta2^step, -, -}.
 __global__ __launch_bounds__(256) void grad_check_kernel(const float* __restrict__ g, long long n, int* __restrict__ ctrl) {
     bool bad = false;
@@ -1215,12 +1218,14 @@ __global__ void guard_commit_kernel(int* __restrict__ ctrl, float b1, float b2) 
 }
 __global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
-                                                           float unscale, const int* __restrict__ ctrl) {
+                                                           float unscale, const int* __restrict__ ctrl, const int* __restrict__ scaler) {
     if (ctrl[2]) return;                                   // uniform over the grid
     const float bc1 = reinterpret_cast<const float*>(ctrl)[4], bc2 = reinterpret_cast<const float*>(ctrl)[5];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i] * unscale;
+    // scaler given: `unscale` is the extra factor (1 / ranks) and the loss scale of this step is divided out (a power of two: exact)
+    const float u = scaler ? unscale / reinterpret_cast<const float*>(scaler)[0] : unscale;
+    const float gi = g[i] * u;
     const float mi = b1 * m[i] + (1.0f - b1) * gi;
     const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
     m[i] = mi; v[i] = vi;
@@ -1235,8 +1240,35 @@ void launch_guard_commit(int* ctrl, float b1, float b2, hipStream_t stream) {
     hipLaunchKernelGGL(guard_commit_kernel, dim3(1), dim3(64), 0, stream, ctrl, b1, b2);
 }
 void launch_adam_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps,
-                         float grad_unscale, const int* ctrl, hipStream_t stream) {
-    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, m, v, n, lr, b1, b2, eps, grad_unscale, ctrl);
+                         float grad_unscale, const int* ctrl, const int* scaler, hipStream_t stream) {
+    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, m, v, n, lr, b1, b2, eps, grad_unscale, ctrl,
+                       scaler);
+}
+
+// ---- dynamic loss scaling: torch's GradScaler.update (torch._amp_update_scale_) on the device, after the step's Adam updates, from the skip
+// decision of guard_commit. scaler = int32[4] = {bits of the fp32 loss scale, growth tracker, consecutive skipped steps, -}.
+// skipped: scale *= backoff, tracker = 0; else tracker += 1 and at `interval` scale *= growth (kept only if finite), tracker = 0.
+__global__ void scaler_update_kernel(const int* __restrict__ ctrl, int* __restrict__ scaler, float growth, float backoff, int interval) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float* scale = reinterpret_cast<float*>(scaler);
+    if (ctrl[2]) {
+        *scale = *scale * backoff;
+        scaler[1] = 0;
+        scaler[2] += 1;
+    } else {
+        scaler[2] = 0;
+        const int ok = scaler[1] + 1;
+        if (ok == interval) {
+            const float grown = *scale * growth;
+            if (isfinite(grown)) *scale = grown;
+            scaler[1] = 0;
+        } else {
+            scaler[1] = ok;
+        }
+    }
+}
+void launch_scaler_update(const int* ctrl, int* scaler, float growth, float backoff, int interval, hipStream_t stream) {
+    hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, stream, ctrl, scaler, growth, backoff, interval);
 }
 
 }  // namespace cddpm

@@ -252,10 +252,12 @@ class EncoderTrainer:
         self.saved = None
         return g
 
-    def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, guarded=False):
+    def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=None, guarded=False, extra_unscale=None):
         """Adam over the flat buffer under the guard of the handle's trainer (`ops`: training.UNetTrainer): the encoder and the UNet are ONE
         optimizer in the reference (`optim.Adam(self.parameters())`, DDPM_2D.py:305-306), so the step count and the skip decision are the
-        UNet trainer's control block. guarded: `ops.guard(others=(self,))` was called for this step; else the encoder is stepped alone."""
+        UNet trainer's control block. guarded: `ops.guard(others=(self,))` was called for this step; else the encoder is stepped alone.
+        grad_scale None: 1, or -- guarded, with the trainer's dynamic loss scaling on -- its device scale, the loss scale too is shared
+        (gradient = gflat * extra_unscale (default 1) / scale; the trainer updates the scale after this)."""
         st = self.state
         if "m" not in st:
             st["m"], st["v"] = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
@@ -267,9 +269,18 @@ class EncoderTrainer:
             ctrl = self.ctrl
         else:
             ctrl = self.ops._ctrl()
-        self._ck(self.lib.cddpm_op_adam_guarded(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(), C.c_float(lr),
-                                                C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(1.0 / grad_scale), _p(ctrl),
-                                                self._s()), "op_adam_guarded")
+        if guarded and grad_scale is None and getattr(self.ops, "loss_scaling", False):
+            if self.ops.scaler is None:
+                raise RuntimeError("adam_step with dynamic loss scaling: no loss was formed yet (loss_and_grad)")
+            self._ck(self.lib.cddpm_op_adam_scaled(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
+                                                   C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps),
+                                                   C.c_float(1.0 if extra_unscale is None else extra_unscale), _p(ctrl), _p(self.ops.scaler),
+                                                   self._s()), "op_adam_scaled")
+        else:
+            unscale = 1.0 / (grad_scale if grad_scale is not None else 1.0)
+            self._ck(self.lib.cddpm_op_adam_guarded(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
+                                                    C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(unscale),
+                                                    _p(ctrl), self._s()), "op_adam_guarded")
         self.repack()
 
     def optimizer_state(self) -> Dict[str, torch.Tensor]:

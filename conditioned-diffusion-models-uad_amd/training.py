@@ -12,8 +12,9 @@ temporaries from one scratch arena, no synchronisation inside a step); loss and 
 oracle, three complete steps against float64 autograd + torch Adam (tests/test_gpu_training.py); the context encoder is trained jointly by
 encoder_training.EncoderTrainer. Convolutions keep the inference path's fp32-grade arithmetic (fp16 two-term splits) by default; the
 reference trainer's `precision: 16` arithmetic (plain fp16 operands, fp32 accumulation) is selected per process (CDDPM_TRAIN_PRECISION=16,
-set from the Trainer's precision by the DDPM_2D mirror). A step whose gradients hold inf / NaN is skipped on the device (`guard`), as
-torch's GradScaler does for the reference. Measured: DESIGN.md section 4b.
+set from the Trainer's precision by the DDPM_2D mirror). A step whose gradients hold inf / NaN is skipped on the device (`guard`). The loss
+scale is fixed by default; `UNetTrainer.enable_loss_scaling` makes it dynamic as torch's GradScaler does for the reference (backed off on a
+skipped step, grown after `growth_interval` clean ones), with the scale kept on the device. Measured: DESIGN.md section 4b.
 """
 from __future__ import annotations
 
@@ -136,6 +137,8 @@ class UNetTrainer:
         self.eng_w: Optional[CddpmEngine] = None
         self.side = None
         self.grad_scale = 1.0
+        self.loss_scaling = False           # dynamic loss scaling (enable_loss_scaling); off: the fixed scale of loss_and_grad
+        self.scaler: Optional[torch.Tensor] = None
         self.exp_refresh = exp_refresh
         self._convs = self._conv_table()
         self._fit(1, 16, 16)
@@ -593,14 +596,70 @@ class UNetTrainer:
 
     # ------------------------------------------------------------------ loss of p_losses + one optimizer step
     def loss_and_grad(self, model_out, target, p2w=None, loss_type="l1", grad_scale=None):
-        """-> (loss, grad_scale * dL/d(model_out)); grad_scale defaults to B*H*W rounded up to a power of two (see cddpm_op_loss)"""
+        """-> (loss, grad_scale * dL/d(model_out)); grad_scale defaults to B*H*W rounded up to a power of two (see cddpm_op_loss). With
+        dynamic loss scaling on and no grad_scale given, the scale is the device one (`loss_scale`; self.grad_scale is then None)."""
         B, _c, H, W = model_out.shape
         dout = torch.empty_like(model_out)
         loss_b = self._new(B)
+        if self.loss_scaling and grad_scale is None:
+            self.join_side()
+            if self.scaler is None:        # the first step: the default start is the fixed path's scale
+                init = self.scaler_init if self.scaler_init is not None else float(2 ** math.ceil(math.log2(B * H * W)))
+                self.scaler = _scaler_block(init, self.scaler_tracker0, 0, self.dev)
+            self.grad_scale = None
+            self._ck(self.lib.cddpm_op_loss_scaled(self.h, _p(model_out), _p(target.contiguous().float()), _p(p2w), int(loss_type == "l2"), B,
+                                                   H * W, _p(self.scaler), _p(dout), _p(loss_b), self._s()), "op_loss_scaled")
+            return loss_b.mean(), dout
         self.grad_scale = float(grad_scale) if grad_scale is not None else float(2 ** math.ceil(math.log2(B * H * W)))
         self._ck(self.lib.cddpm_op_loss(self.h, _p(model_out), _p(target.contiguous().float()), _p(p2w), int(loss_type == "l2"), B, H * W,
                                         C.c_float(self.grad_scale), _p(dout), _p(loss_b), self._s()), "op_loss")
         return loss_b.mean(), dout
+
+    # ------------------------------------------------------------------ dynamic loss scaling (torch's GradScaler, the scale on the device)
+    def enable_loss_scaling(self, init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, growth_tracker=0):
+        """turns on dynamic loss scaling with torch.cuda.amp.GradScaler's rule (torch._amp_update_scale_): a skipped step halves the scale
+        (x backoff_factor), `growth_interval` clean steps in a row double it (x growth_factor). init_scale None: the fixed path's
+        2^ceil(log2(B*H*W)) of the first batch, so the first steps do not change. Scale and factors must be powers of two (the unscale is
+        then exact: a step at scale S is bit-identical to the fixed path with grad_scale=S). Starts a fresh scaler state (growth tracker
+        `growth_tracker`, no skips); the device state is created at the next loss. Invalid values raise ValueError."""
+        cfg = loss_scaling_settings(init_scale, growth_factor, backoff_factor, growth_interval, growth_tracker)
+        self.scaler_init = cfg["init_scale"]
+        self.scaler_cfg = (cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"])
+        self.scaler_tracker0 = cfg["growth_tracker"]
+        self.scaler = None
+        self.loss_scaling = True
+
+    def update_loss_scale(self):
+        """step (d) of include/cddpm.h's dynamic loss scaling: after every Adam update of the step, the scale follows the step's skip
+        decision (one single-thread launch on the main stream)"""
+        self.join_side()
+        g, b, n = self.scaler_cfg
+        self._ck(self.lib.cddpm_op_scaler_update(self.h, _p(self._ctrl()), _p(self.scaler), C.c_float(g), C.c_float(b), n, self._s()),
+                 "op_scaler_update")
+
+    def _scaler_read(self, i):
+        self.join_side()
+        if self.scaler is None:
+            return None
+        return self.scaler[:1].view(torch.float32).item() if i == 0 else int(self.scaler[i].item())
+
+    @property
+    def loss_scale(self) -> Optional[float]:
+        """the loss scale the next step is formed with: the device scale when dynamic scaling is on (reads it: synchronises; before the
+        first step the configured start, None for the batch-size default), else the fixed scale of the last loss_and_grad"""
+        if not self.loss_scaling:
+            return self.grad_scale
+        return self._scaler_read(0) if self.scaler is not None else self.scaler_init
+
+    @property
+    def growth_tracker(self) -> int:
+        """clean steps since the scale last changed (dynamic scaling; reads the device counter)"""
+        return self._scaler_read(1) if self.scaler is not None else getattr(self, "scaler_tracker0", 0)
+
+    @property
+    def consecutive_skips(self) -> int:
+        """skipped steps in a row up to now (dynamic scaling; reads the device counter)"""
+        return self._scaler_read(2) if self.scaler is not None else 0
 
     # ------------------------------------------------------------------ the guarded update (GradScaler's skip of a non-finite step)
     def _ctrl(self):
@@ -627,37 +686,56 @@ class UNetTrainer:
     def skipped_steps(self) -> int:
         return int(self._ctrl()[3].item())
 
-    def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=None, guarded=False):
+    def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=None, guarded=False, extra_unscale=None):
         """torch.optim.Adam(lr=1e-4) of DDPM_2D.configure_optimizers (DDPM_2D.py:305-306) on every parameter: one launch over the flat buffers
         (gradient = gflat / grad_scale), then the convolution images are re-packed from the updated weights. guarded: `guard()` was already
-        called for this step (jointly with the encoder's gradients); otherwise it is called here."""
+        called for this step (jointly with the encoder's gradients); otherwise it is called here. With dynamic loss scaling on and no
+        grad_scale given, the gradient is gflat * extra_unscale (default 1) / the device scale of this step's loss; unguarded, the scale is
+        then updated here (guarded: the caller runs update_loss_scale after the last Adam update of the step)."""
         st = self.state
         if "m" not in st:
             st["m"], st["v"] = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         if not guarded:
             self.guard(betas=betas)
         st["calls"] = st.get("calls", 0) + 1
-        unscale = 1.0 / (grad_scale if grad_scale is not None else self.grad_scale)
-        self._ck(self.lib.cddpm_op_adam_guarded(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(), C.c_float(lr),
-                                                C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(unscale), _p(self._ctrl()),
-                                                self._s()), "op_adam_guarded")
+        if self.loss_scaling and grad_scale is None:
+            if self.scaler is None:
+                raise RuntimeError("adam_step with dynamic loss scaling: no loss was formed yet (loss_and_grad)")
+            self.join_side()
+            self._ck(self.lib.cddpm_op_adam_scaled(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
+                                                   C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps),
+                                                   C.c_float(1.0 if extra_unscale is None else extra_unscale), _p(self._ctrl()), _p(self.scaler),
+                                                   self._s()), "op_adam_scaled")
+            if not guarded:
+                self.update_loss_scale()
+        else:
+            unscale = 1.0 / (grad_scale if grad_scale is not None else self.grad_scale)
+            self._ck(self.lib.cddpm_op_adam_guarded(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
+                                                    C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(unscale),
+                                                    _p(self._ctrl()), self._s()), "op_adam_guarded")
         if self._convs:
             if self.exp_refresh and st["calls"] % self.exp_refresh == 0:
                 self.refresh_exponents()
             self.repack()
 
-    # ------------------------------------------------------------------ checkpoint state (Adam moments, step count)
+    # ------------------------------------------------------------------ checkpoint state (Adam moments, step count, loss scaler)
     def optimizer_state(self) -> Dict[str, torch.Tensor]:
-        """what a checkpoint must carry besides the parameters to resume this optimizer: Adam's m, v (flat, this trainer's layout) and the
-        device control block with the step count"""
+        """what a checkpoint must carry besides the parameters to resume this optimizer: Adam's m, v (flat, this trainer's layout), the
+        device control block with the step count and, with dynamic loss scaling on, the scaler ("scaler": its settings and device block)"""
         st = self.state
         if "m" not in st:
             st["m"], st["v"] = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         # wexp / calls: the convolutions' pre-scale exponents are refreshed every `exp_refresh` updates, not every update -- a resumed run
         # must multiply with the exponents (and refresh on the schedule) the uninterrupted run would
-        return {"m": st["m"].detach().clone(), "v": st["v"].detach().clone(), "ctrl": self._ctrl().detach().clone(),
-                "layout": [(k, int(v.numel())) for k, v in self.p.items()], "wexp": dict(getattr(self, "wexp", {})),
-                "calls": int(st.get("calls", 0))}
+        out = {"m": st["m"].detach().clone(), "v": st["v"].detach().clone(), "ctrl": self._ctrl().detach().clone(),
+               "layout": [(k, int(v.numel())) for k, v in self.p.items()], "wexp": dict(getattr(self, "wexp", {})),
+               "calls": int(st.get("calls", 0))}
+        if self.loss_scaling:
+            self.join_side()
+            g, b, n = self.scaler_cfg
+            out["scaler"] = {"init_scale": self.scaler_init, "growth_factor": g, "backoff_factor": b, "growth_interval": n,
+                             "growth_tracker": self.scaler_tracker0, "state": None if self.scaler is None else self.scaler.detach().clone()}
+        return out
 
     def load_optimizer_state(self, state) -> None:
         layout = [(k, int(v.numel())) for k, v in self.p.items()]
@@ -667,6 +745,13 @@ class UNetTrainer:
         self.state["v"] = state["v"].to(self.dev, torch.float32).clone()
         self._ctrl().copy_(state["ctrl"].to(self.dev, torch.int32))
         self.state["calls"] = int(state.get("calls", 0))
+        sc = state.get("scaler")           # absent: saved without dynamic loss scaling -- the scaler is left as it is
+        if sc is not None:
+            self.enable_loss_scaling(init_scale=sc["init_scale"], growth_factor=sc["growth_factor"], backoff_factor=sc["backoff_factor"],
+                                     growth_interval=sc["growth_interval"], growth_tracker=sc["growth_tracker"])
+            if sc.get("state") is not None:
+                self.join_side()
+                self.scaler = sc["state"].to(self.dev, torch.int32).clone()
         if state.get("wexp") and self._convs:
             self.wexp = {k: int(state["wexp"][k]) for k in self._convs}
             self.repack()
@@ -677,6 +762,50 @@ class UNetTrainer:
         if self._convs:
             self.refresh_exponents()
             self.repack()
+
+
+def _power_of_two(x) -> bool:
+    try:
+        x = float(x)
+    except (TypeError, ValueError):
+        return False
+    return math.isfinite(x) and x > 0 and math.frexp(x)[0] == 0.5
+
+
+def _scaler_block(scale: float, tracker: int, skips: int, dev) -> torch.Tensor:
+    """the device scaler state of include/cddpm.h: int32[4] = {bits of the fp32 loss scale, growth tracker, consecutive skips, 0}"""
+    blk = torch.tensor([0, int(tracker), int(skips), 0], dtype=torch.int32)
+    blk[:1].view(torch.float32).fill_(float(scale))
+    return blk.to(dev)
+
+
+def _integer(x) -> bool:
+    return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x) and int(x) == x
+
+
+def loss_scaling_settings(init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, growth_tracker=0) -> Dict[str, object]:
+    """the checked arguments of UNetTrainer.enable_loss_scaling (torch GradScaler's defaults; init_scale None: the batch-size default).
+    The scale and both factors must be powers of two (growth > 1, backoff < 1) so that unscaling stays exact; ValueError otherwise."""
+    if init_scale is not None and not (_power_of_two(init_scale) and float(init_scale) < 2.0 ** 127):
+        raise ValueError(f"init_scale must be a finite power of two, got {init_scale!r}")
+    if not (_power_of_two(growth_factor) and float(growth_factor) > 1.0):
+        raise ValueError(f"growth_factor must be a power of two > 1, got {growth_factor!r}")
+    if not (_power_of_two(backoff_factor) and float(backoff_factor) < 1.0):
+        raise ValueError(f"backoff_factor must be a power of two < 1, got {backoff_factor!r}")
+    if not (_integer(growth_interval) and 1 <= growth_interval < 2 ** 31):
+        raise ValueError(f"growth_interval must be an integer >= 1, got {growth_interval!r}")
+    if not (_integer(growth_tracker) and 0 <= growth_tracker < 2 ** 31):
+        raise ValueError(f"growth_tracker must be an integer >= 0, got {growth_tracker!r}")
+    return {"init_scale": None if init_scale is None else float(init_scale), "growth_factor": float(growth_factor),
+            "backoff_factor": float(backoff_factor), "growth_interval": int(growth_interval), "growth_tracker": int(growth_tracker)}
+
+
+def loss_scaling_from_grad_scaler(state) -> Dict[str, object]:
+    """UNetTrainer.enable_loss_scaling's arguments from a torch GradScaler.state_dict() -- what Lightning 1.5's native AMP plugin stores in
+    a checkpoint under `native_amp_scaling_state`: {"scale", "growth_factor", "backoff_factor", "growth_interval", "_growth_tracker"}.
+    Values outside what enable_loss_scaling accepts raise ValueError."""
+    return loss_scaling_settings(float(state["scale"]), state.get("growth_factor", 2.0), state.get("backoff_factor", 0.5),
+                                 state.get("growth_interval", 2000), state.get("_growth_tracker", 0))
 
 
 def set_precision(precision) -> int:
@@ -792,6 +921,12 @@ def training_step(trainer: UNetTrainer, x01: torch.Tensor, cond: Optional[torch.
         enc_buckets.finish()
     # one decision for the whole optimizer (after the all-reduce: an inf / NaN on any rank reaches every rank through the sum)
     trainer.guard(others=(encoder,) if encoder is not None else ())
+    if trainer.loss_scaling:             # the device scale: both updates unscale by the scale of this step's loss, then it is updated
+        trainer.adam_step(lr=lr, guarded=True, extra_unscale=1.0 / world)
+        if encoder is not None:
+            encoder.adam_step(lr=lr, guarded=True, extra_unscale=1.0 / world)
+        trainer.update_loss_scale()
+        return loss
     trainer.adam_step(lr=lr, grad_scale=trainer.grad_scale * world, guarded=True)     # the mean over ranks folds into Adam's unscale factor
     if encoder is not None:
         encoder.adam_step(lr=lr, grad_scale=trainer.grad_scale * world, guarded=True)

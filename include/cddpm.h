@@ -322,12 +322,25 @@ int cddpm_op_loss(cddpm_handle h, const float* out_dev, const float* target_dev,
  * g_dev * grad_unscale (1 / the loss scale) */
 int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
                   float eps, int step, float grad_unscale, void* stream);
-/* The guarded form of the update (what torch's GradScaler does for the reference trainer, `precision: 16` in
- * configs/trainer/default.yaml:7: a step whose gradients hold inf / NaN is skipped and does not count), entirely on the device.
+/* The guarded form of the update, entirely on the device: a step whose gradients hold inf / NaN is skipped and does not count. With a
+ * fixed loss scale this is only the skip half of torch's GradScaler (the reference trainer's `precision: 16`,
+ * configs/trainer/default.yaml:7); the dynamic scale is the scaler form below.
  * ctrl_dev: int32[8], zero-initialised by the caller once = {non-finite flag, optimizer step, skip, skipped so far, bits of
  * 1 - beta1^step, bits of 1 - beta2^step, 0, 0}. Per optimisation step: cddpm_op_grad_check on every gradient buffer (ORs the flag),
  * ONE cddpm_op_guard_commit (flag set: skip = 1, skipped += 1; else skip = 0, step += 1, bias corrections refreshed; flag cleared),
- * then cddpm_op_adam_guarded on every parameter buffer (a no-op when skip is set; step and bias corrections come from ctrl_dev). */
+ * then cddpm_op_adam_guarded on every parameter buffer (a no-op when skip is set; step and bias corrections come from ctrl_dev).
+ *
+ * Dynamic loss scaling (torch's GradScaler: the scale backs off on a skipped step and grows after `interval` clean ones), the scale on the
+ * device: scaler_dev = int32[4] = {bits of the fp32 loss scale, growth tracker, consecutive skipped steps, 0}, initialised by the caller
+ * (scale a power of two; tracker and skips 0 for a fresh run). Per optimisation step, in this order:
+ *   (a) cddpm_op_loss_scaled: cddpm_op_loss with the loss scale read from scaler_dev (dout_dev = scale * dL/d(out));
+ *   (b) the backward pass, then cddpm_op_grad_check on every gradient buffer and ONE cddpm_op_guard_commit, as above;
+ *   (c) cddpm_op_adam_scaled on every parameter buffer (UNet and encoder): cddpm_op_adam_guarded with gradient
+ *       g_dev * extra_unscale / scale (extra_unscale: e.g. 1 / ranks for the mean over data-parallel ranks), the scale (a) was formed with;
+ *   (d) ONE cddpm_op_scaler_update: torch._amp_update_scale_ from ctrl_dev's skip decision -- skipped: scale *= backoff, tracker = 0,
+ *       skips += 1; else skips = 0, tracker += 1, and when it reaches `interval`: scale *= growth (kept only if finite), tracker = 0.
+ * growth > 1 and backoff < 1 must be powers of two (refused otherwise): the scale stays one, 1 / scale is exact, and a step at scale S is
+ * bit-identical to the fixed-scale calls with grad_scale = S and grad_unscale = extra_unscale / S. */
 /* Arithmetic of the training operators, process-wide: 32 (default) = fp32-grade products from two-term fp16 splits; 16 = plain fp16
  * operands with fp32 accumulation in cddpm_op_conv_packed and cddpm_op_conv_wgrad -- what the reference trainer's `precision: 16`
  * (configs/trainer/default.yaml:7) computes under autocast; GroupNorm, attention, embeddings, Adam and the master weights stay fp32 in both.
@@ -339,6 +352,12 @@ int cddpm_op_grad_check(cddpm_handle h, const float* g_dev, int64_t n, int32_t* 
 int cddpm_op_guard_commit(cddpm_handle h, int32_t* ctrl_dev, float beta1, float beta2, void* stream);
 int cddpm_op_adam_guarded(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1,
                           float beta2, float eps, float grad_unscale, const int32_t* ctrl_dev, void* stream);
+int cddpm_op_loss_scaled(cddpm_handle h, const float* out_dev, const float* target_dev, const float* w_b_dev, int l2, int B, int HW,
+                         const int32_t* scaler_dev, float* dout_dev, float* loss_b_dev, void* stream);
+int cddpm_op_adam_scaled(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1,
+                         float beta2, float eps, float extra_unscale, const int32_t* ctrl_dev, const int32_t* scaler_dev, void* stream);
+int cddpm_op_scaler_update(cddpm_handle h, const int32_t* ctrl_dev, int32_t* scaler_dev, float growth, float backoff, int interval,
+                           void* stream);
 /* ---- device-resident operator calls (what the training step runs on: no host staging, no synchronisation) ----
  * cddpm_op_set_scratch gives the handle an arena of `bytes` (0: release it) from which the operators of this header take their
  * temporaries instead of a hipMalloc / synchronise / hipFree per call; calls then only enqueue work on `stream` (one stream).
