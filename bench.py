@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- reconstructed 128x128 slices/sec @ T=1000 of the cDDPM reverse-diffusion path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--size S] [--no-cpu] [--no-alt] [--no-profile]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--size S] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-alt] [--no-profile]]
         (N > 1 without RANK in the environment: starts the N ranks itself -- the torchrun line below as a child process --
          and relays rank 0's JSON line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -20,8 +20,12 @@ driver passes) is ONE COMPLETE reconstruction x_T -> x_0 in [0,1] of the whole b
 reconstructions, inside the timed region. Other K: K*50 reverse steps = floor(K/20) complete reconstructions
 plus the head of the next chain.
     value [slices/s] = n_gpus * B * (K * 50 / 1000) / seconds        (max over ranks, barrier + synchronize both sides)
-Untimed before it: W segments of warm-up. Untimed after it: a short pass with per-kernel HIP events (roofline), the
-small-batch line, the alternative arithmetic paths and the CPU baseline (rank 0, one GPU only).
+Untimed before it: W segments of warm-up. A plain run ends there: it writes --dump-outputs if asked and prints the JSON line.
+
+--full: the side measurements as well, untimed, after the timed region: a short pass with per-kernel HIP events (roofline),
+the small-batch line, the alternative arithmetic paths, the training steps and the CPU baseline (all but the first on rank 0,
+one GPU only). --no-profile, --no-alt and --no-cpu drop single legs of it. The headline and the dumped arrays are the same
+with and without --full. --workload residual has no side measurements.
 
 --dump-outputs DIR: after the timed region, rank 0 writes what the timed path handed its caller, as DIR/<name>.npy (float32):
 `x`, the chain state after the last timed segment (world*B x 1 x S x S: the gathered tensor under torchrun; after K = 20 the
@@ -29,7 +33,7 @@ reconstructions x_0), or `residual_maps` for --workload residual. Over 64 MB in 
 of its slices (sorted indices drawn by numpy's default_rng(0)). Weights, x_T, the context and z_t are seeded, so the same
 arguments give the same inputs on every run and two builds can be compared output for output.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline      dominant kernel = the fused 3x3 convolution (conv_x6.hip: conv_split_kernel<9,8,2,true> and the
                 folded-upsample form <4,8,2,true>). Default arithmetic: every fp32 operand split into two fp16 terms,
                 three v_mfma_f32_16x16x32_f16 per product group (hi*hi + hi*mid + mid*hi), fp32 accumulation.
@@ -345,7 +349,7 @@ def residual_workload(args, torch, dev, rank, world, dist, result_fd):
         raise SystemExit("bench.py --workload residual: the residual maps are not finite / not in [0,1]")
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--workload", default="reverse", choices=("reverse", "residual"),
@@ -357,15 +361,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=64, help="slices per GPU (configs[1]: 64)")
     ap.add_argument("--size", type=int, default=128)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-alt", action="store_true", help="skip the alternative-arithmetic children and the small-batch line")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP event pass (no roofline object)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also the side measurements: per-kernel HIP events (roofline), the small-batch and "
+                         "alternative-arithmetic lines, the training steps and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-alt", action="store_true",
+                    help="with --full: skip the alternative-arithmetic children, the small-batch lines and the training steps")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel HIP event pass (no roofline object)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write what the timed path returned as DIR/<name>.npy (float32, <= 64 MB in all)")
     ap.add_argument("--alt-child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     plan = launch_plan(args.gpus, sys.argv[1:], os.environ)
     if plan is not None:
@@ -476,8 +489,8 @@ def main():
     if dumped is not None:
         out["config"]["outputs_dumped"] = dumped
 
-    # ---- per-kernel-class HIP events: a second, short pass outside the timed region
-    if not args.no_profile:
+    # ---- --full: per-kernel-class HIP events: a second, short pass outside the timed region
+    if args.full and not args.no_profile:
         nprof = 6
         eng.set_profiling(True)
         eng.reverse_range_(scratch, T_TOTAL - 1, T_TOTAL - nprof, seed=3, slice0=slice0)
@@ -523,7 +536,7 @@ def main():
     del eng, x, scratch
     torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_alt:
+    if args.full and rank == 0 and world == 1 and not args.no_alt:
         # the reference's real call shape: 4 slices per volume (DDPM_2D.py:193)
         out["config"]["small_batch"] = short_rate(torch, dev, 4, S, n_rev=50, warm=10)
         try:        # the same call as two half-batches on two streams / two handles (engine.reverse_two_streams: identical bits)
@@ -565,7 +578,7 @@ def main():
             out["config"]["training_step_precision16"] = training_rate(torch, dev, synth, precision=16)
         except Exception as e:
             out["config"]["training_step_precision16"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(synth, S)
         out["config"]["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         out["config"]["speedup_vs_cpu_baseline_range"] = [value / out["cpu_baseline"]["range"][1], value / out["cpu_baseline"]["range"][0]]

@@ -61,6 +61,13 @@ def test_bench_refuses_zero_timed_steps():
     assert r.returncode == 2 and "--steps" in r.stderr and r.stdout.strip() == ""
 
 
+def test_side_measurements_run_only_with_full():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "2"])
+    assert plain.full is False and plain.steps == 20 and plain.warmup == 2
+    full = bench.parse_args(["--full", "--no-cpu"])
+    assert full.full is True and full.no_cpu is True and full.no_alt is False and full.no_profile is False
+
+
 def test_dump_outputs_writes_float32_and_samples_a_fixed_subset(tmp_path):
     import numpy as np
     import torch

@@ -1,9 +1,11 @@
-"""GPU: bench.py keeps its contract -- one JSON line on stdout with the driver's keys, the roofline and (at N = 1) the
-CPU baseline objects; a short run at a reduced batch so that the test stays under a minute."""
+"""GPU: bench.py keeps its contract -- one JSON line on stdout with the driver's keys; a plain run stops after the timed region,
+--full adds the roofline, the side measurements and (at N = 1) the CPU baseline objects; short runs at a reduced batch so that
+each test stays under a minute."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 import torch
@@ -17,8 +19,8 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def test_bench_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu", "--no-alt"],
-                       capture_output=True, text=True, timeout=600, env=dict(os.environ))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--full", "--no-cpu",
+                        "--no-alt"], capture_output=True, text=True, timeout=600, env=dict(os.environ))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                      # exactly one line on stdout; everything else goes to stderr
@@ -37,6 +39,31 @@ def test_bench_contract():
     assert abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-9
     assert "cpu_baseline" not in out                    # --no-cpu
     assert "alt_paths" not in cfg and "small_batch" not in cfg      # --no-alt
+
+
+SIDE_MEASUREMENTS = {"roofline", "kernel_classes", "cpu_baseline"}
+SIDE_CONFIG = {"small_batch", "small_batch_two_streams", "alt_paths", "training_step", "training_step_precision16",
+               "speedup_vs_cpu_baseline", "speedup_vs_cpu_baseline_range"}
+
+
+def test_plain_bench_stops_after_the_timed_region():
+    """without --full: the headline line alone, none of the side measurements, and at most 30 s of the whole run outside the
+    warm-up and timed segments"""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8"],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ))
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert REQUIRED <= set(out), REQUIRED - set(out)
+    assert out["metric"] == "reconstructed 128x128 slices/sec @ T=1000" and out["unit"] == "slices/s" and out["higher_is_better"] is True
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["config"]["finite"] is True
+    assert abs(out["value"] - 8 * 0.05 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert not SIDE_MEASUREMENTS & set(out), SIDE_MEASUREMENTS & set(out)
+    assert not SIDE_CONFIG & set(out["config"]), SIDE_CONFIG & set(out["config"])
+    assert wall - 3 * out["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 def test_bench_dump_outputs_are_the_same_on_every_run(tmp_path):
@@ -66,7 +93,7 @@ def test_bench_complete_reconstruction_small():
     """K = 20 segments = ONE complete reconstruction (a single cddpm_reverse(t_start = 1000)); here at B = 2, 32x32 so
     that the test stays short; also exercises the small-batch line and one alternative-arithmetic child"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "1", "--batch", "2", "--size", "32",
-                        "--no-cpu"], capture_output=True, text=True, timeout=900, env=dict(os.environ))
+                        "--full", "--no-cpu"], capture_output=True, text=True, timeout=900, env=dict(os.environ))
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     cfg = out["config"]
