@@ -344,6 +344,9 @@ int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev
 /* Arithmetic of the training operators, process-wide: 32 (default) = fp32-grade products from two-term fp16 splits; 16 = plain fp16
  * operands with fp32 accumulation in cddpm_op_conv_packed and cddpm_op_conv_wgrad -- what the reference trainer's `precision: 16`
  * (configs/trainer/default.yaml:7) computes under autocast; GroupNorm, attention, embeddings, Adam and the master weights stay fp32 in both.
+ * Precision 16 rounds each operand to fp16 to nearest even with gradual underflow, as torch's .half(): measured on gfx950, the 16-bit
+ * MFMA inputs keep fp16 subnormals (|x| < 2^-14 is carried to 2^-25, not flushed), in both operators and on either operand
+ * (tests/test_gpu_train_ops_edges.py::test_precision16_keeps_fp16_subnormals).
  * Initial value: environment CDDPM_TRAIN_PRECISION (16 | unset). set returns the previous value, -1 for an unsupported `bits`.
  * The reconstruction entry points are not affected. */
 int cddpm_set_train_precision(int bits);
