@@ -15,7 +15,8 @@ The context encoder is this package's native ResNet
 `encoder=` module is supplied; `cfg.pretrained_encoder` loads a SparK pre-training checkpoint into it with the reference's key rewrite
 (:79-96). `training_step` runs the optimisation step of the UNet AND of the native context encoder (trained jointly, as
 `optim.Adam(self.parameters())` does in the reference) on the HIP operators (training.py, encoder_training.py); Adam's state travels in
-checkpoints (`on_save_checkpoint` / `on_load_checkpoint`). The scipy post-processing of utils_eval lives in utils_eval.py. pytorch_lightning / omegaconf are used when installed and replaced by
+checkpoints (`on_save_checkpoint` / `on_load_checkpoint`). The evaluation's residual post-processing and metric pass (the reference's
+utils_eval, used standalone) live in utils_eval.py. pytorch_lightning / omegaconf are used when installed and replaced by
 nn.Module / a plain attribute dict when not.
 """
 from __future__ import annotations
@@ -187,9 +188,9 @@ class DDPM_2D(_Base):
         experiment yaml :22: reconstructions at t in `step_ensemble` = [250, 500, 750], each from a FRESH `gen_noise`
         field, averaged, :225-236) or one reconstruction at `test_timesteps` (:240-247); volume re-assembled as
         [1,1,H,W,D] (:256-275). cfg.reverse_sampling (absent in the reference) swaps the single-step estimate for the
-        reverse loop at the same call site. The scipy/sklearn post-processing `_test_step` (:277) runs when the reference's
-        `src.utils.utils_eval` is importable (this class dropped into the reference tree) and the batch carries its
-        inputs; the tensors are returned either way."""
+        reverse loop at the same call site. When the batch carries its inputs and on_test_start ran, `_test_step` (:277)
+        follows: the reference's (scipy / sklearn) when `src.utils.utils_eval` is importable (this class dropped into the
+        reference tree), this package's device metric pass (utils_eval.py) otherwise; the tensors are returned either way."""
         def data_of(key):
             v = batch.get(key) if hasattr(batch, "get") else None
             if v is None:
@@ -240,10 +241,9 @@ class DDPM_2D(_Base):
         if data_orig is not None and data_mask is not None and hasattr(self, "eval_dict"):
             try:
                 from src.utils.utils_eval import _test_step  # type: ignore  (reference tree on sys.path)
-            except ImportError:                 # standalone (no reference tree): the reconstruction is returned without the metric pass
-                _test_step = None
-            if _test_step is not None:
-                _test_step(self, final_volume, data_orig, data_seg, data_mask, batch_idx, field("ID"), field("label"))
+            except ImportError:                 # standalone (no reference tree): the native metric pass on the device
+                from .utils_eval import _test_step
+            _test_step(self, final_volume, data_orig, data_seg, data_mask, batch_idx, field("ID"), field("label"))
         return out
 
     def _record_volume_scores(self, features, input, loss_diff):
@@ -267,25 +267,25 @@ class DDPM_2D(_Base):
             ed.setdefault("AnomalyScoreCombiPriorPerVol", []).append(score * 0)
 
     def on_test_start(self):
-        """reference :156-170: the bookkeeping `_test_step` / `_test_end` of the reference's evaluation write into. The metric code itself
-        (src/utils/utils_eval.py: sklearn / monai / skimage) is outside the hot path and is used from the reference tree when this class
-        runs inside it; standalone, the lists are created and test_step returns its reconstruction without the metric pass."""
+        """reference :156-170: the bookkeeping `_test_step` / `_test_end` of the reference's evaluation write into. Inside the reference
+        tree its own metric code (src/utils/utils_eval.py: sklearn / monai / skimage) is used; standalone, the package's device metric
+        pass (utils_eval.py) with the same eval_dict keys."""
         try:
             from src.utils.utils_eval import get_eval_dictionary  # type: ignore  (reference tree on sys.path)
-            self.eval_dict = get_eval_dictionary()
-        except ImportError:       # standalone: no eval_dict, test_step returns its tensors; a BROKEN reference install still raises
-            pass
+        except ImportError:       # standalone: the package's native metric pass (utils_eval.py); a BROKEN reference install still raises
+            from .utils_eval import get_eval_dictionary
+        self.eval_dict = get_eval_dictionary()
         self.inds, self.latentSpace_slice, self.diffs_list, self.seg_list = [], [], [], []
         self.new_size = [160, 190, 160]
         if not hasattr(self, "threshold"):
             self.threshold = {}
 
     def on_test_end(self):
-        """reference :288-291: `_test_end(self)` of the reference's utils_eval when it is importable; nothing to aggregate otherwise"""
+        """reference :288-291: `_test_end(self)` of the reference's utils_eval when it is importable, the package's native one otherwise"""
         try:
             from src.utils.utils_eval import _test_end  # type: ignore
         except ImportError:
-            return
+            from .utils_eval import _test_end
         _test_end(self)
 
     # ------------------------------------------------------------------ training (reference :114-135, :305-306)

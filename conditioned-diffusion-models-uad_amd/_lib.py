@@ -55,6 +55,9 @@ SYMBOLS = {
     "cddpm_noise_fill": (_i, [_vp, _fp, _u64, _u32, _i, _u64, _i, _i, _i, _vp]),
     "cddpm_residual_postprocess": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _vp]),
     "cddpm_simplex_fill": (_i, [_vp, _fp, _i64, _i, _i, _i, _i, C.c_double, C.c_double, _vp]),
+    "cddpm_eval_workspace_bytes": (_sz, [_i64, _i]),
+    "cddpm_eval_volume": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_double, _vp, _sz, _fp, _fp, _fp, _fp, _fp, _vp]),
+    "cddpm_eval_set": (_i, [_vp, _fp, _fp, _i64, _i, _vp, _sz, _fp, _vp]),
     "cddpm_q_sample": (_i, [_vp, _fp, _fp, _fp, _i, _fp, _fp, _i, _fp, _i, _i, _i, _vp]),
     "cddpm_set_clip_denoised": (_i, [_vp, _i]),
     "cddpm_set_accumulation_switch": (_i, [_vp, _i]),

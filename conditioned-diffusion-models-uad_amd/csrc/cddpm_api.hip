@@ -1258,6 +1258,43 @@ int cddpm_residual_postprocess(cddpm_handle h, const float* orig_dev, const floa
     return 0;
 }
 
+size_t cddpm_eval_workspace_bytes(int64_t n, int rows) {
+    if (n < 1 || n >= (1ll << 31) || rows < 0) return 0;
+    return eval_workspace_bytes((int)n, rows);
+}
+
+int cddpm_eval_volume(cddpm_handle h, const float* recon_dev, const float* orig_dev, const float* seg_dev, const float* mask_dev,
+                      const float* diff_dev, int R, int D1, int D2, int flags, double threshold, void* ws_dev, size_t ws_bytes,
+                      double* record_dev, float* row_score_dev, int32_t* row_label_dev, int32_t* row_counts_dev,
+                      uint8_t* pred_dev, void* stream) {
+    if (!h) return -1;
+    if (!recon_dev || !orig_dev || !seg_dev || !mask_dev || !diff_dev || !ws_dev || !record_dev || !row_score_dev ||
+        !row_label_dev || !row_counts_dev)
+        return fail(h, "cddpm_eval_volume: NULL argument");
+    if (R < 1 || D1 < 1 || D2 < 1 || (long long)R * D1 * D2 >= (1ll << 31)) return fail(h, "cddpm_eval_volume: bad R/D1/D2");
+    if (flags & ~(CDDPM_EVAL_VOXEL_METRICS | CDDPM_EVAL_COMPONENT_FILTER | CDDPM_EVAL_ROW_CURVE | CDDPM_EVAL_THRESHOLD_OVERRIDE))
+        return fail(h, "cddpm_eval_volume: unknown flags 0x%x", flags);
+    const size_t need = eval_workspace_bytes(R * D1 * D2, R);
+    if (ws_bytes < need) return fail(h, "cddpm_eval_volume: workspace of %zu bytes, need %zu", ws_bytes, need);
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, launch_eval_volume(recon_dev, orig_dev, seg_dev, mask_dev, diff_dev, R, D1, D2, flags, threshold, ws_dev,
+                                   ws_bytes, record_dev, row_score_dev, row_label_dev, row_counts_dev, pred_dev,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+int cddpm_eval_set(cddpm_handle h, const float* x_dev, const int8_t* y_dev, int64_t n, int healthy, void* ws_dev,
+                   size_t ws_bytes, double* out_dev, void* stream) {
+    if (!h) return -1;
+    if (!x_dev || !y_dev || !ws_dev || !out_dev) return fail(h, "cddpm_eval_set: NULL argument");
+    if (n < 1 || n >= (1ll << 31)) return fail(h, "cddpm_eval_set: n = %lld outside [1, 2^31)", (long long)n);
+    const size_t need = eval_workspace_bytes((int)n, 0);
+    if (ws_bytes < need) return fail(h, "cddpm_eval_set: workspace of %zu bytes, need %zu", ws_bytes, need);
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, launch_eval_set(x_dev, y_dev, (int)n, healthy ? 1 : 0, ws_dev, ws_bytes, out_dev, (hipStream_t)stream));
+    return 0;
+}
+
 int cddpm_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev, const int32_t* t_dev, int t_uniform,
                    const float* sqrt_ac_host, const float* sqrt_1mac_host, int T, float* out_dev, int B, int H, int W,
                    void* stream) {

@@ -218,6 +218,14 @@ void launch_residual_mask(const float* orig, const float* recon, const float* ma
                           int squared, int iters, hipStream_t stream);
 void launch_median3d(const float* in, float* out, int S, int H, int W, int k, hipStream_t stream);
 
+// segmentation metrics of the evaluation step (eval_metrics.hip; src/utils/utils_eval.py:18-297)
+size_t eval_workspace_bytes(int n, int rows);
+hipError_t launch_eval_volume(const float* recon, const float* orig, const float* seg, const float* mask, const float* diff,
+                              int R, int D1, int D2, int flags, double thr_override, void* ws, size_t ws_bytes, double* rec,
+                              float* row_score, int* row_label, int* row_counts, uint8_t* pred_out, hipStream_t s);
+hipError_t launch_eval_set(const float* x, const int8_t* y, int n, int healthy, void* ws, size_t ws_bytes, double* out,
+                           hipStream_t s);
+
 // ---- training-mode kernels of the context encoder (encoder_train.hip)
 int enc_conv_split(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);     // planes of `part` (1: not used)
 void launch_enc_conv(const float* src, const float* w_img, float* dst, int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed,

@@ -326,6 +326,69 @@ class CddpmEngine:
                                                      _stream_ptr(self.device)), "cddpm_residual_postprocess")
         return out
 
+    # ------------------------------------------------------------------ evaluation metrics (eval_metrics.hip)
+    EVAL_FLAGS = {"voxel_metrics": 1, "component_filter": 2, "row_curve": 4, "threshold_override": 8}   # include/cddpm.h
+    EVAL_RECORD, EVAL_SET_RESULT = 24, 8
+
+    def _eval_workspace(self, n: int, rows: int) -> torch.Tensor:
+        """caller-side workspace of the metric entry points: sized once per (n, rows) by cddpm_eval_workspace_bytes, grown on demand"""
+        sizes = self.__dict__.setdefault("_eval_ws_sizes", {})
+        if (n, rows) not in sizes:
+            b = int(self.lib.cddpm_eval_workspace_bytes(int(n), int(rows)))
+            if b == 0:
+                raise RuntimeError(f"cddpm_eval_workspace_bytes: {n} voxels in {rows} rows is outside the supported range")
+            sizes[(n, rows)] = b
+        need = sizes[(n, rows)]
+        ws = getattr(self, "_eval_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._eval_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def eval_volume(self, recon: torch.Tensor, orig: torch.Tensor, seg: torch.Tensor, mask: torch.Tensor, diff: torch.Tensor, *,
+                    voxel_metrics: bool, component_filter: bool, row_curve: bool, threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
+        """One volume's metric record on the device (cddpm_eval_volume; _test_step, utils_eval.py:36-178). All five volumes are
+        [R, D1, D2] fp32 with R = axis 0 of the reference's [H, W, D] volume; `diff` is the post-processed residual. threshold:
+        the test stage's override (None: the volume's own find_best_val). Returns device tensors: record [EVAL_RECORD] float64,
+        row_score [R] fp32, row_label [R] int32, row_counts [R, 3] int32 (#pred, #pred & seg, #seg, unfiltered), pred [R, D1, D2]
+        uint8 (the filtered prediction)."""
+        vols = {}
+        for name, t in (("recon", recon), ("orig", orig), ("seg", seg), ("mask", mask), ("diff", diff)):
+            vols[name] = _check_dev(t, name, self.device)
+            if t.dim() != 3 or t.shape != diff.shape:
+                raise RuntimeError(f"{name} must be an [R, D1, D2] volume of the residual's shape {tuple(diff.shape)}, got {tuple(t.shape)}")
+        R, D1, D2 = diff.shape
+        flags = ((self.EVAL_FLAGS["voxel_metrics"] if voxel_metrics else 0) | (self.EVAL_FLAGS["component_filter"] if component_filter else 0)
+                 | (self.EVAL_FLAGS["row_curve"] if row_curve else 0) | (self.EVAL_FLAGS["threshold_override"] if threshold is not None else 0))
+        ws = self._eval_workspace(R * D1 * D2, R)
+        out = dict(record=torch.empty(self.EVAL_RECORD, dtype=torch.float64, device=self.device),
+                   row_score=torch.empty(R, dtype=torch.float32, device=self.device),
+                   row_label=torch.empty(R, dtype=torch.int32, device=self.device),
+                   row_counts=torch.zeros(R, 3, dtype=torch.int32, device=self.device),
+                   pred=torch.zeros(R, D1, D2, dtype=torch.uint8, device=self.device))
+        self._ck(self.lib.cddpm_eval_volume(self._h, vols["recon"].data_ptr(), vols["orig"].data_ptr(), vols["seg"].data_ptr(),
+                                            vols["mask"].data_ptr(), vols["diff"].data_ptr(), R, D1, D2, flags,
+                                            float(threshold) if threshold is not None else 0.0, ws.data_ptr(), ws.numel(),
+                                            out["record"].data_ptr(), out["row_score"].data_ptr(), out["row_label"].data_ptr(),
+                                            out["row_counts"].data_ptr(), out["pred"].data_ptr(), _stream_ptr(self.device)),
+                 "cddpm_eval_volume")
+        return out
+
+    def eval_set(self, x: torch.Tensor, y: torch.Tensor, *, healthy: bool) -> torch.Tensor:
+        """Over an accumulated validation set (cddpm_eval_set; _test_end, utils_eval.py:247-286): x [n] fp32 residuals, y [n] int8
+        labels. Returns [EVAL_SET_RESULT] float64 on the device: AUROC, AUPRC, t_1p, t_5p, t_10p (healthy: labels read as zero),
+        best dice, its threshold (threshold['total']), max."""
+        x = _check_dev(x, "x", self.device)
+        if not isinstance(y, torch.Tensor) or not y.is_cuda or y.device != self.device or y.dtype != torch.int8:
+            raise RuntimeError(f"y must be an int8 tensor on {self.device}")
+        if x.dim() != 1 or y.shape != x.shape or x.numel() < 1:
+            raise RuntimeError(f"x and y must be non-empty 1-D tensors of one length, got {tuple(x.shape)} and {tuple(y.shape)}")
+        y = y.contiguous()
+        ws = self._eval_workspace(x.numel(), 0)
+        out = torch.empty(self.EVAL_SET_RESULT, dtype=torch.float64, device=self.device)
+        self._ck(self.lib.cddpm_eval_set(self._h, x.data_ptr(), y.data_ptr(), x.numel(), int(bool(healthy)), ws.data_ptr(), ws.numel(),
+                                         out.data_ptr(), _stream_ptr(self.device)), "cddpm_eval_set")
+        return out
+
     def simplex_noise(self, B: int, H: int, W: int, *, seed: int, octaves: int = 6, persistence: float = 0.8,
                       frequency: float = 64.0) -> torch.Tensor:
         """gen_noise for noisetype 'simplex': float16 [B,1,H,W], the same field for every batch item, bit-exact

@@ -185,6 +185,67 @@ int cddpm_residual_postprocess(cddpm_handle h, const float* orig_dev, const floa
                                int S, int H, int W, int squared, int erode_iterations, int median_k, float* tmp_dev,
                                float* out_dev, void* stream);
 
+/* ---- evaluation metrics (csrc/eval_metrics.hip) -------------------------------------------------------
+ * Replace the metric half of _test_step / _test_end (src/utils/utils_eval.py:18-194, :196-297), which the reference runs in
+ * sklearn / skimage / numpy on the CPU. Volumes are flat [R][D1][D2] fp32 on the device, R = axis 0 of the reference's
+ * [H, W, D] volume (the axis its per-slice loop walks). The caller provides the workspace (cddpm_eval_workspace_bytes);
+ * nothing allocates or synchronises inside; results stay on the device. */
+#define CDDPM_EVAL_VOXEL_METRICS 1       /* AUROC / AUPRC / find_best_val / threshold / confusion counts (:78-139) */
+#define CDDPM_EVAL_COMPONENT_FILTER 2    /* remove 26-connected components of <= 7 voxels (:98-99, :485-499) */
+#define CDDPM_EVAL_ROW_CURVE 4           /* AUROC / AUPRC of the per-row anomaly scores (:175-178) */
+#define CDDPM_EVAL_THRESHOLD_OVERRIDE 8  /* threshold the volume at `threshold` instead of the search's value (:92-93) */
+/* slots of the volume record (float64; NaN where not computed) */
+#define CDDPM_EVAL_L1_ALL 0              /* l1 / l2 reconstruction errors over all voxels, seg > 0, seg == 0 (fp32 values, :36-41) */
+#define CDDPM_EVAL_L1_LESION 1
+#define CDDPM_EVAL_L1_HEALTHY 2
+#define CDDPM_EVAL_L2_ALL 3
+#define CDDPM_EVAL_L2_LESION 4
+#define CDDPM_EVAL_L2_HEALTHY 5
+#define CDDPM_EVAL_SCORE_VOL 6           /* mean residual over mask > 0 (fp32 value, :153) */
+#define CDDPM_EVAL_LESION 7              /* #(seg > 0) */
+#define CDDPM_EVAL_VOXELS 8
+#define CDDPM_EVAL_AUROC 9               /* roc_curve + auc (:80, :549-552) */
+#define CDDPM_EVAL_AUPRC 10              /* average_precision_score (:81, :555-558) */
+#define CDDPM_EVAL_BEST_DICE 11          /* find_best_val(max_steps = 10) (:84-90) */
+#define CDDPM_EVAL_BEST_THRESHOLD 12
+#define CDDPM_EVAL_THRESHOLD 13          /* the threshold applied: the search's, or the override */
+#define CDDPM_EVAL_MAX 14                /* max of the residual */
+#define CDDPM_EVAL_PRED1_SEG0 15         /* filtered prediction 1, seg 0 */
+#define CDDPM_EVAL_PRED1_SEG1 16         /* filtered prediction 1, seg 1 */
+#define CDDPM_EVAL_ROW_AUROC 17
+#define CDDPM_EVAL_ROW_AUPRC 18
+#define CDDPM_EVAL_RECORD 24
+/* slots of the set result (float64) */
+#define CDDPM_EVAL_SET_AUROC 0
+#define CDDPM_EVAL_SET_AUPRC 1
+#define CDDPM_EVAL_SET_T1P 2             /* threshold at the first point roc_curve retains with fpr > 0.01 (:280-283) */
+#define CDDPM_EVAL_SET_T5P 3
+#define CDDPM_EVAL_SET_T10P 4
+#define CDDPM_EVAL_SET_BEST_DICE 5
+#define CDDPM_EVAL_SET_BEST_THRESHOLD 6  /* find_best_val over the set: threshold['total'] (:247-254) */
+#define CDDPM_EVAL_SET_MAX 7
+#define CDDPM_EVAL_SET_RESULT 8
+
+/* workspace bytes for n voxels in `rows` rows (rows = 0: a set search); host arithmetic, callable without a GPU */
+size_t cddpm_eval_workspace_bytes(int64_t n, int rows);
+
+/* One volume's metric record (_test_step :36-41, :78-139, :146-178). recon_dev: the squeezed final_volume; orig_dev,
+ * seg_dev, mask_dev: data_orig / data_seg / data_mask (raw, binarised inside as > 0); diff_dev: the post-processed residual
+ * (cddpm_residual_postprocess). Outputs: record_dev [CDDPM_EVAL_RECORD] float64; row_score_dev [R] fp32 (masked mean per
+ * row, 0 for a row without mask); row_label_dev [R] int32 (row has lesion); row_counts_dev [R][3] int32 (#pred, #pred & seg,
+ * #seg per row on the UNFILTERED prediction, with CDDPM_EVAL_VOXEL_METRICS); pred_dev [R*D1*D2] uint8: the filtered
+ * prediction (may be NULL). Counts are exact (integer atomics), float sums are fixed-order float64: bitwise reproducible. */
+int cddpm_eval_volume(cddpm_handle h, const float* recon_dev, const float* orig_dev, const float* seg_dev, const float* mask_dev,
+                      const float* diff_dev, int R, int D1, int D2, int flags, double threshold, void* ws_dev, size_t ws_bytes,
+                      double* record_dev, float* row_score_dev, int32_t* row_label_dev, int32_t* row_counts_dev,
+                      uint8_t* pred_dev, void* stream);
+
+/* Over an accumulated set x_dev [n] fp32 with labels y_dev [n] int8 (_test_end :247-286): healthy = 0: find_best_val ->
+ * threshold['total'], plus AUROC / AUPRC; healthy = 1: labels taken as all zero, the t_1p / t_5p / t_10p thresholds.
+ * out_dev [CDDPM_EVAL_SET_RESULT] float64. */
+int cddpm_eval_set(cddpm_handle h, const float* x_dev, const int8_t* y_dev, int64_t n, int healthy, void* ws_dev,
+                   size_t ws_bytes, double* out_dev, void* stream);
+
 /* Replaces q_sample (src/models/modules/cond_DDPM.py:548-554) fused with normalize_to_neg_one_to_one (:75):
  * out = sqrt_ac[t_b] * (2 x01 - 1) + sqrt_1mac[t_b] * noise; coefficient tables are host arrays [T]
  * uploaded on first use. Used by the single-step reconstruction (GaussianDiffusion.forward, :647-655). */
