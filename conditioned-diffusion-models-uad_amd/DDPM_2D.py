@@ -8,6 +8,9 @@ Added, behind a cfg switch that is absent (= reference behaviour) by default:
     cfg.reverse_sampling: true   ->  test-time reconstruction = the iterative reverse loop
                                      (GaussianDiffusion.p_sample_loop) instead of the single-step x0 estimate
     cfg.reverse_start_t: int     ->  start_t of that loop (0 = all `timesteps` steps)
+    cfg.conv_family: h3|x6|f32   ->  convolution family of the UNet's engine (unset: the process default, CDDPM_CONV or h3)
+    cfg.conv_fallback: x6|f32    ->  slices whose reconstruction left the fp16 range of the h3 family are run again in this exact
+                                     family, with a warning, instead of failing the batch (unset: off)
 
 `test_step` follows the reference's evaluation call (:171-286): 4 centre slices, `noise_ensemble` / `step_ensemble`
 averaging, a fresh `gen_noise` (device simplex) field per reconstruction.
@@ -128,6 +131,7 @@ class DDPM_2D(_Base):
             use_new_attention_order=True, use_spatial_transformer=_cfg_get(cfg, "spatial_transformer", False),
             transformer_depth=1)
         model.convert_to_fp16()
+        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None))
         timesteps = _cfg_get(cfg, "timesteps", 1000)
         self.test_timesteps = _cfg_get(cfg, "test_timesteps", 150)
         self.diffusion = GaussianDiffusion(

@@ -11,7 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from . import schedule as _schedule
-from .engine import CddpmEngine
+from .engine import EXACT_FAMILIES, CddpmEngine, conv_family_code
 
 
 class HipBackend:
@@ -27,6 +27,22 @@ class HipBackend:
         self.engine: Optional[CddpmEngine] = None
         self._key = None
         self._sched_key = None
+        self.conv_family: Optional[str] = None       # None: the process default (CDDPM_CONV, else h3)
+        self.conv_fallback: Optional[str] = None     # None: off; 'x6' / 'f32': re-run slices that left the fp16 range there
+        self._fallback_engine: Optional[CddpmEngine] = None
+
+    def configure(self, conv_family: Optional[str] = None, conv_fallback: Optional[str] = None):
+        """the engine's convolution family and the exact family non-finite slices are re-run in (DDPM_2D: cfg.conv_family,
+        cfg.conv_fallback); both default to unset = the behaviour without them"""
+        if conv_family is not None:
+            conv_family_code(conv_family)
+        if conv_fallback is not None:
+            conv_family_code(conv_fallback)
+            if conv_fallback not in EXACT_FAMILIES:
+                raise ValueError(f"conv_fallback must be an exact family ({' or '.join(EXACT_FAMILIES)}), got {conv_fallback!r}")
+        if (conv_family, conv_fallback) != (self.conv_family, self.conv_fallback):
+            self.conv_family, self.conv_fallback = conv_family, conv_fallback
+            self.close()
 
     # the diffusion wrapper registers its schedule here; a bare UNetModel uses the default cosine one
     def set_schedule(self, buffers: Dict[str, torch.Tensor], objective: str):
@@ -50,11 +66,12 @@ class HipBackend:
         if need:
             if e is not None:
                 e.close()
+            self._close_fallback()                   # same geometry, weights and schedule as the main engine, or none
             max_b = max(B, e.max_batch if e is not None else 1)
             max_h = max(H, e.max_h if e is not None else 0)
             max_w = max(W, e.max_w if e is not None else 0)
             e = CddpmEngine(timesteps=self.timesteps, max_batch=max_b, max_h=max_h, max_w=max_w, device=device,
-                            **self._unet_desc)
+                            conv_family=self.conv_family, **self._unet_desc)
             e.load_weights(unet.state_dict())
             self.engine, self._key, self._sched_key = e, wkey, None
         skey = (id(self.buffers), self.objective)
@@ -62,7 +79,33 @@ class HipBackend:
             bufs = self.buffers if self.buffers is not None else _schedule.schedule_buffers(self.timesteps)
             e.set_schedule(bufs, self.objective)
             self._sched_key = skey
+            self._close_fallback()
         return e
+
+    def fallback(self, unet):
+        """what the engine's `fallback=` argument takes: None when cfg.conv_fallback is unset, else a callable that creates the
+        fallback engine on the first flagged slice -- the main engine's geometry, weights and schedule in the exact family --
+        and returns the same one until the main engine is rebuilt"""
+        if self.conv_fallback is None:
+            return None
+
+        def make() -> CddpmEngine:
+            e = self.engine
+            if e is None:
+                raise RuntimeError("no main engine yet: the fallback engine mirrors it")
+            if self._fallback_engine is None:
+                fb = CddpmEngine(timesteps=e.timesteps, max_batch=e.max_batch, max_h=e.max_h, max_w=e.max_w, device=e.device,
+                                 conv_family=self.conv_fallback, **self._unet_desc)
+                fb.load_weights(unet.state_dict())
+                fb.set_schedule(self.buffers if self.buffers is not None else _schedule.schedule_buffers(self.timesteps), self.objective)
+                self._fallback_engine = fb
+            return self._fallback_engine
+        return make
+
+    def _close_fallback(self):
+        if self._fallback_engine is not None:
+            self._fallback_engine.close()
+            self._fallback_engine = None
 
     def invalidate(self):
         """the parameters were updated outside torch's version counters (the training step's Adam kernel writes them in place): the next
@@ -70,6 +113,7 @@ class HipBackend:
         self._key = None
 
     def close(self):
+        self._close_fallback()
         if self.engine is not None:
             self.engine.close()
             self.engine = None

@@ -185,7 +185,8 @@ class GaussianDiffusion(nn.Module):
             x_T = eng.noise_fill(B, H, W, seed=seed, stream_id=_synth.STREAM_XT, slice0=slice0)
         if box is not None:
             x_T = mask_x_T_to_box(x_T, box)
-        return eng.reverse(x_T, cond.float() if cond is not None else None, T, noise=z_noise, seed=seed, slice0=slice0)
+        return eng.reverse(x_T, cond.float() if cond is not None else None, T, noise=z_noise, seed=seed, slice0=slice0,
+                           fallback=self.model._hip.fallback(self.model))       # cfg.conv_fallback (None = off: the plain call)
 
     def ddim_time_pairs(self, start_t=0):
         """(time, time_next) pairs of ddim_sample (cond_DDPM.py:468-474): sampling_timesteps + 1 ints from
@@ -310,7 +311,7 @@ class GaussianDiffusion(nn.Module):
             for i, (x0, y1, x2, y3) in enumerate(boxes):
                 xb[i, :, y1:y3, x0:x2] = x[i, :, y1:y3, x0:x2]
             x = xb.contiguous()
-        out = eng.unet_forward(x, t, cond.float() if cond is not None else None)
+        out = eng.unet_forward(x, t, cond.float() if cond is not None else None, fallback=self.model._hip.fallback(self.model))
         if self.objective == "pred_noise":
             if boxes is not None:
                 target = torch.zeros_like(noise)

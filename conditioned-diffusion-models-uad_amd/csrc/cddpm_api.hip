@@ -68,6 +68,11 @@ struct cddpm_ctx {
     std::string err;
     bool weights_loaded = false, schedule_set = false;
     int cond_B = -1;
+    // convolution family of this handle (numbering of conv_mode(); cddpm_set_conv_family): what every launch and every packed
+    // weight image of the handle uses. weights_dropped: a family change freed the images of the previous family.
+    int family = conv_mode();
+    bool weights_dropped = false;
+    size_t weight_allocs_begin = 0;      // allocs[weight_allocs_begin ..) are what cddpm_load_weights uploaded
 
     std::vector<ResW> res;
     std::vector<AttnW> attn;
@@ -197,7 +202,7 @@ double conv_bytes(const ConvArgs& a) {
 // as it is computed on handles of the same maximum geometry (sharded runs: the same engine configuration on every rank).
 constexpr int KSPLIT_PLANE_FLOATS = 256 * 256 * 128;      // S * workgroups <= 256, a workgroup's tile <= 256 x 128 outputs
 int plan_ksplit(const cddpm_ctx* h, const ConvArgs& a, short* kbound) {
-    if (conv_mode() != 2 || h->cur_H <= 0) return 1;
+    if (h->family != 2 || h->cur_H <= 0) return 1;
     const bool up2 = (a.taps == 4);
     const int Hm = (int)((long long)a.H * h->d.max_h / h->cur_H), Wm = (int)((long long)a.W * h->d.max_w / h->cur_W);
     const int gh = up2 ? Hm / 2 : Hm, gw = up2 ? Wm / 2 : Wm;
@@ -258,7 +263,7 @@ int conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s) {
     }
     // large-batch plan: 256-cout workgroups where the handle's maximum geometry still fills the chip with them (a property of the
     // handle like S above, never of the call)
-    a.nb2 = ((h->nb2_now || conv_nb2_env() == 2) && conv_nb2_ok(a.Cout, conv_workgroups_at_max(h, a), 1)) ? 1 : 0;
+    a.nb2 = ((h->nb2_now || conv_nb2_env() == 2) && conv_nb2_ok(a.Cout, conv_workgroups_at_max(h, a), 1, h->family)) ? 1 : 0;
     const int nrec = (a.taps == 4) ? conv_stat_records_up2(a.H, a.W) : conv_stat_records(a.H, a.W);
     if (a.stats) {
         // a statically sized buffer against a shape-derived count: refuse to launch rather than write past the end
@@ -579,9 +584,9 @@ int upload_conv(cddpm_ctx* h, const HostWeights& hw, const std::string& p, int C
                 bool with_bias = true, int wexp = -1) {
     c->Cin = Cin; c->Cout = Cout; c->taps = taps;
     const float* w = hw.get(p + ".weight");
-    c->wexp = wexp >= 0 ? wexp : conv_weight_exp(w, (size_t)Cout * Cin * taps);
-    std::vector<float> pk(packed_conv_floats(Cout, Cin, taps));
-    pack_conv_weights(w, Cout, Cin, taps, pk.data(), c->wexp);
+    c->wexp = wexp >= 0 ? wexp : conv_weight_exp(w, (size_t)Cout * Cin * taps, h->family);
+    std::vector<float> pk(packed_conv_floats(Cout, Cin, taps, h->family));
+    pack_conv_weights(w, Cout, Cin, taps, pk.data(), c->wexp, h->family);
     if (upload(h, &c->wpk, pk.data(), pk.size())) return -1;
     if (with_bias) return upload(h, &c->bias, hw.get(p + ".bias"), Cout);
     return 0;
@@ -620,7 +625,7 @@ int gn_coef(cddpm_ctx* h, const float* x0, int C0, const float* x1, int C1, int 
     return 0;
 }
 
-void zero_conv_args(ConvArgs& a) { memset(&a, 0, sizeof a); }
+void zero_conv_args(ConvArgs& a, const cddpm_ctx* h) { memset(&a, 0, sizeof a); a.family = h->family; }
 
 // One ResBlock (src/models/modules/OpenAI_Unet.py:284-338): input x0 (+ x1 concatenated), output dst.
 int run_res(cddpm_ctx* h, const ResW& r, const float* x0, int C0, const float* x1, int C1, float* dst, int B, int H,
@@ -628,7 +633,7 @@ int run_res(cddpm_ctx* h, const ResW& r, const float* x0, int C0, const float* x
     // H, W: resolution of the block INPUT
     if (gn_coef(h, x0, C0, x1, C1, B, H * W, r.gn1, false, 0, s)) return -1;
     ConvArgs a;
-    zero_conv_args(a);
+    zero_conv_args(a, h);
     a.B = B; a.Cout = r.Cout; a.taps = 9; a.wpk = r.conv1.wpk; a.bias = r.conv1.bias; a.out = h->bufH;
     a.wscale_inv = ldexpf(1.0f, -r.conv1.wexp);
     int Ho = H, Wo = W;
@@ -655,7 +660,7 @@ int run_res(cddpm_ctx* h, const ResW& r, const float* x0, int C0, const float* x
     // out_layers: GroupNorm * (1 + scale) + shift -> SiLU -> conv, + skip
     if (gn_coef(h, h->bufH, r.Cout, nullptr, 0, B, Ho * Wo, r.gn2, true, r.eoff, s)) return -1;
     ConvArgs c;
-    zero_conv_args(c);
+    zero_conv_args(c, h);
     c.B = B; c.H = Ho; c.W = Wo; c.Cout = r.Cout; c.taps = 9;
     c.src0 = h->bufH; c.C0 = r.Cout; c.srcH = Ho; c.srcW = Wo; c.coef = h->coef; c.silu = 1;
     c.wpk = r.conv2.wpk; c.bias = r.bias2; c.out = dst; c.wscale_inv = ldexpf(1.0f, -r.conv2.wexp);
@@ -672,7 +677,7 @@ int run_attn(cddpm_ctx* h, const AttnW& w, const float* x, float* dst, int B, in
     const int N = H * W;
     if (gn_coef(h, x, w.C, nullptr, 0, B, N, w.norm, false, 0, s)) return -1;
     ConvArgs a;
-    zero_conv_args(a);
+    zero_conv_args(a, h);
     a.B = B; a.H = H; a.W = W; a.Cout = 3 * w.C; a.taps = 1;
     a.src0 = x; a.C0 = w.C; a.srcH = H; a.srcW = W; a.coef = h->coef; a.silu = 0;
     a.wpk = w.qkv.wpk; a.bias = w.qkv.bias; a.out = h->qkvbuf; a.wscale_inv = ldexpf(1.0f, -w.qkv.wexp);
@@ -682,16 +687,24 @@ int run_attn(cddpm_ctx* h, const AttnW& w, const float* x, float* dst, int B, in
         launch_attention(h->qkvbuf, h->attbuf, B, N, w.C, s);
     }
     ConvArgs p;
-    zero_conv_args(p);
+    zero_conv_args(p, h);
     p.B = B; p.H = H; p.W = W; p.Cout = w.C; p.taps = 1;
     p.src0 = h->attbuf; p.C0 = w.C; p.srcH = H; p.srcW = W;
     p.wpk = w.proj.wpk; p.bias = w.proj.bias; p.res = x; p.out = dst; p.wscale_inv = ldexpf(1.0f, -w.proj.wexp);
     return conv_launch(h, p, s);
 }
 
+// a call that needs weights on a handle that has none: which of the two reasons
+int weights_missing(cddpm_ctx* h) {
+    if (h->weights_dropped)
+        return fail(h, "the convolution family was changed after cddpm_load_weights: the packed weights of the previous family were "
+                       "dropped, load the weights (and set the schedule) again");
+    return fail(h, "weights not loaded (cddpm_load_weights)");
+}
+
 int check_call(cddpm_ctx* h, int B, int H, int W) {
     if (!h) return -1;
-    if (!h->weights_loaded) return fail(h, "weights not loaded (cddpm_load_weights)");
+    if (!h->weights_loaded) return weights_missing(h);
     if (!h->schedule_set) return fail(h, "schedule not set (cddpm_set_schedule)");
     const int q = 1 << (h->d.num_levels - 1);
     if (B < 1 || B > h->d.max_batch) return fail(h, "B=%d outside [1, max_batch=%d]", B, h->d.max_batch);
@@ -917,6 +930,7 @@ int cddpm_load_weights(cddpm_handle h, const char* const* names, const float* co
     h->gen++;
     if (h->weights_loaded) return fail(h, "weights already loaded for this handle (create a new handle)");
     HIPCHECK(h, hipSetDevice(h->device));
+    h->weight_allocs_begin = h->allocs.size();
     HostWeights hw;
     for (int i = 0; i < n; ++i) hw.m[names[i]] = {host_ptrs[i], numels[i]};
     for (const WeightSpec& w : h->wspecs) {
@@ -950,15 +964,15 @@ int cddpm_load_weights(cddpm_handle h, const char* const* names, const float* co
             // the upsampled tensor is never built: Upsample(nearest x2) + Conv3x3 (OpenAI_Unet.py:118-128, :289-293) is
             // evaluated as four 2x2-tap convolutions of the low-resolution input (4/9 of the multiplies)
             r.conv1.Cin = r.Cin; r.conv1.Cout = r.Cout; r.conv1.taps = 4;
-            std::vector<float> pk(4 * packed_conv_floats(r.Cout, r.Cin, 4));
-            r.conv1.wexp = pack_conv_weights_up2(hw.get(r.prefix + ".in_layers.2.weight"), r.Cout, r.Cin, pk.data());
+            std::vector<float> pk(4 * packed_conv_floats(r.Cout, r.Cin, 4, h->family));
+            r.conv1.wexp = pack_conv_weights_up2(hw.get(r.prefix + ".in_layers.2.weight"), r.Cout, r.Cin, pk.data(), h->family);
             if (upload(h, &r.conv1_up2, pk.data(), pk.size())) return -1;
             if (upload(h, &r.conv1.bias, hw.get(r.prefix + ".in_layers.2.bias"), r.Cout)) return -1;
         } else if (upload_conv(h, hw, r.prefix + ".in_layers.2", r.Cin, r.Cout, 9, &r.conv1)) return -1;
         if (upload_norm(h, hw, r.prefix + ".out_layers.0", r.Cout, &r.gn2)) return -1;
         // conv2 and the fused 1x1 skip_connection accumulate into the same tile: one pre-scale exponent for both
-        int e2 = conv_weight_exp(hw.get(r.prefix + ".out_layers.3.weight"), (size_t)r.Cout * r.Cout * 9);
-        if (r.has_skip) e2 = std::min(e2, conv_weight_exp(hw.get(r.prefix + ".skip_connection.weight"), (size_t)r.Cout * r.Cin));
+        int e2 = conv_weight_exp(hw.get(r.prefix + ".out_layers.3.weight"), (size_t)r.Cout * r.Cout * 9, h->family);
+        if (r.has_skip) e2 = std::min(e2, conv_weight_exp(hw.get(r.prefix + ".skip_connection.weight"), (size_t)r.Cout * r.Cin, h->family));
         if (upload_conv(h, hw, r.prefix + ".out_layers.3", r.Cout, r.Cout, 9, &r.conv2, false, e2)) return -1;
         std::vector<float> b2(hw.get(r.prefix + ".out_layers.3.bias"), hw.get(r.prefix + ".out_layers.3.bias") + r.Cout);
         if (r.has_skip) {
@@ -989,6 +1003,7 @@ int cddpm_load_weights(cddpm_handle h, const char* const* names, const float* co
         h->head_bias = hw.get("out.2.bias")[0];
     }
     h->weights_loaded = true;
+    h->weights_dropped = false;
     return 0;
 }
 
@@ -1032,7 +1047,7 @@ int cddpm_set_schedule(cddpm_handle h, const float* coef1, const float* coef2, c
 
 int cddpm_prepare_cond(cddpm_handle h, const float* cond_dev, int B, void* stream) {
     if (!h) return -1;
-    if (!h->weights_loaded) return fail(h, "weights not loaded");
+    if (!h->weights_loaded) return h->weights_dropped ? weights_missing(h) : fail(h, "weights not loaded");
     if (B < 1 || B > h->d.max_batch) return fail(h, "B=%d outside [1, %d]", B, h->d.max_batch);
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(h, hipSetDevice(h->device));
@@ -1330,6 +1345,45 @@ int cddpm_set_clip_denoised(cddpm_handle h, int on) {
     return 0;
 }
 
+int cddpm_get_conv_family(cddpm_handle h) { return h ? h->family : -1; }
+
+int cddpm_set_conv_family(cddpm_handle h, int family) {
+    if (!h) return -1;
+    if (family < 0 || family > 2) return fail(h, "cddpm_set_conv_family: unknown family %d (2 = h3, 1 = x6, 0 = f32)", family);
+    if (family == h->family) return 0;
+    HIPCHECK(h, hipSetDevice(h->device));
+    if (h->weights_loaded) {
+        // the packed images are in the previous family's format: free everything cddpm_load_weights uploaded (work in flight
+        // may still read it) and ask for the weights again
+        HIPCHECK(h, hipDeviceSynchronize());
+        drop_step_graph(h);
+        for (size_t i = h->weight_allocs_begin; i < h->allocs.size(); ++i) (void)hipFree(h->allocs[i]);
+        h->allocs.resize(h->weight_allocs_begin);
+        for (ResW& r : h->res) { r.gn1 = r.gn2 = NormW(); r.conv1 = r.conv2 = r.skip = ConvW(); r.conv1_up2 = nullptr; r.bias2 = nullptr; }
+        for (AttnW& a : h->attn) { a.norm = NormW(); a.qkv = a.proj = ConvW(); }
+        h->weights_loaded = false;
+        h->schedule_set = false;         // the embedding tables are rebuilt from the reloaded weights
+        h->cond_B = -1;
+        h->weights_dropped = true;
+    }
+    h->gen++;                            // a captured step graph has the family's kernels baked in
+    h->family = family;
+    return 0;
+}
+
+int cddpm_slice_status(cddpm_handle h, const float* x_dev, int B, int H, int W, int* status_dev, void* stream) {
+    if (!h) return -1;
+    if (!x_dev || !status_dev) return fail(h, "cddpm_slice_status: NULL argument");
+    if (B < 1 || H < 1 || W < 1 || (long long)H * W >= (1ll << 31) || ((long long)H * W) % 4)
+        return fail(h, "cddpm_slice_status: B=%d H=%d W=%d unsupported (H * W must be a multiple of 4)", B, H, W);
+    if (reinterpret_cast<uintptr_t>(x_dev) % 16) return fail(h, "cddpm_slice_status: x_dev must be 16-byte aligned");
+    HIPCHECK(h, hipSetDevice(h->device));
+    Prof prof_(h, PC_OTHER, 0.0, 4.0 * B * (double)H * W, (hipStream_t)stream);
+    launch_slice_status(x_dev, B, H * W, status_dev, (hipStream_t)stream);
+    HIPCHECK(h, hipGetLastError());
+    return 0;
+}
+
 int cddpm_set_profiling(cddpm_handle h, int on) {
     if (!h) return -1;
     h->profiling = on != 0;
@@ -1386,7 +1440,7 @@ int cddpm_op_absmax(cddpm_handle h, const float* x_dev, int64_t n, float* out_de
 int cddpm_op_pack_conv(cddpm_handle h, const float* w_dev, int Cout, int Cin, int ksize, int mode, int scale_exp, void* packed_dev,
                        void* stream) {
     if (!h) return -1;
-    if (conv_mode() != 2) return fail(h, "cddpm_op_pack_conv: the device packer serves the default convolution family (CDDPM_CONV=h3) only");
+    if (h->family != 2) return fail(h, "cddpm_op_pack_conv: the device packer serves the default convolution family (CDDPM_CONV=h3) only");
     // O / I: output / input channels of the PACKED operator (mode 1 swaps the roles of the forward tensor's dimensions)
     const int O = mode == 1 ? Cin : Cout, I = mode == 1 ? Cout : Cin;
     if (!w_dev || !packed_dev || (ksize != 1 && ksize != 3) || mode < 0 || mode > 2 || (mode == 2 && ksize != 3) || O <= 0 || I <= 0 ||
@@ -1401,7 +1455,7 @@ int cddpm_op_pack_conv(cddpm_handle h, const float* w_dev, int Cout, int Cin, in
 
 int cddpm_op_pack_conv_batch(cddpm_handle h, const cddpm_pack_job* jobs_dev, int njobs, int64_t max_units, void* stream) {
     if (!h) return -1;
-    if (conv_mode() != 2) return fail(h, "cddpm_op_pack_conv_batch: the device packer serves the default convolution family (CDDPM_CONV=h3) only");
+    if (h->family != 2) return fail(h, "cddpm_op_pack_conv_batch: the device packer serves the default convolution family (CDDPM_CONV=h3) only");
     if (!jobs_dev || njobs < 1 || njobs > 65535 || max_units < 1) return fail(h, "cddpm_op_pack_conv_batch: bad arguments");
     static_assert(sizeof(cddpm_pack_job) == sizeof(PackJob), "job table layout");
     HIPCHECK(h, hipSetDevice(h->device));
@@ -1416,7 +1470,7 @@ int cddpm_op_conv_packed(cddpm_handle h, const float* src0, int C0, const float*
                          int res_upsample, const float* skip_dev, int S0, const float* skip1_dev, int S1, const void* skip_packed_dev,
                          float* out_dev, float* stats_dev, int B, int H, int W, void* stream) {
     if (!h) return -1;
-    if (conv_mode() != 2) return fail(h, "cddpm_op_conv_packed: default convolution family (CDDPM_CONV=h3) only");
+    if (h->family != 2) return fail(h, "cddpm_op_conv_packed: default convolution family (CDDPM_CONV=h3) only");
     if ((ksize != 1 && ksize != 3) || C0 <= 0 || C0 % 32 || C1 < 0 || C1 % 32 || Cout <= 0 || Cout % 128 || Cout > 4096 || B < 1 || H < 1 || W < 1 ||
         (folded_up && (ksize != 3 || C1 || H % 2 || W % 2)) || (skip_dev && (S0 <= 0 || S0 % 32 || !skip_packed_dev || ksize != 3 || S1 < 0 || S1 % 32 || (S1 > 0 && !skip1_dev))) ||
         (C1 && !src1) || scale_exp < 0 || scale_exp > 24)
@@ -1425,7 +1479,7 @@ int cddpm_op_conv_packed(cddpm_handle h, const float* src0, int C0, const float*
     HIPCHECK(h, hipSetDevice(h->device));
     if (!bias_dev) { if (need_zero_bias(h)) return -1; bias_dev = h->zero_bias; }
     ConvArgs a;
-    zero_conv_args(a);
+    zero_conv_args(a, h);
     a.src0 = src0; a.C0 = C0; a.src1 = src1; a.C1 = C1;
     a.srcH = folded_up ? H / 2 : H; a.srcW = folded_up ? W / 2 : W;
     a.coef = coef_dev; a.silu = silu; a.wpk = static_cast<const float*>(packed_dev); a.bias = bias_dev; a.res = res_dev; a.res_up = res_upsample;
@@ -1438,7 +1492,7 @@ int cddpm_op_conv_packed(cddpm_handle h, const float* src0, int C0, const float*
     a.hi_only = train_precision() == 16 ? 1 : 0;
     // the training operators plan per call, and DO take the 256-cout workgroups wherever the call fills the chip with them: a gradient's
     // accuracy need (2e-5 of float64 autograd; SGD noise far above that) is not the 1000-step chain's, and +9...12 % per layer is
-    a.nb2 = (conv_nb2_env() >= 1 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() >= 1 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, h->family)) ? 1 : 0;
     Prof prof_(h, a.taps == 1 ? PC_CONV1 : PC_CONV3, conv_flops(a), conv_bytes(a), (hipStream_t)stream);
     launch_conv(a, (hipStream_t)stream);
     HIPCHECK(h, hipGetLastError());
@@ -1477,23 +1531,24 @@ int cddpm_op_conv(cddpm_handle h, const float* src0, int C0, const float* src1, 
     if (folded && (ksize != 3 || C1 != 0)) return fail(h, "folded upsample needs a 3x3 kernel and a single source");
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(h, hipSetDevice(h->device));
-    std::vector<float> pk(folded ? 4 * packed_conv_floats(Cout, Cin, 4) : packed_conv_floats(Cout, Cin, taps));
+    const int fam = h->family;
+    std::vector<float> pk(folded ? 4 * packed_conv_floats(Cout, Cin, 4, fam) : packed_conv_floats(Cout, Cin, taps, fam));
     int wexp = 0;
-    if (folded) wexp = pack_conv_weights_up2(w_host, Cout, Cin, pk.data());
-    else { wexp = conv_weight_exp(w_host, (size_t)Cout * Cin * taps); pack_conv_weights(w_host, Cout, Cin, taps, pk.data(), wexp); }
+    if (folded) wexp = pack_conv_weights_up2(w_host, Cout, Cin, pk.data(), fam);
+    else { wexp = conv_weight_exp(w_host, (size_t)Cout * Cin * taps, fam); pack_conv_weights(w_host, Cout, Cin, taps, pk.data(), wexp, fam); }
     float *dw = nullptr, *db = nullptr;
     HIPCHECK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
     HIPCHECK(h, hipMalloc((void**)&db, (size_t)Cout * sizeof(float)));
     HIPCHECK(h, hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(h, hipMemcpy(db, bias_host, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice));
     ConvArgs a;
-    zero_conv_args(a);
+    zero_conv_args(a, h);
     a.src0 = src0; a.C0 = C0; a.src1 = src1; a.C1 = C1;
     a.srcH = upsample ? H / 2 : H; a.srcW = upsample ? W / 2 : W; a.upsample = folded ? 0 : upsample;
     a.coef = coef_dev; a.silu = silu; a.wpk = dw; a.bias = db; a.res = res_dev; a.res_up = res_upsample;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = folded ? 4 : taps;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, h->family)) ? 1 : 0;
     launch_conv(a, s);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(s));
@@ -1512,10 +1567,11 @@ int cddpm_op_conv_skip(cddpm_handle h, const float* src0, int C0, const float* c
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(h, hipSetDevice(h->device));
     // one pre-scale exponent for both tensors, as cddpm_load_weights chooses it
-    const int wexp = std::min(conv_weight_exp(w_host, (size_t)Cout * C0 * 9), conv_weight_exp(wskip_host, (size_t)Cout * S0));
-    std::vector<float> pk(packed_conv_floats(Cout, C0, 9)), pks(packed_conv_floats(Cout, S0, 1));
-    pack_conv_weights(w_host, Cout, C0, 9, pk.data(), wexp);
-    pack_conv_weights(wskip_host, Cout, S0, 1, pks.data(), wexp);
+    const int fam = h->family;
+    const int wexp = std::min(conv_weight_exp(w_host, (size_t)Cout * C0 * 9, fam), conv_weight_exp(wskip_host, (size_t)Cout * S0, fam));
+    std::vector<float> pk(packed_conv_floats(Cout, C0, 9, fam)), pks(packed_conv_floats(Cout, S0, 1, fam));
+    pack_conv_weights(w_host, Cout, C0, 9, pk.data(), wexp, fam);
+    pack_conv_weights(wskip_host, Cout, S0, 1, pks.data(), wexp, fam);
     float *dw = nullptr, *dws = nullptr, *db = nullptr;
     HIPCHECK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
     HIPCHECK(h, hipMalloc((void**)&dws, pks.size() * sizeof(float)));
@@ -1524,12 +1580,12 @@ int cddpm_op_conv_skip(cddpm_handle h, const float* src0, int C0, const float* c
     HIPCHECK(h, hipMemcpy(dws, pks.data(), pks.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(h, hipMemcpy(db, bias_host, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice));
     ConvArgs a;
-    zero_conv_args(a);
+    zero_conv_args(a, h);
     a.src0 = src0; a.C0 = C0; a.srcH = H; a.srcW = W; a.coef = coef_dev; a.silu = silu; a.wpk = dw; a.bias = db;
     a.skip0 = skip_dev; a.S0 = S0; a.skip_wpk = dws;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = 9;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, h->family)) ? 1 : 0;
     launch_conv(a, s);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(s));
@@ -1545,9 +1601,9 @@ int cddpm_op_conv_gn(cddpm_handle h, const float* src0, int C0, const float* w_h
     if (!src0 || !w_host || !bias_host || !gamma_host || !beta_host || !out_dev || !coef_dev) return fail(h, "cddpm_op_conv_gn: NULL argument");
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(h, hipSetDevice(h->device));
-    const int wexp = conv_weight_exp(w_host, (size_t)Cout * C0 * 9);
-    std::vector<float> pk(packed_conv_floats(Cout, C0, 9));
-    pack_conv_weights(w_host, Cout, C0, 9, pk.data(), wexp);
+    const int wexp = conv_weight_exp(w_host, (size_t)Cout * C0 * 9, h->family);
+    std::vector<float> pk(packed_conv_floats(Cout, C0, 9, h->family));
+    pack_conv_weights(w_host, Cout, C0, 9, pk.data(), wexp, h->family);
     const int nrec = conv_stat_records(H, W);
     float *dw = nullptr, *db = nullptr, *rec = nullptr, *g = nullptr, *bt = nullptr;
     HIPCHECK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
@@ -1560,11 +1616,11 @@ int cddpm_op_conv_gn(cddpm_handle h, const float* src0, int C0, const float* w_h
     HIPCHECK(h, hipMemcpy(g, gamma_host, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(h, hipMemcpy(bt, beta_host, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice));
     ConvArgs a;
-    zero_conv_args(a);
+    zero_conv_args(a, h);
     a.src0 = src0; a.C0 = C0; a.srcH = H; a.srcW = W; a.wpk = dw; a.bias = db; a.stats = rec;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = 9;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, h->family)) ? 1 : 0;
     launch_conv(a, s);
     launch_gn_finalize(rec, Cout, nrec, nullptr, 0, 0, B, H * W, g, bt, nullptr, nullptr, 0, 0, nullptr, nullptr, coef_dev, s);
     HIPCHECK(h, hipGetLastError());
@@ -1612,9 +1668,9 @@ int cddpm_op_conv_dgrad(cddpm_handle h, const float* dy_dev, int Cout, const flo
         for (int ci = 0; ci < Cin; ++ci)
             for (int t = 0; t < taps; ++t)
                 wt[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = w_host[((size_t)co * Cin + ci) * taps + t];
-    const int wexp = conv_weight_exp(wt.data(), wt.size());
-    std::vector<float> pk(packed_conv_floats(Cin, Cout, taps));
-    pack_conv_weights(wt.data(), Cin, Cout, taps, pk.data(), wexp);
+    const int wexp = conv_weight_exp(wt.data(), wt.size(), h->family);
+    std::vector<float> pk(packed_conv_floats(Cin, Cout, taps, h->family));
+    pack_conv_weights(wt.data(), Cin, Cout, taps, pk.data(), wexp, h->family);
     std::vector<float> zb(Cin, 0.f);
     float *dw = nullptr, *db = nullptr;
     HIPCHECK(h, hipMalloc((void**)&dw, pk.size() * sizeof(float)));
@@ -1622,11 +1678,11 @@ int cddpm_op_conv_dgrad(cddpm_handle h, const float* dy_dev, int Cout, const flo
     HIPCHECK(h, hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(h, hipMemcpy(db, zb.data(), (size_t)Cin * sizeof(float), hipMemcpyHostToDevice));
     ConvArgs a;
-    zero_conv_args(a);
+    zero_conv_args(a, h);
     a.src0 = dy_dev; a.C0 = Cout; a.srcH = H; a.srcW = W; a.wpk = dw; a.bias = db;
     a.wscale_inv = ldexpf(1.0f, -wexp);
     a.out = dx_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cin; a.taps = taps;
-    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1)) ? 1 : 0;
+    a.nb2 = (conv_nb2_env() == 2 && conv_nb2_ok(a.Cout, conv_workgroups_of_call(a), 1, h->family)) ? 1 : 0;
     launch_conv(a, s);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipStreamSynchronize(s));
@@ -1969,13 +2025,13 @@ int cddpm_stat_records(int H, int W, int kind) {
 
 size_t cddpm_packed_conv_bytes(int Cout, int Cin, int taps) {
     if (Cout <= 0 || Cin <= 0 || Cout % 128 || Cin % 32 || (taps != 1 && taps != 9 && taps != 4)) return 0;
-    return packed_conv_floats(Cout, Cin, taps) * sizeof(float);
+    return packed_conv_floats(Cout, Cin, taps, conv_mode()) * sizeof(float);      // handle-less: the process default family
 }
 
 int cddpm_pack_conv_weights(const float* w_host, int Cout, int Cin, int taps, void* dst_host, int* scale_exp_out) {
     if (!w_host || !dst_host || cddpm_packed_conv_bytes(Cout, Cin, taps) == 0) return -1;
-    const int wexp = conv_weight_exp(w_host, (size_t)Cout * Cin * taps);
-    pack_conv_weights(w_host, Cout, Cin, taps, static_cast<float*>(dst_host), wexp);
+    const int wexp = conv_weight_exp(w_host, (size_t)Cout * Cin * taps, conv_mode());     // handle-less: the process default family
+    pack_conv_weights(w_host, Cout, Cin, taps, static_cast<float*>(dst_host), wexp, conv_mode());
     if (scale_exp_out) *scale_exp_out = wexp;
     return conv_mode();
 }

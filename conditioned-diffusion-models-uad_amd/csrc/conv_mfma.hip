@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
 }
 
 void launch_conv(const ConvArgs& a, hipStream_t stream) {
-    if (conv_mode() != 0) { launch_conv_split(a, stream); return; }
+    if (a.family != 0) { launch_conv_split(a, stream); return; }
     const bool up2 = (a.taps == 4);
     const int gh = up2 ? a.H / 2 : a.H, gw = up2 ? a.W / 2 : a.W;
     const int tilesX = (gw + 31) / 32, tilesY = (gh + 3) / 4;
@@ -360,14 +360,14 @@ void launch_conv(const ConvArgs& a, hipStream_t stream) {
     else hipLaunchKernelGGL((conv_mfma_kernel<1>), dim3(grid), dim3(256), need1, stream, a);
 }
 
-size_t packed_conv_floats(int Cout, int Cin, int taps) {
+size_t packed_conv_floats(int Cout, int Cin, int taps, int family) {
     const size_t n = (size_t)Cout * Cin * taps;
-    return conv_mode() == 1 ? n + n / 2 : n;      // x6: three bf16 per weight; h3: two fp16; f32: one float
+    return family == 1 ? n + n / 2 : n;      // x6: three bf16 per weight; h3: two fp16; f32: one float
 }
 
 // w: PyTorch [Cout][Cin][k][k] (taps = k*k, tap = ky*3+kx) -> [Cout/128][Cin/32][taps][128][8 slots][4]
-void pack_conv_weights(const float* w, int Cout, int Cin, int taps, float* dst, int wexp) {
-    if (conv_mode() != 0) { pack_conv_weights_split(w, Cout, Cin, taps, dst, wexp); return; }
+void pack_conv_weights(const float* w, int Cout, int Cin, int taps, float* dst, int wexp, int family) {
+    if (family != 0) { pack_conv_weights_split(w, Cout, Cin, taps, dst, wexp, family); return; }
     const int ncb = Cout / 128, nch = Cin / 32;
     for (int cb = 0; cb < ncb; ++cb)
         for (int ch = 0; ch < nch; ++ch)
@@ -389,7 +389,7 @@ void pack_conv_weights(const float* w, int Cout, int Cin, int taps, float* dst, 
 //   rows  a = 0: ty 0 <- ky {0},    ty 1 <- ky {1, 2};   a = 1: ty 0 <- ky {0, 1}, ty 1 <- ky {2}   (columns alike)
 // dst: [4 classes][Cout/128][Cin/32][4 taps][image], each class packed like pack_conv_weights with taps = 4
 // (4 * packed_conv_floats(Cout, Cin, 4) floats).
-int pack_conv_weights_up2(const float* w /*[Cout][Cin][3][3]*/, int Cout, int Cin, float* dst) {
+int pack_conv_weights_up2(const float* w /*[Cout][Cin][3][3]*/, int Cout, int Cin, float* dst, int family) {
     std::vector<float> wf((size_t)Cout * Cin * 4);
     int wexp = 24;      // one exponent for the four classes: they share the bias / epilogue of one launch
     for (int pass = 0; pass < 2; ++pass)
@@ -405,8 +405,8 @@ int pack_conv_weights_up2(const float* w /*[Cout][Cin][3][3]*/, int Cout, int Ci
                         for (int kx = kx0; kx <= kx1; ++kx) acc += (double)w[oc * 9 + ky * 3 + kx];
                     wf[oc * 4 + ty * 2 + tx] = (float)acc;
                 }
-        if (pass == 0) { const int e = conv_weight_exp(wf.data(), wf.size()); if (e < wexp) wexp = e; }
-        else pack_conv_weights(wf.data(), Cout, Cin, 4, dst + (size_t)cls * packed_conv_floats(Cout, Cin, 4), wexp);
+        if (pass == 0) { const int e = conv_weight_exp(wf.data(), wf.size(), family); if (e < wexp) wexp = e; }
+        else pack_conv_weights(wf.data(), Cout, Cin, 4, dst + (size_t)cls * packed_conv_floats(Cout, Cin, 4, family), wexp, family);
     }
     return wexp;
 }

@@ -726,13 +726,13 @@ int conv_nb2_env() {
     static const int v = [] { const char* e = getenv("CDDPM_NB2"); return (e && e[0] == '0') ? 0 : (e && !strcmp(e, "force")) ? 2 : 1; }();
     return v;
 }
-bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit) {
+bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit, int family) {
     const int on = conv_nb2_env();
-    return on && conv_mode() == 2 && ksplit <= 1 && (Cout % 256) == 0 && (on == 2 || workgroups128 >= 512);
+    return on && family == 2 && ksplit <= 1 && (Cout % 256) == 0 && (on == 2 || workgroups128 >= 512);
 }
 
 void launch_conv_split(const ConvArgs& a, hipStream_t stream) {
-    if (conv_mode() == 1) launch_split<3>(a, stream);
+    if (a.family == 1) launch_split<3>(a, stream);
     else launch_split<2>(a, stream);
 }
 
@@ -754,8 +754,8 @@ static inline uint16_t f16_rne(float x) { const _Float16 h = (_Float16)x; uint16
 static inline float f16_to_f(uint16_t b) { _Float16 h; memcpy(&h, &b, 2); return (float)h; }
 
 // power-of-two pre-scale of a weight tensor for the fp16 split: the largest e in [0, 24] with max|w| * 2^e < 2^14
-int conv_weight_exp(const float* w, size_t n) {
-    if (conv_mode() != 2) return 0;
+int conv_weight_exp(const float* w, size_t n, int family) {
+    if (family != 2) return 0;
     float mx = 0.f;
     for (size_t i = 0; i < n; ++i) { const float v = w[i] < 0 ? -w[i] : w[i]; if (v > mx) mx = v; }
     int e = 24;
@@ -766,10 +766,10 @@ int conv_weight_exp(const float* w, size_t n) {
 // w: PyTorch [Cout][Cin][k][k] (taps = k*k) -> [Cout/128][Cin/32][taps][128 rows][4 NS slots][8 x 16 bit]
 //   NS = 3 (bf16): slot (split s, u = channel/8 in the chunk) of row j at 4 s + (u ^ ((j>>2)&3)); 6 bytes per weight
 //   NS = 2 (fp16): w * 2^wexp is split; slot at (4 s + u) ^ ((j>>1)&7); 4 bytes per weight
-void pack_conv_weights_split(const float* w, int Cout, int Cin, int taps, void* dst_, int wexp) {
+void pack_conv_weights_split(const float* w, int Cout, int Cin, int taps, void* dst_, int wexp, int family) {
     uint16_t* dst = static_cast<uint16_t*>(dst_);
     const int ncb = Cout / 128, nch = Cin / 32;
-    const int ns = (conv_mode() == 1) ? 3 : 2, sp = 4 * ns;
+    const int ns = (family == 1) ? 3 : 2, sp = 4 * ns;
     for (int cb = 0; cb < ncb; ++cb)
         for (int ch = 0; ch < nch; ++ch)
             for (int t = 0; t < taps; ++t) {

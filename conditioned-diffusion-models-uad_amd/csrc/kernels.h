@@ -34,7 +34,7 @@ struct ConvArgs {
     // optional GroupNorm statistics of the OUTPUT tensor, produced by the epilogue: fp32 records
     // [B][nrec = 2 * tilesX * tilesY][Cout][2] = per-channel (sum, sum of squares) over the 64 pixels a wave owns
     float* stats;
-    float wscale_inv;    // conv_mode() == 2: 2^-wexp of the packed weights (main and skip segment share it); else unused
+    float wscale_inv;    // family 2: 2^-wexp of the packed weights (main and skip segment share it); else unused
     // split-K (fp16-split family only; 0 / 1 = off): the K loop (32-channel chunks of the main segment, then of the skip segment)
     // is cut into `ksplit` consecutive ranges kbound[j] .. kbound[j + 1]; workgroup (tile, j) stores its scaled raw sums to plane j
     // of `out` ([ksplit][B][H][W][Cout]; the caller passes no bias / residual / stats) and launch_conv_reduce combines the planes.
@@ -47,8 +47,11 @@ struct ConvArgs {
     // fp16-split family, unsplit K: 1 = workgroups of 256 pixels x 256 couts (two cout blocks per workgroup sharing the
     // chunk's transformed patch; two-level accumulation, see conv_x6.hip). Decided by the caller with conv_nb2_ok.
     int nb2;
+    // convolution family of the launch (the numbering of conv_mode()): a property of the calling handle, which also fixes the
+    // format of `wpk` / `skip_wpk`. Every ConvArgs is built by a handle-taking path and carries its handle's family.
+    int family;
 };
-bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit);
+bool conv_nb2_ok(int Cout, long long workgroups128, int ksplit, int family);
 int conv_nb2_env();      // CDDPM_NB2: 0 never, 1 by plan (default), 2 forced
 // out[b][p][c] = ((plane 0 + plane 1) + ...) + bias[c] + residual, in this fixed order; optional GroupNorm statistics records of
 // `out`: one record per 64 consecutive pixels, [B][ceil(HW / 64)][Cout][2]
@@ -62,18 +65,20 @@ void launch_conv(const ConvArgs& a, hipStream_t stream);
 // fp32-accurate variants on the 16-bit matrix pipe (conv_x6.hip): operands split into 16-bit terms whose partial
 // products are exact in fp32. conv_mode(): 2 = fp16 two-term split, three MFMAs per product group (default,
 // CDDPM_CONV=h3 or unset); 1 = bf16 three-term split, six MFMAs (CDDPM_CONV=x6); 0 = the fp32-MFMA kernels of
-// conv_mfma.hip (CDDPM_CONV=f32). Chosen once per process; it also selects the packed weight format.
+// conv_mfma.hip (CDDPM_CONV=f32). conv_mode() is the PROCESS DEFAULT, read once: the family a new handle starts with and the one
+// the handle-less helpers use. A handle carries its own family (cddpm_set_conv_family); launchers and packers take it as
+// `family` (ConvArgs::family) and never read conv_mode() themselves. The family also selects the packed weight format.
 int conv_mode();
 void launch_conv_split(const ConvArgs& a, hipStream_t stream);
 // mode 2 only (else 0): power-of-two pre-scale exponent of a weight tensor, max|w| * 2^e in [2^13, 2^14)
-int conv_weight_exp(const float* w, size_t n);
-void pack_conv_weights_split(const float* w /*[Cout][Cin][k][k]*/, int Cout, int Cin, int taps, void* dst, int wexp);
+int conv_weight_exp(const float* w, size_t n, int family);
+void pack_conv_weights_split(const float* w /*[Cout][Cin][k][k]*/, int Cout, int Cin, int taps, void* dst, int wexp, int family);
 
 // packed weight image sizes / packing (host side, cddpm_api.hip)
 // fp32 layout: [Cout/128][Cin/32][taps][128 rows x 8 slots of float4], slot s of row j stored at s ^ ((j>>1)&7)
 // x6 layout  : [Cout/128][Cin/32][taps][128 rows x 12 slots of 8 bf16] (conv_x6.hip), 1.5 floats per weight
 // split layouts (conv_x6.hip): [..][128 rows x 4 NS slots of 8 x 16 bit]: 1.5 (bf16 x 3) | 1 (fp16 x 2) floats per weight
-size_t packed_conv_floats(int Cout, int Cin, int taps);
+size_t packed_conv_floats(int Cout, int Cin, int taps, int family);
 // wexp: conv_weight_exp() of the tensor (and of every tensor accumulated into the same output tile); ignored unless mode 2
 // device packer of the fp16 two-term family (mode 0 forward, 1 transposed + flipped for the input gradient, 2 folded upsample classes) and
 // max |x| (the power-of-two pre-scale is chosen from it on the host)
@@ -83,10 +88,10 @@ void launch_pack_conv_split(const float* w_dev, int O, int I, int taps, int mode
 struct PackJob { const float* w; void* dst; int O, I, taps, mode, wexp, cls; };
 void launch_pack_conv_split_batch(const PackJob* jobs_dev, int njobs, long long max_units, hipStream_t stream);
 void launch_absmax(const float* x, long long n, float* out, hipStream_t stream);
-void pack_conv_weights(const float* w /*[Cout][Cin][k][k]*/, int Cout, int Cin, int taps, float* dst, int wexp);
+void pack_conv_weights(const float* w /*[Cout][Cin][k][k]*/, int Cout, int Cin, int taps, float* dst, int wexp, int family);
 // folded weights of nearest-x2-upsample + 3x3: 4 parity classes x 4 taps = 4 * packed_conv_floats(Cout, Cin, 4) floats
 // returns the pre-scale exponent it chose for the folded weights (0 unless mode 2)
-int pack_conv_weights_up2(const float* w /*[Cout][Cin][3][3]*/, int Cout, int Cin, float* dst);
+int pack_conv_weights_up2(const float* w /*[Cout][Cin][3][3]*/, int Cout, int Cin, float* dst, int family);
 
 // ------------------------------------------------------------------------------------------------
 // GroupNorm(32) statistics and per-(sample, channel) coefficients (norm_kernels.hip)
@@ -123,6 +128,9 @@ void launch_fill_int(int* p, int n, int v, hipStream_t stream);
 void launch_add_int(int* p, int n, int v, hipStream_t stream);
 // dst[i] = clamp(src[i], lo, hi): per-sample timesteps handed in by the caller index device tables
 void launch_copy_clamp_int(int* dst, const int* src, int n, int lo, int hi, hipStream_t stream);
+// status[b] = 1 if slice b of x [B][HW] holds an inf or a NaN, else 0; HW a multiple of 4, x 16-byte aligned. One launch, one
+// workgroup per slice, every status word written (nothing to clear first)
+void launch_slice_status(const float* x, int B, int HW, int* status, hipStream_t stream);
 
 // posterior step (cond_DDPM.py:391-444): x <- c1[t] * x0hat + c2[t] * x + exp(0.5 logvar[t]) * z (t > 0)
 struct StepArgs {

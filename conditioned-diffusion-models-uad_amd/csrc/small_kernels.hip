@@ -326,6 +326,37 @@ void launch_fill_int(int* p, int n, int v, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-slice status of a [B][HW] fp32 tensor: status[b] = 1 when slice b holds an inf or a NaN (exponent field all ones), else 0.
+// One workgroup of 16 waves per slice, 16-B loads (four in flight per lane), the largest exponent field seen is reduced over the
+// wave by __shfl_xor and over the 16 waves through one LDS step; lane 0 stores the word. Every status word is written by exactly
+// one workgroup, so nothing is cleared first and no atomics are needed: one launch serves the whole batch.
+// ------------------------------------------------------------------------------------------------
+constexpr int STATUS_THREADS = 1024;
+__global__ __launch_bounds__(STATUS_THREADS) void slice_status_kernel(const float* __restrict__ x, int nquad, int* __restrict__ status) {
+    __shared__ unsigned wave_max[STATUS_THREADS / 64];
+    const uint4* src = reinterpret_cast<const uint4*>(x) + (size_t)blockIdx.x * nquad;
+    unsigned m = 0;
+#pragma unroll 4
+    for (int q = threadIdx.x; q < nquad; q += STATUS_THREADS) {
+        const uint4 v = src[q];
+        m = max(max(m, v.x & 0x7f800000u), max(max(v.y & 0x7f800000u, v.z & 0x7f800000u), v.w & 0x7f800000u));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d, 64));
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int i = 0; i < STATUS_THREADS / 64; ++i) t = max(t, wave_max[i]);
+        status[blockIdx.x] = (t == 0x7f800000u) ? 1 : 0;
+    }
+}
+void launch_slice_status(const float* x, int B, int HW, int* status, hipStream_t stream) {
+    hipLaunchKernelGGL(slice_status_kernel, dim3(B), dim3(STATUS_THREADS), 0, stream, x, HW / 4, status);
+}
+
+// ------------------------------------------------------------------------------------------------
 // counter RNG: Philox4x32-10, key = seed, counter = (quad, t, slice, stream) -- must match synth.py
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,

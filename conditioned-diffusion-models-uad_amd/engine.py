@@ -6,7 +6,8 @@ every FLOP of the path runs in csrc/*.hip through the C ABI of include/cddpm.h.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Mapping, Optional, Sequence
+import warnings
+from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -14,6 +15,32 @@ import torch
 from . import _lib
 
 OBJECTIVES = {"pred_x0": 0, "pred_noise": 1}
+# convolution families of a handle, in the numbering of include/cddpm.h (cddpm_set_conv_family)
+CONV_FAMILIES = {"h3": 2, "x6": 1, "f32": 0}
+EXACT_FAMILIES = ("x6", "f32")      # no range limit on the activations: what a fallback engine must be
+
+
+def conv_family_code(name: str) -> int:
+    """'h3' / 'x6' / 'f32' -> the library's family number; anything else is a ValueError (no GPU needed)"""
+    if not isinstance(name, str) or name not in CONV_FAMILIES:
+        raise ValueError(f"unknown convolution family {name!r}: expected one of {', '.join(CONV_FAMILIES)}")
+    return CONV_FAMILIES[name]
+
+
+def flagged_runs(flags: Sequence) -> List[Tuple[int, int]]:
+    """Maximal contiguous runs [i, j) of truthy entries of a per-slice flag sequence: [0,1,1,0,1] -> [(1,3),(4,5)].
+    Runs, not single slices, because the device Philox keys a slice's noise by slice0 + its position in the batch: a run
+    re-submitted with slice0 + i draws what its slices drew in the whole batch."""
+    runs, start = [], None
+    for k, f in enumerate(flags):
+        if f and start is None:
+            start = k
+        elif not f and start is not None:
+            runs.append((start, k))
+            start = None
+    if start is not None:
+        runs.append((start, len(flags)))
+    return runs
 
 
 def _stream_ptr(device) -> int:
@@ -36,7 +63,10 @@ class CddpmEngine:
 
     def __init__(self, *, model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3,
                  attention_resolutions=(3, 6, 12), head_channels=64, cond_dim=128, timesteps=1000,
-                 max_batch=1, max_h=128, max_w=128, device=None, in_channels=1, out_channels=1):
+                 max_batch=1, max_h=128, max_w=128, device=None, in_channels=1, out_channels=1, conv_family=None):
+        """conv_family: None (the process default: CDDPM_CONV, else h3), 'h3', 'x6' or 'f32' -- set on the handle before any
+        weights are loaded."""
+        family = None if conv_family is None else conv_family_code(conv_family)
         self.lib = _lib.load_library()
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device visible: the cDDPM HIP path needs an MI355X (gfx950); there is no CPU fallback")
@@ -65,6 +95,8 @@ class CddpmEngine:
             self._h = None
             raise RuntimeError(f"cddpm_create failed: {msg}")
         self._keep = []   # tensors whose pointers the library may still read (taps)
+        if family is not None:
+            self._ck(self.lib.cddpm_set_conv_family(self._h, family), "cddpm_set_conv_family")
 
     # ------------------------------------------------------------------ lifetime / errors
     def close(self):
@@ -84,6 +116,16 @@ class CddpmEngine:
             raise RuntimeError(f"{what} failed: {self.lib.cddpm_last_error(self._h).decode()}")
 
     # ------------------------------------------------------------------ setup
+    @property
+    def conv_family(self) -> str:
+        code = self.lib.cddpm_get_conv_family(self._h)
+        return {v: k for k, v in CONV_FAMILIES.items()}[code]
+
+    def set_conv_family(self, name: str):
+        """Change the handle's convolution family. Packed weights belong to a family: after a change to a DIFFERENT family the
+        caller must call load_weights (and set_schedule) again -- until then every forward / reverse call raises."""
+        self._ck(self.lib.cddpm_set_conv_family(self._h, conv_family_code(name)), "cddpm_set_conv_family")
+
     def weight_names(self):
         n = self.lib.cddpm_num_weights(self._h)
         return [(self.lib.cddpm_weight_name(self._h, i).decode(), int(self.lib.cddpm_weight_numel(self._h, i)))
@@ -134,9 +176,12 @@ class CddpmEngine:
         self._cond_keep = cond
 
     # ------------------------------------------------------------------ the path
-    def unet_forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def unet_forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, *, fallback=None) -> torch.Tensor:
         """UNetModel.forward: x [B,1,H,W] fp32 on device, t int or int tensor [B]; cond [B,cond_dim] or None
-        to reuse the context of the previous prepare_cond."""
+        to reuse the context of the previous prepare_cond. fallback: as in `reverse` (needs `cond` when the model is conditional:
+        the fallback engine prepares the flagged slices' context itself)."""
+        if fallback is not None:
+            return self._unet_forward_with_fallback(x, t, cond, fallback)
         x = _check_dev(x, "x", self.device)
         B, c, H, W = x.shape
         if c != 1:
@@ -165,9 +210,90 @@ class CddpmEngine:
         return t.to(self.device, torch.int32).contiguous()
 
     def reverse(self, x_T: torch.Tensor, cond: Optional[torch.Tensor], t_start: int, *, noise: Optional[torch.Tensor] = None,
-                seed: int = 0, slice0: int = 0) -> torch.Tensor:
+                seed: int = 0, slice0: int = 0, fallback=None) -> torch.Tensor:
         """p_sample_loop from x_T: steps t_start-1 .. 0, returns the reconstruction in [0,1] (new tensor).
-        noise: [t_start, B, 1, H, W] with z_t at index t (index 0 unused), or None for the device Philox."""
+        noise: [t_start, B, 1, H, W] with z_t at index t (index 0 unused), or None for the device Philox.
+        fallback: None, or an engine of an exact family ('x6' / 'f32') with this engine's geometry, weights and schedule (or a
+        callable returning one, called on the first flagged slice): slices whose result is not finite -- an activation left the
+        fp16 range of the h3 family -- are run again on it from their x_T, in contiguous runs, and scattered back; every other
+        slice keeps the bits of the plain call. One warning names the count; a slice still not finite afterwards (a NaN in the
+        input) raises FloatingPointError."""
+        if fallback is not None:
+            return self._reverse_with_fallback(x_T, cond, t_start, noise, seed, slice0, fallback)
+        x = self.reverse_unchecked(x_T, cond, t_start, noise=noise, seed=seed, slice0=slice0)
+        self._check_finite(x, "cddpm_reverse")
+        return x
+
+    # ------------------------------------------------------------------ per-slice fallback out of the fp16 range
+    def slice_status(self, x: torch.Tensor) -> torch.Tensor:
+        """int32 [B] on the device: 1 where slice b of x [B,1,H,W] holds an inf or a NaN, else 0 (cddpm_slice_status: one launch,
+        no host synchronisation)"""
+        x = _check_dev(x, "x", self.device)
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise RuntimeError("x must be [B,1,H,W]")
+        B, _c, H, W = x.shape
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._ck(self.lib.cddpm_slice_status(self._h, x.data_ptr(), B, H, W, status.data_ptr(), _stream_ptr(self.device)),
+                 "cddpm_slice_status")
+        return status
+
+    def _fallback_engine(self, fallback) -> "CddpmEngine":
+        fb = fallback() if callable(fallback) and not isinstance(fallback, CddpmEngine) else fallback
+        if not isinstance(fb, CddpmEngine):
+            raise RuntimeError(f"fallback must be a CddpmEngine (or a callable returning one), got {type(fb).__name__}")
+        if fb.conv_family not in EXACT_FAMILIES:
+            raise RuntimeError(f"the fallback engine must be of an exact convolution family ({' or '.join(EXACT_FAMILIES)}), "
+                               f"got {fb.conv_family}")
+        if (fb.max_batch, fb.max_h, fb.max_w, fb.timesteps) != (self.max_batch, self.max_h, self.max_w, self.timesteps):
+            raise RuntimeError("the fallback engine must be created with the same geometry (the kernel plan is part of a slice's bits)")
+        if fb.device != self.device:
+            raise RuntimeError(f"the fallback engine lives on {fb.device}, this engine on {self.device}")
+        return fb
+
+    def _rerun_flagged(self, out: torch.Tensor, fallback, what: str, rerun: Callable[["CddpmEngine", int, int], torch.Tensor]):
+        """the shared tail of the fallback paths: flags of `out` (B ints to the host), `rerun(engine, i, j)` for every flagged run,
+        results scattered into `out`, one warning, and the existing error when a re-run slice is still not finite"""
+        flags = self.slice_status(out).cpu().tolist()
+        runs = flagged_runs(flags)
+        if not runs:
+            return out
+        fb = self._fallback_engine(fallback)
+        for i, j in runs:
+            out[i:j] = rerun(fb, i, j)
+        n = sum(j - i for i, j in runs)
+        warnings.warn(f"{what}: {n} of {len(flags)} slices left the fp16 range of the {self.conv_family} convolution family and were "
+                      f"run again in the {fb.conv_family} family (slices {', '.join(f'[{i}, {j})' for i, j in runs)})", RuntimeWarning,
+                      stacklevel=4)
+        still = [k for i, j in runs for k, f in zip(range(i, j), self.slice_status(out[i:j]).cpu().tolist()) if f]
+        if still:
+            raise FloatingPointError(f"{what}: slices {still} are still non-finite after the re-run in the exact {fb.conv_family} "
+                                     "convolution family: the input or the weights hold non-finite values, not an fp16 overflow.")
+        return out
+
+    def _reverse_with_fallback(self, x_T, cond, t_start, noise, seed, slice0, fallback):
+        x_T = _check_dev(x_T, "x_T", self.device)
+        out = self.reverse_unchecked(x_T, cond, t_start, noise=noise, seed=seed, slice0=slice0)
+        B, _c, H, W = x_T.shape
+        nz = None if noise is None else _check_dev(noise, "noise", self.device).reshape(t_start, B, 1, H, W)
+
+        def rerun(fb, i, j):
+            return fb.reverse_unchecked(x_T[i:j], None if cond is None else cond[i:j].contiguous(), t_start,
+                                        noise=None if nz is None else nz[:, i:j].contiguous(), seed=seed, slice0=slice0 + i)
+        return self._rerun_flagged(out, fallback, "cddpm_reverse", rerun)
+
+    def _unet_forward_with_fallback(self, x, t, cond, fallback):
+        if cond is None and self.cond_dim > 0:
+            raise RuntimeError("unet_forward(fallback=...) needs cond: the fallback engine prepares the flagged slices' context itself")
+        x = _check_dev(x, "x", self.device)
+        out = self.unet_forward(x, t, cond)
+
+        def rerun(fb, i, j):
+            return fb.unet_forward(x[i:j], t[i:j] if isinstance(t, torch.Tensor) else t, None if cond is None else cond[i:j].contiguous())
+        return self._rerun_flagged(out, fallback, "cddpm_unet_forward", rerun)
+
+    def reverse_unchecked(self, x_T: torch.Tensor, cond: Optional[torch.Tensor], t_start: int, *, noise: Optional[torch.Tensor] = None,
+                          seed: int = 0, slice0: int = 0) -> torch.Tensor:
+        """`reverse` without the final finiteness check (the fallback path reads per-slice flags instead)"""
         x = _check_dev(x_T, "x_T", self.device).clone()
         B, c, H, W = x.shape
         if c != 1:
@@ -181,7 +307,6 @@ class CddpmEngine:
             nptr = noise.data_ptr()
         self._ck(self.lib.cddpm_reverse(self._h, x.data_ptr(), nptr, seed, slice0, t_start, B, H, W,
                                         _stream_ptr(self.device)), "cddpm_reverse")
-        self._check_finite(x, "cddpm_reverse")
         return x
 
     def reverse_two_streams(self, twin: "CddpmEngine", x_T: torch.Tensor, cond: Optional[torch.Tensor], t_start: int, *, seed: int = 0,

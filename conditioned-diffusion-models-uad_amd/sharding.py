@@ -68,9 +68,10 @@ def reconstruct_sharded(n_slices: int, shape_hw: Tuple[int, int], reconstruct_ch
 
 
 def residual_maps_sharded(engine, n_slices: int, H: int, W: int, *, seed_inputs: int, seed_cond: int, seed_noise: int,
-                          t_start: int, chunk: int = 64, gather: str = "all", progress=None) -> Optional[torch.Tensor]:
+                          t_start: int, chunk: int = 64, gather: str = "all", progress=None, fallback=None) -> Optional[torch.Tensor]:
     """BASELINE config 4: synthetic slices x in (0,1), reconstruct each from noise, gather |x - reco|.
-    progress: optional callable(slice0, count) called before every chunk (a long run's sign of life)."""
+    progress: optional callable(slice0, count) called before every chunk (a long run's sign of life).
+    fallback: handed to `engine.reverse` (an engine of an exact convolution family for the slices that leave the fp16 range)."""
     from . import synth
 
     dev = engine.device
@@ -81,7 +82,7 @@ def residual_maps_sharded(engine, n_slices: int, H: int, W: int, *, seed_inputs:
         x = torch.from_numpy(synth.synth_slices(seed_inputs, slice0, count, H, W)).to(dev)
         cond = torch.from_numpy(synth.synth_cond(seed_cond, slice0, count)).to(dev)
         x_T = engine.noise_fill(count, H, W, seed=seed_noise, stream_id=synth.STREAM_XT, slice0=slice0)
-        reco = engine.reverse(x_T, cond, t_start, seed=seed_noise, slice0=slice0)
+        reco = engine.reverse(x_T, cond, t_start, seed=seed_noise, slice0=slice0, fallback=fallback)
         return (x - reco).abs()
 
     return reconstruct_sharded(n_slices, (H, W), run, chunk=chunk, gather=gather)

@@ -15,8 +15,9 @@
  *   - one handle per device; a handle is not thread-safe.
  *
  * Environment variables the library reads
- *   - CDDPM_CONV: convolution family and packed weight format. h3 or unset = fp16 two-term split (default), x6 = bf16
- *     three-term split, f32 = fp32 MFMA (see cddpm_pack_conv_weights).
+ *   - CDDPM_CONV: the PROCESS DEFAULT convolution family and packed weight format: what a new handle starts with and what the
+ *     handle-less helpers (cddpm_pack_conv_weights, cddpm_packed_conv_bytes) use. h3 or unset = fp16 two-term split (default),
+ *     x6 = bf16 three-term split, f32 = fp32 MFMA (see cddpm_pack_conv_weights). A handle overrides it: cddpm_set_conv_family.
  *   - CDDPM_NB2: 256-cout workgroups of the default family. Unset = where the plan takes them (cddpm_set_accumulation_switch,
  *     cddpm_op_conv_packed); 0 = never; force = wherever the kernel can, in every entry point and at any geometry.
  *   - CDDPM_GRAPH: 1 = cddpm_reverse / cddpm_reverse_range (>= 5 steps, not while profiling) replay each step as a captured
@@ -127,6 +128,26 @@ int cddpm_reverse(cddpm_handle h, float* img_inout_dev, const float* noise_dev, 
  * Single forwards (cddpm_unet_forward, cddpm_ddim_step) use the three-level kernel. cddpm_op_conv_packed plans per call instead: it
  * takes the 256-cout form wherever the call itself has >= 512 workgroups of the 128-cout form (CDDPM_NB2=0 disables it). */
 int cddpm_set_accumulation_switch(cddpm_handle h, int t_switch);
+
+/* Convolution family of a handle. family: CDDPM_CONV_H3 = fp16 two-term split (needs |activation| < 65504; the fastest),
+ * CDDPM_CONV_X6 = bf16 three-term split (exact products, no range limit), CDDPM_CONV_F32 = fp32 MFMA; any other value is an error.
+ * A new handle starts with the process default (CDDPM_CONV, else h3). Every launch of the handle and every weight image it packs
+ * is in its family, so handles of different families work side by side in one process, interleaved on one stream.
+ * Packed weights belong to a family: setting a DIFFERENT family after cddpm_load_weights waits for the device, frees the packed
+ * images, and cddpm_unet_forward / cddpm_reverse / cddpm_reverse_range / cddpm_p_sample / cddpm_ddim_step fail with a message
+ * saying so until cddpm_load_weights and cddpm_set_schedule have run again. Setting the current family does nothing.
+ * The device packer and cddpm_op_conv_packed (the training step) serve h3 handles only. */
+#define CDDPM_CONV_F32 0
+#define CDDPM_CONV_X6 1
+#define CDDPM_CONV_H3 2
+int cddpm_set_conv_family(cddpm_handle h, int family);
+int cddpm_get_conv_family(cddpm_handle h);      /* the family, or -1 for a NULL handle */
+
+/* Per-slice status of x_dev [B,1,H,W] (16-byte aligned, H * W a multiple of 4): status_dev[b] (int32 [B]) = 1 if slice b holds an
+ * inf or a NaN, else 0. One kernel launch for the whole batch on `stream`, no host synchronisation: the caller copies the B flags.
+ * What a caller uses to find the slices of a reconstruction that left the fp16 range of an h3 handle and re-run only those on a
+ * handle of an exact family. Not part of the reverse step: cddpm_reverse and its kin never launch it. */
+int cddpm_slice_status(cddpm_handle h, const float* x_dev, int B, int H, int W, int* status_dev, void* stream);
 
 /* `clip_denoised` of p_sample / ddim_sample (src/models/modules/cond_DDPM.py:433, :467): on (the reference's default, and the
  * handle's) clamps the x0 estimate to [-1,1] before the posterior mean / the DDIM update; off uses it as predicted.
@@ -305,7 +326,8 @@ int cddpm_op_gn_coef(cddpm_handle h, const float* src0_dev, int C0, const float*
                      const float* gamma_host, const float* beta_host, const float* film_dev,
                      float* coef_dev, int B, int HW, void* stream);
 
-/* host-only: the packed weight image of one convolution as the active kernel family expects it (no GPU needed).
+/* host-only: the packed weight image of one convolution as the process default family (CDDPM_CONV) expects it (no GPU needed; handle-less,
+ * so a handle's own family does not enter).
  * format = 2: conv_x6.hip, fp16 split (default) -- w * 2^e (e = *scale_exp_out, the largest exponent <= 24 that keeps
  *   max|w| * 2^e below 2^14) split into two fp16 terms, hi + mid == w * 2^e to within 2^-23 relative (rms 0.73 x 2^-24);
  *   [Cout/128][Cin/32][taps][128 rows][8 slots of 8 fp16], slot (split s, u = channel/8 in the 32-channel chunk) of
