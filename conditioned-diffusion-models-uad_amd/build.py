@@ -11,7 +11,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["conv_mfma.hip", "conv_x6.hip", "norm_kernels.hip", "small_kernels.hip", "attention.hip", "simplex.hip", "encoder.hip", "eval_post.hip", "eval_metrics.hip", "train_kernels.hip", "encoder_train.hip", "cddpm_api.hip"]
+SOURCES = ["conv_mfma.hip", "conv_x6.hip", "norm_kernels.hip", "small_kernels.hip", "attention.hip", "simplex.hip", "encoder.hip", "eval_post.hip", "eval_metrics.hip", "train_kernels.hip", "encoder_train.hip", "cddpm_api.hip", "cddpm_ops.hip"]
 LIB = os.path.join(CSRC, "libcddpm_hip.so")
 OBJ = os.path.join(CSRC, "_obj")      # object files: git-ignored and .gpurunignore-d (only the .so travels to the GPU box)
 ARCH = "gfx950"
@@ -28,7 +28,7 @@ def lib_is_current() -> bool:
     if not os.path.exists(LIB):
         return False
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + ["kernels.h", "conv_split.h"]]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + ["kernels.h", "cddpm_ctx.h", "conv_split.h"]]
     deps.append(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "cddpm.h"))
     return all(os.path.getmtime(d) <= t for d in deps if os.path.exists(d))
 
@@ -47,7 +47,7 @@ def build_lib(force: bool = False, verbose: bool = False, tag: str = "") -> str:
     def compile_one(src):
         obj = os.path.join(OBJ, src.replace(".hip", f"{('_' + tag) if tag else ''}.o"))
         path = os.path.join(CSRC, src)
-        deps = [path, os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "conv_split.h"),
+        deps = [path, os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "cddpm_ctx.h"), os.path.join(CSRC, "conv_split.h"),
                 os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "cddpm.h"), os.path.abspath(__file__)]
         stamp = obj + ".flags"          # an object is reused when it is newer than its inputs and was built with the same flags
         if (not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == " ".join(flags + [path])

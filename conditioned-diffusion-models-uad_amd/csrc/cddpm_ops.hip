@@ -1,0 +1,537 @@
+// The standalone operators of libcddpm_hip.so's C ABI (cddpm_op_* of include/cddpm.h): single kernels and small kernel groups behind
+// argument checks, what the training step (training.py, encoder_training.py) is sequenced from and what the kernel tests call. Host
+// code only. Every operator has one form: OP_CHECK (once per message), OP_PROLOGUE, temporaries from an OpScratch, launches,
+// OP_EPILOGUE (cddpm_ctx.h). The handle, the forward program and the reverse loop are in cddpm_api.hip.
+#include "cddpm_ctx.h"
+
+#include <cmath>
+
+using namespace cddpm;
+
+extern "C" {
+
+int cddpm_op_set_scratch(cddpm_handle h, size_t bytes) {      // the arena's setter: no stream, nothing to launch
+    if (!h) return -1;
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    if (h->arena) { (void)hipFree(h->arena); h->arena = nullptr; h->arena_bytes = 0; }
+    if (bytes) { HIPCHECK(h, hipMalloc(&h->arena, bytes)); h->arena_bytes = bytes; }
+    return 0;
+}
+
+static int need_zero_bias(cddpm_ctx* h) {
+    if (h->zero_bias) return 0;
+    HIPCHECK(h, hipMalloc((void**)&h->zero_bias, 4096 * sizeof(float)));
+    HIPCHECK(h, hipMemset(h->zero_bias, 0, 4096 * sizeof(float)));
+    return 0;
+}
+
+int cddpm_op_absmax(cddpm_handle h, const float* x_dev, int64_t n, float* out_dev, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, x_dev && out_dev && n >= 1, "cddpm_op_absmax: bad arguments")
+    launch_absmax(x_dev, n, out_dev, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_pack_conv(cddpm_handle h, const float* w_dev, int Cout, int Cin, int ksize, int mode, int scale_exp, void* packed_dev,
+                       void* stream) {
+    OP_CHECK(h->family == 2, "cddpm_op_pack_conv: the device packer serves the default convolution family (CDDPM_CONV=h3) only")
+    // O / I: output / input channels of the PACKED operator (mode 1 swaps the roles of the forward tensor's dimensions)
+    const int O = mode == 1 ? Cin : Cout, I = mode == 1 ? Cout : Cin;
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0,
+                w_dev && packed_dev && (ksize == 1 || ksize == 3) && mode >= 0 && mode <= 2 && (mode != 2 || ksize == 3) && O > 0 && I > 0 &&
+                    O % 128 == 0 && I % 32 == 0 && scale_exp >= 0 && scale_exp <= 24,
+                "cddpm_op_pack_conv: unsupported arguments (Cout %d, Cin %d, k %d, mode %d, exponent %d)", Cout, Cin, ksize, mode, scale_exp)
+    launch_pack_conv_split(w_dev, O, I, mode == 2 ? 4 : ksize * ksize, mode, scale_exp, packed_dev, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_pack_conv_batch(cddpm_handle h, const cddpm_pack_job* jobs_dev, int njobs, int64_t max_units, void* stream) {
+    OP_CHECK(h->family == 2, "cddpm_op_pack_conv_batch: the device packer serves the default convolution family (CDDPM_CONV=h3) only")
+    static_assert(sizeof(cddpm_pack_job) == sizeof(PackJob), "job table layout");
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, jobs_dev && njobs >= 1 && njobs <= 65535 && max_units >= 1, "cddpm_op_pack_conv_batch: bad arguments")
+    launch_pack_conv_split_batch(reinterpret_cast<const PackJob*>(jobs_dev), njobs, max_units, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_conv_packed(cddpm_handle h, const float* src0, int C0, const float* src1, int C1, const float* coef_dev, int silu, int folded_up,
+                         const void* packed_dev, int scale_exp, const float* bias_dev, int Cout, int ksize, const float* res_dev,
+                         int res_upsample, const float* skip_dev, int S0, const float* skip1_dev, int S1, const void* skip_packed_dev,
+                         float* out_dev, float* stats_dev, int B, int H, int W, void* stream) {
+    OP_CHECK(h->family == 2, "cddpm_op_conv_packed: default convolution family (CDDPM_CONV=h3) only")
+    OP_CHECK(!((ksize != 1 && ksize != 3) || C0 <= 0 || C0 % 32 || C1 < 0 || C1 % 32 || Cout <= 0 || Cout % 128 || Cout > 4096 || B < 1 || H < 1 || W < 1 ||
+               (folded_up && (ksize != 3 || C1 || H % 2 || W % 2)) ||
+               (skip_dev && (S0 <= 0 || S0 % 32 || !skip_packed_dev || ksize != 3 || S1 < 0 || S1 % 32 || (S1 > 0 && !skip1_dev))) ||
+               (C1 && !src1) || scale_exp < 0 || scale_exp > 24),
+             "cddpm_op_conv_packed: unsupported shape (k %d, C0 %d, C1 %d, Cout %d, S0 %d)", ksize, C0, C1, Cout, S0)
+    ConvArgs a;
+    zero_conv_args(a, h);
+    a.src0 = src0; a.C0 = C0; a.src1 = src1; a.C1 = C1;
+    a.srcH = folded_up ? H / 2 : H; a.srcW = folded_up ? W / 2 : W;
+    a.coef = coef_dev; a.silu = silu; a.wpk = static_cast<const float*>(packed_dev); a.res = res_dev; a.res_up = res_upsample;
+    a.skip0 = skip_dev; a.S0 = skip_dev ? S0 : 0; a.skip_wpk = static_cast<const float*>(skip_packed_dev);
+    a.skip1 = (skip_dev && S1 > 0) ? skip1_dev : nullptr; a.S1 = (skip_dev && S1 > 0) ? S1 : 0;      // the skip input as two concatenated tensors
+    a.wscale_inv = ldexpf(1.0f, -scale_exp);
+    a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = folded_up ? 4 : ksize * ksize;
+    a.stats = stats_dev;       // [B][cddpm_stat_records(H, W, folded_up ? 1 : 0)][Cout][2]: the output's GroupNorm statistics records, for free
+    // CDDPM_TRAIN_PRECISION=16: the training operators multiply plain fp16 operands (hi terms only), as the reference trainer's precision 16 does
+    a.hi_only = train_precision() == 16 ? 1 : 0;
+    conv_set_nb2(a, h, NB2_CALL_PLAN, conv_workgroups(a, B, H, W));
+    OP_PROLOGUE(a.taps == 1 ? PC_CONV1 : PC_CONV3, conv_flops(a), conv_bytes(a), src0 && packed_dev && out_dev, "cddpm_op_conv_packed: NULL argument")
+    if (!bias_dev && need_zero_bias(h)) return -1;
+    a.bias = bias_dev ? bias_dev : h->zero_bias;
+    launch_conv(a, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_gn_coef_rec(cddpm_handle h, const float* rec0_dev, int n0, int C0, const float* rec1_dev, int n1, int C1, const float* gamma_host,
+                         const float* beta_host, const float* film_dev, float* coef_dev, int B, int HW, void* stream) {
+    const int C = C0 + C1;
+    OP_CHECK(!(C0 % 4 || C1 % 4 || C % 32 || C > MAX_CONCAT_CHANNELS || C0 > 1024 || C1 > 1024 || C0 <= 0 || n0 < 1 || (C1 > 0 && (n1 < 1 || !rec1_dev))),
+             "cddpm_op_gn_coef_rec: unsupported channels / record counts")
+    OP_PROLOGUE(PC_GN, 0.0, 0.0, rec0_dev && gamma_host && beta_host && coef_dev, "cddpm_op_gn_coef_rec: NULL argument")
+    OpScratch sc(h, s);
+    const float* g = sc.param(gamma_host, C);
+    const float* bt = sc.param(beta_host, C);
+    SCRATCH_CHECK(sc)
+    launch_gn_finalize(rec0_dev, C0, n0, C1 ? rec1_dev : nullptr, C1, C1 ? n1 : 0, B, HW, g, bt, nullptr, nullptr, 0, 0, nullptr, film_dev, coef_dev, s);
+    OP_EPILOGUE()
+}
+
+// ---- standalone ops for kernel tests ---------------------------------------------------------------
+// The four convolutions below take their weights from HOST memory. One path: pack on the host for the handle's family (host_pack),
+// stage the image and the bias through a scratch of the call (never the arena: a trainer sizes that for its own operators), fill the
+// rest of ConvArgs and launch (test_conv_launch), synchronise (OP_EPILOGUE_SYNC): the copies read the packed image and the caller's
+// host arrays until the stream has run them, so every host image is declared BEFORE the OpScratch, whose destructor waits for the
+// stream on every path before it frees.
+static std::vector<float> host_pack(const cddpm_ctx* h, const float* w, int Cout, int Cin, int taps, int wexp) {
+    std::vector<float> pk(packed_conv_floats(Cout, Cin, taps, h->family));
+    pack_conv_weights(w, Cout, Cin, taps, pk.data(), wexp, h->family);
+    return pk;
+}
+static int test_conv_launch(cddpm_ctx* h, OpScratch& sc, ConvArgs& a, const std::vector<float>& pk, const float* bias_host, int wexp) {
+    a.wpk = sc.param(pk.data(), pk.size());
+    a.bias = sc.param(bias_host, a.Cout);
+    SCRATCH_CHECK(sc)
+    a.wscale_inv = ldexpf(1.0f, -wexp);
+    conv_set_nb2(a, h, NB2_FORCED_ONLY, conv_workgroups(a, a.B, a.H, a.W));
+    launch_conv(a, sc.s);
+    return 0;
+}
+#define OP_EPILOGUE_SYNC()                                        \
+    HIPCHECK(h, hipGetLastError());                               \
+    HIPCHECK(h, hipStreamSynchronize(s));                         \
+    return 0;
+
+int cddpm_op_conv(cddpm_handle h, const float* src0, int C0, const float* src1, int C1, const float* coef_dev, int silu,
+                  int upsample, const float* w_host, const float* bias_host, int Cout, int ksize, const float* res_dev,
+                  int res_upsample, float* out_dev, int B, int H, int W, void* stream) {
+    const int Cin = C0 + C1, taps = ksize * ksize;
+    OP_CHECK(!((ksize != 1 && ksize != 3) || C0 % 32 || C1 % 32 || Cin <= 0 || Cout % 128 || Cout <= 0),
+             "cddpm_op_conv: unsupported shape (ksize %d, C0 %d, C1 %d, Cout %d)", ksize, C0, C1, Cout)
+    OP_CHECK(!(upsample && (H % 2 || W % 2)), "upsample needs even H, W")
+    const bool folded = (upsample == 2);      // upsample: 1 = gather form, 2 = folded 2x2-tap form (what the UNet uses)
+    OP_PROLOGUE(PC_NONE, 0.0, 0.0, !(folded && (ksize != 3 || C1 != 0)), "folded upsample needs a 3x3 kernel and a single source")
+    std::vector<float> pk(folded ? 4 * packed_conv_floats(Cout, Cin, 4, h->family) : 0);
+    const int wexp = folded ? pack_conv_weights_up2(w_host, Cout, Cin, pk.data(), h->family)
+                            : conv_weight_exp(w_host, (size_t)Cout * Cin * taps, h->family);
+    if (!folded) pk = host_pack(h, w_host, Cout, Cin, taps, wexp);
+    OpScratch sc(h, s, true);
+    ConvArgs a;
+    zero_conv_args(a, h);
+    a.src0 = src0; a.C0 = C0; a.src1 = src1; a.C1 = C1;
+    a.srcH = upsample ? H / 2 : H; a.srcW = upsample ? W / 2 : W; a.upsample = folded ? 0 : upsample;
+    a.coef = coef_dev; a.silu = silu; a.res = res_dev; a.res_up = res_upsample;
+    a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = folded ? 4 : taps;
+    if (test_conv_launch(h, sc, a, pk, bias_host, wexp)) return -1;
+    OP_EPILOGUE_SYNC()
+}
+
+int cddpm_op_conv_skip(cddpm_handle h, const float* src0, int C0, const float* coef_dev, int silu, const float* w_host,
+                       const float* bias_host, int Cout, const float* skip_dev, int S0, const float* wskip_host,
+                       float* out_dev, int B, int H, int W, void* stream) {
+    OP_CHECK(!(C0 % 32 || C0 <= 0 || S0 % 32 || S0 <= 0 || Cout % 128 || Cout <= 0),
+             "cddpm_op_conv_skip: unsupported shape (C0 %d, S0 %d, Cout %d)", C0, S0, Cout)
+    OP_PROLOGUE(PC_NONE, 0.0, 0.0, src0 && skip_dev && w_host && wskip_host && bias_host && out_dev, "cddpm_op_conv_skip: NULL argument")
+    // one pre-scale exponent for both tensors, as cddpm_load_weights chooses it
+    const int fam = h->family;
+    const int wexp = std::min(conv_weight_exp(w_host, (size_t)Cout * C0 * 9, fam), conv_weight_exp(wskip_host, (size_t)Cout * S0, fam));
+    const std::vector<float> pk = host_pack(h, w_host, Cout, C0, 9, wexp), pks = host_pack(h, wskip_host, Cout, S0, 1, wexp);
+    OpScratch sc(h, s, true);
+    ConvArgs a;
+    zero_conv_args(a, h);
+    a.src0 = src0; a.C0 = C0; a.srcH = H; a.srcW = W; a.coef = coef_dev; a.silu = silu;
+    a.skip0 = skip_dev; a.S0 = S0; a.skip_wpk = sc.param(pks.data(), pks.size());
+    a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = 9;
+    if (test_conv_launch(h, sc, a, pk, bias_host, wexp)) return -1;
+    OP_EPILOGUE_SYNC()
+}
+
+int cddpm_op_conv_gn(cddpm_handle h, const float* src0, int C0, const float* w_host, const float* bias_host, int Cout,
+                     const float* gamma_host, const float* beta_host, float* out_dev, float* coef_dev, int B, int H, int W,
+                     void* stream) {
+    OP_CHECK(!(C0 % 32 || C0 <= 0 || Cout % 128 || Cout <= 0 || Cout > 1024), "cddpm_op_conv_gn: unsupported shape")
+    OP_PROLOGUE(PC_NONE, 0.0, 0.0, src0 && w_host && bias_host && gamma_host && beta_host && out_dev && coef_dev, "cddpm_op_conv_gn: NULL argument")
+    const int wexp = conv_weight_exp(w_host, (size_t)Cout * C0 * 9, h->family);
+    const std::vector<float> pk = host_pack(h, w_host, Cout, C0, 9, wexp);
+    const int nrec = conv_stat_records(H, W);
+    OpScratch sc(h, s, true);
+    const float* g = sc.param(gamma_host, Cout);
+    const float* bt = sc.param(beta_host, Cout);
+    float* rec = sc.n<float>((size_t)B * nrec * Cout * CDDPM_STAT_FLOATS);
+    ConvArgs a;
+    zero_conv_args(a, h);
+    a.src0 = src0; a.C0 = C0; a.srcH = H; a.srcW = W; a.stats = rec;
+    a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = 9;
+    if (test_conv_launch(h, sc, a, pk, bias_host, wexp)) return -1;
+    launch_gn_finalize(rec, Cout, nrec, nullptr, 0, 0, B, H * W, g, bt, nullptr, nullptr, 0, 0, nullptr, nullptr, coef_dev, s);
+    OP_EPILOGUE_SYNC()
+}
+
+int cddpm_op_gn_coef(cddpm_handle h, const float* src0, int C0, const float* src1, int C1, const float* gamma_host,
+                     const float* beta_host, const float* film_dev, float* coef_dev, int B, int HW, void* stream) {
+    const int C = C0 + C1;
+    OP_PROLOGUE(PC_GN, 0.0, 0.0, !(C0 % 4 || C1 % 4 || C % 32 || C > MAX_CONCAT_CHANNELS || C0 > 1024 || C1 > 1024),
+                "cddpm_op_gn_coef: unsupported channels (each source <= 1024, together <= %d)", MAX_CONCAT_CHANNELS)
+    const int ns = gn_nsplit(B, HW);
+    OpScratch sc(h, s);
+    float* rec0 = sc.n<float>((size_t)B * ns * C0 * 2);
+    float* rec1 = src1 ? sc.n<float>((size_t)B * ns * C1 * 2) : nullptr;
+    const float* g = sc.param(gamma_host, C);
+    const float* bt = sc.param(beta_host, C);
+    SCRATCH_CHECK(sc)
+    launch_gn_partial(src0, C0, B, HW, ns, rec0, s);
+    if (src1) launch_gn_partial(src1, C1, B, HW, ns, rec1, s);
+    launch_gn_finalize(rec0, C0, ns, rec1, C1, src1 ? ns : 0, B, HW, g, bt, nullptr, nullptr, 0, 0, nullptr, film_dev,
+                       coef_dev, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_conv_dgrad(cddpm_handle h, const float* dy_dev, int Cout, const float* w_host, int Cin, int ksize, float* dx_dev,
+                        int B, int H, int W, void* stream) {
+    const int taps = ksize * ksize;
+    OP_CHECK(!((ksize != 1 && ksize != 3) || Cin <= 0 || Cin % 128 || Cout <= 0 || Cout % 32),
+             "cddpm_op_conv_dgrad: unsupported shape (ksize %d, Cin %d must be a multiple of 128, Cout %d of 32)", ksize, Cin, Cout)
+    OP_PROLOGUE(PC_NONE, 0.0, 0.0, dy_dev && w_host && dx_dev, "cddpm_op_conv_dgrad: NULL argument")
+    // wt[ci][co][ky][kx] = w[co][ci][k-1-ky][k-1-kx]: the gradient of a cross-correlation is a cross-correlation with this tensor
+    std::vector<float> wt((size_t)Cin * Cout * taps);
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci)
+            for (int t = 0; t < taps; ++t)
+                wt[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = w_host[((size_t)co * Cin + ci) * taps + t];
+    const int wexp = conv_weight_exp(wt.data(), wt.size(), h->family);
+    const std::vector<float> pk = host_pack(h, wt.data(), Cin, Cout, taps, wexp), zb(Cin, 0.f);
+    OpScratch sc(h, s, true);
+    ConvArgs a;
+    zero_conv_args(a, h);
+    a.src0 = dy_dev; a.C0 = Cout; a.srcH = H; a.srcW = W;
+    a.out = dx_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cin; a.taps = taps;
+    if (test_conv_launch(h, sc, a, pk, zb.data(), wexp)) return -1;
+    OP_EPILOGUE_SYNC()
+}
+
+int cddpm_op_bias_grad(cddpm_handle h, const float* dy_dev, int64_t npix, int C, float* db_dev, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, !(!dy_dev || !db_dev || npix < 1 || C % 4 || C > 1024), "cddpm_op_bias_grad: bad arguments")
+    OpScratch sc(h, s);
+    double* part = sc.n<double>((size_t)512 * C);
+    SCRATCH_CHECK(sc)
+    launch_bias_grad(dy_dev, npix, C, db_dev, part, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_conv_wgrad(cddpm_handle h, const float* x0_dev, int C0, const float* x1_dev, int C1, const float* coef_dev, int silu,
+                        int upsample, const float* dy_dev, int Cout, int ksize, float* dw_dev, float* db_dev, int B, int H, int W,
+                        void* stream) {
+    const int Cin = C0 + C1, taps = ksize * ksize;
+    OP_CHECK(!((ksize != 1 && ksize != 3) || C0 <= 0 || C1 < 0 || Cin % 32 || (C1 > 0 && C0 % 32) || Cout <= 0 || Cout % 64 || H < 1 ||
+               W < 1 || B < 1 || (C1 > 0 && !x1_dev) || (upsample && (C1 > 0 || (W & 1) || (H & 1)))),
+             "cddpm_op_conv_wgrad: unsupported shape (k %d, C0 %d, C1 %d, Cout %d, H %d)", ksize, C0, C1, Cout, H)
+    OP_PROLOGUE(PC_WGRAD, 2.0 * B * H * W * (double)Cout * Cin * taps, 4.0 * B * (double)H * W * (Cin + Cout), x0_dev && dy_dev && dw_dev,
+                "cddpm_op_conv_wgrad: NULL argument")
+    const int P = conv_wgrad_parts(B, H, W, Cin, Cout, taps);
+    OpScratch sc(h, s);
+    float* part = sc.n<float>((size_t)P * Cout * Cin * taps);
+    const size_t iu = conv_wgrad_image_units(B, H, W, Cin, Cout, taps);
+    void* images = iu ? sc.get(iu * 16) : nullptr;
+    SCRATCH_CHECK(sc)
+    launch_conv_wgrad(x0_dev, C0, x1_dev, C1, coef_dev, silu, upsample ? 1 : 0, dy_dev, B, H, W, Cout, taps, part, P, images, dw_dev, db_dev, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
+                                void* stream) {
+    OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_backward: C must be a multiple of 64")
+    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && da_dev && dqkv_dev, "cddpm_op_attention_backward: NULL argument")
+    OpScratch sc(h, s);
+    float* stats = sc.n<float>((size_t)B * (C / 64) * N * 2);
+    SCRATCH_CHECK(sc)
+    launch_attention_backward_flash(qkv_dev, da_dev, dqkv_dev, stats, B, N, C, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_linear_backward(cddpm_handle h, const float* x_dev, const float* w_dev, const float* dy_dev, int M, int N, int K,
+                             int silu_in, float* dw_dev, float* db_dev, float* dx_dev, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, M >= 1 && N >= 1 && K >= 1 && x_dev && w_dev && dy_dev && dw_dev, "cddpm_op_linear_backward: bad arguments")
+    OpScratch sc(h, s);
+    const size_t nscr = linear_backward_scratch_floats(M, N, K, silu_in);
+    float* a = nscr ? sc.n<float>(nscr) : nullptr;
+    SCRATCH_CHECK(sc)
+    launch_linear_backward(x_dev, w_dev, dy_dev, M, N, K, silu_in, a, dw_dev, db_dev, dx_dev, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_linear(cddpm_handle h, const float* x_dev, const float* w_dev, const float* b_dev, int M, int N, int K, int silu_in,
+                    float* y_dev, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && w_dev && y_dev && M > 0 && N > 0 && K > 0, "cddpm_op_linear: bad arguments")
+    launch_linear(x_dev, K, w_dev, K, 0, b_dev, y_dev, N, M, N, K, silu_in, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_conv_in1(cddpm_handle h, const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int B, int H, int W,
+                      int C, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && w_dev && b_dev && out_dev && C % 64 == 0 && C <= 512, "cddpm_op_conv_in1: bad arguments")
+    launch_conv_in1(x_dev, w_dev, b_dev, out_dev, B, H, W, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_head(cddpm_handle h, const float* x_dev, const float* coef_dev, const float* w9_dev, float bias, const float* bias_dev,
+                  float* out_dev, int B, int H, int W, int C, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && coef_dev && w9_dev && out_dev && C % 32 == 0, "cddpm_op_head: bad arguments")
+    OpScratch sc(h, s);
+    float* P = sc.n<float>((size_t)B * H * W * 9);
+    SCRATCH_CHECK(sc)
+    launch_head_dots(x_dev, coef_dev, w9_dev, P, B, H * W, C, s);
+    launch_head_gather(P, bias, bias_dev, out_dev, B, H, W, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_pool_act(cddpm_handle h, const float* x_dev, const float* coef_dev, float* hp_dev, float* xp_dev, int B, int H, int W, int C,
+                      void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && coef_dev && hp_dev && xp_dev && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "cddpm_op_pool_act: bad arguments")
+    launch_pool_act(x_dev, coef_dev, hp_dev, xp_dev, B, H, W, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_unpool2(cddpm_handle h, const float* dyp_dev, float* dx_dev, int B, int H, int W, int C, float scale, int accumulate, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dyp_dev && dx_dev && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "cddpm_op_unpool2: bad arguments")
+    launch_unpool2(dyp_dev, dx_dev, B, H, W, C, scale, accumulate, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_sumpool2(cddpm_handle h, const float* dy_dev, float* dxp_dev, int B, int H, int W, int C, int accumulate, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dy_dev && dxp_dev && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "cddpm_op_sumpool2: bad arguments")
+    launch_sumpool2(dy_dev, dxp_dev, B, H, W, C, accumulate, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_add_inplace(cddpm_handle h, float* a_dev, const float* b_dev, int64_t n, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, a_dev && b_dev && n > 0 && n % 4 == 0, "cddpm_op_add_inplace: bad arguments")
+    launch_add_inplace(a_dev, b_dev, n, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_chan_image_corr(cddpm_handle h, const float* t_dev, const float* coef_dev, int silu, const float* s_dev, int sign, float* dw_dev,
+                             int B, int H, int W, int C, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, t_dev && s_dev && dw_dev && C % 64 == 0 && (sign == 1 || sign == -1), "cddpm_op_chan_image_corr: bad arguments")
+    OpScratch sc(h, s);
+    double* part = sc.n<double>((size_t)256 * C * 9);
+    SCRATCH_CHECK(sc)
+    launch_chan_image_corr(t_dev, coef_dev, silu, s_dev, sign, B, H, W, C, part, dw_dev, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_head_dgrad(cddpm_handle h, const float* dout_dev, const float* w9_dev, float* dact_dev, int B, int H, int W, int C, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dout_dev && w9_dev && dact_dev && C % 4 == 0, "cddpm_op_head_dgrad: bad arguments")
+    launch_head_dgrad(dout_dev, w9_dev, dact_dev, B, H, W, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_loss(cddpm_handle h, const float* out_dev, const float* target_dev, const float* w_b_dev, int l2, int B, int HW, float grad_scale,
+                  float* dout_dev, float* loss_b_dev, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, out_dev && target_dev && dout_dev && loss_b_dev && B > 0 && HW > 0, "cddpm_op_loss: bad arguments")
+    launch_loss(out_dev, target_dev, w_b_dev, l2, B, HW, grad_scale, nullptr, dout_dev, loss_b_dev, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_loss_scaled(cddpm_handle h, const float* out_dev, const float* target_dev, const float* w_b_dev, int l2, int B, int HW,
+                         const int32_t* scaler_dev, float* dout_dev, float* loss_b_dev, void* stream) {
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, out_dev && target_dev && scaler_dev && dout_dev && loss_b_dev && B > 0 && HW > 0, "cddpm_op_loss_scaled: bad arguments")
+    launch_loss(out_dev, target_dev, w_b_dev, l2, B, HW, 0.0f, scaler_dev, dout_dev, loss_b_dev, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
+                  float eps, int step, float grad_unscale, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && n > 0 && step >= 1, "cddpm_op_adam: bad arguments")
+    launch_adam(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, step, grad_unscale, s);
+    OP_EPILOGUE()
+}
+int cddpm_set_train_precision(int bits) {
+    if (bits != 16 && bits != 32) return -1;
+    return set_train_precision(bits);
+}
+int cddpm_get_train_precision(void) { return train_precision(); }
+int cddpm_op_grad_check(cddpm_handle h, const float* g_dev, int64_t n, int32_t* ctrl_dev, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, g_dev && ctrl_dev && n > 0 && ((uintptr_t)g_dev & 15) == 0, "cddpm_op_grad_check: bad arguments (g_dev 16-byte aligned)")
+    launch_grad_check(g_dev, n, ctrl_dev, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_guard_commit(cddpm_handle h, int32_t* ctrl_dev, float beta1, float beta2, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, ctrl_dev != nullptr, "cddpm_op_guard_commit: bad arguments")
+    launch_guard_commit(ctrl_dev, beta1, beta2, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_adam_guarded(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1,
+                          float beta2, float eps, float grad_unscale, const int32_t* ctrl_dev, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && ctrl_dev && n > 0, "cddpm_op_adam_guarded: bad arguments")
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, grad_unscale, ctrl_dev, nullptr, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_adam_scaled(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1,
+                         float beta2, float eps, float extra_unscale, const int32_t* ctrl_dev, const int32_t* scaler_dev, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && ctrl_dev && scaler_dev && n > 0, "cddpm_op_adam_scaled: bad arguments")
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, extra_unscale, ctrl_dev, scaler_dev, s);
+    OP_EPILOGUE()
+}
+static bool power_of_two(float x) {
+    int e;
+    return std::isfinite(x) && x > 0.0f && std::frexp(x, &e) == 0.5f;
+}
+int cddpm_op_scaler_update(cddpm_handle h, const int32_t* ctrl_dev, int32_t* scaler_dev, float growth, float backoff, int interval,
+                           void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, ctrl_dev && scaler_dev && power_of_two(growth) && growth > 1.0f && power_of_two(backoff) && backoff < 1.0f && interval >= 1,
+                "cddpm_op_scaler_update: bad arguments (growth > 1 and backoff < 1 powers of two, interval >= 1)")
+    launch_scaler_update(ctrl_dev, scaler_dev, growth, backoff, interval, s);
+    OP_EPILOGUE()
+}
+
+// ---- training-mode operators of the context encoder (encoder_train.hip): NHWC fp32 device tensors ---------------------------------------
+int cddpm_op_enc_pack_w(cddpm_handle h, const float* w_dev, int Cout, int Cin, int K, float* wf_dev, float* wd_dev, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, w_dev && wf_dev && Cout > 0 && Cin > 0 && (K == 1 || K == 3), "cddpm_op_enc_pack_w: bad arguments")
+    launch_enc_pack_w(w_dev, Cout, Cin, K * K, wf_dev, wd_dev, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_conv(cddpm_handle h, const float* src_dev, const float* w_img_dev, float* dst_dev, int B, int H, int W, int Cin, int Cout, int K,
+                      int stride, int transposed, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0,
+                src_dev && w_img_dev && dst_dev && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (K == 1 || K == 3) && (stride == 1 || stride == 2) &&
+                    (transposed ? (Cout % 16 == 0 && Cin % 64 == 0) : (Cin % 16 == 0 && Cout % 64 == 0)),
+                "cddpm_op_enc_conv: unsupported shape (contraction channels a multiple of 16, produced channels of 64; K 1|3, stride 1|2)")
+    const int Z = enc_conv_split(B, H, W, Cin, Cout, K, stride, transposed);
+    OpScratch sc(h, s);
+    float* part = nullptr;
+    if (Z > 1) {
+        const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+        part = sc.n<float>((size_t)Z * B * (transposed ? (size_t)H * W * Cin : (size_t)Ho * Wo * Cout));
+        SCRATCH_CHECK(sc)
+    }
+    launch_enc_conv(src_dev, w_img_dev, dst_dev, B, H, W, Cin, Cout, K, stride, transposed, part, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_conv_wgrad(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, int Cin, int Cout, int K,
+                            int stride, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && dz_dev && dw_dev && B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 64 == 0 && (K == 1 || K == 3) &&
+                    (stride == 1 || stride == 2), "cddpm_op_enc_conv_wgrad: unsupported shape")
+    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+    const int P = enc_wgrad_parts(B, Ho, Wo, Cin, Cout, K);
+    OpScratch sc(h, s);
+    float* part = sc.n<float>((size_t)P * K * K * Cin * Cout);
+    SCRATCH_CHECK(sc)
+    launch_enc_wgrad(x_dev, dz_dev, part, P, dw_dev, B, H, W, Cin, Cout, K, stride, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_stem(cddpm_handle h, const float* x_dev, const float* w_dev, float* z_dev, int B, int H, int W, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && w_dev && z_dev && B > 0 && H > 0 && W > 0, "cddpm_op_enc_stem: bad arguments")
+    launch_enc_stem_fwd(x_dev, w_dev, z_dev, B, H, W, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_stem_wgrad(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && dz_dev && dw_dev && B > 0 && H > 0 && W > 0, "cddpm_op_enc_stem_wgrad: bad arguments")
+    OpScratch sc(h, s);
+    double* part = sc.n<double>((size_t)32 * 49 * 64);
+    SCRATCH_CHECK(sc)
+    launch_enc_stem_wgrad(x_dev, dz_dev, part, dw_dev, B, H, W, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_bn_forward(cddpm_handle h, const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* sample_scale_dev,
+                            const float* res_dev, int relu, float eps, float momentum, float* run_mean_dev, float* run_var_dev, float* mean_rstd_dev,
+                            float* y_dev, int64_t N, int HW, int C, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, z_dev && gamma_dev && beta_dev && mean_rstd_dev && y_dev && N > 0 && HW > 0 && C > 0 && C % 64 == 0 && (!run_mean_dev == !run_var_dev),
+                "cddpm_op_enc_bn_forward: bad arguments (C a multiple of 64)")
+    OpScratch sc(h, s);
+    double* part = sc.n<double>((size_t)enc_bn_chunks(N) * 2 * C);
+    SCRATCH_CHECK(sc)
+    launch_enc_bn_forward(z_dev, gamma_dev, beta_dev, sample_scale_dev, res_dev, relu, eps, momentum, run_mean_dev, run_var_dev, mean_rstd_dev, y_dev,
+                          part, N, HW, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_bn_backward(cddpm_handle h, const float* z_dev, const float* y_dev, const float* dy_dev, const float* mean_rstd_dev,
+                             const float* gamma_dev, const float* sample_scale_dev, int relu, float* dz_dev, float* dres_dev, float* dgamma_dev,
+                             float* dbeta_dev, int64_t N, int HW, int C, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, z_dev && dy_dev && mean_rstd_dev && gamma_dev && dz_dev && dgamma_dev && dbeta_dev && (!relu || y_dev) && N > 0 && HW > 0 && C > 0 &&
+                    C % 64 == 0, "cddpm_op_enc_bn_backward: bad arguments (C a multiple of 64)")
+    OpScratch sc(h, s);
+    double* part = sc.n<double>((size_t)enc_bn_chunks(N) * 2 * C);
+    float* k = sc.n<float>((size_t)2 * C);
+    SCRATCH_CHECK(sc)
+    launch_enc_bn_backward(z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, sample_scale_dev, relu, dz_dev, dres_dev, dgamma_dev, dbeta_dev, k, part, N,
+                           HW, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_maxpool(cddpm_handle h, const float* x_dev, float* y_dev, int B, int H, int W, int C, int backward, const float* dy_dev, float* dx_dev,
+                         void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && (backward ? (dy_dev && dx_dev) : (y_dev != nullptr)),
+                "cddpm_op_enc_maxpool: bad arguments")
+    if (backward) launch_enc_maxpool_backward(x_dev, dy_dev, dx_dev, B, H, W, C, s);
+    else launch_enc_maxpool(x_dev, y_dev, B, H, W, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_enc_avgpool(cddpm_handle h, const float* x_dev, float* g_dev, int B, int HW, int C, int backward, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && g_dev && B > 0 && HW > 0 && C > 0, "cddpm_op_enc_avgpool: bad arguments")
+    if (backward) launch_enc_avgpool_backward(x_dev /* dL/dg [B][C] */, g_dev /* dL/dx [B][HW][C] */, B, HW, C, s);
+    else launch_enc_avgpool(x_dev, g_dev, B, HW, C, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_gn_silu_backward(cddpm_handle h, const float* x_dev, const float* x1_dev, int C1, const float* da_dev, const float* gamma_host,
+                              const float* beta_host, const float* film_dev, int silu, float* dx_dev, float* dx1_dev, float* dgamma_dev,
+                              float* dbeta_dev, float* dfilm_dev, const float* rec_dev, int nrec, const float* add_dev, int B, int HW, int C,
+                              void* stream) {
+    OP_CHECK(!(C % 32 || C <= 0 || C > 1024 || B < 1 || HW < 1 || (rec_dev && nrec < 1) || C1 < 0 || C1 % 4 || C1 >= C ||
+               (C1 > 0 && (!x1_dev || !dx1_dev || !rec_dev))),
+             "cddpm_op_gn_silu_backward: unsupported shape (C %d, C1 %d; a two-source input needs its statistics records)", C, C1)
+    OP_PROLOGUE(PC_GNBWD, 0.0, 12.0 * B * (double)HW * C,      // reads x and da, writes dx
+                !(!x_dev || !da_dev || !gamma_host || !beta_host || !dx_dev || !dgamma_dev || !dbeta_dev || (film_dev && !dfilm_dev)),
+                "cddpm_op_gn_silu_backward: NULL argument")
+    const int ns = gn_nsplit(B, HW);
+    OpScratch sc(h, s);
+    float* rec = rec_dev ? nullptr : sc.n<float>((size_t)B * ns * C * 2);
+    const float* g = sc.param(gamma_host, C);
+    const float* bt = sc.param(beta_host, C);
+    float* planes = sc.n<float>((size_t)4 * B * C);
+    float* out_bc = sc.n<float>((size_t)4 * B * C);
+    double* part = sc.n<double>((size_t)B * ns * C * 2);
+    SCRATCH_CHECK(sc)
+    if (!rec_dev) launch_gn_partial(x_dev, C, B, HW, ns, rec, s);      // statistics records of x: given (kept from the forward pass) or swept here
+    launch_gn_bwd_planes(rec_dev ? rec_dev : rec, rec_dev ? nrec : ns, g, bt, film_dev, B, C, HW, planes, s);
+    launch_gn_silu_backward(x_dev, C1 ? x1_dev : nullptr, C - C1, C1 ? dx1_dev : nullptr, da_dev, planes, g, bt, film_dev, silu, B, C, HW, ns, part,
+                            out_bc, dx_dev, dgamma_dev, dbeta_dev, dfilm_dev, add_dev, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_stat_records(int H, int W, int kind) {
+    if (H < 1 || W < 1) return -1;
+    if (kind == 0) return conv_stat_records(H, W);
+    if (kind == 1) return conv_stat_records_up2(H, W);
+    if (kind == 2) return gn_nsplit(1, H * W);
+    return -1;
+}
+
+size_t cddpm_packed_conv_bytes(int Cout, int Cin, int taps) {
+    if (Cout <= 0 || Cin <= 0 || Cout % 128 || Cin % 32 || (taps != 1 && taps != 9 && taps != 4)) return 0;
+    return packed_conv_floats(Cout, Cin, taps, conv_mode()) * sizeof(float);      // handle-less: the process default family
+}
+
+int cddpm_pack_conv_weights(const float* w_host, int Cout, int Cin, int taps, void* dst_host, int* scale_exp_out) {
+    if (!w_host || !dst_host || cddpm_packed_conv_bytes(Cout, Cin, taps) == 0) return -1;
+    const int wexp = conv_weight_exp(w_host, (size_t)Cout * Cin * taps, conv_mode());     // handle-less: the process default family
+    pack_conv_weights(w_host, Cout, Cin, taps, static_cast<float*>(dst_host), wexp, conv_mode());
+    if (scale_exp_out) *scale_exp_out = wexp;
+    return conv_mode();
+}
+
+int cddpm_op_attention(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream) {
+    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, !(C % 64 || N < 1), "cddpm_op_attention: C must be a multiple of 64")
+    launch_attention(qkv_dev, out_dev, B, N, C, s);
+    OP_EPILOGUE()
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Internal launcher interface of libcddpm_hip.so (gfx950 only). Each launcher enqueues on `stream`
-// and returns; shape preconditions are checked by the callers in cddpm_api.hip.
+// and returns; shape preconditions are checked by the callers in cddpm_api.hip and cddpm_ops.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,7 +45,7 @@ struct ConvArgs {
     // the reconstruction path.
     int hi_only;
     // fp16-split family, unsplit K: 1 = workgroups of 256 pixels x 256 couts (two cout blocks per workgroup sharing the
-    // chunk's transformed patch; two-level accumulation, see conv_x6.hip). Decided by the caller with conv_nb2_ok.
+    // chunk's transformed patch; two-level accumulation, see conv_x6.hip). Decided by the caller (cddpm_ctx.h::conv_set_nb2).
     int nb2;
     // convolution family of the launch (the numbering of conv_mode()): a property of the calling handle, which also fixes the
     // format of `wpk` / `skip_wpk`. Every ConvArgs is built by a handle-taking path and carries its handle's family.
@@ -74,7 +74,7 @@ void launch_conv_split(const ConvArgs& a, hipStream_t stream);
 int conv_weight_exp(const float* w, size_t n, int family);
 void pack_conv_weights_split(const float* w /*[Cout][Cin][k][k]*/, int Cout, int Cin, int taps, void* dst, int wexp, int family);
 
-// packed weight image sizes / packing (host side, cddpm_api.hip)
+// packed weight image sizes / packing (host side: cddpm_load_weights in cddpm_api.hip, the host-weight operators in cddpm_ops.hip)
 // fp32 layout: [Cout/128][Cin/32][taps][128 rows x 8 slots of float4], slot s of row j stored at s ^ ((j>>1)&7)
 // x6 layout  : [Cout/128][Cin/32][taps][128 rows x 12 slots of 8 bf16] (conv_x6.hip), 1.5 floats per weight
 // split layouts (conv_x6.hip): [..][128 rows x 4 NS slots of 8 x 16 bit]: 1.5 (bf16 x 3) | 1 (fp16 x 2) floats per weight

@@ -6,7 +6,7 @@
 //
 // * conv dgrad (dL/da from dL/dy) needs no new kernel: it IS the fused forward convolution (conv_x6.hip / conv_mfma.hip) run on
 //   dL/dy with the weight tensor transposed in (Cout, Cin) and flipped in (ky, kx), packed by the same host packer
-//   (cddpm_op_conv_dgrad in cddpm_api.hip) -- every Cin of the UNet is a multiple of 128, every Cout of 32.
+//   (cddpm_op_conv_dgrad in cddpm_ops.hip) -- every Cin of the UNet is a multiple of 128, every Cout of 32.
 // * GroupNorm/FiLM/SiLU backward (here): with x^ = (x - mu_g) r_g, u = x^ g' + b' (g' = gamma (1 + scale), b' = beta (1 + scale) +
 //   shift), a = SiLU(u) and du = da * SiLU'(u):
 //       S1[b,c] = sum_p du,  S2[b,c] = sum_p du x^          -> d b' = S1, d g' = S2
