@@ -130,9 +130,12 @@ int validate_desc(cddpm_ctx* h, const cddpm_unet_desc* d) {
     if (d->model_channels <= 0 || d->model_channels % 128 != 0 || d->model_channels > 512)
         return fail(h, "model_channels must be 128, 256, 384 or 512 (MFMA tile N = 128), got %d", d->model_channels);
     if (d->num_levels < 1 || d->num_levels > CDDPM_MAX_LEVELS) return fail(h, "num_levels out of range: %d", d->num_levels);
-    for (int i = 0; i < d->num_levels; ++i)
-        if (d->channel_mult[i] < 1 || d->channel_mult[i] * d->model_channels > 1024)
-            return fail(h, "channel_mult[%d]=%d unsupported", i, d->channel_mult[i]);
+    for (int i = 0; i < d->num_levels; ++i) {
+        if (d->channel_mult[i] < 1) return fail(h, "channel_mult[%d]=%d unsupported: channel_mult must be >= 1", i, d->channel_mult[i]);
+        if ((long long)d->channel_mult[i] * d->model_channels > 1024)
+            return fail(h, "channel_mult[%d]=%d unsupported: channel_mult[%d] * model_channels = %lld exceeds 1024", i,
+                        d->channel_mult[i], i, (long long)d->channel_mult[i] * d->model_channels);
+    }
     if (d->num_res_blocks < 1) return fail(h, "num_res_blocks must be >= 1");
     if (d->num_attention_resolutions < 0 || d->num_attention_resolutions > CDDPM_MAX_LEVELS)
         return fail(h, "num_attention_resolutions out of range");

@@ -396,12 +396,14 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     if constexpr (TPS == 1) {
     // ---- main loop: weights double-buffered in LDS and prefetched through registers one stage ahead;
     //      the next chunk's patch is fetched into registers behind the last tap's MFMAs.
+    //      Like the LDS-DMA loop below it runs over this workgroup's split-K range [kc0, kc1) (all chunks when the layer is not split):
+    //      a 1x1 convolution of 576 input channels or more is split by cddpm_api.hip::plan_ksplit.
     {
-        const v4f* p0 = wslab(0, 0);
+        const v4f* p0 = wslab(kc0, 0);
 #pragma unroll
         for (int i = 0; i < WK; ++i) wreg[i] = p0[tid + THREADS * i];
     }
-    load_act(0);
+    load_act(kc0);
     if (have_coef) {
         const int nq = Cin >> 2;
         const size_t plane = (size_t)a.B * Cin;
@@ -411,7 +413,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         }
     }
     int buf = 0;
-    for (int chunk = 0; chunk < nch; ++chunk) {
+    for (int chunk = kc0; chunk < kc1; ++chunk) {
         const bool main_seg = chunk < nch_main;
         const int ntap = main_seg ? TAPS : 1;
         __syncthreads();   // every wave is done reading the previous patch
@@ -423,7 +425,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             const v4f* pn = last_tap ? wslab(chunk + 1, 0) : wslab(chunk, t + 1);
 #pragma unroll
             for (int i = 0; i < WK; ++i) wreg[i] = pn[tid + THREADS * i];
-            if (last_tap && chunk + 1 < nch) load_act(chunk + 1);
+            if (last_tap && chunk + 1 < kc1) load_act(chunk + 1);
             __syncthreads();
             // accumulation in three levels: an MFMA sums 16 products, `acc` collects FOLD taps of a 32-channel chunk
             // (<= 96 products per chain), `tot` sums those groups. The rounding noise of an fp32 chain grows with the

@@ -197,7 +197,7 @@ def unet_param_shapes(model_channels=128, channel_mult=(1, 2, 2), num_res_blocks
                 ds //= 2
             idx += 1
     gn("out.0", ch)
-    conv("out.2", C, out_channels, 3)
+    conv("out.2", ch, out_channels, 3)     # ch = channel_mult[0] * model_channels after the last output block
     return shapes
 
 

@@ -85,6 +85,40 @@ def conv_table(program):
     return t
 
 
+def program_param_names(program):
+    """the state_dict keys (without the embedding MLPs) of the modules `program` visits"""
+    keys = set()
+    for kind, n, a in program:
+        if kind == "in":
+            mods = [n]
+        elif kind == "res":
+            mods = [n + m for m in (".in_layers.0", ".in_layers.2", ".emb_layers.1", ".out_layers.0", ".out_layers.3")]
+            if a["cin"] != a["cout"]:
+                mods.append(n + ".skip_connection")
+        elif kind == "attn":
+            mods = [n + m for m in (".norm", ".qkv", ".proj_out")]
+        elif kind == "head":
+            mods = [n + ".0", n + ".2"]
+        else:
+            raise ValueError(f"training: unknown program entry {kind!r} ({n})")
+        keys.update(m + s for m in mods for s in (".weight", ".bias"))
+    return keys
+
+
+def unsupported_blocks(names, program):
+    """the UNet blocks that hold parameters (`names`: state_dict keys) of modules `program` never visits, e.g. 'input_blocks.1.1' of a
+    model with attention inside its levels. Their parameters would never receive a gradient. Keys outside the UNet's own name space
+    (anything but input_blocks / middle_block / output_blocks / out) are not judged."""
+    known, missing = program_param_names(program), []
+    for k in names:
+        if k.startswith(("input_blocks.", "middle_block.", "output_blocks.", "out.")) and k not in known:
+            parts = k.split(".")
+            blk = "out" if parts[0] == "out" else ".".join(parts[:2] if parts[0] == "middle_block" else parts[:3])
+            if blk not in missing:
+                missing.append(blk)
+    return missing
+
+
 class UNetTrainer:
     """Forward + backward + Adam of the conditioned UNet on NHWC device tensors, device-resident: the parameters live in ONE flat fp32
     buffer (`flat`; `p[name]` are views with the reference's state_dict names and shapes), their gradients in a second one (`gflat`,
@@ -102,6 +136,11 @@ class UNetTrainer:
         # ONE [sum 2 Cout, E] matrix (11776 x 1024) -- one Linear forward and one backward per step instead of 27 (the inference engine's
         # table does the same); then every other tensor, each 256-byte aligned
         self.program = self._build_program()
+        missing = unsupported_blocks(params, self.program)
+        if missing:
+            raise NotImplementedError(f"training: the state dict holds parameters of blocks the training program does not build: {', '.join(missing)} "
+                                      "(attention inside the resolution levels is not built for training; the program has it in the middle "
+                                      "block only). They would silently keep zero gradients.")
         emb_names = [n + ".emb_layers.1" for kind, n, _a in self.program if kind == "res" and n + ".emb_layers.1.weight" in params]
         lead = [n + ".weight" for n in emb_names] + [n + ".bias" for n in emb_names]
         names = lead + [k for k in params if k not in set(lead)]

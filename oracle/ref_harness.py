@@ -51,12 +51,13 @@ def import_reference():
 
 
 def build_reference(sd_torch, image_size=(128, 128), timesteps=1000, objective="pred_x0",
-                    model_channels=128, channel_mult=(1, 2, 2), num_classes=128):
+                    model_channels=128, channel_mult=(1, 2, 2), num_classes=128, num_res_blocks=3,
+                    attention_resolutions=(3, 6, 12)):
     """Reference UNet + GaussianDiffusion with the ctor arguments of src/models/DDPM_2D.py:37-77."""
     UNetModel, GaussianDiffusion = import_reference()
     model = UNetModel(
         image_size=image_size, in_channels=1, model_channels=model_channels, out_channels=1,
-        num_res_blocks=3, attention_resolutions=(3, 6, 12), dropout=0, channel_mult=list(channel_mult),
+        num_res_blocks=num_res_blocks, attention_resolutions=tuple(attention_resolutions), dropout=0, channel_mult=list(channel_mult),
         conv_resample=True, dims=2, num_classes=num_classes, use_checkpoint=False, use_fp16=True,
         num_heads=1, num_head_channels=64, num_heads_upsample=-1, use_scale_shift_norm=True,
         resblock_updown=True, use_new_attention_order=True, use_spatial_transformer=False,

@@ -479,3 +479,54 @@ def test_training_program_covers_the_state_dict(synth):
             if k.startswith(("time_embed", "label_emb")):
                 continue
             assert any(k.startswith(v + ".") for v in visited), k
+
+
+def test_training_program_names_the_blocks_it_does_not_build(synth):
+    """training.unsupported_blocks: a state dict with attention inside the resolution levels (tests/arch_cases.py `attn_levels`) holds
+    parameters the training program never visits -- they are named (UNetTrainer raises on them) instead of silently keeping zero
+    gradients; every descriptor the trainer does build, and a dict that is no UNet at all, name nothing"""
+    import arch_cases as A
+    tr = load_pkg("training")
+    case = A.CASES["attn_levels"]
+    prog = tr.unet_program(case["model_channels"], case["channel_mult"], case["num_res_blocks"])
+    missing = tr.unsupported_blocks(synth.unet_param_shapes(**A.synth_kw(case)), prog)
+    # output_blocks.1 and .3 hold the attention at sub-index 1 and the up-ResBlock at 2, where the program expects the up-ResBlock at 1
+    assert missing == ["input_blocks.1.1", "input_blocks.3.1", "input_blocks.5.1", "output_blocks.0.1", "output_blocks.1.1", "output_blocks.1.2",
+                       "output_blocks.2.1", "output_blocks.3.1", "output_blocks.3.2", "output_blocks.4.1", "output_blocks.5.1"], missing
+    shapes = synth.unet_param_shapes(**A.synth_kw(case))
+    assert "output_blocks.1.2.in_layers.2.weight" in shapes and "output_blocks.1.1.qkv.weight" in shapes
+    for name in ("w256", "deep4", "mult0_2", "w512_uncond", "w384_limit", "cond4"):
+        c = A.CASES[name]
+        prog = tr.unet_program(c["model_channels"], c["channel_mult"], c["num_res_blocks"])
+        assert tr.unsupported_blocks(synth.unet_param_shapes(**A.synth_kw(c)), prog) == [], name
+    assert tr.unsupported_blocks({"w": 0}, prog) == []
+
+
+def test_descriptor_table_is_accepted_and_the_refusal_list_refused_by_name():
+    """tests/arch_cases.py against the host half of cddpm_create (validate_desc + check_program, reached without a GPU through
+    cddpm_workspace_bytes): every case of the table is a descriptor the library accepts, at its own geometry and at the large-batch
+    handle's; every entry of the refusal list is refused with the message that names its reason"""
+    import arch_cases as A
+    lib_mod = load_pkg("_lib")
+    lib = lib_mod.load_library()
+
+    def desc(model_channels, channel_mult, num_res_blocks, attention_resolutions, cond_dim, max_batch, max_h, max_w):
+        d = lib_mod.UnetDesc()
+        d.in_channels = d.out_channels = 1
+        d.model_channels, d.num_levels, d.num_res_blocks, d.head_channels, d.cond_dim = model_channels, len(channel_mult), num_res_blocks, 64, cond_dim
+        for i, m in enumerate(channel_mult):
+            d.channel_mult[i] = m
+        d.num_attention_resolutions = len(attention_resolutions)
+        for i, a in enumerate(attention_resolutions):
+            d.attention_resolutions[i] = a
+        d.timesteps, d.max_batch, d.max_h, d.max_w = 1000, max_batch, max_h, max_w
+        return d
+
+    for name, case in A.CASES.items():
+        for geo in (case["geometry"], (64, 128, 128)):
+            d = desc(max_batch=geo[0], max_h=geo[1], max_w=geo[2], **A.engine_kw(case))
+            assert lib.cddpm_workspace_bytes(ctypes.byref(d)) > 0, (name, geo, lib.cddpm_last_error(None))
+    for name, r in A.REFUSALS.items():
+        d = desc(**dict(A.REFUSAL_BASE, **r["desc"]))
+        assert lib.cddpm_workspace_bytes(ctypes.byref(d)) == 0, name
+        assert r["message"].encode() in lib.cddpm_last_error(None), (name, lib.cddpm_last_error(None))

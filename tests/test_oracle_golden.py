@@ -232,3 +232,39 @@ def test_box_branch_of_p_sample_loop(oracle, synth, sd_torch):
     out = oracle.p_sample_loop(xT, cond, sd_torch, oracle.schedule_buffers(T),
                                lambda t: torch.from_numpy(synth.noise_z(3, t, 0, B, H, W)), start_t=start_t)
     assert float(np.abs(out.numpy() - g["out"]).max()) < 2e-6
+
+
+# ---- descriptors beyond the experiment's (tests/arch_cases.py; oracle/make_golden_arch.py) ---------------------------------------------
+import arch_cases as A  # noqa: E402
+
+
+@pytest.mark.parametrize("name", list(A.CASES))
+def test_unet_forward_at_other_descriptors(oracle, synth, name):
+    """the oracle and the synthetic weights at every descriptor the GPU tests run, against the reference's own output and its own
+    state_dict inventory (names and shapes, in registration order) at that descriptor"""
+    case, g = A.CASES[name], golden("arch_" + name)
+    B = case["geometry"][0]
+    shapes = synth.unet_param_shapes(**A.synth_kw(case))
+    names, dims = A.shapes_record(shapes)
+    assert list(names) == list(g["names"]), set(names) ^ set(g["names"])
+    bad = [(n, tuple(a), tuple(b)) for n, a, b in zip(names, dims, g["shapes"]) if tuple(a) != tuple(b)]
+    assert not bad, bad
+    sd = oracle.to_torch_sd(synth.synth_state_dict(A.SEED_W, **A.synth_kw(case)))
+    x, cond = A.inputs(synth, case)
+    assert set(g.files) == set(A.GOLDEN_T) | {"names", "shapes"}
+    for key in A.GOLDEN_T:
+        with torch.no_grad():
+            out = oracle.unet_forward(x, A.timesteps(key, B), cond, sd, **A.unet_kw(case)).numpy()
+        assert out.shape == g[key].shape == (B, 1) + tuple(case["geometry"][1:])
+        assert np.abs(out - g[key]).max() <= TOL, key
+        assert np.abs(g[key]).max() > 0.1
+    assert np.abs(g["t500"] - g["tmixed"]).max() > 1e-3          # the per-sample timesteps matter
+
+
+def test_other_descriptors_manifest():
+    cases = json.load(open(os.path.join(GOLD, "MANIFEST.json")))["cases"]
+    for name, case in A.CASES.items():
+        m = cases["arch_" + name]
+        assert (m["B"], m["H"], m["W"]) == tuple(case["geometry"]) and m["threads"] == 8 and m["mkl_cbwr"] == "COMPATIBLE"
+        assert all(v == 0.0 for v in m["oracle_vs_reference_maxabs"].values()), (name, m["oracle_vs_reference_maxabs"])
+        assert os.path.getsize(os.path.join(GOLD, f"arch_{name}.npz")) < 64 * 1024

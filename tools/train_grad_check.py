@@ -1,6 +1,8 @@
 """Worst / median relative error of the training step's gradients against float64 autograd through the oracle, as JSON (one process per
 arithmetic: the families are chosen once per process from the environment, e.g. CDDPM_TRAIN_PRECISION=16).
-usage: python tools/train_grad_check.py [B H W]"""
+usage: python tools/train_grad_check.py [B H W [DESCRIPTOR]]
+DESCRIPTOR: a JSON object {"model_channels":, "channel_mult":, "num_res_blocks":, "cond_dim":} of another UNet than the experiment's (cond_dim 0:
+unconditioned)"""
 import importlib
 import json
 import os
@@ -18,20 +20,23 @@ import cddpm_oracle as oracle  # noqa: E402  (test infrastructure: this tool is 
 B, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (2, 32, 32)
 tr, synth, sched = (importlib.import_module(PKG + "." + m) for m in ("training", "synth", "schedule"))
 T = 1000
-sd_np = synth.synth_state_dict(0)
+desc = json.loads(sys.argv[4]) if len(sys.argv) >= 5 else {}
+arch = {k: (tuple(desc[k]) if k == "channel_mult" else desc[k]) for k in ("model_channels", "channel_mult", "num_res_blocks") if k in desc}
+cond_dim = desc.get("cond_dim", 128)
+sd_np = synth.synth_state_dict(0, num_classes=cond_dim or None, **arch)
 x01 = torch.from_numpy(synth.synth_slices(3, 0, B, H, W)).reshape(B, 1, H, W)
-cond = torch.from_numpy(synth.synth_cond(3, 0, B))
+cond = torch.from_numpy(synth.synth_cond(3, 0, B, cond_dim)) if cond_dim else None
 noise = torch.from_numpy(synth.noise_xT(3, 0, B, H, W)).reshape(B, 1, H, W)
 t = torch.tensor([(137 * (i + 1) + 3) % T for i in range(B)], dtype=torch.long)
 sd = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in sd_np.items()}
 buf64 = oracle.to_float64(oracle.schedule_buffers(T))
 x0 = x01 * 2 - 1
-ref_out = oracle.unet_forward(oracle.q_sample(x0.double(), t, noise.double(), buf64), t, cond.double(), sd)
+ref_out = oracle.unet_forward(oracle.q_sample(x0.double(), t, noise.double(), buf64), t, cond.double() if cond_dim else None, sd, **arch)
 dev = torch.device("cuda", 0)
-trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd_np.items()}, device=dev)
+trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd_np.items()}, device=dev, cond_dim=cond_dim or None, **arch)
 buf = sched.schedule_buffers(T)
 xt = buf["sqrt_alphas_cumprod"][t].reshape(-1, 1, 1, 1) * x0 + buf["sqrt_one_minus_alphas_cumprod"][t].reshape(-1, 1, 1, 1) * noise
-out = trainer.forward(xt.to(dev), t.to(dev), cond.to(dev))
+out = trainer.forward(xt.to(dev), t.to(dev), cond.to(dev) if cond_dim else None)
 loss, dout = trainer.loss_and_grad(out, noise.to(dev), buf["p2_loss_weight"][t].to(dev).contiguous(), "l2")
 grads = trainer.backward(dout)
 torch.cuda.synchronize()
