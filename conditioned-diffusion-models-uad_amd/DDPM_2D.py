@@ -307,7 +307,7 @@ class DDPM_2D(_Base):
                 ds *= 2
             self._hip_unet_trainer = UNetTrainer({k: v for k, v in unet.state_dict().items()}, model_channels=unet.model_channels,
                                         channel_mult=tuple(unet.channel_mult), num_res_blocks=unet.num_res_blocks,
-                                        cond_dim=unet.num_classes, device=device)
+                                        cond_dim=unet.num_classes, device=device, dropout=float(unet.dropout or 0))      # cfg.dropout_unet
             self._alias_unet()
             self._load_pending_optimizer_state()
         return self._hip_unet_trainer
@@ -483,8 +483,9 @@ class DDPM_2D(_Base):
         d = self.diffusion
         t = torch.randint(0, d.num_timesteps, (input.shape[0],), device=dev).long()
         ddp = torch.distributed.is_available() and torch.distributed.is_initialized()
+        slice0 = torch.distributed.get_rank() * input.shape[0] if ddp else 0       # the rank's slice offset: keys the dropout masks
         loss = _training.training_step(trainer, input, None if features is None else features.float(), t=t, noise=noise.float(),
-                                       timesteps=d.num_timesteps, encoder=enc_trainer,
+                                       timesteps=d.num_timesteps, encoder=enc_trainer, slice0=slice0,
                                        objective=d.objective, loss_type=d.loss_type, all_reduce=ddp, lr=_cfg_get(self.cfg, "lr", 1e-4),
                                        buffers={k: getattr(d, k) for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
                                                                            "p2_loss_weight")})

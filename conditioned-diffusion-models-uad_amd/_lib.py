@@ -94,6 +94,8 @@ SYMBOLS = {
     "cddpm_op_unpool2": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, C.c_float, _i, _vp]),
     "cddpm_op_sumpool2": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
     "cddpm_op_add_inplace": (_i, [_vp, _fp, _fp, _i64, _vp]),
+    "cddpm_op_act_dropout": (_i, [_vp, _fp, _fp, _i, _fp, _u64, _u32, _u64, _u32, C.c_double, _i, _i, _i, _vp]),
+    "cddpm_op_dropout_scale": (_i, [_vp, _fp, _u64, _u32, _u64, _u32, C.c_double, _i, _i, _i, _vp]),
     "cddpm_op_chan_image_corr": (_i, [_vp, _fp, _fp, _i, _fp, _i, _fp, _i, _i, _i, _i, _vp]),
     "cddpm_op_head_dgrad": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "cddpm_op_loss": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, C.c_float, _fp, _fp, _vp]),

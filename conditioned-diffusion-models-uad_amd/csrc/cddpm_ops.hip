@@ -322,6 +322,31 @@ int cddpm_op_add_inplace(cddpm_handle h, float* a_dev, const float* b_dev, int64
     launch_add_inplace(a_dev, b_dev, n, s);
     OP_EPILOGUE()
 }
+// nn.Dropout(p) of the ResBlocks' out_layers (OpenAI_Unet.py:255): the mask is drawn from (seed, step, slice0 + b, stream_id), never stored
+static bool dropout_shape_ok(int B, int HW, int C) {
+    return B >= 1 && HW >= 1 && C >= 4 && C % 4 == 0 && (long long)HW * C / 4 <= 0xFFFFFFFFLL && (long long)B * HW * C / 1024 < 0x7FFFFFFFLL;
+}
+int cddpm_op_act_dropout(cddpm_handle h, const float* x_dev, const float* coef_dev, int silu, float* out_dev, uint64_t seed, uint32_t step,
+                         uint64_t slice0, uint32_t stream_id, double p, int B, int HW, int C, void* stream) {
+    OP_CHECK(p >= 0.0 && p < 1.0, "cddpm_op_act_dropout: the drop probability must lie in [0, 1), got %g", p)
+    OP_CHECK(dropout_shape_ok(B, HW, C) && (coef_dev || !silu), "cddpm_op_act_dropout: unsupported arguments (B %d, HW %d, C %d, silu %d without coefficients)",
+             B, HW, C, silu)
+    OP_PROLOGUE(PC_OTHER, 0.0, 8.0 * B * (double)HW * C, x_dev && out_dev && !(((uintptr_t)x_dev | (uintptr_t)out_dev | (uintptr_t)coef_dev) & 15),
+                "cddpm_op_act_dropout: NULL argument or a pointer that is not 16-byte aligned")
+    launch_act_dropout(x_dev, coef_dev, silu, out_dev, seed, step, slice0, stream_id, p, B, HW, C, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_dropout_scale(cddpm_handle h, float* da_dev, uint64_t seed, uint32_t step, uint64_t slice0, uint32_t stream_id, double p, int B, int HW,
+                           int C, void* stream) {
+    OP_CHECK(p >= 0.0 && p < 1.0, "cddpm_op_dropout_scale: the drop probability must lie in [0, 1), got %g", p)
+    OP_CHECK(dropout_shape_ok(B, HW, C), "cddpm_op_dropout_scale: unsupported shape (B %d, HW %d, C %d)", B, HW, C)
+    OP_PROLOGUE(PC_OTHER, 0.0, 8.0 * B * (double)HW * C, da_dev && !((uintptr_t)da_dev & 15),
+                "cddpm_op_dropout_scale: NULL argument or a pointer that is not 16-byte aligned")
+    launch_dropout_scale(da_dev, seed, step, slice0, stream_id, p, B, HW, C, s);
+    OP_EPILOGUE()
+}
+
 int cddpm_op_chan_image_corr(cddpm_handle h, const float* t_dev, const float* coef_dev, int silu, const float* s_dev, int sign, float* dw_dev,
                              int B, int H, int W, int C, void* stream) {
     OP_PROLOGUE(PC_OTHER, 0.0, 0.0, t_dev && s_dev && dw_dev && C % 64 == 0 && (sign == 1 || sign == -1), "cddpm_op_chan_image_corr: bad arguments")

@@ -195,6 +195,12 @@ void launch_linear_backward(const float* x, const float* W, const float* dy, int
 void launch_unpool2(const float* dyp, float* dx, int B, int H, int W, int C, float scale, int accumulate, hipStream_t stream);
 void launch_sumpool2(const float* dy, float* dxp, int B, int H, int W, int C, int accumulate, hipStream_t stream);
 void launch_add_inplace(float* a, const float* b, long long n, hipStream_t stream);
+// dropout of a ResBlock's out_layers, the mask a function of (seed, step, global slice, stream_id) -- train_kernels.hip:
+// out = mask / (1 - p) * [SiLU]((x - mean) a + d) (coef nullptr: of x itself; x may be out); da *= mask / (1 - p)
+void launch_act_dropout(const float* x, const float* coef, int silu, float* out, uint64_t seed, uint32_t step, uint64_t slice0, uint32_t stream_id,
+                        double p, int B, long long HW, int C, hipStream_t stream);
+void launch_dropout_scale(float* da, uint64_t seed, uint32_t step, uint64_t slice0, uint32_t stream_id, double p, int B, long long HW, int C,
+                          hipStream_t stream);
 // dw [C][9] = sum_{b,q} act(T)[b,q,c] * simg[b, q + sign * tap]; part: 256 * C * 9 doubles of scratch
 void launch_chan_image_corr(const float* T, const float* coef, int silu, const float* simg, int sign, int B, int H, int W, int C,
                             double* part, float* dw, hipStream_t stream);

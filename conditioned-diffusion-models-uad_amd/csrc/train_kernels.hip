@@ -1050,6 +1050,88 @@ void launch_add_inplace(float* a, const float* b, long long n, hipStream_t strea
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Dropout of the ResBlocks' out_layers (GroupNorm -> FiLM -> SiLU -> nn.Dropout(p) -> conv, OpenAI_Unet.py:255). The mask is never stored:
+// it is a pure function of its counters, drawn again by the backward pass. Philox4x32-10 (the generator of small_kernels.hip and synth.py,
+// restated here: every .hip keeps its own device helpers), key = seed, counter = (element quad within the slice's [HW][C] tensor,
+// dropout step, GLOBAL slice index slice0 + b, stream = synth.STREAM_DROPOUT + the ResBlock's ordinal): word i of the quad's draw decides
+// element 4 quad + i, dropped iff word < thresh = floor(p 2^32); kept elements are scaled by fp32(1 / (1 - p)). Host restatement:
+// synth.dropout_mask. HBM bound: 16 B in, 16 B out per lane, ~70 integer operations for the draw.
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void philox4x32_10_t(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+struct DropoutArgs {
+    uint64_t seed, slice0;
+    uint32_t step, stream_id, thresh;
+    float scale;
+    int B, C;
+    long long nq;          // quads per slice: HW * C / 4
+};
+
+// out = mask / (1 - p) * act(x): AFF: act = [SiLU]((x - mean) a + d) from the coefficient planes coef [3][B][C]; else the identity.
+// x and out may be the same tensor (every lane reads its quad before it writes it): no __restrict__.
+template <bool AFF>
+__device__ __forceinline__ void dropout_body(const float* x, const float* __restrict__ coef, int silu, float* out, const DropoutArgs& a) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)a.B * a.nq) return;
+    const long long q = e % a.nq;
+    const int b = (int)(e / a.nq);
+    float4 v = *reinterpret_cast<const float4*>(x + 4 * e);
+    if (AFF) {
+        const size_t plane = (size_t)a.B * a.C;
+        const size_t ci = (size_t)b * a.C + (size_t)((4 * q) % a.C);
+        const float4 m = *reinterpret_cast<const float4*>(coef + ci);
+        const float4 ca = *reinterpret_cast<const float4*>(coef + plane + ci);
+        const float4 cd = *reinterpret_cast<const float4*>(coef + 2 * plane + ci);
+        v.x = (v.x - m.x) * ca.x + cd.x; v.y = (v.y - m.y) * ca.y + cd.y; v.z = (v.z - m.z) * ca.z + cd.z; v.w = (v.w - m.w) * ca.w + cd.w;
+        if (silu) { v.x = silu_t(v.x); v.y = silu_t(v.y); v.z = silu_t(v.z); v.w = silu_t(v.w); }
+    }
+    uint32_t r[4];
+    philox4x32_10_t((uint32_t)q, a.step, (uint32_t)(a.slice0 + (uint64_t)b), a.stream_id, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), r);
+    float4 o;
+    o.x = r[0] < a.thresh ? 0.f : v.x * a.scale;
+    o.y = r[1] < a.thresh ? 0.f : v.y * a.scale;
+    o.z = r[2] < a.thresh ? 0.f : v.z * a.scale;
+    o.w = r[3] < a.thresh ? 0.f : v.w * a.scale;
+    *reinterpret_cast<float4*>(out + 4 * e) = o;
+}
+__global__ __launch_bounds__(256) void act_dropout_kernel(const float* x, const float* __restrict__ coef, int silu, float* out, const DropoutArgs a) {
+    if (coef) dropout_body<true>(x, coef, silu, out, a);
+    else dropout_body<false>(x, nullptr, 0, out, a);
+}
+// da *= mask / (1 - p), in place: the backward of the dropout, the mask drawn again from the forward's counters
+__global__ __launch_bounds__(256) void dropout_scale_kernel(float* da, const DropoutArgs a) { dropout_body<false>(da, nullptr, 0, da, a); }
+
+static DropoutArgs dropout_args(uint64_t seed, uint32_t step, uint64_t slice0, uint32_t stream_id, double p, int B, long long HW, int C) {
+    DropoutArgs a;
+    a.seed = seed; a.slice0 = slice0; a.step = step; a.stream_id = stream_id;
+    a.thresh = (uint32_t)(p * 4294967296.0);            // floor(p 2^32), p in [0, 1): exact in double
+    a.scale = (float)(1.0 / (1.0 - p));
+    a.B = B; a.C = C; a.nq = HW * C / 4;
+    return a;
+}
+void launch_act_dropout(const float* x, const float* coef, int silu, float* out, uint64_t seed, uint32_t step, uint64_t slice0, uint32_t stream_id,
+                        double p, int B, long long HW, int C, hipStream_t stream) {
+    const DropoutArgs a = dropout_args(seed, step, slice0, stream_id, p, B, HW, C);
+    hipLaunchKernelGGL(act_dropout_kernel, dim3((unsigned)((B * a.nq + 255) / 256)), dim3(256), 0, stream, x, coef, silu, out, a);
+}
+void launch_dropout_scale(float* da, uint64_t seed, uint32_t step, uint64_t slice0, uint32_t stream_id, double p, int B, long long HW, int C,
+                          hipStream_t stream) {
+    const DropoutArgs a = dropout_args(seed, step, slice0, stream_id, p, B, HW, C);
+    hipLaunchKernelGGL(dropout_scale_kernel, dim3((unsigned)((B * a.nq + 255) / 256)), dim3(256), 0, stream, da, a);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The two single-channel convolutions at the ends of the UNet (input_blocks.0: Conv2d(1 -> C); out.2: Conv2d(C -> 1), OpenAI_Unet.py
 // :606-612, :793-797). Both weight gradients are a correlation of a C-channel tensor T with a one-channel image s:
 //     dW[c][tap] = sum_{b,q} T'[b,q,c] * s[b, q + sign * tap],   T' = act(T) (coefficient planes + SiLU) or T itself

@@ -684,3 +684,19 @@ class CddpmEngine:
         self._ck(self.lib.cddpm_op_attention(self._h, qkv.data_ptr(), out.data_ptr(), B, N, C3 // 3,
                                              _stream_ptr(self.device)), "cddpm_op_attention")
         return out
+
+    def op_act_dropout(self, x, coef, silu, *, seed, step, slice0, stream_id, p):
+        """mask / (1 - p) * [SiLU]((x - mean) a + d) with coef [3][B][C] (None: mask / (1 - p) * x); x NHWC [B,H,W,C]; the mask is
+        synth.dropout_mask's (stream_id = synth.STREAM_DROPOUT + layer)"""
+        B, H, W, C = x.shape
+        out = torch.empty_like(x)
+        self._ck(self.lib.cddpm_op_act_dropout(self._h, x.data_ptr(), coef.data_ptr() if coef is not None else None, int(bool(silu)), out.data_ptr(),
+                                               seed, step, slice0, stream_id, p, B, H * W, C, _stream_ptr(self.device)), "cddpm_op_act_dropout")
+        return out
+
+    def op_dropout_scale(self, da, *, seed, step, slice0, stream_id, p):
+        """da *= mask / (1 - p) in place (NHWC [B,H,W,C]); returns da"""
+        B, H, W, C = da.shape
+        self._ck(self.lib.cddpm_op_dropout_scale(self._h, da.data_ptr(), seed, step, slice0, stream_id, p, B, H * W, C, _stream_ptr(self.device)),
+                 "cddpm_op_dropout_scale")
+        return da

@@ -115,6 +115,39 @@ def synth_slices(seed: int, slice0: int, nslices: int, H: int, W: int) -> np.nda
     return _per_slice(uniform_quads, H * W, 0, slice0, nslices, STREAM_INPUT, seed).reshape(nslices, 1, H, W)
 
 
+STREAM_DROPOUT = 0x4000  # + the ResBlock's ordinal in program order: training dropout masks (clear of 0x1001-4, 0x2000+ and 0x3000+ ordinals)
+
+
+def dropout_threshold(p: float) -> int:
+    """an element is dropped iff its 32-bit word is below floor(p 2^32)"""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must lie in [0, 1), got {p!r}")
+    return int(math.floor(float(p) * 4294967296.0))
+
+
+def dropout_scale(p: float) -> np.float32:
+    """what kept elements are multiplied by: 1 / (1 - p), rounded once to fp32"""
+    return np.float32(1.0 / (1.0 - float(p)))
+
+
+def dropout_mask(seed: int, step: int, layer: int, slice0: int, B: int, H: int, W: int, C: int, p: float) -> np.ndarray:
+    """keep mask (1 = kept) of the dropout in front of ResBlock `layer`'s second convolution (nn.Dropout(p), reference
+    OpenAI_Unet.py:255) at training forward `step`, for global slices [slice0, slice0 + B): uint8 [B, H, W, C] -- the host restatement of
+    csrc/train_kernels.hip's act_dropout / dropout_scale. Counter = (quad of the slice's [HW][C] tensor, step, slice, STREAM_DROPOUT +
+    layer), key = seed; word i of quad q decides element 4 q + i. The training forward multiplies by mask * dropout_scale(p)."""
+    n = H * W * C
+    if n % 4:
+        raise ValueError("H * W * C must be a multiple of 4")
+    thresh = np.uint32(dropout_threshold(p))
+    q = np.arange(n // 4, dtype=np.uint32)
+    out = np.empty((B, n), dtype=np.uint8)
+    for i in range(B):
+        xs = philox4x32(q, np.uint32(step & 0xFFFFFFFF), np.uint32((slice0 + i) & 0xFFFFFFFF), np.uint32((STREAM_DROPOUT + layer) & 0xFFFFFFFF),
+                        seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+        out[i] = (np.stack(xs, axis=-1).reshape(-1) >= thresh).astype(np.uint8)
+    return out.reshape(B, H, W, C)
+
+
 # ----------------------------------------------------------------------------------------------
 # synthetic UNet weights with the reference's state_dict names and shapes
 # ----------------------------------------------------------------------------------------------

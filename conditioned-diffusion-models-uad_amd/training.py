@@ -14,7 +14,9 @@ encoder_training.EncoderTrainer. Convolutions keep the inference path's fp32-gra
 reference trainer's `precision: 16` arithmetic (plain fp16 operands, fp32 accumulation) is selected per process (CDDPM_TRAIN_PRECISION=16,
 set from the Trainer's precision by the DDPM_2D mirror). A step whose gradients hold inf / NaN is skipped on the device (`guard`). The loss
 scale is fixed by default; `UNetTrainer.enable_loss_scaling` makes it dynamic as torch's GradScaler does for the reference (backed off on a
-skipped step, grown after `growth_interval` clean ones), with the scale kept on the device. Measured: DESIGN.md section 4b.
+skipped step, grown after `growth_interval` clean ones), with the scale kept on the device. `dropout` > 0 (the experiment's
+`dropout_unet`) applies nn.Dropout in front of every ResBlock's second convolution with a mask that is drawn on the device from counters
+and never stored (csrc/train_kernels.hip, synth.dropout_mask). Measured: DESIGN.md section 4b.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import schedule as _schedule
+from . import synth as _synth
 from .engine import CddpmEngine, _stream_ptr
 
 
@@ -128,7 +131,7 @@ class UNetTrainer:
     input gradient. No operator synchronises: temporaries come from the handle's scratch arena."""
 
     def __init__(self, params: Dict[str, torch.Tensor], *, model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3,
-                 cond_dim=128, device=None, exp_refresh=50, overlap_wgrad=None):
+                 cond_dim=128, device=None, exp_refresh=50, overlap_wgrad=None, dropout=0.0, dropout_seed=None):
         self.dev = torch.device(device) if device is not None else next(iter(params.values())).device
         self._cfg = dict(model_channels=model_channels, channel_mult=tuple(channel_mult), num_res_blocks=num_res_blocks, cond_dim=cond_dim)
         self.C, self.mult, self.nres, self.cond_dim = model_channels, tuple(channel_mult), num_res_blocks, cond_dim
@@ -136,6 +139,12 @@ class UNetTrainer:
         # ONE [sum 2 Cout, E] matrix (11776 x 1024) -- one Linear forward and one backward per step instead of 27 (the inference engine's
         # table does the same); then every other tensor, each 256-byte aligned
         self.program = self._build_program()
+        # nn.Dropout(p) between the SiLU and the second convolution of every ResBlock (OpenAI_Unet.py:255; cfg.dropout_unet). The mask is a
+        # function of (seed, dropout step = training forwards so far, global slice index, ResBlock ordinal): regenerated by the backward
+        # pass, never stored. seed None: torch.initial_seed(), as the diffusion mirror seeds its noise. 0: no launch and no tensor changes.
+        self.dropout, self.dropout_seed = dropout_settings(dropout, dropout_seed)
+        self.dropout_step = 0
+        self._res_ordinal = {n: i for i, n in enumerate(n for kind, n, _a in self.program if kind == "res")}
         missing = unsupported_blocks(params, self.program)
         if missing:
             raise NotImplementedError(f"training: the state dict holds parameters of blocks the training program does not build: {', '.join(missing)} "
@@ -397,6 +406,23 @@ class UNetTrainer:
                                               int(bool(upsample)), _p(dy), co, ks, _p(self.g[name + ".weight"]),
                                               _p(self.g[name + ".bias"]) if bias else None, B, H, W, self._s()), "op_conv_wgrad")
 
+    def _drop_args(self, name, drop, x):
+        step, slice0 = drop
+        B, H, W, Cc = x.shape
+        return (self.dropout_seed, step & 0xFFFFFFFF, slice0, _synth.STREAM_DROPOUT + self._res_ordinal[name], self.dropout, B, H * W, Cc, self._s())
+
+    def act_dropout(self, name, x, coef, drop):
+        """mask / (1 - p) * SiLU(GroupNorm + FiLM of x) of ResBlock `name`, materialised once (the second convolution's input);
+        drop = (dropout step, global index of the batch's first slice)"""
+        out = torch.empty_like(x)
+        self._ck(self.lib.cddpm_op_act_dropout(self.h, _p(x), _p(coef), 1, _p(out), *self._drop_args(name, drop, x)), "op_act_dropout")
+        return out
+
+    def dropout_scale_(self, name, da, drop):
+        """da *= mask / (1 - p) with the forward's mask of ResBlock `name`"""
+        self._ck(self.lib.cddpm_op_dropout_scale(self.h, _p(da), *self._drop_args(name, drop, da)), "op_dropout_scale")
+        return da
+
     def close(self):
         """releases the handles (operator arenas, workspaces)"""
         for e in (self.eng, self.eng_w):
@@ -429,9 +455,15 @@ class UNetTrainer:
         return a
 
     # ------------------------------------------------------------------ forward (OpenAI_Unet.py:823-1006), activations saved
-    def forward(self, x: torch.Tensor, t: torch.Tensor, cond: torch.Tensor) -> torch.Tensor:
-        """x [B,1,H,W], t [B] int, cond [B,cond_dim] on the device -> model output [B,1,H,W]; everything backward needs is kept"""
+    def forward(self, x: torch.Tensor, t: torch.Tensor, cond: torch.Tensor, slice0: int = 0) -> torch.Tensor:
+        """x [B,1,H,W], t [B] int, cond [B,cond_dim] on the device -> model output [B,1,H,W]; everything backward needs is kept.
+        slice0: the global index of the batch's first slice (dropout masks are keyed by it: a slice's mask does not depend on the rank
+        or the batch it is trained in); with dropout > 0 every call is one dropout step."""
         p, sv = self.p, {}
+        drop = None
+        if self.dropout > 0:
+            drop = sv["drop"] = (self.dropout_step, int(slice0))
+            self.dropout_step += 1
         B, _c, H, W = x.shape
         self._fit(B, H, W)
         self.rec: Dict[int, torch.Tensor] = {}             # data_ptr of a saved activation -> its GroupNorm statistics records
@@ -494,11 +526,15 @@ class UNetTrainer:
                     resid, res_up = cur, False
                 coef2 = self.gn_coef(h1, None, name + ".out_layers.0", film)
                 r.update(h1=h1, coef2=coef2, rec_h1=self.rec_of(h1))
+                a2, c2coef, c2silu = h1, coef2, True
+                if drop is not None:             # GroupNorm -> FiLM -> SiLU -> Dropout materialised once; the convolution reads it as it is
+                    a2 = r["a2"] = self.act_dropout(name, h1, coef2, drop)
+                    c2coef, c2silu = None, False
                 if a["cin"] != a["cout"]:        # the 1x1 skip_connection reads cat[cur, x1] as two tensors: nothing is concatenated in memory
-                    out = self.conv(c2, h1, None, coef2, True, skip=cur, skip1=x1, skip_name=name + ".skip_connection",
+                    out = self.conv(c2, a2, None, c2coef, c2silu, skip=cur, skip1=x1, skip_name=name + ".skip_connection",
                                     bias=p[c2 + ".bias"] + p[name + ".skip_connection.bias"])
                 else:
-                    out = self.conv(c2, h1, None, coef2, True, res=resid, res_up=res_up)
+                    out = self.conv(c2, a2, None, c2coef, c2silu, res=resid, res_up=res_up)
                 sv[name] = r
                 cur = out
                 if a.get("push"):
@@ -570,10 +606,15 @@ class UNetTrainer:
                 x0, x1, h1, film = r["x0"], r["x1"], r["h1"], r["film"]
                 c1, c2 = name + ".in_layers.2", name + ".out_layers.3"
                 # out = conv2(act2(h1)) + skip(x)
-                self.wgrad(c2, h1, None, r["coef2"], True, d)             # (weight gradients first: they start on the side stream while
+                if "a2" in r:                                             # dropout: the convolution read the masked activation a2
+                    self.wgrad(c2, r["a2"], None, None, False, d)
+                else:
+                    self.wgrad(c2, h1, None, r["coef2"], True, d)         # (weight gradients first: they start on the side stream while
                 if a["cin"] != a["cout"]:                                  #  the main stream runs the input gradients)
                     self.wgrad(name + ".skip_connection", x0, x1, None, False, d)
                 da2 = self.dgrad(c2, d)
+                if "a2" in r:
+                    self.dropout_scale_(name, da2, sv["drop"])
                 dxs = None
                 if a["cin"] != a["cout"]:
                     dxs = self.dgrad(name + ".skip_connection", d)            # [B,H,W,Cin] over the concatenation
@@ -769,6 +810,8 @@ class UNetTrainer:
         out = {"m": st["m"].detach().clone(), "v": st["v"].detach().clone(), "ctrl": self._ctrl().detach().clone(),
                "layout": [(k, int(v.numel())) for k, v in self.p.items()], "wexp": dict(getattr(self, "wexp", {})),
                "calls": int(st.get("calls", 0))}
+        if self.dropout > 0:               # a resumed run continues the mask sequence
+            out["dropout"] = dropout_state(self.dropout_seed, self.dropout_step)
         if self.loss_scaling:
             self.join_side()
             g, b, n = self.scaler_cfg
@@ -794,6 +837,8 @@ class UNetTrainer:
         if state.get("wexp") and self._convs:
             self.wexp = {k: int(state["wexp"][k]) for k in self._convs}
             self.repack()
+        if state.get("dropout") is not None:       # absent: saved without dropout -- seed and step are left as they are
+            self.dropout_seed, self.dropout_step = dropout_from_state(state["dropout"])
 
     def parameters_changed(self) -> None:
         """the flat parameter buffer was written from outside (load_state_dict into the aliased module parameters): refresh the
@@ -801,6 +846,39 @@ class UNetTrainer:
         if self._convs:
             self.refresh_exponents()
             self.repack()
+
+
+def dropout_settings(dropout=0.0, seed=None):
+    """the checked `dropout`, `dropout_seed` arguments of UNetTrainer -> (p, 64-bit seed); seed None: torch.initial_seed()"""
+    try:
+        p = float(dropout if dropout is not None else 0.0)
+    except (TypeError, ValueError):
+        raise ValueError(f"dropout must be a number in [0, 1), got {dropout!r}") from None
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout must lie in [0, 1), got {dropout!r}")
+    if seed is not None and not _integer(seed):
+        raise ValueError(f"dropout_seed must be an integer, got {seed!r}")
+    return p, int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def dropout_state(seed: int, step: int) -> Dict[str, int]:
+    """what optimizer_state() carries under "dropout": the mask generator's key and the number of training forwards so far"""
+    if not (_integer(seed) and 0 <= seed < 2 ** 64):
+        raise ValueError(f"dropout seed must be an integer in [0, 2^64), got {seed!r}")
+    if not (_integer(step) and step >= 0):
+        raise ValueError(f"dropout step must be an integer >= 0, got {step!r}")
+    return {"seed": int(seed), "step": int(step)}
+
+
+def dropout_from_state(state) -> "tuple[int, int]":
+    """(seed, step) from what dropout_state returned (a checkpoint may hand the numbers back as 0-d tensors); ValueError otherwise"""
+    try:
+        seed, step = state["seed"], state["step"]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError(f"dropout state must hold 'seed' and 'step', got {state!r}") from None
+    seed, step = (int(v) if isinstance(v, torch.Tensor) and v.numel() == 1 else v for v in (seed, step))
+    d = dropout_state(seed, step)
+    return d["seed"], d["step"]
 
 
 def _power_of_two(x) -> bool:
@@ -925,14 +1003,15 @@ def all_reduce_sum_(flat: torch.Tensor) -> int:
 
 
 def training_step(trainer: UNetTrainer, x01: torch.Tensor, cond: Optional[torch.Tensor], *, t: torch.Tensor, noise: torch.Tensor, timesteps=1000,
-                  objective="pred_x0", loss_type="l1", all_reduce=False, lr=1e-4, buffers=None, encoder=None):
+                  objective="pred_x0", loss_type="l1", all_reduce=False, lr=1e-4, buffers=None, encoder=None, slice0=0):
     """One optimisation step of the diffusion loss (cond_DDPM.py:647-655 -> :565-645; DDPM_2D.py:114-135): x01 [B,1,H,W] in [0,1], context
     cond [B,cond_dim], per-sample timesteps t and noise given by the caller; `buffers`: the diffusion's schedule tables (default: the
     cosine schedule of `timesteps`). Returns the loss. `all_reduce`: sum the gradients over the ranks of torch.distributed (RCCL) before
     the update -- the data-parallel training of the reference (Lightning DDP, src/train.py:62-65).
     `encoder` (an encoder_training.EncoderTrainer): the context is computed by it in training mode (cond is ignored) and it is trained
     jointly -- dL/d(context) of the UNet's backward flows into its backward, its gradients join the all-reduce and its own Adam step runs
-    with the same learning rate: `features = self(input)` + `optim.Adam(self.parameters())` of the reference."""
+    with the same learning rate: `features = self(input)` + `optim.Adam(self.parameters())` of the reference.
+    `slice0`: the global index of this rank's first slice (keys the dropout masks of a trainer built with dropout > 0)."""
     buf = buffers if buffers is not None else _schedule.schedule_buffers(timesteps)
     dev = trainer.dev
     trainer._fit(*[x01.shape[i] for i in (0, 2, 3)])       # the handle and its scratch arena before the first operator runs
@@ -942,7 +1021,7 @@ def training_step(trainer: UNetTrainer, x01: torch.Tensor, cond: Optional[torch.
     sa = buf["sqrt_alphas_cumprod"].to(dev)[t].reshape(-1, 1, 1, 1)
     s1 = buf["sqrt_one_minus_alphas_cumprod"].to(dev)[t].reshape(-1, 1, 1, 1)
     xt = (sa * x0 + s1 * noise.float()).contiguous()      # q_sample (cond_DDPM.py:548-554); elementwise plumbing, not a hot operator
-    out = trainer.forward(xt, t, cond)
+    out = trainer.forward(xt, t, cond, slice0=slice0)
     target = noise if objective == "pred_noise" else x0
     p2w = buf["p2_loss_weight"].to(dev)[t].contiguous()
     loss, dout = trainer.loss_and_grad(out, target, p2w, loss_type)

@@ -389,6 +389,19 @@ int cddpm_op_pool_act(cddpm_handle h, const float* x_dev, const float* coef_dev,
 int cddpm_op_unpool2(cddpm_handle h, const float* dyp_dev, float* dx_dev, int B, int H, int W, int C, float scale, int accumulate, void* stream);
 int cddpm_op_sumpool2(cddpm_handle h, const float* dy_dev, float* dxp_dev, int B, int H, int W, int C, int accumulate, void* stream);
 int cddpm_op_add_inplace(cddpm_handle h, float* a_dev, const float* b_dev, int64_t n, void* stream);
+/* nn.Dropout(p) between the SiLU and the second convolution of every ResBlock (OpenAI_Unet.py:255), for training with dropout_unet > 0.
+ * The mask is a pure function of its counters and is never stored: Philox4x32-10 (the generator of cddpm_noise_fill), key = seed, counter =
+ * (element quad within the slice's [HW][C] tensor, step, global slice index slice0 + b, stream_id); word i of a quad's draw decides element
+ * 4 quad + i, which is dropped iff word < floor(p 2^32); kept elements are multiplied by fp32(1 / (1 - p)). A slice's mask depends on its
+ * global index only, never on the batch or the rank it is trained in. stream_id: synth.STREAM_DROPOUT + the ResBlock's ordinal.
+ *   act_dropout:   out[b,q,c] = mask / (1 - p) * [SiLU]((x[b,q,c] - mean[b,c]) a[b,c] + d[b,c]) with coef_dev [3][B][C] = (mean, a, d) as
+ *                  cddpm_op_gn_coef writes it; coef_dev NULL (silu must be 0): mask / (1 - p) * x. out_dev may be x_dev.
+ *   dropout_scale: da *= mask / (1 - p) in place -- the backward, the mask drawn again from the same counters.
+ * p outside [0, 1), NULL or not 16-byte aligned pointers, C % 4 != 0 or HW * C / 4 >= 2^32 are refused with a message. */
+int cddpm_op_act_dropout(cddpm_handle h, const float* x_dev, const float* coef_dev, int silu, float* out_dev, uint64_t seed, uint32_t step,
+                         uint64_t slice0, uint32_t stream_id, double p, int B, int HW, int C, void* stream);
+int cddpm_op_dropout_scale(cddpm_handle h, float* da_dev, uint64_t seed, uint32_t step, uint64_t slice0, uint32_t stream_id, double p, int B,
+                           int HW, int C, void* stream);
 /* weight gradients of the two single-channel convolutions: dw_dev [C][9] = sum_{b,q} act(T)[b,q,c] * s[b, q + sign * tap]
  * (input conv: T = dL/d(output), s = the image, sign +1; head conv: T = the head's input, act = its GroupNorm + SiLU, s = dL/d(out),
  * sign -1), and the head's input gradient dact[b,q,c] = sum_tap w9[tap][c] dout[b, q - tap]. */

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--encoder", action="store_true", help="train the context encoder (ResNet-50) jointly, as the reference does")
+    ap.add_argument("--dropout", type=float, default=0.0, help="the UNet's dropout probability (cfg.dropout_unet); 0: no dropout launches")
     ap.add_argument("--phases", action="store_true", help="time forward / backward / adam separately (synchronises between them)")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without RANK in the environment: start the N ranks (torchrun child) and relay rank 0's line")
     a = ap.parse_args()
@@ -40,7 +41,7 @@ def main():
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=dev)
     sd = synth.synth_state_dict(0)
-    trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd.items()}, device=dev)
+    trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd.items()}, device=dev, dropout=a.dropout, dropout_seed=1)
     enc = None
     if a.encoder:
         et = importlib.import_module(PKG + ".encoder_training")
@@ -52,13 +53,13 @@ def main():
     t = torch.tensor([(137 * (i + 1)) % T for i in range(B)], dtype=torch.long, device=dev)
     losses = []
     for _ in range(a.warmup):
-        losses.append(float(tr.training_step(trainer, x01, cond, t=t, noise=noise, objective="pred_noise", loss_type="l2", all_reduce=ddp, encoder=enc)))
+        losses.append(float(tr.training_step(trainer, x01, cond, t=t, noise=noise, objective="pred_noise", loss_type="l2", all_reduce=ddp, encoder=enc, slice0=rank * B)))
     torch.cuda.synchronize()
     if ddp:
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = tr.training_step(trainer, x01, cond, t=t, noise=noise, objective="pred_noise", loss_type="l2", all_reduce=ddp, encoder=enc)
+        loss = tr.training_step(trainer, x01, cond, t=t, noise=noise, objective="pred_noise", loss_type="l2", all_reduce=ddp, encoder=enc, slice0=rank * B)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     if ddp:
@@ -69,7 +70,7 @@ def main():
     bits = tr.get_precision()
     arith = "fp32-emulated convolutions" if bits == 32 else "fp16-operand convolutions (precision 16)"
     res = {"workload": f"training step {B}x1x{S}x{S} (noise-pred MSE, {arith}, Adam" + (", context encoder trained jointly)" if enc else ")"), "ms_per_step": dt * 1e3,
-           "precision": bits,
+           "precision": bits, "dropout": a.dropout,
            "slices_per_s": world * B / dt, "n_gpus": world, "losses": losses, "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
     if a.phases:
         buf = importlib.import_module(PKG + ".schedule").schedule_buffers(T)
