@@ -299,15 +299,10 @@ class DDPM_2D(_Base):
         if getattr(self, "_hip_unet_trainer", None) is None:
             from .training import UNetTrainer
             unet = self.diffusion.model
-            ds, levels = 1, len(unet.channel_mult)
-            for _lvl in range(levels):
-                if ds in tuple(unet.attention_resolutions):
-                    raise NotImplementedError("training: attention inside the resolution levels is not built (the cDDPM experiment has none: "
-                                              "att_res [3, 6, 12] never matches ds in {1, 2, 4})")
-                ds *= 2
             self._hip_unet_trainer = UNetTrainer({k: v for k, v in unet.state_dict().items()}, model_channels=unet.model_channels,
                                         channel_mult=tuple(unet.channel_mult), num_res_blocks=unet.num_res_blocks,
-                                        cond_dim=unet.num_classes, device=device, dropout=float(unet.dropout or 0))      # cfg.dropout_unet
+                                        cond_dim=unet.num_classes, device=device, dropout=float(unet.dropout or 0),       # cfg.dropout_unet
+                                        attention_resolutions=tuple(unet.attention_resolutions))                         # cfg.att_res
             self._alias_unet()
             self._load_pending_optimizer_state()
         return self._hip_unet_trainer

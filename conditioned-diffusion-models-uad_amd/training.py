@@ -16,7 +16,9 @@ set from the Trainer's precision by the DDPM_2D mirror). A step whose gradients 
 scale is fixed by default; `UNetTrainer.enable_loss_scaling` makes it dynamic as torch's GradScaler does for the reference (backed off on a
 skipped step, grown after `growth_interval` clean ones), with the scale kept on the device. `dropout` > 0 (the experiment's
 `dropout_unet`) applies nn.Dropout in front of every ResBlock's second convolution with a mask that is drawn on the device from counters
-and never stored (csrc/train_kernels.hip, synth.dropout_mask). Measured: DESIGN.md section 4b.
+and never stored (csrc/train_kernels.hip, synth.dropout_mask). `attention_resolutions` (the experiment's `att_res`) puts attention
+blocks inside the resolution levels as the reference's constructor does; they run on the middle block's operators. Measured: DESIGN.md
+section 4b.
 """
 from __future__ import annotations
 
@@ -35,19 +37,27 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def unet_program(model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3):
+def unet_program(model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3, attention_resolutions=(3, 6, 12)):
     """the UNet as a list of (kind, state_dict prefix, attributes) in forward order -- UNetModel.__init__ / forward of the reference
-    (OpenAI_Unet.py:604-797, :823-1006) for the cDDPM configuration (resblock_updown, attention in the middle block only): the input
-    convolution, ResBlocks ('plain' | 'down' | 'up'; `push`: the output also goes on the skip stack; `concat`: channels popped from it
-    and concatenated to the input), the middle attention block, the output head."""
+    (OpenAI_Unet.py:604-797, :823-1006) for the cDDPM configuration (resblock_updown): the input convolution, ResBlocks ('plain' |
+    'down' | 'up'; `concat`: channels popped from the skip stack and concatenated to the input), attention blocks (the middle one, and
+    one behind every ResBlock of a level whose down-sampling factor ds = 2^level is in `attention_resolutions`; the experiment's
+    (3, 6, 12) matches none), the output head. `push`: the entry is the LAST of its input block, its output also goes on the skip stack
+    -- the attention's where a block has one (sub-index 1), else the ResBlock's. In an output block the attention sits at sub-index 1
+    and moves a level's closing up-ResBlock from sub-index 1 to 2."""
     C_, prog, chans = model_channels, [], []
-    ch, idx = C_, 1
+    att = tuple(int(a) for a in attention_resolutions)
+    ch, idx, ds = C_, 1, 1
     prog.append(("in", "input_blocks.0.0", None))
     chans.append(C_)
     for level, m in enumerate(channel_mult):
         co = m * C_
         for _ in range(num_res_blocks):
-            prog.append(("res", f"input_blocks.{idx}.0", dict(cin=ch, cout=co, kind="plain", push=True)))
+            if ds in att:
+                prog.append(("res", f"input_blocks.{idx}.0", dict(cin=ch, cout=co, kind="plain")))
+                prog.append(("attn", f"input_blocks.{idx}.1", dict(c=co, push=True)))
+            else:
+                prog.append(("res", f"input_blocks.{idx}.0", dict(cin=ch, cout=co, kind="plain", push=True)))
             ch = co
             chans.append(ch)
             idx += 1
@@ -55,6 +65,7 @@ def unet_program(model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3):
             prog.append(("res", f"input_blocks.{idx}.0", dict(cin=ch, cout=ch, kind="down", push=True)))
             chans.append(ch)
             idx += 1
+            ds *= 2
     prog.append(("res", "middle_block.0", dict(cin=ch, cout=ch, kind="plain")))
     prog.append(("attn", "middle_block.1", dict(c=ch)))
     prog.append(("res", "middle_block.2", dict(cin=ch, cout=ch, kind="plain")))
@@ -65,8 +76,13 @@ def unet_program(model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3):
             ich = chans.pop()
             prog.append(("res", f"output_blocks.{idx}.0", dict(cin=ch + ich, cout=co, kind="plain", concat=ich)))
             ch = co
+            sub = 1
+            if ds in att:
+                prog.append(("attn", f"output_blocks.{idx}.{sub}", dict(c=ch)))
+                sub += 1
             if level > 0 and i == num_res_blocks:
-                prog.append(("res", f"output_blocks.{idx}.1", dict(cin=ch, cout=ch, kind="up")))
+                prog.append(("res", f"output_blocks.{idx}.{sub}", dict(cin=ch, cout=ch, kind="up")))
+                ds //= 2
             idx += 1
     prog.append(("head", "out", dict(c=ch)))
     return prog
@@ -110,8 +126,8 @@ def program_param_names(program):
 
 def unsupported_blocks(names, program):
     """the UNet blocks that hold parameters (`names`: state_dict keys) of modules `program` never visits, e.g. 'input_blocks.1.1' of a
-    model with attention inside its levels. Their parameters would never receive a gradient. Keys outside the UNet's own name space
-    (anything but input_blocks / middle_block / output_blocks / out) are not judged."""
+    model with attention inside its levels against a program built without it. Their parameters would never receive a gradient. Keys
+    outside the UNet's own name space (anything but input_blocks / middle_block / output_blocks / out) are not judged."""
     known, missing = program_param_names(program), []
     for k in names:
         if k.startswith(("input_blocks.", "middle_block.", "output_blocks.", "out.")) and k not in known:
@@ -120,6 +136,64 @@ def unsupported_blocks(names, program):
             if blk not in missing:
                 missing.append(blk)
     return missing
+
+
+def attention_scratch_bytes(program, B, H, W):
+    """what cddpm_op_attention_backward takes from the operator arena at the largest attention block of `program` on a B x H x W batch:
+    B x (C / 64) heads x N tokens x 2 floats of row statistics (include/cddpm.h), rounded up to the arena's 256-byte granule"""
+    lv, worst = 0, 0
+    for kind, _name, a in program:
+        if kind == "res":
+            lv += 1 if a["kind"] == "down" else -1 if a["kind"] == "up" else 0
+        elif kind == "attn":
+            worst = max(worst, B * (a["c"] // 64) * (H >> lv) * (W >> lv) * 2 * 4)
+    return (worst + 255) // 256 * 256
+
+
+ARENA_FLOOR = 192 << 20      # what every handle's operator arena holds besides the weight gradient's k-images, at the least
+
+
+def operator_scratch_bytes(program, B, H, W, emb_dim=2048):
+    """-> (main, wgrad): the largest temporaries ONE operator call of the training step takes from its handle's arena on a B x H x W
+    batch, the weight gradient's two k-images aside (UNetTrainer._fit adds those) -- a host restatement of the OpScratch requests of
+    csrc/cddpm_ops.hip, every request rounded up to the arena's 256-byte granule. `wgrad`: cddpm_op_conv_wgrad alone (partial tiles as
+    conv_wgrad_parts plans them + the bias gradient's partial rows), what the side-stream handle runs; `main`: that and every other
+    operator -- the head's nine partial dot products per pixel (B H W 9 floats: the one that grows fastest with the geometry), the
+    GroupNorm backward's planes and partial sums and a swept GroupNorm's records (B x pixel ranges x C), the attention backward's row
+    statistics (attention_scratch_bytes), the batched embedding Linear's backward (33 x B x emb_dim), the input convolution's and the
+    head's weight-gradient partials. UNetTrainer._fit sizes the arena as max(ARENA_FLOOR, this) + the k-images."""
+    r = lambda n: (n + 255) // 256 * 256
+    G = (B + 7) // 8
+
+    def gn(c, h, w):
+        ns = -(-(h * w) // (256 if h * w >= 4096 else 64))
+        return r(B * ns * c * 8) + 2 * r(16 * B * c) + r(B * ns * c * 16)
+
+    def wg(co, ci, taps, h, w):
+        img = taps == 9 or ci % 64 == 0
+        per = (co // 64) * (ci // (64 if taps == 1 and img else 32))
+        P = max(1, min(-(-512 // per), G * ((h + 1) // 2) * ((w + 7) // 8), 64))
+        P = (P + 7) // 8 * 8 if img else P
+        rows = -(-(h * w) // 8) * G
+        return r(P * co * ci * taps * 4) + (r(((rows + -(-rows // 128)) * co + 3) // 4 * 16) if img else 0)
+
+    main = max(r(33 * B * emb_dim * 4), attention_scratch_bytes(program, B, H, W))
+    wgrad, lv = 0, 0
+    for kind, _name, a in program:
+        h, w = H >> lv, W >> lv
+        if kind in ("in", "head"):
+            c = a["c"] if a else program[1][2]["cin"]
+            main = max(main, r(256 * c * 9 * 8), r(512 * c * 8), r(B * H * W * 9 * 4) if kind == "head" else 0, gn(c, h, w) if kind == "head" else 0)
+        elif kind == "attn":
+            main = max(main, gn(a["c"], h, w))
+            wgrad = max(wgrad, wg(3 * a["c"], a["c"], 1, h, w), wg(a["c"], a["c"], 1, h, w))
+        else:
+            lv += 1 if a["kind"] == "down" else -1 if a["kind"] == "up" else 0
+            ho, wo = H >> lv, W >> lv                          # the ResBlock's output resolution: where its convolutions run
+            main = max(main, gn(a["cin"], h, w), gn(a["cout"], ho, wo))
+            wgrad = max(wgrad, wg(a["cout"], a["cin"], 9, ho, wo), wg(a["cout"], a["cout"], 9, ho, wo),
+                        wg(a["cout"], a["cin"], 1, ho, wo) if a["cin"] != a["cout"] else 0)
+    return max(main, wgrad), wgrad
 
 
 class UNetTrainer:
@@ -131,10 +205,12 @@ class UNetTrainer:
     input gradient. No operator synchronises: temporaries come from the handle's scratch arena."""
 
     def __init__(self, params: Dict[str, torch.Tensor], *, model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3,
-                 cond_dim=128, device=None, exp_refresh=50, overlap_wgrad=None, dropout=0.0, dropout_seed=None):
+                 cond_dim=128, device=None, exp_refresh=50, overlap_wgrad=None, dropout=0.0, dropout_seed=None,
+                 attention_resolutions=(3, 6, 12)):
         self.dev = torch.device(device) if device is not None else next(iter(params.values())).device
         self._cfg = dict(model_channels=model_channels, channel_mult=tuple(channel_mult), num_res_blocks=num_res_blocks, cond_dim=cond_dim)
         self.C, self.mult, self.nres, self.cond_dim = model_channels, tuple(channel_mult), num_res_blocks, cond_dim
+        self.att_res = tuple(int(a) for a in attention_resolutions)      # the model's: attention behind the ResBlocks of the levels it names
         # flat layout: the 27 ResBlocks' emb_layers.1 weights first, in program order and without gaps, then their biases: together they are
         # ONE [sum 2 Cout, E] matrix (11776 x 1024) -- one Linear forward and one backward per step instead of 27 (the inference engine's
         # table does the same); then every other tensor, each 256-byte aligned
@@ -145,11 +221,16 @@ class UNetTrainer:
         self.dropout, self.dropout_seed = dropout_settings(dropout, dropout_seed)
         self.dropout_step = 0
         self._res_ordinal = {n: i for i, n in enumerate(n for kind, n, _a in self.program if kind == "res")}
+        if "input_blocks.0.0.weight" in params:
+            absent = sorted(k for k in program_param_names([e for e in self.program if e[0] == "attn"]) if k not in params)
+            if absent:
+                raise ValueError(f"training: the program built for attention_resolutions={self.att_res} has attention blocks whose parameters "
+                                 f"the state dict does not hold: {', '.join(absent)}")
         missing = unsupported_blocks(params, self.program)
         if missing:
             raise NotImplementedError(f"training: the state dict holds parameters of blocks the training program does not build: {', '.join(missing)} "
-                                      "(attention inside the resolution levels is not built for training; the program has it in the middle "
-                                      "block only). They would silently keep zero gradients.")
+                                      f"(the program was built for attention_resolutions={self.att_res}: attention in the middle block and "
+                                      "inside the levels those factors name; pass the model's). They would silently keep zero gradients.")
         emb_names = [n + ".emb_layers.1" for kind, n, _a in self.program if kind == "res" and n + ".emb_layers.1.weight" in params]
         lead = [n + ".weight" for n in emb_names] + [n + ".bias" for n in emb_names]
         names = lead + [k for k in params if k not in set(lead)]
@@ -196,32 +277,32 @@ class UNetTrainer:
 
     # ------------------------------------------------------------------ program (mirrors UNetModel.__init__, OpenAI_Unet.py:604-797)
     def _build_program(self):
-        return unet_program(self.C, self.mult, self.nres)
+        return unet_program(self.C, self.mult, self.nres, self.att_res)
 
     def _conv_table(self):
         return conv_table(self.program) if "input_blocks.0.0.weight" in self.p else {}
 
     # ------------------------------------------------------------------ handle, packed weights
     def _fit(self, B, H, W):
-        """the handle the operators run on; its scratch arena is sized for the batch (attention backward keeps two B x heads x N x N
-        planes, the weight-gradient kernel its partial tiles)"""
+        """the handle the operators run on; its scratch arena is sized for the batch. Every operator takes its temporaries from the
+        arena's start, so the arena holds the largest single call (operator_scratch_bytes: the attention backward's row statistics, B x
+        heads x N x 2 floats -- the N x N matrices stay in registers --, the head's partial products, the GroupNorm backward's partial
+        sums, the weight gradient's partial tiles, ...; at least ARENA_FLOOR) and the weight gradient's two k-images"""
         e = self.eng
         if e is None or e.max_batch < B or e.max_h < H or e.max_w < W:
             if e is not None:
                 torch.cuda.synchronize(self.dev)
                 e.close()
             self.eng = CddpmEngine(timesteps=2, max_batch=B, max_h=H, max_w=W, device=self.dev, **self._cfg)
-            nmid = (H >> (len(self.mult) - 1)) * (W >> (len(self.mult) - 1))
-            cmid = self.mult[-1] * self.C
-            arena = 2 * B * (cmid // 64) * nmid * nmid * 4 + (192 << 20)
+            main, side = operator_scratch_bytes(self.program, B, H, W, 8 * self.C) if self._convs else (0, 0)
             # the 3x3 weight gradient's two k-images (fp16 hi | mid, batch padded to groups of 8): the largest (Cin + Cout) x pixels of the net
             lv, worst = 0, 0
             for kind, _name, a_ in self.program:
                 if kind == "res":
                     worst = max(worst, (a_["cin"] + a_["cout"]) * (H >> lv) * (W >> lv), 2 * a_["cout"] * (H >> lv) * (W >> lv))
                     lv += 1 if a_["kind"] == "down" else -1 if a_["kind"] == "up" else 0
-            arena += 2 * ((B + 7) // 8) * worst * 16
-            rc = self.eng.lib.cddpm_op_set_scratch(self.eng._h, arena)
+            images = 2 * ((B + 7) // 8) * worst * 16
+            rc = self.eng.lib.cddpm_op_set_scratch(self.eng._h, max(ARENA_FLOOR, main) + images)
             if rc != 0:
                 raise RuntimeError("cddpm_op_set_scratch failed: " + self.eng.lib.cddpm_last_error(self.eng._h).decode())
             if self.overlap_wgrad:
@@ -229,7 +310,7 @@ class UNetTrainer:
                     self.eng_w.close()
                 # the weight-gradient handle: only its operator arena is used (k-images + partial tiles); smallest geometry
                 self.eng_w = CddpmEngine(timesteps=2, max_batch=1, max_h=16, max_w=16, device=self.dev, **self._cfg)
-                if self.eng_w.lib.cddpm_op_set_scratch(self.eng_w._h, 2 * ((B + 7) // 8) * worst * 16 + (192 << 20)) != 0:
+                if self.eng_w.lib.cddpm_op_set_scratch(self.eng_w._h, max(ARENA_FLOOR, side) + images) != 0:
                     raise RuntimeError("cddpm_op_set_scratch failed: " + self.eng_w.lib.cddpm_last_error(self.eng_w._h).decode())
                 if self.side is None:
                     self.side = torch.cuda.Stream(device=self.dev)
@@ -492,7 +573,7 @@ class UNetTrainer:
             film_all = self._new(B, self.emb_rows)
             self._ck(self.lib.cddpm_op_linear(self.h, _p(emb), _p(self.emb_w), _p(self.emb_b), B, self.emb_rows, emb.shape[1], 1, _p(film_all),
                                               self._s()), "op_linear")
-        hs: List[torch.Tensor] = []
+        hs: List[torch.Tensor] = []          # the skip stack: every input block's output (pushed by its last entry)
         cur = None
         for kind, name, a in self.program:
             if kind == "in":
@@ -548,6 +629,8 @@ class UNetTrainer:
                 out = self.conv(name + ".proj_out", att, res=cur)
                 sv[name] = dict(x=cur, coefn=coefn, qkv=qkv, att=att, rec=self.rec_of(cur))
                 cur = out
+                if a.get("push"):                # the last entry of its input block: the skip stack takes the attention's output
+                    hs.append(cur)
             else:   # head: GroupNorm -> SiLU -> Conv2d(C -> 1)
                 coefo = self.gn_coef(cur, None, "out.0")
                 w9 = p["out.2.weight"].reshape(a["c"], 9).t().contiguous()
@@ -556,6 +639,7 @@ class UNetTrainer:
                                                 self._s()), "op_head")
                 sv["out"] = dict(x=cur, coefo=coefo, w9=w9, rec=self.rec_of(cur))
                 cur = out
+        assert not hs, "the output blocks pop every skip tensor"
         self.saved = sv
         return cur
 
@@ -589,6 +673,8 @@ class UNetTrainer:
                 g["out.2.bias"].copy_(dout.sum().reshape(1))          # one scalar
                 d, _ = self.gn_bwd(r["x"], dact, "out.0", rec=r["rec"])
             elif kind == "attn":
+                if a.get("push"):        # this block's output also fed a skip connection: add that gradient
+                    d = self.add_(d, skip_grads.pop())
                 r = sv[name]
                 self.wgrad(name + ".proj_out", r["att"], None, None, False, d)
                 da = self.dgrad(name + ".proj_out", d)

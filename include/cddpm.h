@@ -365,7 +365,12 @@ int cddpm_op_conv_wgrad(cddpm_handle h, const float* x0_dev, int C0, const float
 int cddpm_op_bias_grad(cddpm_handle h, const float* dy_dev, int64_t npix, int C, float* db_dev, void* stream);
 /* backward of the attention core QKVAttention (src/models/modules/OpenAI_Unet.py:457-476): qkv_dev [B,N,3C] (q | k | v, heads of 64
  * channels), da_dev [B,N,C] = dL/d(output) -> dqkv_dev [B,N,3C]. The probabilities are recomputed (flash-style: B x C/64 x N x 2
- * floats of scratch for the row statistics). */
+ * floats of scratch for the row statistics; nothing of size N x N is stored). C: a multiple of 64 (heads of 64 channels).
+ * Tested against float64 autograd: C = 128 and 256, N = 16 ... 1536, multiples of neither the 128-query workgroup nor the 64-key tile
+ * included (N = 240, 576; tests/test_gpu_train_ops.py, tests/test_gpu_attention_shapes.py), and inside the training step at N = 15 ... 1024
+ * (tests/test_gpu_training*.py). Expected to hold, not checked against a reference: any N >= 1 with B x C/64 x ceil(N / 128) < 2^31
+ * (the one-dimensional grid) -- tails are masked and every row offset is formed in 64 bits; N = 16384 (B 16, C 128) has been run and
+ * timed only. */
 int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
                                 void* stream);
 /* backward of torch.nn.Linear behind an optional SiLU, y = [SiLU](x) W^T + b (emb_layers / time_embed / label_emb,
@@ -543,8 +548,9 @@ int cddpm_op_gn_silu_backward(cddpm_handle h, const float* x_dev, const float* x
  * every producer launch is refused if its count would not fit (tests/test_host_logic.py checks the counts are monotone). */
 int cddpm_stat_records(int H, int W, int kind);
 
-/* standalone attention core on qkv NHWC [B,N,3C] (q | k | v, heads = contiguous groups of head_channels):
- * out [B,N,C] = softmax(q k^T / sqrt(head_channels)) v  (QKVAttention, OpenAI_Unet.py:457-476). */
+/* standalone attention core on qkv NHWC [B,N,3C] (q | k | v, heads = contiguous groups of head_channels = 64):
+ * out [B,N,C] = softmax(q k^T / sqrt(head_channels)) v  (QKVAttention, OpenAI_Unet.py:457-476). C: a multiple of 64; tested and
+ * expected ranges of N as for cddpm_op_attention_backward. */
 int cddpm_op_attention(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream);
 
 /* ---- context encoder ---------------------------------------------------------------

@@ -1,8 +1,9 @@
 """Worst / median relative error of the training step's gradients against float64 autograd through the oracle, as JSON (one process per
 arithmetic: the families are chosen once per process from the environment, e.g. CDDPM_TRAIN_PRECISION=16).
 usage: python tools/train_grad_check.py [B H W [DESCRIPTOR]]
-DESCRIPTOR: a JSON object {"model_channels":, "channel_mult":, "num_res_blocks":, "cond_dim":} of another UNet than the experiment's (cond_dim 0:
-unconditioned)"""
+DESCRIPTOR: a JSON object {"model_channels":, "channel_mult":, "num_res_blocks":, "cond_dim":, "attention_resolutions":} of another UNet
+than the experiment's (cond_dim 0: unconditioned; attention_resolutions absent: the experiment's (3, 6, 12), attention in the middle
+block only)"""
 import importlib
 import json
 import os
@@ -21,7 +22,8 @@ B, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (2, 32, 32)
 tr, synth, sched = (importlib.import_module(PKG + "." + m) for m in ("training", "synth", "schedule"))
 T = 1000
 desc = json.loads(sys.argv[4]) if len(sys.argv) >= 5 else {}
-arch = {k: (tuple(desc[k]) if k == "channel_mult" else desc[k]) for k in ("model_channels", "channel_mult", "num_res_blocks") if k in desc}
+arch = {k: (tuple(desc[k]) if k in ("channel_mult", "attention_resolutions") else desc[k])
+        for k in ("model_channels", "channel_mult", "num_res_blocks", "attention_resolutions") if k in desc}
 cond_dim = desc.get("cond_dim", 128)
 sd_np = synth.synth_state_dict(0, num_classes=cond_dim or None, **arch)
 x01 = torch.from_numpy(synth.synth_slices(3, 0, B, H, W)).reshape(B, 1, H, W)
