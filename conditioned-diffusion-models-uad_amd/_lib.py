@@ -99,6 +99,9 @@ SYMBOLS = {
     "cddpm_op_chan_image_corr": (_i, [_vp, _fp, _fp, _i, _fp, _i, _fp, _i, _i, _i, _i, _vp]),
     "cddpm_op_head_dgrad": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "cddpm_op_loss": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, C.c_float, _fp, _fp, _vp]),
+    "cddpm_op_loss_box": (_i, [_vp, _fp, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _i, _i, C.c_float, _vp, _fp, _fp, _vp]),
+    "cddpm_box_q_sample": (_i, [_vp, _fp, _fp, _vp, _i, _fp, _fp, _i, _vp, _fp, _i, _i, _i, _i, _vp]),
+    "cddpm_box_stitch": (_i, [_vp, _fp, _vp, _vp, _i, _fp, _i, _i, _i, _i, _vp]),
     "cddpm_op_adam": (_i, [_vp, _fp, _fp, _fp, _fp, _i64, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.c_float, _vp]),
     "cddpm_set_train_precision": (_i, [_i]),
     "cddpm_get_train_precision": (_i, []),

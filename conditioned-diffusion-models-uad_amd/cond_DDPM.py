@@ -338,6 +338,68 @@ class GaussianDiffusion(nn.Module):
             reco = out
         return loss.mean(), unnormalize_to_zero_to_one(reco)
 
+    @torch.no_grad()
+    def p_losses_grid(self, x_start, t, boxes, noise=None, *, stitch="paste", cut=None, chunk=64):
+        """The K box reconstructions of the patched DDPM's test_step (DDPM_2D_patched.py:185-215) as ceil(K S / chunk) UNet calls instead of
+        K calls with a host loop of pastes each: x_start [S,1,H,W] in [-1,1], t [S], boxes [S,K,4] (BoxSampler.sample_grid's shape; rows
+        (x0, y1, x2, y3)). One cddpm_box_q_sample forms the K S box-noised inputs (box-major, n = k S + s) without K copies of the
+        input, the UNet runs over them in batches of `chunk` into one buffer, `inpaint`'s paste and pred_noise's x - sqrt(1 - abar) out
+        are elementwise on the device, and one cddpm_box_stitch aggregates: stitch 'paste' (no overlap), 'cut' (with `cut` =
+        sample_grid_cut's boxes) or 'avg' (the reference's running division, as written). Returns (the loss of the LAST box -- the
+        reference's `loss_diff` is its last iteration's --, the stitched reconstruction in [0,1]). The kernel noises 2 x01 - 1 of x01 =
+        (x_start + 1) / 2: exact for every x_start that is itself 2 x01 - 1 of a float, which is what `forward` passes."""
+        if getattr(self.model, "num_classes", None):
+            raise NotImplementedError("p_losses_grid serves the unconditioned UNet of the patched DDPM (num_classes=None)")
+        if stitch not in ("paste", "cut", "avg"):
+            raise ValueError(f"unknown stitch mode {stitch!r}: expected 'paste', 'cut' or 'avg'")
+        if x_start.dim() != 4 or x_start.shape[1] != 1:
+            raise RuntimeError(f"x_start must be [S,1,H,W], got {tuple(x_start.shape)}")
+        S, _c, H, W = x_start.shape
+        if not (isinstance(boxes, torch.Tensor) and boxes.dim() == 3 and boxes.shape[0] == S and boxes.shape[2] == 4):
+            raise RuntimeError(f"boxes must be [{S}, K, 4], got {tuple(getattr(boxes, 'shape', ()))}")
+        K = int(boxes.shape[1])
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        dev = x_start.device
+        N = K * S
+        eng = self._engine(min(chunk, N), H, W, dev)
+        from .engine import check_boxes
+        box_km = check_boxes(boxes.permute(1, 0, 2), N, dev)                     # box-major rows
+        cut_km = None
+        if stitch == "cut":
+            if cut is None or tuple(cut.shape) != tuple(boxes.shape):
+                raise RuntimeError("stitch='cut' needs cut = sample_grid_cut's boxes, shaped like `boxes`")
+            cut_km = check_boxes(cut.permute(1, 0, 2), N, dev)
+        x_start = x_start.float().contiguous()
+        noise = noise.float().contiguous()
+        t = t.to(dev).long()
+        x_t = eng.box_q_sample((x_start + 1) * 0.5, t, noise, box_km)            # [K S,1,H,W]
+        t_rep = t.repeat(K)
+        out = torch.empty_like(x_t)
+        fb = self.model._hip.fallback(self.model)
+        for n0 in range(0, N, chunk):
+            n1 = min(N, n0 + chunk)
+            eng.unet_forward(x_t[n0:n1], t_rep[n0:n1], None, fallback=fb, out=out[n0:n1])
+        last = slice((K - 1) * S, N)
+        loss_b, _ = eng.loss_box(out[last], x_start, noise, box_km[last], objective=self.objective, loss_type=self.loss_type,
+                                 inpaint=self.inpaint, w_b=self.p2_loss_weight.gather(-1, t).float(), want_grad=False)
+        o5, x5 = out.view(K, S, 1, H, W), x_t.view(K, S, 1, H, W)
+        if self.inpaint:
+            b5 = box_km.view(K, S, 4, 1, 1, 1).long()
+            ys = torch.arange(H, device=dev).view(1, 1, 1, H, 1)
+            xs = torch.arange(W, device=dev).view(1, 1, 1, 1, W)
+            inside = (xs >= b5[:, :, 0]) & (xs < b5[:, :, 2]) & (ys >= b5[:, :, 1]) & (ys < b5[:, :, 3])
+            o5 = torch.where(inside, o5, x_start.unsqueeze(0))
+        if self.objective == "pred_noise":
+            reco = x5 - _extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape).unsqueeze(0) * o5
+        else:
+            reco = o5
+        reco = unnormalize_to_zero_to_one(reco).reshape(N, 1, H, W).contiguous()
+        return loss_b.mean(), eng.box_stitch(reco, box_km, cut_km, stitch, slices=S)
+
     def forward(self, img, t=None, *args, **kwargs):
         """(cond_DDPM.py:647-655) img in [0,1]; t: scalar timestep for the whole batch or None for random."""
         b = img.shape[0]

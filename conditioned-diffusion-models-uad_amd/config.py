@@ -102,12 +102,25 @@ def compose(config_dir: str, experiment: str = "cDDPM/DDPM_cond_spark_2D", overr
 
 
 def instantiate_model(cfg: Dict[str, Any], encoder=None):
-    """what `hydra.utils.instantiate(cfg.model)` does for `_target_: src.models.DDPM_2D.DDPM_2D`
-    (reference src/train.py:98), bound to this package's DDPM_2D."""
-    from .DDPM_2D import DDPM_2D, AttrDict
+    """what `hydra.utils.instantiate(cfg.model)` does for `_target_: src.models.DDPM_2D.DDPM_2D` and
+    `src.models.DDPM_2D_patched.DDPM_2D` (reference src/train.py:98), bound to this package's mirrors."""
+    cls, patched = model_class(cfg["model"].get("_target_", ""))
+    from .mirror_common import AttrDict
+    if patched:
+        if encoder is not None:
+            raise ValueError("the patched DDPM is unconditioned: it takes no encoder")
+        return cls(AttrDict(cfg["model"]["cfg"]), prefix=None)
+    return cls(AttrDict(cfg["model"]["cfg"]), prefix=None, encoder=encoder)
 
-    model_cfg = cfg["model"]
-    target = model_cfg.get("_target_", "")
-    if not target.endswith("DDPM_2D.DDPM_2D"):
-        raise NotImplementedError(f"only the cDDPM target src.models.DDPM_2D.DDPM_2D is provided, got {target!r}")
-    return DDPM_2D(AttrDict(model_cfg["cfg"]), prefix=None, encoder=encoder)
+
+def model_class(target: str):
+    """the mirror class a Hydra `_target_` names -> (class, is the patched DDPM): `src.models.DDPM_2D.DDPM_2D` (experiments
+    DDPM_cond_spark_2D and DDPM) or `src.models.DDPM_2D_patched.DDPM_2D` (experiment DDPM_patched); anything else is refused"""
+    if target.endswith("DDPM_2D_patched.DDPM_2D"):
+        from .DDPM_2D_patched import DDPM_2D as Patched
+        return Patched, True
+    if target.endswith("DDPM_2D.DDPM_2D"):
+        from .DDPM_2D import DDPM_2D
+        return DDPM_2D, False
+    raise NotImplementedError("only the targets src.models.DDPM_2D.DDPM_2D and src.models.DDPM_2D_patched.DDPM_2D are provided, "
+                              f"got {target!r}")

@@ -373,6 +373,41 @@ int cddpm_op_loss_scaled(cddpm_handle h, const float* out_dev, const float* targ
     launch_loss(out_dev, target_dev, w_b_dev, l2, B, HW, 0.0f, scaler_dev, dout_dev, loss_b_dev, s);
     OP_EPILOGUE()
 }
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int cddpm_op_loss_box(cddpm_handle h, const float* out_dev, const float* x0_dev, const float* noise_dev, const int32_t* box_dev,
+                      const float* w_b_dev, int pred_noise, int inpaint, int l2, int B, int H, int W, float grad_scale,
+                      const int32_t* scaler_dev, float* dout_dev, float* loss_b_dev, void* stream) {
+    OP_CHECK(B > 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 31), "cddpm_op_loss_box: bad B/H/W (%d, %d, %d)", B, H, W)
+    OP_CHECK(out_dev && x0_dev && box_dev && loss_b_dev && (noise_dev || !pred_noise), "cddpm_op_loss_box: NULL argument")
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0,
+                aligned16(box_dev) && (W % 4 || (aligned16(out_dev) && aligned16(x0_dev) && aligned16(noise_dev) && aligned16(dout_dev))),
+                "cddpm_op_loss_box: box_dev (and, for W a multiple of 4, every image) must be 16-byte aligned")
+    launch_loss_box(out_dev, x0_dev, noise_dev, box_dev, w_b_dev, pred_noise ? 1 : 0, inpaint ? 1 : 0, l2 ? 1 : 0, B, H, W, grad_scale, scaler_dev,
+                    dout_dev, loss_b_dev, s);
+    OP_EPILOGUE()
+}
+int cddpm_box_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev, const int32_t* t_dev, int t_uniform,
+                       const float* sqrt_ac_dev, const float* sqrt_1mac_dev, int T, const int32_t* box_dev, float* out_dev, int S, int N, int H,
+                       int W, void* stream) {
+    OP_CHECK(S > 0 && N > 0 && N % S == 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 31), "cddpm_box_q_sample: bad S/N/H/W (%d, %d, %d, %d)", S, N, H, W)
+    OP_CHECK(T > 0 && (t_dev || (t_uniform >= 0 && t_uniform < T)), "cddpm_box_q_sample: t=%d outside [0, %d)", t_uniform, T)
+    OP_CHECK(x01_dev && noise_dev && sqrt_ac_dev && sqrt_1mac_dev && box_dev && out_dev, "cddpm_box_q_sample: NULL argument")
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, aligned16(box_dev) && (W % 4 || (aligned16(x01_dev) && aligned16(noise_dev) && aligned16(out_dev))),
+                "cddpm_box_q_sample: box_dev (and, for W a multiple of 4, every image) must be 16-byte aligned")
+    launch_box_q_sample(x01_dev, noise_dev, t_dev, t_uniform, sqrt_ac_dev, sqrt_1mac_dev, T, box_dev, out_dev, S, N, H, W, s);
+    OP_EPILOGUE()
+}
+int cddpm_box_stitch(cddpm_handle h, const float* reco_dev, const int32_t* box_dev, const int32_t* cut_dev, int mode, float* out_dev, int S, int K,
+                     int H, int W, void* stream) {
+    OP_CHECK(S > 0 && K > 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 31), "cddpm_box_stitch: bad S/K/H/W (%d, %d, %d, %d)", S, K, H, W)
+    OP_CHECK(mode == CDDPM_STITCH_PASTE || mode == CDDPM_STITCH_CUT || mode == CDDPM_STITCH_AVG, "cddpm_box_stitch: unknown mode %d", mode)
+    const int32_t* rows = mode == CDDPM_STITCH_CUT ? cut_dev : box_dev;
+    OP_CHECK(reco_dev && box_dev && out_dev && rows, "cddpm_box_stitch: NULL argument (CDDPM_STITCH_CUT needs cut_dev)")
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, aligned16(rows) && (W % 4 || (aligned16(reco_dev) && aligned16(out_dev))),
+                "cddpm_box_stitch: the box rows (and, for W a multiple of 4, every image) must be 16-byte aligned")
+    launch_box_stitch(reco_dev, rows, mode, out_dev, S, K, H, W, s);
+    OP_EPILOGUE()
+}
 int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
                   float eps, int step, float grad_unscale, void* stream) {
     OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && n > 0 && step >= 1, "cddpm_op_adam: bad arguments")

@@ -165,6 +165,23 @@ void launch_noise_fill(float* out, uint64_t seed, uint32_t stream_id, int t, uin
 void launch_q_sample(const float* x01, const float* noise, const int* t_dev, const float* sa, const float* s1ma,
                      float* out, int B, int HW, hipStream_t stream);
 
+// The patched DDPM's boxes (patch_sampling.py): device int32 rows (x0, y1, x2, y3) = columns [x0, x2) x rows [y1, y3), clipped to
+// the image as Python slicing clips a non-negative range; a box that is empty after clipping selects nothing. 16-byte aligned rows.
+struct BoxClip { int x0, y1, x2, y3; };
+__device__ __forceinline__ BoxClip load_box(const int* __restrict__ box, long long row, int H, int W) {
+    const int4 b = *reinterpret_cast<const int4*>(box + row * 4);
+    BoxClip c;
+    c.x0 = min(max(b.x, 0), W); c.x2 = min(max(b.z, 0), W);
+    c.y1 = min(max(b.y, 0), H); c.y3 = min(max(b.w, 0), H);
+    return c;
+}
+__device__ __forceinline__ bool in_box(const BoxClip& c, int y, int x) { return y >= c.y1 && y < c.y3 && x >= c.x0 && x < c.x2; }
+// out [N][H][W]: slice n reads x01 / noise / t of slice n % S; t_dev nullptr: t_uniform. sa, s1ma: DEVICE tables [T]
+void launch_box_q_sample(const float* x01, const float* noise, const int* t_dev, int t_uniform, const float* sa, const float* s1ma, int T,
+                         const int* box, float* out, int S, int N, int H, int W, hipStream_t stream);
+// reco [K S][H][W] box-major, box [K S][4] (the rows the mode pastes with) -> out [S][H][W]; mode 0 paste, 1 cut, 2 avg
+void launch_box_stitch(const float* reco, const int* box, int mode, float* out, int S, int K, int H, int W, hipStream_t stream);
+
 // 2-D OpenSimplex fractal noise, fp16 bits, the same field for every batch item (simplex.hip)
 void launch_simplex(unsigned short* out, long long seed, int B, int H, int W, int octaves, double persistence,
                     double frequency, hipStream_t stream);
@@ -208,6 +225,9 @@ void launch_head_dgrad(const float* dout, const float* w9, float* dact, int B, i
 // scaler: nullptr = loss scale `grad_scale`; else the device loss scale (bits of scaler[0], see launch_scaler_update)
 void launch_loss(const float* out, const float* target, const float* w_b, int l2, int B, int HW, float grad_scale, const int* scaler, float* dout,
                  float* loss_b, hipStream_t stream);
+// the loss with one box per slice (box [B][4]): x0 the image in [-1, 1], noise read under pred_noise only, dout may be nullptr
+void launch_loss_box(const float* out, const float* x0, const float* noise, const int* box, const float* w_b, int pred_noise, int inpaint, int l2,
+                     int B, int H, int W, float grad_scale, const int* scaler, float* dout, float* loss_b, hipStream_t stream);
 void launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step, float grad_unscale,
                  hipStream_t stream);
 void launch_grad_check(const float* g, long long n, int* ctrl, hipStream_t stream);

@@ -511,6 +511,14 @@ void launch_ddim_step(const DdimArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(ddim_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
 }
 
+// One value of q_sample on x01 in [0, 1]: sqrt_ac (2 x01 - 1) + sqrt_1mac noise, as ONE fused multiply-add over the rounded second
+// product. Stated explicitly because a plain a * b + c * d leaves the choice of which product is fused to the compiler, per kernel
+// (__fmul_rn / __fadd_rn are plain operators to it): q_sample_kernel and box_q_sample_kernel must give the same bits. This is the
+// form q_sample_kernel has always compiled to.
+__device__ __forceinline__ float q_sample_value(float ca, float cb, float x01, float n) {
+    return __builtin_fmaf(ca, x01 * 2.f - 1.f, cb * n);
+}
+
 // q_sample fused with normalize_to_neg_one_to_one (cond_DDPM.py:548-554, :75, :653)
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x01, const float* __restrict__ noise,
                                                        const int* __restrict__ t_dev, const float* __restrict__ sa,
@@ -526,10 +534,10 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     const float4 x = *reinterpret_cast<const float4*>(x01 + off);
     const float4 n = *reinterpret_cast<const float4*>(noise + off);
     float4 r;
-    r.x = __fadd_rn(__fmul_rn(ca, x.x * 2.f - 1.f), __fmul_rn(cb, n.x));
-    r.y = __fadd_rn(__fmul_rn(ca, x.y * 2.f - 1.f), __fmul_rn(cb, n.y));
-    r.z = __fadd_rn(__fmul_rn(ca, x.z * 2.f - 1.f), __fmul_rn(cb, n.z));
-    r.w = __fadd_rn(__fmul_rn(ca, x.w * 2.f - 1.f), __fmul_rn(cb, n.w));
+    r.x = q_sample_value(ca, cb, x.x, n.x);
+    r.y = q_sample_value(ca, cb, x.y, n.y);
+    r.z = q_sample_value(ca, cb, x.z, n.z);
+    r.w = q_sample_value(ca, cb, x.w, n.w);
     *reinterpret_cast<float4*>(out + off) = r;
 }
 
@@ -538,6 +546,111 @@ void launch_q_sample(const float* x01, const float* noise, const int* t_dev, con
     const long long total = (long long)B * (HW / 4);
     hipLaunchKernelGGL(q_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x01, noise, t_dev, sa,
                        s1ma, out, B, HW);
+}
+
+// ---- the patched DDPM (DDPM_2D_patched.py, patch_sampling.py): box rows are (x0, y1, x2, y3) = columns [x0, x2) x rows [y1, y3),
+// clipped to the image as Python slicing clips a non-negative range (BoxClip, kernels.h). One thread owns V consecutive pixels of a row (V = 4: float4 accesses, W a multiple of 4; V = 1: any W).
+template <int V> struct PixVec;
+template <> struct PixVec<4> {
+    float v[4];
+    __device__ __forceinline__ void load(const float* p) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+    __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <> struct PixVec<1> {
+    float v[1];
+    __device__ __forceinline__ void load(const float* p) { v[0] = *p; }
+    __device__ __forceinline__ void store(float* p) const { *p = v[0]; }
+};
+
+// q_sample of the box alone (cond_DDPM.py:587-604) for N output slices over S source slices (n reads slice n % S, its t too): outside
+// the box 2 x01 - 1, inside q_sample_kernel's arithmetic to the bit. K boxes per slice without K copies of the input.
+template <int V>
+__global__ __launch_bounds__(256) void box_q_sample_kernel(const float* __restrict__ x01, const float* __restrict__ noise,
+                                                           const int* __restrict__ t_dev, int t_uniform, const float* __restrict__ sa,
+                                                           const float* __restrict__ s1ma, int T, const int* __restrict__ box,
+                                                           float* __restrict__ out, int S, int N, int H, int W) {
+    const int wq = W / V, nq = H * wq;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)N * nq) return;
+    const int n = (int)(e / nq), q = (int)(e % nq);
+    const int y = q / wq, xb = (q % wq) * V, s = n % S;
+    const int t = t_dev ? min(max(t_dev[s], 0), T - 1) : t_uniform;
+    const float ca = sa[t], cb = s1ma[t];
+    const BoxClip c = load_box(box, n, H, W);
+    const size_t src = ((size_t)s * H + y) * W + xb, dst = ((size_t)n * H + y) * W + xb;
+    PixVec<V> x, r;
+    x.load(x01 + src);
+    const bool row_in = y >= c.y1 && y < c.y3 && xb < c.x2 && xb + V > c.x0;      // the noise is read only where a box pixel needs it
+    PixVec<V> z;
+    if (row_in) z.load(noise + src);
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const float x0 = x.v[i] * 2.f - 1.f;
+        r.v[i] = (row_in && in_box(c, y, xb + i)) ? q_sample_value(ca, cb, x.v[i], z.v[i]) : x0;
+    }
+    r.store(out + dst);
+}
+
+void launch_box_q_sample(const float* x01, const float* noise, const int* t_dev, int t_uniform, const float* sa, const float* s1ma, int T,
+                         const int* box, float* out, int S, int N, int H, int W, hipStream_t stream) {
+    if (W % 4 == 0) {
+        const long long total = (long long)N * H * (W / 4);
+        hipLaunchKernelGGL(box_q_sample_kernel<4>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x01, noise, t_dev, t_uniform, sa,
+                           s1ma, T, box, out, S, N, H, W);
+    } else {
+        const long long total = (long long)N * H * W;
+        hipLaunchKernelGGL(box_q_sample_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x01, noise, t_dev, t_uniform, sa,
+                           s1ma, T, box, out, S, N, H, W);
+    }
+}
+
+// The stitching of DDPM_2D_patched.test_step (:175-215) after its last box, as written: every pixel of slice s walks the K box
+// reconstructions reco[k S + s] in order from 0. mode 0 (paste) / 1 (cut: the sample_grid_cut rows): the value becomes reco_k where
+// box k covers the pixel. mode 2 (avg): v <- (v + [pixel in box k] reco_k) / count after EVERY box, count = the boxes covering the
+// pixel -- the reference divides the running image by the full mask inside its loop over boxes; count 0 gives 0 / 0 as torch does.
+template <int V>
+__global__ __launch_bounds__(256) void box_stitch_kernel(const float* __restrict__ reco, const int* __restrict__ box, int mode,
+                                                         float* __restrict__ out, int S, int K, int H, int W) {
+    const int wq = W / V, nq = H * wq;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)S * nq) return;
+    const int s = (int)(e / nq), q = (int)(e % nq);
+    const int y = q / wq, xb = (q % wq) * V;
+    float cnt[V];
+    PixVec<V> v;
+#pragma unroll
+    for (int i = 0; i < V; ++i) { v.v[i] = 0.f; cnt[i] = 0.f; }
+    if (mode == 2) {
+        for (int k = 0; k < K; ++k) {
+            const BoxClip c = load_box(box, (long long)k * S + s, H, W);
+#pragma unroll
+            for (int i = 0; i < V; ++i) cnt[i] += in_box(c, y, xb + i) ? 1.f : 0.f;
+        }
+    }
+    for (int k = 0; k < K; ++k) {
+        const long long n = (long long)k * S + s;
+        const BoxClip c = load_box(box, n, H, W);
+        const bool touch = y >= c.y1 && y < c.y3 && xb < c.x2 && xb + V > c.x0;
+        PixVec<V> r;
+        if (touch) r.load(reco + ((size_t)n * H + y) * W + xb);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const bool in = touch && in_box(c, y, xb + i);
+            if (mode == 2) v.v[i] = __fdiv_rn(in ? __fadd_rn(v.v[i], r.v[i]) : v.v[i], cnt[i]);
+            else if (in) v.v[i] = r.v[i];
+        }
+    }
+    v.store(out + ((size_t)s * H + y) * W + xb);
+}
+
+void launch_box_stitch(const float* reco, const int* box, int mode, float* out, int S, int K, int H, int W, hipStream_t stream) {
+    if (W % 4 == 0) {
+        const long long total = (long long)S * H * (W / 4);
+        hipLaunchKernelGGL(box_stitch_kernel<4>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reco, box, mode, out, S, K, H, W);
+    } else {
+        const long long total = (long long)S * H * W;
+        hipLaunchKernelGGL(box_stitch_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reco, box, mode, out, S, K, H, W);
+    }
 }
 
 }  // namespace cddpm

@@ -1246,6 +1246,66 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ out
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
     if (tid == 0) loss_b[b] = (float)(red[0] / HW * wb);
 }
+// loss of p_losses with a box (cond_DDPM.py:612-645), one box per slice: the target is x0 (pred_x0) or the noise inside the box and 0
+// outside (pred_noise); under `inpaint` the compared tensor is `out` inside the box and x0 outside, so dout is 0 there -- while under
+// pred_noise the outside still adds |x0| or x0^2 to the value. The mean is over all H W pixels, times w_b. dout may be nullptr (the
+// loss only). V pixels of a row per thread and step (V = 4: float4 accesses); the reduction is loss_kernel's: fixed order.
+template <int V>
+__global__ __launch_bounds__(256) void loss_box_kernel(const float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                       const int* __restrict__ box, const float* __restrict__ w_b, int pred_noise, int inpaint,
+                                                       int l2, int B, int H, int W, float grad_scale, const int* __restrict__ scaler,
+                                                       float* __restrict__ dout, float* __restrict__ loss_b) {
+    __shared__ double red[256];
+    const int b = blockIdx.x, tid = threadIdx.x, HW = H * W, wq = W / V;
+    const float wb = w_b ? w_b[b] : 1.0f;
+    const float scale = scaler ? reinterpret_cast<const float*>(scaler)[0] : grad_scale;
+    const float gscale = scale * wb / ((float)B * (float)HW);
+    const BoxClip c = load_box(box, b, H, W);
+    double s = 0;
+    for (int q = tid; q < H * wq; q += 256) {
+        const int y = q / wq, xb = (q % wq) * V;
+        const size_t off = (size_t)b * HW + (size_t)y * W + xb;
+        float o[V], xs[V], nz[V], g[V];
+        const bool touch = y >= c.y1 && y < c.y3 && xb < c.x2 && xb + V > c.x0;
+        if constexpr (V == 4) {
+            const float4 a = *reinterpret_cast<const float4*>(out + off), e = *reinterpret_cast<const float4*>(x0 + off);
+            o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+            xs[0] = e.x; xs[1] = e.y; xs[2] = e.z; xs[3] = e.w;
+            float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (pred_noise && touch) n4 = *reinterpret_cast<const float4*>(noise + off);
+            nz[0] = n4.x; nz[1] = n4.y; nz[2] = n4.z; nz[3] = n4.w;
+        } else {
+            o[0] = out[off]; xs[0] = x0[off];
+            nz[0] = (pred_noise && touch) ? noise[off] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const bool in = touch && in_box(c, y, xb + i);
+            const float target = pred_noise ? (in ? nz[i] : 0.f) : xs[i];
+            const float cmp = (inpaint && !in) ? xs[i] : o[i];
+            const float d = cmp - target;
+            s += l2 ? (double)d * d : fabs((double)d);
+            g[i] = (inpaint && !in) ? 0.f : (l2 ? 2.0f * d * gscale : ((d > 0.f) - (d < 0.f)) * gscale);
+        }
+        if (dout) {
+            if constexpr (V == 4) *reinterpret_cast<float4*>(dout + off) = make_float4(g[0], g[1], g[2], g[3]);
+            else dout[off] = g[0];
+        }
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int o_ = 128; o_ > 0; o_ >>= 1) { if (tid < o_) red[tid] += red[tid + o_]; __syncthreads(); }
+    if (tid == 0) loss_b[b] = (float)(red[0] / HW * wb);
+}
+void launch_loss_box(const float* out, const float* x0, const float* noise, const int* box, const float* w_b, int pred_noise, int inpaint, int l2,
+                     int B, int H, int W, float grad_scale, const int* scaler, float* dout, float* loss_b, hipStream_t stream) {
+    if (W % 4 == 0)
+        hipLaunchKernelGGL(loss_box_kernel<4>, dim3(B), dim3(256), 0, stream, out, x0, noise, box, w_b, pred_noise, inpaint, l2, B, H, W, grad_scale,
+                           scaler, dout, loss_b);
+    else
+        hipLaunchKernelGGL(loss_box_kernel<1>, dim3(B), dim3(256), 0, stream, out, x0, noise, box, w_b, pred_noise, inpaint, l2, B, H, W, grad_scale,
+                           scaler, dout, loss_b);
+}
 void launch_bias_grad(const float* dy, long long npix, int C, float* db, double* scratch /* 512 * C doubles */, hipStream_t stream) {
     bias_grad_run(dy, npix, C, db, scratch, bias_grad_chunks(npix, C, (size_t)1024 * C), stream);
 }

@@ -58,6 +58,29 @@ def _check_dev(t: torch.Tensor, name: str, device) -> torch.Tensor:
     return t.contiguous()
 
 
+def box_rows(boxes, rows: Optional[int] = None) -> torch.Tensor:
+    """The patched DDPM's boxes as an integer [rows, 4] tensor of (x0, y1, x2, y3), where they lie: accepts [rows,4], the reference's
+    [rows,4,1] (sample_single_box) and [K,S,4] (flattened box-major), tensors or nested lists. A host tensor is checked for negative
+    coordinates (Python slicing would wrap them around; the kernels clip at 0); a device tensor is taken as it is. No GPU needed."""
+    b = boxes if isinstance(boxes, torch.Tensor) else torch.as_tensor(boxes)
+    if b.dtype.is_floating_point or b.dtype == torch.bool:
+        raise RuntimeError(f"boxes must be integers, got {b.dtype}")
+    if b.dim() == 3 and b.shape[-1] == 1:
+        b = b[..., 0]
+    if b.dim() == 3 and b.shape[-1] == 4:
+        b = b.reshape(-1, 4)
+    if b.dim() != 2 or b.shape[1] != 4 or b.shape[0] < 1 or (rows is not None and b.shape[0] != rows):
+        raise RuntimeError(f"boxes must be [{'N' if rows is None else rows}, 4] rows (x0, y1, x2, y3), got {tuple(boxes.shape) if hasattr(boxes, 'shape') else type(boxes).__name__}")
+    if not b.is_cuda and int(b.min()) < 0:
+        raise ValueError("box coordinates must not be negative")
+    return b
+
+
+def check_boxes(boxes, rows: Optional[int], device) -> torch.Tensor:
+    """box_rows on the device as contiguous int32 (what the kernels read)"""
+    return box_rows(boxes, rows).to(device, torch.int32).contiguous()
+
+
 class CddpmEngine:
     """One device's packed UNet + schedule tables + workspace (cddpm_create .. cddpm_destroy)."""
 
@@ -176,19 +199,27 @@ class CddpmEngine:
         self._cond_keep = cond
 
     # ------------------------------------------------------------------ the path
-    def unet_forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, *, fallback=None) -> torch.Tensor:
+    def unet_forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor] = None, *, fallback=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """UNetModel.forward: x [B,1,H,W] fp32 on device, t int or int tensor [B]; cond [B,cond_dim] or None
         to reuse the context of the previous prepare_cond. fallback: as in `reverse` (needs `cond` when the model is conditional:
-        the fallback engine prepares the flagged slices' context itself)."""
+        the fallback engine prepares the flagged slices' context itself). out: a contiguous fp32 tensor of x's shape on the device
+        that receives the result (e.g. a slice of a larger buffer) instead of a new one."""
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == self.device and out.dtype == torch.float32
+                    and out.is_contiguous() and out.shape == x.shape):
+                raise RuntimeError(f"out must be a contiguous float32 tensor of shape {tuple(x.shape)} on {self.device}")
         if fallback is not None:
-            return self._unet_forward_with_fallback(x, t, cond, fallback)
+            res = self._unet_forward_with_fallback(x, t, cond, fallback)
+            return res if out is None else out.copy_(res)
         x = _check_dev(x, "x", self.device)
         B, c, H, W = x.shape
         if c != 1:
             raise RuntimeError("x must be [B,1,H,W]")
         if cond is not None or self.cond_dim == 0:
             self.prepare_cond(cond, B)
-        out = torch.empty_like(x)
+        if out is None:
+            out = torch.empty_like(x)
         if isinstance(t, torch.Tensor):
             tt = self._t_tensor(t, B)
             rc = self.lib.cddpm_unet_forward(self._h, x.data_ptr(), tt.data_ptr(), 0, out.data_ptr(), B, H, W,
@@ -538,6 +569,119 @@ class CddpmEngine:
                                          sa.shape[0], out.data_ptr(), B, H, W, _stream_ptr(self.device)), "cddpm_q_sample")
         torch.cuda.current_stream(self.device).synchronize()   # host tables were read asynchronously
         return out
+
+    # ------------------------------------------------------------------ the patched DDPM: box noising, stitching, box loss
+    STITCH_MODES = {"paste": 0, "cut": 1, "avg": 2}        # CDDPM_STITCH_* of include/cddpm.h
+
+    def _q_tables(self):
+        """the q_sample coefficient tables of set_schedule on the device (uploaded once per schedule)"""
+        if getattr(self, "_qs", None) is None:
+            raise RuntimeError("no schedule installed: call set_schedule first")
+        if getattr(self, "_qs_dev_of", None) is not self._qs:
+            self._qs_dev = tuple(torch.from_numpy(a).to(self.device) for a in self._qs)
+            self._qs_dev_of = self._qs
+        return self._qs_dev
+
+    def box_q_sample(self, x01: torch.Tensor, t, noise: torch.Tensor, boxes: torch.Tensor, *, tables=None) -> torch.Tensor:
+        """cddpm_box_q_sample: x01, noise [S,1,H,W]; boxes [N,4] rows (x0, y1, x2, y3), N a multiple of S -> [N,1,H,W], slice n made
+        from slice n % S: 2 x01 - 1 outside its box, q_sample inside. t: int, or an int tensor [S]. tables: (sqrt_alphas_cumprod,
+        sqrt_one_minus_alphas_cumprod) as float32 device tensors [T] (default: the installed schedule's)."""
+        x01 = _check_dev(x01, "x01", self.device)
+        noise = _check_dev(noise, "noise", self.device)
+        if x01.dim() != 4 or x01.shape[1] != 1 or noise.shape != x01.shape:
+            raise RuntimeError(f"x01 and noise must both be [S,1,H,W], got {tuple(x01.shape)} and {tuple(noise.shape)}")
+        S, _c, H, W = x01.shape
+        boxes = check_boxes(boxes, None, self.device)
+        N = boxes.shape[0]
+        if N < S or N % S:
+            raise RuntimeError(f"{N} boxes for {S} slices: the number of boxes must be a multiple of the number of slices")
+        sa, s1 = tables if tables is not None else self._q_tables()
+        sa, s1 = _check_dev(sa, "sqrt_alphas_cumprod", self.device), _check_dev(s1, "sqrt_one_minus_alphas_cumprod", self.device)
+        T = sa.numel()
+        if s1.numel() != T:
+            raise RuntimeError("the two coefficient tables differ in length")
+        if isinstance(t, torch.Tensor):
+            if t.numel() != S:
+                raise RuntimeError("t must have one element per source slice")
+            if not t.is_cuda:                               # a host tensor is range-checked for free; a device one is clamped by the kernel
+                lo, hi = int(t.min()), int(t.max())
+                if lo < 0 or hi >= T:
+                    raise IndexError(f"timestep indices must lie in [0, {T}), got [{lo}, {hi}]")
+            tt = t.to(self.device, torch.int32).contiguous()
+            tp, tu = tt.data_ptr(), 0
+        else:
+            tt, tp, tu = None, None, int(t)
+        out = torch.empty((N, 1, H, W), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.cddpm_box_q_sample(self._h, x01.data_ptr(), noise.data_ptr(), tp, tu, sa.data_ptr(), s1.data_ptr(), T,
+                                             boxes.data_ptr(), out.data_ptr(), S, N, H, W, _stream_ptr(self.device)), "cddpm_box_q_sample")
+        return out
+
+    def box_stitch(self, reco: torch.Tensor, boxes: torch.Tensor, cut: Optional[torch.Tensor] = None, mode: str = "paste", *,
+                   slices: Optional[int] = None) -> torch.Tensor:
+        """cddpm_box_stitch: reco [K*S,1,H,W] box-major (n = k S + s), boxes / cut [K*S,4] in the same order -> [S,1,H,W], the
+        reference's `reco_patched` after its last box. mode 'paste' | 'cut' (pastes the `cut` rows) | 'avg'. slices: S (default:
+        taken from a [K,S,4] boxes tensor)."""
+        if mode not in self.STITCH_MODES:
+            raise ValueError(f"unknown stitch mode {mode!r}: expected one of {', '.join(self.STITCH_MODES)}")
+        reco = _check_dev(reco, "reco", self.device)
+        if reco.dim() != 4 or reco.shape[1] != 1:
+            raise RuntimeError(f"reco must be [K*S,1,H,W], got {tuple(reco.shape)}")
+        N, _c, H, W = reco.shape
+        if slices is None:
+            if not (isinstance(boxes, torch.Tensor) and boxes.dim() == 3 and boxes.shape[-1] == 4):
+                raise RuntimeError("box_stitch: pass slices=S, or boxes as a [K,S,4] tensor")
+            slices = boxes.shape[1]
+        S = int(slices)
+        if S < 1 or N % S:
+            raise RuntimeError(f"{N} reconstructions are not a multiple of {S} slices")
+        boxes = check_boxes(boxes, N, self.device)
+        if mode == "cut":
+            if cut is None:
+                raise RuntimeError("stitch mode 'cut' needs the sample_grid_cut boxes")
+            cut = check_boxes(cut, N, self.device)
+        else:
+            cut = None
+        out = torch.empty((S, 1, H, W), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.cddpm_box_stitch(self._h, reco.data_ptr(), boxes.data_ptr(), cut.data_ptr() if cut is not None else None,
+                                           self.STITCH_MODES[mode], out.data_ptr(), S, N // S, H, W, _stream_ptr(self.device)), "cddpm_box_stitch")
+        return out
+
+    def loss_box(self, out: torch.Tensor, x0: torch.Tensor, noise: Optional[torch.Tensor], boxes: torch.Tensor, *, objective="pred_x0",
+                 loss_type="l1", inpaint=False, w_b: Optional[torch.Tensor] = None, grad_scale: float = 1.0,
+                 scaler: Optional[torch.Tensor] = None, want_grad: bool = True):
+        """cddpm_op_loss_box: the loss of p_losses with one box per slice -> (loss_b [B], dout or None). out, x0 (the image in [-1,1]),
+        noise: [B,1,H,W]; dout = scale * dL/d(out) with scale = grad_scale, or the device loss scale of `scaler` (int32[4])."""
+        if objective not in OBJECTIVES:
+            raise ValueError(f"unknown objective {objective!r}")
+        if loss_type not in ("l1", "l2"):
+            raise ValueError(f"invalid loss type {loss_type}")
+        out = _check_dev(out, "out", self.device)
+        x0 = _check_dev(x0, "x0", self.device)
+        if out.dim() != 4 or out.shape[1] != 1 or x0.shape != out.shape:
+            raise RuntimeError(f"out and x0 must both be [B,1,H,W], got {tuple(out.shape)} and {tuple(x0.shape)}")
+        B, _c, H, W = out.shape
+        pn = objective == "pred_noise"
+        if pn:
+            if noise is None:
+                raise RuntimeError("the pred_noise loss needs the noise")
+            noise = _check_dev(noise, "noise", self.device)
+            if noise.shape != out.shape:
+                raise RuntimeError(f"noise must be {tuple(out.shape)}, got {tuple(noise.shape)}")
+        boxes = check_boxes(boxes, B, self.device)
+        if w_b is not None:
+            w_b = _check_dev(w_b, "w_b", self.device)
+            if w_b.numel() != B:
+                raise RuntimeError("w_b must have one weight per slice")
+        if scaler is not None and not (scaler.is_cuda and scaler.dtype == torch.int32 and scaler.numel() >= 4):
+            raise RuntimeError("scaler must be the int32[4] device block of the dynamic loss scaling")
+        dout = torch.empty_like(out) if want_grad else None
+        loss_b = torch.empty(B, dtype=torch.float32, device=self.device)
+        self._ck(self.lib.cddpm_op_loss_box(self._h, out.data_ptr(), x0.data_ptr(), noise.data_ptr() if pn else None, boxes.data_ptr(),
+                                            w_b.data_ptr() if w_b is not None else None, int(pn), int(bool(inpaint)), int(loss_type == "l2"),
+                                            B, H, W, C.c_float(float(grad_scale)), scaler.data_ptr() if scaler is not None else None,
+                                            dout.data_ptr() if dout is not None else None, loss_b.data_ptr(), _stream_ptr(self.device)),
+                 "cddpm_op_loss_box")
+        return loss_b, dout
 
     # ------------------------------------------------------------------ test surface
     def block_names(self):

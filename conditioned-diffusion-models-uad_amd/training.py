@@ -30,7 +30,7 @@ import torch
 
 from . import schedule as _schedule
 from . import synth as _synth
-from .engine import CddpmEngine, _stream_ptr
+from .engine import CddpmEngine, _stream_ptr, check_boxes
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -781,6 +781,24 @@ class UNetTrainer:
                                         C.c_float(self.grad_scale), _p(dout), _p(loss_b), self._s()), "op_loss")
         return loss_b.mean(), dout
 
+    def loss_and_grad_box(self, model_out, x0, noise, box, p2w=None, loss_type="l1", objective="pred_x0", inpaint=False, grad_scale=None):
+        """loss_and_grad for p_losses with a box (cond_DDPM.py:612-645; cddpm_op_loss_box): x0 the image in [-1,1], box [B,4] int32 rows
+        (x0, y1, x2, y3) on the device, one per slice. The target (x0, or the noise inside the box and 0 outside) and `inpaint`'s paste
+        are formed inside the kernel. The loss scale follows loss_and_grad: fixed, or the device one under dynamic loss scaling."""
+        B, _c, H, W = model_out.shape
+        scaler = None
+        if self.loss_scaling and grad_scale is None:
+            self.join_side()
+            if self.scaler is None:
+                init = self.scaler_init if self.scaler_init is not None else float(2 ** math.ceil(math.log2(B * H * W)))
+                self.scaler = _scaler_block(init, self.scaler_tracker0, 0, self.dev)
+            self.grad_scale, scaler, scale = None, self.scaler, 0.0
+        else:
+            scale = self.grad_scale = float(grad_scale) if grad_scale is not None else float(2 ** math.ceil(math.log2(B * H * W)))
+        loss_b, dout = self.eng.loss_box(model_out, x0.contiguous().float(), noise.contiguous().float() if noise is not None else None, box,
+                                         objective=objective, loss_type=loss_type, inpaint=inpaint, w_b=p2w, grad_scale=scale, scaler=scaler)
+        return loss_b.mean(), dout
+
     # ------------------------------------------------------------------ dynamic loss scaling (torch's GradScaler, the scale on the device)
     def enable_loss_scaling(self, init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, growth_tracker=0):
         """turns on dynamic loss scaling with torch.cuda.amp.GradScaler's rule (torch._amp_update_scale_): a skipped step halves the scale
@@ -1089,7 +1107,7 @@ def all_reduce_sum_(flat: torch.Tensor) -> int:
 
 
 def training_step(trainer: UNetTrainer, x01: torch.Tensor, cond: Optional[torch.Tensor], *, t: torch.Tensor, noise: torch.Tensor, timesteps=1000,
-                  objective="pred_x0", loss_type="l1", all_reduce=False, lr=1e-4, buffers=None, encoder=None, slice0=0):
+                  objective="pred_x0", loss_type="l1", all_reduce=False, lr=1e-4, buffers=None, encoder=None, slice0=0, box=None, inpaint=False):
     """One optimisation step of the diffusion loss (cond_DDPM.py:647-655 -> :565-645; DDPM_2D.py:114-135): x01 [B,1,H,W] in [0,1], context
     cond [B,cond_dim], per-sample timesteps t and noise given by the caller; `buffers`: the diffusion's schedule tables (default: the
     cosine schedule of `timesteps`). Returns the loss. `all_reduce`: sum the gradients over the ranks of torch.distributed (RCCL) before
@@ -1097,20 +1115,32 @@ def training_step(trainer: UNetTrainer, x01: torch.Tensor, cond: Optional[torch.
     `encoder` (an encoder_training.EncoderTrainer): the context is computed by it in training mode (cond is ignored) and it is trained
     jointly -- dL/d(context) of the UNet's backward flows into its backward, its gradients join the all-reduce and its own Adam step runs
     with the same learning rate: `features = self(input)` + `optim.Adam(self.parameters())` of the reference.
-    `slice0`: the global index of this rank's first slice (keys the dropout masks of a trainer built with dropout > 0)."""
+    `slice0`: the global index of this rank's first slice (keys the dropout masks of a trainer built with dropout > 0).
+    `box` ([B,4] or the reference's [B,4,1]; rows (x0, y1, x2, y3)): the patched DDPM's step (DDPM_2D_patched.py:76-102) -- only the box
+    of each slice is noised (cddpm_box_q_sample) and the loss is p_losses' box loss, with `inpaint`'s paste when set
+    (cddpm_op_loss_box); everything after the loss is the same step. `inpaint` without a box is an error, as in p_losses."""
     buf = buffers if buffers is not None else _schedule.schedule_buffers(timesteps)
     dev = trainer.dev
     trainer._fit(*[x01.shape[i] for i in (0, 2, 3)])       # the handle and its scratch arena before the first operator runs
     if encoder is not None:
         cond = encoder.forward(x01)
+    if inpaint and box is None:
+        raise ValueError("inpaint=True needs a box (the reference indexes box[i] unconditionally, cond_DDPM.py:632)")
     x0 = x01.float() * 2 - 1
-    sa = buf["sqrt_alphas_cumprod"].to(dev)[t].reshape(-1, 1, 1, 1)
-    s1 = buf["sqrt_one_minus_alphas_cumprod"].to(dev)[t].reshape(-1, 1, 1, 1)
-    xt = (sa * x0 + s1 * noise.float()).contiguous()      # q_sample (cond_DDPM.py:548-554); elementwise plumbing, not a hot operator
-    out = trainer.forward(xt, t, cond, slice0=slice0)
-    target = noise if objective == "pred_noise" else x0
     p2w = buf["p2_loss_weight"].to(dev)[t].contiguous()
-    loss, dout = trainer.loss_and_grad(out, target, p2w, loss_type)
+    if box is not None:
+        boxes = check_boxes(box, x01.shape[0], dev)
+        tables = tuple(buf[k].to(dev, torch.float32).contiguous() for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod"))
+        xt = trainer.eng.box_q_sample(x01.float(), t.to(dev), noise.float(), boxes, tables=tables)
+        out = trainer.forward(xt, t, cond, slice0=slice0)
+        loss, dout = trainer.loss_and_grad_box(out, x0, noise, boxes, p2w, loss_type, objective, inpaint)
+    else:
+        sa = buf["sqrt_alphas_cumprod"].to(dev)[t].reshape(-1, 1, 1, 1)
+        s1 = buf["sqrt_one_minus_alphas_cumprod"].to(dev)[t].reshape(-1, 1, 1, 1)
+        xt = (sa * x0 + s1 * noise.float()).contiguous()      # q_sample (cond_DDPM.py:548-554); elementwise plumbing, not a hot operator
+        out = trainer.forward(xt, t, cond, slice0=slice0)
+        target = noise if objective == "pred_noise" else x0
+        loss, dout = trainer.loss_and_grad(out, target, p2w, loss_type)
     # the gradient exchange runs bucket by bucket BEHIND the backward pass: a bucket's all-reduce is issued as soon as its slice of the
     # flat buffer is final and overlaps the backward operators that follow (and, for the UNet's last buckets, the encoder's backward)
     buckets = GradBuckets(trainer.gflat, enabled=all_reduce)

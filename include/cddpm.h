@@ -274,6 +274,32 @@ int cddpm_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev,
                    const float* sqrt_ac_host, const float* sqrt_1mac_host, int T,
                    float* out_dev, int B, int H, int W, void* stream);
 
+/* ---- the patched DDPM (src/models/DDPM_2D_patched.py, src/utils/patch_sampling.py) ----------------
+ * Boxes are device int32 rows (x0, y1, x2, y3): columns [x0, x2) and rows [y1, y3), the reference's convention, 16-byte aligned.
+ * They are clipped to the image as Python slicing clips a non-negative range (sample_single_box yields boxes that run past the
+ * right and bottom edge); a box that is empty after clipping is legal and selects nothing. Coordinates are not negative.
+ * All three entries only enqueue work on `stream`: no allocation, no synchronisation, fixed-order arithmetic (bitwise reproducible).
+ *
+ * q_sample of the box alone (cond_DDPM.py:587-604) for N output slices over S source slices, N % S == 0: out_dev [N][H][W], slice n
+ * reads x01_dev / noise_dev [S][H][W] at slice n % S. Outside its box it is 2 x01 - 1, inside sqrt_ac[t] (2 x01 - 1) + sqrt_1mac[t]
+ * noise with the arithmetic of the q_sample entry above, to the bit. t as there: t_dev [S] int32 (slice n: t_dev[n % S], kept
+ * inside [0, T)) or NULL for t_uniform. The coefficient tables are DEVICE arrays [T]: nothing is staged through the handle, so N is
+ * not bound by max_batch and the call serves the training step (whose handle has no schedule). */
+int cddpm_box_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev, const int32_t* t_dev, int t_uniform,
+                       const float* sqrt_ac_dev, const float* sqrt_1mac_dev, int T, const int32_t* box_dev, float* out_dev,
+                       int S, int N, int H, int W, void* stream);
+/* The stitching of DDPM_2D_patched.test_step (:175-215) after its last box, as written: reco_dev [K S][H][W] box-major (n = k S + s),
+ * box_dev [K S][4], cut_dev [K S][4] (the sample_grid_cut rows; read by CDDPM_STITCH_CUT only, NULL otherwise) -> out_dev [S][H][W].
+ * Every pixel walks k = 0 .. K - 1 in order from 0. PASTE: the value becomes reco_k where box k covers the pixel; CUT: the same with
+ * the cut rows; a pixel in no box stays 0. AVG: v <- (v + [pixel in box k] reco_k) / count after EVERY box, count = the number of
+ * boxes covering the pixel -- the reference divides the running image by the full mask inside its loop over boxes, so K boxes divide
+ * K times (pinned by tests/golden/patched); a pixel in no box is 0 / 0, as torch gives it. */
+#define CDDPM_STITCH_PASTE 0
+#define CDDPM_STITCH_CUT 1
+#define CDDPM_STITCH_AVG 2
+int cddpm_box_stitch(cddpm_handle h, const float* reco_dev, const int32_t* box_dev, const int32_t* cut_dev, int mode, float* out_dev,
+                     int S, int K, int H, int W, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------------- */
 /* Per-kernel-class timing with HIP events recorded on the launch stream around every kernel (bench.py's
  * roofline leg). Classes: 0 = fused 3x3 conv (MFMA), 1 = 1x1 conv (MFMA), 2 = attention core,
@@ -419,6 +445,14 @@ int cddpm_op_head_dgrad(cddpm_handle h, const float* dout_dev, const float* w9_d
  * at O(1) magnitude (every backward operator is linear in them, the scaling is exact) and cddpm_op_adam divides it out again. */
 int cddpm_op_loss(cddpm_handle h, const float* out_dev, const float* target_dev, const float* w_b_dev, int l2, int B, int HW, float grad_scale,
                   float* dout_dev, float* loss_b_dev, void* stream);
+/* The loss of p_losses with a box (cond_DDPM.py:612-645), one box per slice (box_dev [B][4], the patched DDPM's rows above): x0_dev
+ * is the image in [-1, 1]. The target is x0 (pred_noise = 0) or the noise inside the box and 0 outside (pred_noise = 1; noise_dev is
+ * read then only). Under `inpaint` the compared tensor is out inside the box and x0 outside, so dout is 0 outside the box -- under
+ * pred_noise the outside still adds |x0| or x0^2 to the value. The mean is over all H W pixels, times w_b. The loss scale is
+ * grad_scale, or the device scale when scaler_dev is given (the scaled entry's block below). dout_dev may be NULL: the loss only. */
+int cddpm_op_loss_box(cddpm_handle h, const float* out_dev, const float* x0_dev, const float* noise_dev, const int32_t* box_dev,
+                      const float* w_b_dev, int pred_noise, int inpaint, int l2, int B, int H, int W, float grad_scale,
+                      const int32_t* scaler_dev, float* dout_dev, float* loss_b_dev, void* stream);
 /* one Adam update (DDPM_2D.py:305-306: lr 1e-4, torch defaults) of a flat parameter vector; step counts from 1; the gradient used is
  * g_dev * grad_unscale (1 / the loss scale) */
 int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
