@@ -11,6 +11,10 @@ Added, behind a cfg switch that is absent (= reference behaviour) by default:
     cfg.conv_family: h3|x6|f32   ->  convolution family of the UNet's engine (unset: the process default, CDDPM_CONV or h3)
     cfg.conv_fallback: x6|f32    ->  slices whose reconstruction left the fp16 range of the h3 family are run again in this exact
                                      family, with a warning, instead of failing the batch (unset: off)
+    cfg.eval_precision: 16       ->  the UNet's engine evaluates (reconstruct, test_step, validation_step) in the arithmetic of the
+                                     reference's `precision: 16` test-time autocast: plain fp16 operands, fp32 accumulation, in the
+                                     convolutions and the attention (unset or 32: fp32-grade, today's behaviour). h3 family only: with
+                                     conv_family x6 | f32 a ValueError at construction. Never read from the Trainer's precision.
 
 `test_step` follows the reference's evaluation call (:171-286): 4 centre slices, `noise_ensemble` / `step_ensemble`
 averaging, a fresh `gen_noise` (device simplex) field per reconstruction.
@@ -95,7 +99,7 @@ class DDPM_2D(HipMirror, _Base):
             use_new_attention_order=True, use_spatial_transformer=_cfg_get(cfg, "spatial_transformer", False),
             transformer_depth=1)
         model.convert_to_fp16()
-        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None))
+        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None), _cfg_get(cfg, "eval_precision", None))
         timesteps = _cfg_get(cfg, "timesteps", 1000)
         self.test_timesteps = _cfg_get(cfg, "test_timesteps", 150)
         self.diffusion = GaussianDiffusion(
@@ -128,7 +132,7 @@ class DDPM_2D(HipMirror, _Base):
         reverse_sampling on : the reverse loop from pure noise / from start_t (p_sample_loop)."""
         if features is None:
             features = self(input)
-        with torch.autocast("cuda", enabled=False):          # the path is fp32 whatever the Trainer's precision
+        with torch.autocast("cuda", enabled=False):          # the engine's arithmetic is cfg.eval_precision's, whatever the Trainer's precision
             if _cfg_get(self.cfg, "reverse_sampling", False):
                 start_t = int(_cfg_get(self.cfg, "reverse_start_t", 0))
                 reco = self.diffusion.p_sample_loop(tuple(input.shape), cond=features, start_t=start_t)

@@ -12,6 +12,8 @@ On the HIP path: training_step runs `training.training_step(..., box=, inpaint=)
 cddpm_box_q_sample, the loss is cddpm_op_loss_box); test_step does the reference's K-box loop (:185-215) as ONE
 `GaussianDiffusion.p_losses_grid` call: batched UNet forwards over all K D (box, slice) pairs and one stitching launch. What the two
 mirrors share (trainer aliasing, checkpoint hooks, precision, loss-scale logging, evaluation bookkeeping) is mirror_common.HipMirror.
+The cfg keys `conv_family`, `conv_fallback` and `eval_precision` (absent in the reference; unset = nothing changes) mean what they
+mean in DDPM_2D.py: `eval_precision: 16` evaluates (test_step, validation_step) with plain fp16 operands in the UNet's engine.
 """
 from __future__ import annotations
 
@@ -44,7 +46,7 @@ class DDPM_2D(HipMirror, _Base):
             num_head_channels=64, num_heads_upsample=-1, use_scale_shift_norm=True, resblock_updown=True,
             use_new_attention_order=True, use_spatial_transformer=False, transformer_depth=1)
         model.convert_to_fp16()
-        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None))
+        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None), _cfg_get(cfg, "eval_precision", None))
         timesteps = _cfg_get(cfg, "timesteps", 1000)
         self.test_timesteps = _cfg_get(cfg, "test_timesteps", 150)
         self.diffusion = GaussianDiffusion(

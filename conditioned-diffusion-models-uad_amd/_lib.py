@@ -63,6 +63,8 @@ SYMBOLS = {
     "cddpm_set_accumulation_switch": (_i, [_vp, _i]),
     "cddpm_set_conv_family": (_i, [_vp, _i]),
     "cddpm_get_conv_family": (_i, [_vp]),
+    "cddpm_set_precision": (_i, [_vp, _i]),
+    "cddpm_get_precision": (_i, [_vp]),
     "cddpm_slice_status": (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
     "cddpm_set_profiling": (_i, [_vp, _i]),
     "cddpm_get_profile": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -76,6 +78,7 @@ SYMBOLS = {
     "cddpm_op_conv_gn": (_i, [_vp, _fp, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_gn_coef": (_i, [_vp, _fp, _i, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _vp]),
     "cddpm_op_attention": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
+    "cddpm_op_attention_p16": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_encoder_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "cddpm_encoder_destroy": (None, [_vp]),
     "cddpm_encoder_last_error": (C.c_char_p, [_vp]),

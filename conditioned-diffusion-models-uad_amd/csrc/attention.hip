@@ -12,10 +12,9 @@
 //                                 lane-half h = key (r&3) + 8 (r>>2) + 4 h), no LDS round trip; the matching A
 //                                 operand V[key(r,h)][c] is a conflict-free ds_read_b32 across 32 channels.
 #include "kernels.h"
+#include "conv_split.h"      // f32x16, f16x8, f16x4
 
 namespace cddpm {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                            int N, int C) {
@@ -149,6 +148,168 @@ void launch_attention(const float* qkv, float* out, int B, int N, int C, hipStre
     const int heads = C / 64;
     const int nqb = (N + 127) / 128;
     hipLaunchKernelGGL(attention_kernel, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, stream, qkv, out, N, C);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same forward with plain fp16 operands on v_mfma_f32_32x32x16_f16 (launch_attention_p16): the arithmetic of the reference's
+// evaluation under `precision: 16` (fp16 autocast over QKVAttention.forward, OpenAI_Unet.py:457-476) with fp32 accumulators.
+//   q (scaled by the exact 2^-3), k and v are rounded to fp16 (RNE) once, where they are staged; S and O accumulate in fp32; the
+//   running max / sum softmax stays in fp32; P is rounded to fp16 only as the MFMA operand; the output is fp32.
+// Work split and accumulator trick as above: workgroup = (sample, head, 128 queries), wave = 32 queries, key tiles of 64.
+//   S^T[key][query] = K . Q^T   : 4 k-steps of 16 channels per 32-key sub-tile; A = a K row's 8 channels (ds_read_b128 of the
+//                                 [key][channel] image, rows padded to 144 B: 16 consecutive rows cover the 16 four-bank groups),
+//                                 B = the query's 8 channels, in registers for the whole kernel.
+//   O^T[c][query]  += V^T . P^T : registers 8s .. 8s+7 of the S^T accumulator, rounded to fp16, ARE the B operand of k-step s:
+//                                 element j of lane-half h is key 16 s + 8 (j >> 2) + 4 h + (j & 3). The A operand is V^T[c][those
+//                                 keys]: two 8-byte reads of the transposed [channel][key] image (rows padded to 136 B: 32
+//                                 consecutive rows cover the 32 bank pairs), which the staging threads write as 4-key columns.
+// One 64-key tile costs a wave 16 MFMAs of 32 cycles instead of 128 of 64.
+__global__ __launch_bounds__(256, 2) void attention_p16_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                               int N, int C) {
+    constexpr int KS = 72;   // fp16 elements of a K row (64 channels + 16 B)
+    constexpr int VS = 68;   // fp16 elements of a V^T row (64 keys + 8 B)
+    __shared__ __attribute__((aligned(16))) _Float16 ldsK[64 * KS];    // [key][channel]
+    __shared__ __attribute__((aligned(16))) _Float16 ldsVt[64 * VS];   // [channel][key]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const int heads = C >> 6;
+    const int nqb = (N + 127) >> 7;
+    int bid = blockIdx.x;
+    const int qb = bid % nqb;
+    bid /= nqb;
+    const int hd = bid % heads;
+    const int b = bid / heads;
+    const int C3 = 3 * C;
+    const float* base = qkv + (size_t)b * N * C3;
+
+    // Q fragments of this lane's query: k-step s = channels 16 s + 8 lh + {0..7}, pre-scaled by 1/8, fp16
+    const int query = qb * 128 + wave * 32 + li;
+    const int qrow = min(query, N - 1);
+    f16x8 qf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const float* qp = base + (size_t)qrow * C3 + hd * 64 + 16 * s + 8 * lh;
+        const float4 a = *reinterpret_cast<const float4*>(qp);
+        const float4 c = *reinterpret_cast<const float4*>(qp + 4);
+        qf[s] = f16x8{(_Float16)(a.x * 0.125f), (_Float16)(a.y * 0.125f), (_Float16)(a.z * 0.125f), (_Float16)(a.w * 0.125f),
+                      (_Float16)(c.x * 0.125f), (_Float16)(c.y * 0.125f), (_Float16)(c.z * 0.125f), (_Float16)(c.w * 0.125f)};
+    }
+
+    f32x16 O[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) O[ct][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+
+    const int cq = tid & 15, kq = tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        float4 kv[4], vv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int key = k0 + 4 * kq + i;
+            kv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            vv[i] = kv[i];
+            if (key < N) {
+                const float* rowp = base + (size_t)key * C3 + hd * 64 + 4 * cq;
+                kv[i] = *reinterpret_cast<const float4*>(rowp + C);
+                vv[i] = *reinterpret_cast<const float4*>(rowp + 2 * C);
+            }
+        }
+        __syncthreads();   // previous tile fully consumed
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            *reinterpret_cast<f16x4*>(&ldsK[(4 * kq + i) * KS + 4 * cq]) =
+                f16x4{(_Float16)kv[i].x, (_Float16)kv[i].y, (_Float16)kv[i].z, (_Float16)kv[i].w};
+        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 0) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].x, (_Float16)vv[1].x, (_Float16)vv[2].x, (_Float16)vv[3].x};
+        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 1) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].y, (_Float16)vv[1].y, (_Float16)vv[2].y, (_Float16)vv[3].y};
+        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 2) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].z, (_Float16)vv[1].z, (_Float16)vv[2].z, (_Float16)vv[3].z};
+        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 3) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].w, (_Float16)vv[1].w, (_Float16)vv[2].w, (_Float16)vv[3].w};
+        __syncthreads();
+
+        // ---- S^T = K . Q^T for 2 sub-tiles of 32 keys
+        f32x16 S[2];
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) S[kt][r] = 0.f;
+            const _Float16* krow = &ldsK[(32 * kt + li) * KS + 8 * lh];
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                S[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(krow + 16 * s), qf[s], S[kt], 0, 0, 0);
+        }
+
+        // ---- online softmax over keys (registers + lane^32), fp32
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (key >= N) S[kt][r] = -INFINITY;
+                tmax = fmaxf(tmax, S[kt][r]);
+            }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+        const float m_new = fmaxf(m_run, tmax);
+        const float alpha = __expf(m_run - m_new);
+        float psum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = __expf(S[kt][r] - m_new);
+                S[kt][r] = p;
+                psum += p;
+            }
+        psum += __shfl_xor(psum, 32, 64);
+        l_run = l_run * alpha + psum;
+        m_run = m_new;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) O[ct][r] *= alpha;
+
+        // ---- O^T += V^T . P^T
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                f16x8 pf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pf[j] = (_Float16)S[kt][8 * s + j];
+                const int key0 = 32 * kt + 16 * s + 4 * lh;
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const _Float16* vp = &ldsVt[(32 * ct + li) * VS + key0];
+                    const f16x4 lo = *reinterpret_cast<const f16x4*>(vp);
+                    const f16x4 hi = *reinterpret_cast<const f16x4*>(vp + 8);
+                    const f16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    O[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, O[ct], 0, 0, 0);
+                }
+            }
+    }
+
+    if (query < N) {
+        const float inv = 1.0f / l_run;
+        float* orow = out + ((size_t)b * N + query) * C + hd * 64;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                float4 v;
+                v.x = O[ct][4 * rq + 0] * inv;
+                v.y = O[ct][4 * rq + 1] * inv;
+                v.z = O[ct][4 * rq + 2] * inv;
+                v.w = O[ct][4 * rq + 3] * inv;
+                *reinterpret_cast<float4*>(orow + 32 * ct + 8 * rq + 4 * lh) = v;
+            }
+    }
+}
+
+void launch_attention_p16(const float* qkv, float* out, int B, int N, int C, hipStream_t stream) {
+    const int heads = C / 64;
+    const int nqb = (N + 127) / 128;
+    hipLaunchKernelGGL(attention_p16_kernel, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, stream, qkv, out, N, C);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -71,6 +71,7 @@ int conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s) {
     auto it = h->stat.find(a.out);           // outputs that can feed a GroupNorm get their statistics for free
     StatBuf* sb = (it != h->stat.end()) ? &it->second : nullptr;
     a.stats = sb ? sb->records : nullptr;
+    a.hi_only = (h->precision == 16) ? 1 : 0;      // plain fp16 operands on every convolution of a precision-16 handle, split-K included
     short kb[CDDPM_MAX_KSPLIT + 1] = {0};
     const int S = plan_ksplit(h, a, kb);
     if (S > 1) {
@@ -492,7 +493,8 @@ int run_attn(cddpm_ctx* h, const AttnW& w, const float* x, float* dst, int B, in
     if (conv_launch(h, a, s)) return -1;
     {
         Prof pa(h, PC_ATTN, 4.0 * B * (double)N * N * w.C, 4.0 * B * (double)N * 4 * w.C, s);
-        launch_attention(h->qkvbuf, h->attbuf, B, N, w.C, s);
+        if (h->precision == 16) launch_attention_p16(h->qkvbuf, h->attbuf, B, N, w.C, s);
+        else launch_attention(h->qkvbuf, h->attbuf, B, N, w.C, s);
     }
     ConvArgs p;
     zero_conv_args(p, h);
@@ -866,7 +868,7 @@ static StepArgs step_args(const cddpm_ctx* h, float* img, const float* noise, ui
 static int step_once(cddpm_ctx* h, float* img, const float* z_dev, uint64_t seed, uint64_t slice0, int t, int finalize,
                      int B, int H, int W, hipStream_t s) {
     launch_fill_int(h->d_t, B, t, s);
-    h->nb2_now = (t >= h->nb2_tmin) ? 1 : 0;        // the step's accumulation plan: a function of t alone
+    h->nb2_now = (t >= h->nb2_tmin) ? 1 : 0;        // the step's accumulation plan: a function of t alone (precision 16: of nothing, see conv_set_nb2)
     const int rc_fwd = forward_impl(h, img, h->model_out, B, H, W, s);
     h->nb2_now = 0;
     if (rc_fwd) return -1;
@@ -893,11 +895,12 @@ static int reverse_by_graph(cddpm_ctx* h, float* img, const float* noise_dev, ui
         HIPCHECK(h, hipEventCreateWithFlags(&h->gev_out, hipEventDisableTiming));
     }
     cddpm_ctx::StepGraph& g = h->sg;
-    if (t_hi >= h->nb2_tmin && t_lo < h->nb2_tmin) {       // the plan switches inside the range: two replays, one graph each
-        if (reverse_by_graph(h, img, noise_dev, seed, slice0, t_hi, h->nb2_tmin, B, H, W, s)) return -1;
-        return reverse_by_graph(h, img, noise_dev, seed, slice0, h->nb2_tmin - 1, t_lo, B, H, W, s);
+    const int tmin = (h->precision == 16) ? (1 << 30) : h->nb2_tmin;      // precision 16: one plan on every step, the switch has no effect
+    if (t_hi >= tmin && t_lo < tmin) {       // the plan switches inside the range: two replays, one graph each
+        if (reverse_by_graph(h, img, noise_dev, seed, slice0, t_hi, tmin, B, H, W, s)) return -1;
+        return reverse_by_graph(h, img, noise_dev, seed, slice0, tmin - 1, t_lo, B, H, W, s);
     }
-    const int plan = (t_lo >= h->nb2_tmin) ? 1 : 0;
+    const int plan = (t_lo >= tmin) ? 1 : 0;
     const bool hit = g.exec && g.img == img && g.noise == noise_dev && g.seed == seed && g.slice0 == slice0 && g.B == B &&
                      g.H == H && g.W == W && g.gen == h->gen && g.nb2 == plan;
     if (!hit) {
@@ -1117,6 +1120,8 @@ int cddpm_get_conv_family(cddpm_handle h) { return h ? h->family : -1; }
 int cddpm_set_conv_family(cddpm_handle h, int family) {
     if (!h) return -1;
     if (family < 0 || family > 2) return fail(h, "cddpm_set_conv_family: unknown family %d (2 = h3, 1 = x6, 0 = f32)", family);
+    if (family != 2 && h->precision == 16)
+        return fail(h, "cddpm_set_conv_family: the handle is at precision 16, which only the h3 family has (cddpm_set_precision(h, 32) first)");
     if (family == h->family) return 0;
     HIPCHECK(h, hipSetDevice(h->device));
     if (h->weights_loaded) {
@@ -1135,6 +1140,19 @@ int cddpm_set_conv_family(cddpm_handle h, int family) {
     }
     h->gen++;                            // a captured step graph has the family's kernels baked in
     h->family = family;
+    return 0;
+}
+
+int cddpm_get_precision(cddpm_handle h) { return h ? h->precision : -1; }
+
+int cddpm_set_precision(cddpm_handle h, int bits) {
+    if (!h) return -1;
+    if (bits != 16 && bits != 32) return fail(h, "cddpm_set_precision: precision must be 32 or 16, got %d", bits);
+    if (bits == 16 && h->family != 2)
+        return fail(h, "cddpm_set_precision: precision 16 needs the h3 convolution family (the handle's family is %s)", h->family == 1 ? "x6" : "f32");
+    if (bits == h->precision) return 0;
+    h->gen++;                            // a captured step graph has the precision's kernels baked in
+    h->precision = bits;                 // no repack: the hi-only kernels read the hi plane of the h3 weight image
     return 0;
 }
 

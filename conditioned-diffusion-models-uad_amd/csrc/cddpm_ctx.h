@@ -70,6 +70,10 @@ struct cddpm_ctx {
     // weight image of the handle uses. weights_dropped: a family change freed the images of the previous family.
     int family = cddpm::conv_mode();
     bool weights_dropped = false;
+    // arithmetic of the handle's reconstruction path (cddpm_set_precision): 32 = fp32-grade products; 16 (h3 handles only) = plain
+    // fp16 operands -- hi_only on every convolution conv_launch plans, the fp16-MFMA attention kernel, and the 256-cout workgroups
+    // wherever the maximum geometry allows them. Not read by the cddpm_op_* operators.
+    int precision = 32;
     size_t weight_allocs_begin = 0;      // allocs[weight_allocs_begin ..) are what cddpm_load_weights uploaded
 
     std::vector<cddpm::ResW> res;
@@ -266,7 +270,9 @@ inline long long conv_workgroups(const ConvArgs& a, int B, int H, int W) {
 enum Nb2Policy {
     // the reconstruction path (conv_launch): the steps the handle's accumulation switch names (nb2_now), and `workgroups` is taken at
     // the handle's MAXIMUM geometry -- a property of the handle like the split-K factor, never of the call, so that a slice's bits do
-    // not depend on the batch it is computed in. The 1000-step chain feeds every rounding error back into itself.
+    // not depend on the batch it is computed in. The 1000-step chain feeds every rounding error back into itself. A precision-16
+    // handle (operand rounding 2^-11: no 1e-4 chain to protect) wants the form on every step and in single forwards, at the same
+    // maximum geometry: still a function of the handle alone.
     NB2_HANDLE_PLAN,
     // the training operators plan per call, and DO take the 256-cout workgroups wherever the call fills the chip with them: a gradient's
     // accuracy need (2e-5 of float64 autograd; SGD noise far above that) is not the 1000-step chain's, and the form is worth
@@ -278,7 +284,7 @@ enum Nb2Policy {
 };
 inline void conv_set_nb2(ConvArgs& a, const cddpm_ctx* h, Nb2Policy policy, long long workgroups) {
     const int env = conv_nb2_env();
-    const bool wanted = policy == NB2_HANDLE_PLAN ? (h->nb2_now || env == 2) : policy == NB2_CALL_PLAN ? env >= 1 : env == 2;
+    const bool wanted = policy == NB2_HANDLE_PLAN ? (h->nb2_now || h->precision == 16 || env == 2) : policy == NB2_CALL_PLAN ? env >= 1 : env == 2;
     a.nb2 = (wanted && conv_nb2_ok(a.Cout, workgroups, 1, h->family)) ? 1 : 0;
 }
 

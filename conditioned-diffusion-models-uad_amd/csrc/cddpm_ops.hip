@@ -588,6 +588,13 @@ int cddpm_pack_conv_weights(const float* w_host, int Cout, int Cin, int taps, vo
     return conv_mode();
 }
 
+int cddpm_op_attention_p16(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream) {
+    OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_p16: C must be a multiple of 64")
+    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && out_dev, "cddpm_op_attention_p16: NULL argument")
+    launch_attention_p16(qkv_dev, out_dev, B, N, C, s);
+    OP_EPILOGUE()
+}
+
 int cddpm_op_attention(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream) {
     OP_PROLOGUE(PC_ATTN, 0.0, 0.0, !(C % 64 || N < 1), "cddpm_op_attention: C must be a multiple of 64")
     launch_attention(qkv_dev, out_dev, B, N, C, s);

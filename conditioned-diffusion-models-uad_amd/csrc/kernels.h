@@ -41,8 +41,10 @@ struct ConvArgs {
     int ksplit;
     short kbound[CDDPM_MAX_KSPLIT + 1];
     // fp16-split family only: 1 = multiply the hi terms only (plain fp16 operands, fp32 accumulation -- the arithmetic of the
-    // reference trainer's `precision: 16`; a third of the MFMAs). Set by the training operators under CDDPM_TRAIN_PRECISION=16, never by
-    // the reconstruction path.
+    // reference's `precision: 16`; a third of the MFMAs). Two callers set it, independently of each other: the training operators under
+    // CDDPM_TRAIN_PRECISION=16 (the process-wide cddpm_set_train_precision), and the reconstruction path of a handle at precision 16
+    // (cddpm_set_precision: every convolution conv_launch plans, the split-K plan included). The packed h3 weight image serves both
+    // forms: the hi-only kernel reads its hi plane.
     int hi_only;
     // fp16-split family, unsplit K: 1 = workgroups of 256 pixels x 256 couts (two cout blocks per workgroup sharing the
     // chunk's transformed patch; two-level accumulation, see conv_x6.hip). Decided by the caller (cddpm_ctx.h::conv_set_nb2).
@@ -246,6 +248,9 @@ void launch_gn_silu_backward(const float* x, const float* x1 /* second source of
 // attention core (attention.hip): qkv NHWC [B,N,3C] -> out [B,N,C], heads of 64 channels
 // ------------------------------------------------------------------------------------------------
 void launch_attention(const float* qkv, float* out, int B, int N, int C, hipStream_t stream);
+// the same contract with plain fp16 operands (q / 8, k, v and P rounded to fp16; fp32 accumulators, softmax and output) on
+// v_mfma_f32_32x32x16_f16: what a precision-16 handle runs (cddpm_set_precision) and cddpm_op_attention_p16
+void launch_attention_p16(const float* qkv, float* out, int B, int N, int C, hipStream_t stream);
 
 // residual-map post-processing (eval_post.hip; src/utils/utils_eval.py:29-33, :447-464)
 void launch_residual_mask(const float* orig, const float* recon, const float* mask, float* out, int S, int H, int W,

@@ -27,6 +27,18 @@ def conv_family_code(name: str) -> int:
     return CONV_FAMILIES[name]
 
 
+# precision of a handle's reconstruction path (cddpm_set_precision): the spellings of Lightning's Trainer(precision=...) that mean
+# fp16 autocast or full precision. There is no bf16 reconstruction: 'bf16' is refused, not mapped.
+PRECISIONS = {16: 16, 32: 32, "16": 16, "16-mixed": 16, "32": 32}
+
+
+def precision_bits(value) -> int:
+    """16 / 32 / '16' / '16-mixed' / '32' -> 16 or 32; anything else (None, 8, 'bf16', '64', True) is a ValueError (no GPU needed)"""
+    if isinstance(value, bool) or not isinstance(value, (int, str)) or value not in PRECISIONS:
+        raise ValueError(f"unknown precision {value!r}: expected 32, 16, '32', '16' or '16-mixed' (there is no bf16 reconstruction)")
+    return PRECISIONS[value]
+
+
 def flagged_runs(flags: Sequence) -> List[Tuple[int, int]]:
     """Maximal contiguous runs [i, j) of truthy entries of a per-slice flag sequence: [0,1,1,0,1] -> [(1,3),(4,5)].
     Runs, not single slices, because the device Philox keys a slice's noise by slice0 + its position in the batch: a run
@@ -86,10 +98,14 @@ class CddpmEngine:
 
     def __init__(self, *, model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3,
                  attention_resolutions=(3, 6, 12), head_channels=64, cond_dim=128, timesteps=1000,
-                 max_batch=1, max_h=128, max_w=128, device=None, in_channels=1, out_channels=1, conv_family=None):
+                 max_batch=1, max_h=128, max_w=128, device=None, in_channels=1, out_channels=1, conv_family=None,
+                 precision=None):
         """conv_family: None (the process default: CDDPM_CONV, else h3), 'h3', 'x6' or 'f32' -- set on the handle before any
-        weights are loaded."""
+        weights are loaded. precision: None (32), 32, 16, '32', '16' or '16-mixed' -- see set_precision; 16 needs the h3 family."""
         family = None if conv_family is None else conv_family_code(conv_family)
+        bits = None if precision is None else precision_bits(precision)
+        if bits == 16 and conv_family is not None and conv_family != "h3":
+            raise ValueError(f"precision 16 needs the h3 convolution family, got conv_family={conv_family!r}")
         self.lib = _lib.load_library()
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device visible: the cDDPM HIP path needs an MI355X (gfx950); there is no CPU fallback")
@@ -120,6 +136,8 @@ class CddpmEngine:
         self._keep = []   # tensors whose pointers the library may still read (taps)
         if family is not None:
             self._ck(self.lib.cddpm_set_conv_family(self._h, family), "cddpm_set_conv_family")
+        if bits is not None:
+            self._ck(self.lib.cddpm_set_precision(self._h, bits), "cddpm_set_precision")
 
     # ------------------------------------------------------------------ lifetime / errors
     def close(self):
@@ -148,6 +166,19 @@ class CddpmEngine:
         """Change the handle's convolution family. Packed weights belong to a family: after a change to a DIFFERENT family the
         caller must call load_weights (and set_schedule) again -- until then every forward / reverse call raises."""
         self._ck(self.lib.cddpm_set_conv_family(self._h, conv_family_code(name)), "cddpm_set_conv_family")
+
+    @property
+    def precision(self) -> int:
+        return int(self.lib.cddpm_get_precision(self._h))
+
+    def set_precision(self, value):
+        """Arithmetic of this engine's forward / reverse calls (cddpm_set_precision). 32: fp32-grade products (the default). 16 (also
+        '16', '16-mixed'; h3 engines only): what the reference evaluates with under `precision: 16` -- plain fp16 operands with fp32
+        accumulation in the convolutions and the attention, everything else fp32; about the accuracy of fp16 autocast, the h3
+        family's range limit (|activation| < 65504: `fallback=` re-runs the slices that leave it). No weights are reloaded. Any
+        other value raises ValueError before the library is called."""
+        bits = precision_bits(value)
+        self._ck(self.lib.cddpm_set_precision(self._h, bits), "cddpm_set_precision")
 
     def weight_names(self):
         n = self.lib.cddpm_num_weights(self._h)
@@ -430,7 +461,8 @@ class CddpmEngine:
         return x
 
     def set_accumulation_switch(self, t_switch: int):
-        """reverse steps t >= t_switch use the faster two-level-accumulation convolution plan (include/cddpm.h); default off (2^30)"""
+        """reverse steps t >= t_switch use the faster two-level-accumulation convolution plan (include/cddpm.h); default off (2^30).
+        No effect at precision 16, which takes that plan on every step."""
         self._ck(self.lib.cddpm_set_accumulation_switch(self._h, int(t_switch)), "cddpm_set_accumulation_switch")
 
     def set_clip_denoised(self, on: bool):
@@ -822,11 +854,13 @@ class CddpmEngine:
                                            coef.data_ptr(), B, HW, _stream_ptr(self.device)), "cddpm_op_gn_coef")
         return coef
 
-    def op_attention(self, qkv):
+    def op_attention(self, qkv, precision=32):
+        """the attention core on qkv [B,N,3C]; precision 16: the fp16-MFMA kernel (cddpm_op_attention_p16), whatever the engine's own"""
+        what = "cddpm_op_attention_p16" if precision_bits(precision) == 16 else "cddpm_op_attention"
+        fn = getattr(self.lib, what)
         B, N, C3 = qkv.shape
         out = torch.empty((B, N, C3 // 3), dtype=torch.float32, device=self.device)
-        self._ck(self.lib.cddpm_op_attention(self._h, qkv.data_ptr(), out.data_ptr(), B, N, C3 // 3,
-                                             _stream_ptr(self.device)), "cddpm_op_attention")
+        self._ck(fn(self._h, qkv.data_ptr(), out.data_ptr(), B, N, C3 // 3, _stream_ptr(self.device)), what)
         return out
 
     def op_act_dropout(self, x, coef, silu, *, seed, step, slice0, stream_id, p):

@@ -126,7 +126,8 @@ int cddpm_reverse(cddpm_handle h, float* img_inout_dev, const float* noise_dev, 
  * -- the extra rounding noise of ANY part of the chain survives to the end (there is no late switch step that hides it), which is why
  * the default keeps three-level accumulation on every step. A function of t alone: a slice's bits do not depend on its batch.
  * Single forwards (cddpm_unet_forward, cddpm_ddim_step) use the three-level kernel. cddpm_op_conv_packed plans per call instead: it
- * takes the 256-cout form wherever the call itself has >= 512 workgroups of the 128-cout form (CDDPM_NB2=0 disables it). */
+ * takes the 256-cout form wherever the call itself has >= 512 workgroups of the 128-cout form (CDDPM_NB2=0 disables it).
+ * No effect on a handle at precision 16 (cddpm_set_precision): it takes the 256-cout form on every step and in single forwards. */
 int cddpm_set_accumulation_switch(cddpm_handle h, int t_switch);
 
 /* Convolution family of a handle. family: CDDPM_CONV_H3 = fp16 two-term split (needs |activation| < 65504; the fastest),
@@ -142,6 +143,27 @@ int cddpm_set_accumulation_switch(cddpm_handle h, int t_switch);
 #define CDDPM_CONV_H3 2
 int cddpm_set_conv_family(cddpm_handle h, int family);
 int cddpm_get_conv_family(cddpm_handle h);      /* the family, or -1 for a NULL handle */
+
+/* Precision of a handle's reconstruction path: the arithmetic of the reference's evaluation under the Trainer's `precision: 16`, i.e.
+ * fp16 autocast over ResBlock._forward (src/models/modules/OpenAI_Unet.py:284-338) and QKVAttention.forward (:457-476).
+ * bits: 32 (what a handle starts with: fp32-grade products, fp32 attention) or 16; any other value is an error, and so is 16 on a
+ * handle whose family is not CDDPM_CONV_H3. On a precision-16 handle cddpm_set_conv_family(h, CDDPM_CONV_X6 | CDDPM_CONV_F32) fails
+ * with "cddpm_set_conv_family: the handle is at precision 16, which only the h3 family has (cddpm_set_precision(h, 32) first)".
+ * At 16, cddpm_unet_forward / cddpm_p_sample / cddpm_reverse / cddpm_reverse_range / cddpm_ddim_step
+ *   - multiply plain fp16 operands (fp32 accumulation) in every convolution planned through the split family: 3x3, folded
+ *     upsample, 1x1, the 1x1 skip segment and the split-K small-batch plan -- one MFMA per product group instead of three;
+ *   - run every attention block, middle and in-level, on the fp16-MFMA kernel of cddpm_op_attention_p16;
+ *   - take the 256-cout workgroup form wherever the handle's MAXIMUM geometry allows it (>= 512 workgroups of the 128-cout form;
+ *     CDDPM_NB2=0 disables it), on every step and in single forwards: a function of the handle, never of the batch in the call, so
+ *     a slice's bits still do not depend on the batch it is computed in. cddpm_set_accumulation_switch has no effect.
+ * The one-channel input convolution, the head, GroupNorm, the embedding linears and the step kernels stay fp32.
+ * Accuracy: that of fp16 autocast (operand rounding 2^-11, not 2^-24) -- NOT the 1e-4 full-length chain of precision 32; the
+ * measured ratios against the reference under autocast are in DESIGN.md section 7.4. Range: as for every h3 handle an activation
+ * beyond +-65504 gives a non-finite slice (cddpm_slice_status finds it; re-run it on a handle of an exact family).
+ * No repack: the packed h3 weight image is read hi-term only. A change invalidates a captured step graph. The cddpm_op_*
+ * operators and the process-wide cddpm_set_train_precision neither read nor change a handle's precision. */
+int cddpm_set_precision(cddpm_handle h, int bits);
+int cddpm_get_precision(cddpm_handle h);        /* 32 or 16, or -1 for a NULL handle */
 
 /* Per-slice status of x_dev [B,1,H,W] (16-byte aligned, H * W a multiple of 4): status_dev[b] (int32 [B]) = 1 if slice b holds an
  * inf or a NaN, else 0. One kernel launch for the whole batch on `stream`, no host synchronisation: the caller copies the B flags.
@@ -586,6 +608,10 @@ int cddpm_stat_records(int H, int W, int kind);
  * out [B,N,C] = softmax(q k^T / sqrt(head_channels)) v  (QKVAttention, OpenAI_Unet.py:457-476). C: a multiple of 64; tested and
  * expected ranges of N as for cddpm_op_attention_backward. */
 int cddpm_op_attention(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream);
+/* the same contract in the arithmetic of fp16 autocast over QKVAttention.forward (OpenAI_Unet.py:457-476): q / 8, k and v rounded to
+ * fp16 (RNE) once, products on v_mfma_f32_32x32x16_f16 with fp32 accumulators, the running max / sum softmax in fp32, P rounded to
+ * fp16 only as an MFMA operand, fp32 output. The attention kernel of a precision-16 handle (cddpm_set_precision); any handle may call it. */
+int cddpm_op_attention_p16(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream);
 
 /* ---- context encoder ---------------------------------------------------------------
  * Replaces the module get_encoder builds (src/models/modules/DDPM_encoder.py:6-29): timm resnet50(in_chans=1,
