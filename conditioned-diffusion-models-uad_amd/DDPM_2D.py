@@ -15,6 +15,10 @@ Added, behind a cfg switch that is absent (= reference behaviour) by default:
                                      reference's `precision: 16` test-time autocast: plain fp16 operands, fp32 accumulation, in the
                                      convolutions and the attention (unset or 32: fp32-grade, today's behaviour). h3 family only: with
                                      conv_family x6 | f32 a ValueError at construction. Never read from the Trainer's precision.
+    cfg.train_attention_precision: 16 -> training_step runs every attention core of the UNet, forward and backward, on the fp16-MFMA
+                                     kernels (UNetTrainer's attention_precision: the arithmetic of the reference's `precision: 16`
+                                     autocast over QKVAttention; unset or 32: exact fp32 attention, today's behaviour). Independent of
+                                     the Trainer's precision, which selects the convolutions' arithmetic; 'bf16' is a ValueError.
 
 `test_step` follows the reference's evaluation call (:171-286): 4 centre slices, `noise_ensemble` / `step_ensemble`
 averaging, a fresh `gen_noise` (device simplex) field per reconstruction.

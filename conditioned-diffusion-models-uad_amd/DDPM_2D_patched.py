@@ -12,8 +12,9 @@ On the HIP path: training_step runs `training.training_step(..., box=, inpaint=)
 cddpm_box_q_sample, the loss is cddpm_op_loss_box); test_step does the reference's K-box loop (:185-215) as ONE
 `GaussianDiffusion.p_losses_grid` call: batched UNet forwards over all K D (box, slice) pairs and one stitching launch. What the two
 mirrors share (trainer aliasing, checkpoint hooks, precision, loss-scale logging, evaluation bookkeeping) is mirror_common.HipMirror.
-The cfg keys `conv_family`, `conv_fallback` and `eval_precision` (absent in the reference; unset = nothing changes) mean what they
-mean in DDPM_2D.py: `eval_precision: 16` evaluates (test_step, validation_step) with plain fp16 operands in the UNet's engine.
+The cfg keys `conv_family`, `conv_fallback`, `eval_precision` and `train_attention_precision` (absent in the reference; unset = nothing
+changes) mean what they mean in DDPM_2D.py: `eval_precision: 16` evaluates (test_step, validation_step) with plain fp16 operands in the
+UNet's engine; `train_attention_precision: 16` trains the attention cores on the fp16-MFMA kernels.
 """
 from __future__ import annotations
 

@@ -89,6 +89,7 @@ SYMBOLS = {
     "cddpm_op_conv_wgrad": (_i, [_vp, _fp, _i, _fp, _i, _fp, _i, _i, _fp, _i, _i, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_bias_grad": (_i, [_vp, _fp, _i64, _i, _fp, _vp]),
     "cddpm_op_attention_backward": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
+    "cddpm_op_attention_backward_p16": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_linear_backward": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
     "cddpm_op_linear": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
     "cddpm_op_conv_in1": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),

@@ -638,4 +638,356 @@ void launch_attention_backward_flash(const float* qkv, const float* da, float* d
     hipLaunchKernelGGL(attention_bwd_kv_kernel, dim3((unsigned)(B * heads * nb)), dim3(256), 0, stream, qkv, da, dqkv, stats, N, C);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The same backward with plain fp16 operands on v_mfma_f32_32x32x16_f16 (launch_attention_backward_p16): the arithmetic of fp16
+// autocast over QKVAttention.forward and its backward (the reference trains under `precision: 16`), with fp32 accumulators.
+//   q . 2^-3, k, v and dA are rounded to fp16 (RNE, gradual underflow) once, where they are staged; S, dP, dQ, dK and dV accumulate in
+//   fp32; the running max / sum, P = exp(S - lse), D_i = sum_c dA_ic a_ic (rounded dA, fp32 sweep-1 output) and dS = P (dP - D) are
+//   fp32 VALU work; P and dS are rounded to fp16 only as MFMA operands; dqkv is fp32. |dA| >= 65504 rounds to +-inf as under autocast
+//   and gives non-finite gradients of that sample (what the loss scale's device guard catches), never a finite wrong number.
+// Two kernels, work split, masking and row statistics as the fp32 pair above; LDS images as attention_p16_kernel:
+//   row images [row][channel], 144-B rows : A operands of the first products (ds_read_b128 of a row's 8 channels)
+//   transposed images [channel][row], 136-B rows, written as 4-row columns : A operands of the second products (2 x ds_read_b64);
+//   registers 8s .. 8s+7 of a first product's accumulator, rounded to fp16, are the B operand of k-step s of the second.
+//   attention_bwd_q_p16_kernel  : sweep 1 = attention_p16_kernel (K rows, V^T); sweep 2: K rows, V rows, K^T (27 KB)
+//   attention_bwd_kv_p16_kernel : k, v fragments in registers; per 64-query tile Q/8 and dA rows, (Q/8)^T and dA^T (35 KB)
+// Per 64-row tile a wave issues 16 + 24 (q kernel, sweeps 1 + 2) and 32 (kv kernel) MFMAs of 32 cycles instead of 128 + 192 and 256 of 64.
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int P16_RS = 72;   // fp16 elements of a row-image row (64 channels + 16 B)
+constexpr int P16_TS = 68;   // fp16 elements of a transposed-image row (64 rows + 8 B)
+
+__device__ __forceinline__ f16x4 p16_round4(float x, float y, float z, float w) {
+    return f16x4{(_Float16)x, (_Float16)y, (_Float16)z, (_Float16)w};
+}
+// this staging thread's 4 rows x 4 channels (rows 4 kq + i, channels 4 cq + {0..3}) into a row image / a transposed image
+__device__ __forceinline__ void p16_stage_rows(_Float16* img, int kq, int cq, const float4 (&v)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<f16x4*>(&img[(4 * kq + i) * P16_RS + 4 * cq]) = p16_round4(v[i].x, v[i].y, v[i].z, v[i].w);
+}
+__device__ __forceinline__ void p16_stage_cols(_Float16* img, int kq, int cq, const float4 (&v)[4]) {
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 0) * P16_TS + 4 * kq]) = p16_round4(v[0].x, v[1].x, v[2].x, v[3].x);
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 1) * P16_TS + 4 * kq]) = p16_round4(v[0].y, v[1].y, v[2].y, v[3].y);
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 2) * P16_TS + 4 * kq]) = p16_round4(v[0].z, v[1].z, v[2].z, v[3].z);
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 3) * P16_TS + 4 * kq]) = p16_round4(v[0].w, v[1].w, v[2].w, v[3].w);
+}
+// 8 channels of a global row as one fp16 MFMA fragment, scaled by `scale` before rounding
+__device__ __forceinline__ f16x8 p16_fragment(const float* p, float scale) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    const float4 c = *reinterpret_cast<const float4*>(p + 4);
+    return f16x8{(_Float16)(a.x * scale), (_Float16)(a.y * scale), (_Float16)(a.z * scale), (_Float16)(a.w * scale),
+                 (_Float16)(c.x * scale), (_Float16)(c.y * scale), (_Float16)(c.z * scale), (_Float16)(c.w * scale)};
+}
+// acc[ct] += T^T-image[channel 32 ct + li][rows row0 + {0..3}, row0 + 8 + {0..3}] . bf for both channel tiles
+__device__ __forceinline__ void p16_second_product(f32x16 (&acc)[2], const _Float16* timg, int li, int row0, f16x8 bf) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+        const _Float16* tp = &timg[(32 * ct + li) * P16_TS + row0];
+        const f16x4 lo = *reinterpret_cast<const f16x4*>(tp);
+        const f16x4 hi = *reinterpret_cast<const f16x4*>(tp + 8);
+        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7), bf, acc[ct], 0, 0, 0);
+    }
+}
+}  // namespace
+
+__global__ __launch_bounds__(256, 2) void attention_bwd_q_p16_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
+                                                                     float* __restrict__ dqkv, float* __restrict__ stats /*[B][heads][N][2]*/,
+                                                                     int N, int C) {
+    __shared__ __attribute__((aligned(16))) _Float16 ldsK[64 * P16_RS];   // K rows [key][channel]
+    __shared__ __attribute__((aligned(16))) _Float16 ldsV[64 * P16_RS];   // V rows [key][channel] (sweep 2: A operand of dP^T = V . dA^T)
+    __shared__ __attribute__((aligned(16))) _Float16 ldsT[64 * P16_TS];   // [channel][key]: V^T in sweep 1, K^T in sweep 2
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const int heads = C >> 6;
+    const int nqb = (N + 127) >> 7;
+    int bid = blockIdx.x;
+    const int qb = bid % nqb;
+    bid /= nqb;
+    const int hd = bid % heads;
+    const int b = bid / heads;
+    const int C3 = 3 * C;
+    const float* base = qkv + (size_t)b * N * C3;
+    const int query = qb * 128 + wave * 32 + li;
+    const int qrow = min(query, N - 1);
+    const float* darow = da + ((size_t)b * N + qrow) * C + hd * 64;
+    // fragments of this lane's query: k-step s = channels 16 s + 8 lh + {0..7}; q pre-scaled by 1/8
+    f16x8 qf[4], daf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        qf[s] = p16_fragment(base + (size_t)qrow * C3 + hd * 64 + 16 * s + 8 * lh, 0.125f);
+        daf[s] = p16_fragment(darow + 16 * s + 8 * lh, 1.0f);
+    }
+    const int cq = tid & 15, kq = tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
+    float m_run = -INFINITY, l_run = 0.f, Dq = 0.f;
+    // ---------------- sweep 1: the p16 forward (running max / sum, O^T) -> D
+    {
+        f32x16 O[2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) O[ct][r] = 0.f;
+        for (int k0 = 0; k0 < N; k0 += 64) {
+            float4 kv[4], vv[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int key = k0 + 4 * kq + i;
+                kv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                vv[i] = kv[i];
+                if (key < N) {
+                    const float* rowp = base + (size_t)key * C3 + hd * 64 + 4 * cq;
+                    kv[i] = *reinterpret_cast<const float4*>(rowp + C);
+                    vv[i] = *reinterpret_cast<const float4*>(rowp + 2 * C);
+                }
+            }
+            __syncthreads();   // previous tile fully consumed
+            p16_stage_rows(ldsK, kq, cq, kv);
+            p16_stage_cols(ldsT, kq, cq, vv);
+            __syncthreads();
+            f32x16 S[2];
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) S[kt][r] = 0.f;
+                const _Float16* krow = &ldsK[(32 * kt + li) * P16_RS + 8 * lh];
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    S[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(krow + 16 * s), qf[s], S[kt], 0, 0, 0);
+            }
+            float tmax = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    if (key >= N) S[kt][r] = -INFINITY;
+                    tmax = fmaxf(tmax, S[kt][r]);
+                }
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+            const float m_new = fmaxf(m_run, tmax);
+            const float alpha = __expf(m_run - m_new);
+            float psum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float pv = __expf(S[kt][r] - m_new);
+                    S[kt][r] = pv;
+                    psum += pv;
+                }
+            psum += __shfl_xor(psum, 32, 64);
+            l_run = l_run * alpha + psum;
+            m_run = m_new;
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) O[ct][r] *= alpha;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    f16x8 pf;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pf[j] = (_Float16)S[kt][8 * s + j];
+                    p16_second_product(O, ldsT, li, 32 * kt + 16 * s + 4 * lh, pf);
+                }
+        }
+        // D = sum_c dA_c a_c, a = O / l, with the fp16-rounded dA. O^T[c][query]: register 4 rq + x of tile ct = channel
+        // 32 ct + 8 rq + 4 lh + x -- not the channels of this lane's MFMA fragments, so those 32 values are read again
+        const float inv = 1.0f / l_run;
+        float dsum = 0.f;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const float4 d4 = *reinterpret_cast<const float4*>(darow + 32 * ct + 8 * rq + 4 * lh);
+                dsum += (float)(_Float16)d4.x * O[ct][4 * rq + 0] + (float)(_Float16)d4.y * O[ct][4 * rq + 1] +
+                        (float)(_Float16)d4.z * O[ct][4 * rq + 2] + (float)(_Float16)d4.w * O[ct][4 * rq + 3];
+            }
+        dsum += __shfl_xor(dsum, 32, 64);
+        Dq = dsum * inv;
+    }
+    const float lse = m_run + __logf(l_run);
+    if (query < N && lh == 0) {
+        float* st = stats + (((size_t)b * heads + hd) * N + query) * 2;
+        st[0] = lse; st[1] = Dq;
+    }
+    // ---------------- sweep 2: S^T = K . Q^T, dP^T = V . dA^T, dQ^T += K^T . dS^T
+    f32x16 dQ[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dQ[ct][r] = 0.f;
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        float4 kv[4], vv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int key = k0 + 4 * kq + i;
+            kv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            vv[i] = kv[i];
+            if (key < N) {
+                const float* rowp = base + (size_t)key * C3 + hd * 64 + 4 * cq;
+                kv[i] = *reinterpret_cast<const float4*>(rowp + C);
+                vv[i] = *reinterpret_cast<const float4*>(rowp + 2 * C);
+            }
+        }
+        __syncthreads();   // previous tile (or sweep 1's last) fully consumed
+        p16_stage_rows(ldsK, kq, cq, kv);
+        p16_stage_rows(ldsV, kq, cq, vv);
+        p16_stage_cols(ldsT, kq, cq, kv);
+        __syncthreads();
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+            f32x16 S, dP;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
+            const _Float16* krow = &ldsK[(32 * kt + li) * P16_RS + 8 * lh];
+            const _Float16* vrow = &ldsV[(32 * kt + li) * P16_RS + 8 * lh];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                S = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(krow + 16 * s), qf[s], S, 0, 0, 0);
+                dP = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(vrow + 16 * s), daf[s], dP, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const float pv = (key < N) ? __expf(S[r] - lse) : 0.f;
+                S[r] = pv * (dP[r] - Dq);            // dS^T
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                f16x8 dsf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dsf[j] = (_Float16)S[8 * s + j];
+                p16_second_product(dQ, ldsT, li, 32 * kt + 16 * s + 4 * lh, dsf);
+            }
+        }
+    }
+    if (query < N) {
+        float* orow = dqkv + ((size_t)b * N + query) * C3 + hd * 64;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                float4 v;
+                v.x = dQ[ct][4 * rq + 0] * 0.125f; v.y = dQ[ct][4 * rq + 1] * 0.125f;
+                v.z = dQ[ct][4 * rq + 2] * 0.125f; v.w = dQ[ct][4 * rq + 3] * 0.125f;
+                *reinterpret_cast<float4*>(orow + 32 * ct + 8 * rq + 4 * lh) = v;
+            }
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void attention_bwd_kv_p16_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
+                                                                      float* __restrict__ dqkv, const float* __restrict__ stats, int N, int C) {
+    __shared__ __attribute__((aligned(16))) _Float16 ldsQ[64 * P16_RS];    // (Q / 8) rows [query][channel]: A operand of S = Q . K^T
+    __shared__ __attribute__((aligned(16))) _Float16 ldsA[64 * P16_RS];    // dA rows: A operand of dP = dA . V^T
+    __shared__ __attribute__((aligned(16))) _Float16 ldsQt[64 * P16_TS];   // [channel][query] images: A operands of dK^T += (Q/8)^T dS
+    __shared__ __attribute__((aligned(16))) _Float16 ldsAt[64 * P16_TS];   //                          and dV^T += dA^T P
+    __shared__ float ldsL[64], ldsD[64];   // per query: m + log l, D
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const int heads = C >> 6;
+    const int nkb = (N + 127) >> 7;
+    int bid = blockIdx.x;
+    const int kb = bid % nkb;
+    bid /= nkb;
+    const int hd = bid % heads;
+    const int b = bid / heads;
+    const int C3 = 3 * C;
+    const float* base = qkv + (size_t)b * N * C3;
+    const int keyi = kb * 128 + wave * 32 + li;
+    const int krow = min(keyi, N - 1);
+    // fragments of this lane's key: k-step s = channels 16 s + 8 lh + {0..7}
+    f16x8 kf[4], vf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        kf[s] = p16_fragment(base + (size_t)krow * C3 + C + hd * 64 + 16 * s + 8 * lh, 1.0f);
+        vf[s] = p16_fragment(base + (size_t)krow * C3 + 2 * C + hd * 64 + 16 * s + 8 * lh, 1.0f);
+    }
+    f32x16 dK[2], dV[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { dK[ct][r] = 0.f; dV[ct][r] = 0.f; }
+    const float* st = stats + ((size_t)b * heads + hd) * N * 2;
+    const int cq = tid & 15, kq = tid >> 4;     // staging: this thread's 4 channels x 4 queries of the tile
+    for (int q0 = 0; q0 < N; q0 += 64) {
+        float4 qv[4], av[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int qq = q0 + 4 * kq + i;
+            qv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            av[i] = qv[i];
+            if (qq < N) {
+                qv[i] = *reinterpret_cast<const float4*>(base + (size_t)qq * C3 + hd * 64 + 4 * cq);
+                qv[i].x *= 0.125f; qv[i].y *= 0.125f; qv[i].z *= 0.125f; qv[i].w *= 0.125f;
+                av[i] = *reinterpret_cast<const float4*>(da + ((size_t)b * N + qq) * C + hd * 64 + 4 * cq);
+            }
+        }
+        float lq = INFINITY, dq_ = 0.f;      // exp(S - inf) = 0: queries past the end contribute nothing
+        if (tid < 64 && q0 + tid < N) {
+            lq = st[(size_t)(q0 + tid) * 2];
+            dq_ = st[(size_t)(q0 + tid) * 2 + 1];
+        }
+        __syncthreads();   // previous tile fully consumed
+        p16_stage_rows(ldsQ, kq, cq, qv);
+        p16_stage_rows(ldsA, kq, cq, av);
+        p16_stage_cols(ldsQt, kq, cq, qv);
+        p16_stage_cols(ldsAt, kq, cq, av);
+        if (tid < 64) { ldsL[tid] = lq; ldsD[tid] = dq_; }
+        __syncthreads();
+        // S[query][key] = (Q/8) . K^T and dP[query][key] = dA . V^T: queries in the accumulator registers, the key on the lane
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+            f32x16 S, dP;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
+            const _Float16* qrow = &ldsQ[(32 * qt + li) * P16_RS + 8 * lh];
+            const _Float16* arow = &ldsA[(32 * qt + li) * P16_RS + 8 * lh];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                S = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(qrow + 16 * s), kf[s], S, 0, 0, 0);
+                dP = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(arow + 16 * s), vf[s], dP, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qq = 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const float pv = __expf(S[r] - ldsL[qq]);
+                S[r] = pv;
+                dP[r] = pv * (dP[r] - ldsD[qq]);     // dS
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                f16x8 pf, dsf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { pf[j] = (_Float16)S[8 * s + j]; dsf[j] = (_Float16)dP[8 * s + j]; }
+                const int row0 = 32 * qt + 16 * s + 4 * lh;
+                p16_second_product(dV, ldsAt, li, row0, pf);
+                p16_second_product(dK, ldsQt, li, row0, dsf);
+            }
+        }
+    }
+    if (keyi < N) {
+        float* krow_o = dqkv + ((size_t)b * N + keyi) * C3 + C + hd * 64;
+        float* vrow_o = krow_o + C;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                *reinterpret_cast<float4*>(krow_o + 32 * ct + 8 * rq + 4 * lh) =
+                    make_float4(dK[ct][4 * rq + 0], dK[ct][4 * rq + 1], dK[ct][4 * rq + 2], dK[ct][4 * rq + 3]);
+                *reinterpret_cast<float4*>(vrow_o + 32 * ct + 8 * rq + 4 * lh) =
+                    make_float4(dV[ct][4 * rq + 0], dV[ct][4 * rq + 1], dV[ct][4 * rq + 2], dV[ct][4 * rq + 3]);
+            }
+    }
+}
+
+// stats: [B][heads][N][2] floats of scratch, as launch_attention_backward_flash
+void launch_attention_backward_p16(const float* qkv, const float* da, float* dqkv, float* stats, int B, int N, int C, hipStream_t stream) {
+    const int heads = C / 64;
+    const int nb = (N + 127) / 128;
+    hipLaunchKernelGGL(attention_bwd_q_p16_kernel, dim3((unsigned)(B * heads * nb)), dim3(256), 0, stream, qkv, da, dqkv, stats, N, C);
+    hipLaunchKernelGGL(attention_bwd_kv_p16_kernel, dim3((unsigned)(B * heads * nb)), dim3(256), 0, stream, qkv, da, dqkv, stats, N, C);
+}
+
 }  // namespace cddpm

@@ -268,6 +268,17 @@ int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const floa
     OP_EPILOGUE()
 }
 
+int cddpm_op_attention_backward_p16(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
+                                    void* stream) {
+    OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_backward_p16: C must be a multiple of 64")
+    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && da_dev && dqkv_dev, "cddpm_op_attention_backward_p16: NULL argument")
+    OpScratch sc(h, s);
+    float* stats = sc.n<float>((size_t)B * (C / 64) * N * 2);
+    SCRATCH_CHECK(sc)
+    launch_attention_backward_p16(qkv_dev, da_dev, dqkv_dev, stats, B, N, C, s);
+    OP_EPILOGUE()
+}
+
 int cddpm_op_linear_backward(cddpm_handle h, const float* x_dev, const float* w_dev, const float* dy_dev, int M, int N, int K,
                              int silu_in, float* dw_dev, float* db_dev, float* dx_dev, void* stream) {
     OP_PROLOGUE(PC_OTHER, 0.0, 0.0, M >= 1 && N >= 1 && K >= 1 && x_dev && w_dev && dy_dev && dw_dev, "cddpm_op_linear_backward: bad arguments")

@@ -206,6 +206,9 @@ void launch_bias_grad(const float* dy, long long npix, int C, float* db, double*
 // QKVAttention backward (attention.hip, flash-style): qkv [B][N][3C] (q | k | v), da [B][N][C] -> dqkv [B][N][3C];
 // stats = B * heads * N * 2 floats of scratch
 void launch_attention_backward_flash(const float* qkv, const float* da, float* dqkv, float* stats, int B, int N, int C, hipStream_t stream);
+// the same contract and scratch with plain fp16 operands (q / 8, k, v, dA, and P / dS as MFMA operands) and fp32 accumulators on
+// v_mfma_f32_32x32x16_f16: cddpm_op_attention_backward_p16, the backward of launch_attention_p16
+void launch_attention_backward_p16(const float* qkv, const float* da, float* dqkv, float* stats, int B, int N, int C, hipStream_t stream);
 // backward of y = [SiLU](x) W^T + b: x [M][K], W [N][K], dy [M][N] -> dW [N][K], db [N] (or nullptr), dx [M][K] (or nullptr);
 // a_scratch [M][K] when silu_in
 size_t linear_backward_scratch_floats(int M, int N, int K, int silu_in);      // floats of a_scratch

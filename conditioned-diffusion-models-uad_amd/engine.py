@@ -808,12 +808,14 @@ class CddpmEngine:
                                               _stream_ptr(self.device)), "cddpm_op_conv_wgrad")
         return dw, db
 
-    def op_attention_backward(self, qkv, da):
-        """dL/dqkv [B,N,3C] of the attention core for da = dL/d(output) [B,N,C]"""
+    def op_attention_backward(self, qkv, da, precision=32):
+        """dL/dqkv [B,N,3C] of the attention core for da = dL/d(output) [B,N,C]; precision 16: the fp16-MFMA kernels
+        (cddpm_op_attention_backward_p16, the backward of op_attention(..., precision=16)), whatever the engine's own"""
+        what = "cddpm_op_attention_backward_p16" if precision_bits(precision) == 16 else "cddpm_op_attention_backward"
+        fn = getattr(self.lib, what)
         B, N, C3 = qkv.shape
         dqkv = torch.empty_like(qkv)
-        self._ck(self.lib.cddpm_op_attention_backward(self._h, qkv.data_ptr(), da.data_ptr(), dqkv.data_ptr(), B, N, C3 // 3,
-                                                      _stream_ptr(self.device)), "cddpm_op_attention_backward")
+        self._ck(fn(self._h, qkv.data_ptr(), da.data_ptr(), dqkv.data_ptr(), B, N, C3 // 3, _stream_ptr(self.device)), what)
         return dqkv
 
     def op_linear_backward(self, x, w, dy, silu_in=False):

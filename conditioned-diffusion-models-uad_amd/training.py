@@ -17,7 +17,9 @@ scale is fixed by default; `UNetTrainer.enable_loss_scaling` makes it dynamic as
 skipped step, grown after `growth_interval` clean ones), with the scale kept on the device. `dropout` > 0 (the experiment's
 `dropout_unet`) applies nn.Dropout in front of every ResBlock's second convolution with a mask that is drawn on the device from counters
 and never stored (csrc/train_kernels.hip, synth.dropout_mask). `attention_resolutions` (the experiment's `att_res`) puts attention
-blocks inside the resolution levels as the reference's constructor does; they run on the middle block's operators. Measured: DESIGN.md
+blocks inside the resolution levels as the reference's constructor does; they run on the middle block's operators. The attention cores
+are exact fp32 at either convolution precision unless the trainer is built with `attention_precision=16` (the mirrors'
+`cfg.train_attention_precision`): then forward and backward run the fp16-MFMA kernels, the arithmetic of autocast. Measured: DESIGN.md
 section 4b.
 """
 from __future__ import annotations
@@ -30,7 +32,7 @@ import torch
 
 from . import schedule as _schedule
 from . import synth as _synth
-from .engine import CddpmEngine, _stream_ptr, check_boxes
+from .engine import CddpmEngine, _stream_ptr, check_boxes, precision_bits
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -206,8 +208,12 @@ class UNetTrainer:
 
     def __init__(self, params: Dict[str, torch.Tensor], *, model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3,
                  cond_dim=128, device=None, exp_refresh=50, overlap_wgrad=None, dropout=0.0, dropout_seed=None,
-                 attention_resolutions=(3, 6, 12)):
+                 attention_resolutions=(3, 6, 12), attention_precision=32):
         self.dev = torch.device(device) if device is not None else next(iter(params.values())).device
+        # arithmetic of every attention core of the program, middle and in-level, forward and backward: 32 = the exact-fp32 kernels;
+        # 16 (the spellings of engine.precision_bits) = cddpm_op_attention_p16 / cddpm_op_attention_backward_p16, what fp16 autocast
+        # over QKVAttention computes. Per trainer, independent of the process-wide convolution precision (set_precision).
+        self.attention_precision = precision_bits(attention_precision)
         self._cfg = dict(model_channels=model_channels, channel_mult=tuple(channel_mult), num_res_blocks=num_res_blocks, cond_dim=cond_dim)
         self.C, self.mult, self.nres, self.cond_dim = model_channels, tuple(channel_mult), num_res_blocks, cond_dim
         self.att_res = tuple(int(a) for a in attention_resolutions)      # the model's: attention behind the ResBlocks of the levels it names
@@ -625,7 +631,8 @@ class UNetTrainer:
                 coefn = self.gn_coef(cur, None, name + ".norm")
                 qkv = self.conv(name + ".qkv", cur, None, coefn, False, stats=False)
                 att = self._new(Bc, h_, w_, Cc)
-                self._ck(self.lib.cddpm_op_attention(self.h, _p(qkv), _p(att), Bc, h_ * w_, Cc, self._s()), "op_attention")
+                attn = self.lib.cddpm_op_attention_p16 if self.attention_precision == 16 else self.lib.cddpm_op_attention
+                self._ck(attn(self.h, _p(qkv), _p(att), Bc, h_ * w_, Cc, self._s()), "op_attention")
                 out = self.conv(name + ".proj_out", att, res=cur)
                 sv[name] = dict(x=cur, coefn=coefn, qkv=qkv, att=att, rec=self.rec_of(cur))
                 cur = out
@@ -680,8 +687,8 @@ class UNetTrainer:
                 da = self.dgrad(name + ".proj_out", d)
                 Bc, h_, w_, Cc = r["x"].shape
                 dqkv = torch.empty_like(r["qkv"])
-                self._ck(self.lib.cddpm_op_attention_backward(self.h, _p(r["qkv"]), _p(da), _p(dqkv), Bc, h_ * w_, Cc, self._s()),
-                         "op_attention_backward")
+                attn_bwd = self.lib.cddpm_op_attention_backward_p16 if self.attention_precision == 16 else self.lib.cddpm_op_attention_backward
+                self._ck(attn_bwd(self.h, _p(r["qkv"]), _p(da), _p(dqkv), Bc, h_ * w_, Cc, self._s()), "op_attention_backward")
                 self.wgrad(name + ".qkv", r["x"], None, r["coefn"], False, dqkv)
                 dn = self.dgrad(name + ".qkv", dqkv)
                 d, _ = self.gn_bwd(r["x"], dn, name + ".norm", None, False, rec=r["rec"], add=d)       # + the residual path x + h

@@ -421,6 +421,18 @@ int cddpm_op_bias_grad(cddpm_handle h, const float* dy_dev, int64_t npix, int C,
  * timed only. */
 int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
                                 void* stream);
+/* the same contract (arguments, scratch, errors, profiling class 2) in the arithmetic of fp16 autocast over QKVAttention.forward and
+ * its backward, the backward of cddpm_op_attention_p16: q / 8, k, v and da are rounded to fp16 (RNE, gradual underflow) once; every
+ * product runs on v_mfma_f32_32x32x16_f16 with fp32 accumulators (S, dP, dq, dk, dv); the running max / sum, P = exp(S - lse),
+ * D_i = sum_c da_ic a_ic (rounded da, fp32 a) and dS = P (dP - D) are fp32; P and dS are rounded to fp16 only as MFMA operands; dqkv is
+ * fp32. Range: |da| >= 65504 rounds to +-inf as under autocast and makes that sample's dqkv non-finite (what the training step's device
+ * guard and the dynamic loss scale catch: da carries the loss scale), never a finite wrong number; other samples are unaffected.
+ * Tested against float64 autograd by the rule of tests/precision16_cases.py (no further from it than torch's fp16 autocast is):
+ * C = 64, 128, 256, N = 15 ... 1536, multiples of neither the 128-row workgroup nor the 64-row tile included (N = 130, 240;
+ * tests/test_gpu_attention_backward_p16.py). Expected to hold as for cddpm_op_attention_backward: tails are masked and every row
+ * offset is formed in 64 bits; N = 16384 (B 4, C 128) has been run and timed only. */
+int cddpm_op_attention_backward_p16(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
+                                    void* stream);
 /* backward of torch.nn.Linear behind an optional SiLU, y = [SiLU](x) W^T + b (emb_layers / time_embed / label_emb,
  * OpenAI_Unet.py:201-207, :583-602): x_dev [M,K], w_dev [N,K], dy_dev [M,N] -> dw_dev [N,K], db_dev [N] (may be NULL), dx_dev [M,K]
  * (may be NULL). */
@@ -500,7 +512,10 @@ int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev
  * bit-identical to the fixed-scale calls with grad_scale = S and grad_unscale = extra_unscale / S. */
 /* Arithmetic of the training operators, process-wide: 32 (default) = fp32-grade products from two-term fp16 splits; 16 = plain fp16
  * operands with fp32 accumulation in cddpm_op_conv_packed and cddpm_op_conv_wgrad -- what the reference trainer's `precision: 16`
- * (configs/trainer/default.yaml:7) computes under autocast; GroupNorm, attention, embeddings, Adam and the master weights stay fp32 in both.
+ * (configs/trainer/default.yaml:7) computes under autocast; GroupNorm, embeddings, Adam and the master weights stay fp32 in both, and so
+ * does attention unless the trainer asks otherwise: the training step calls cddpm_op_attention / cddpm_op_attention_backward at either
+ * value, and cddpm_op_attention_p16 / cddpm_op_attention_backward_p16 only where its caller selects them (UNetTrainer's
+ * attention_precision=16), independently of this setting.
  * Precision 16 rounds each operand to fp16 to nearest even with gradual underflow, as torch's .half(): measured on gfx950, the 16-bit
  * MFMA inputs keep fp16 subnormals (|x| < 2^-14 is carried to 2^-25, not flushed), in both operators and on either operand
  * (tests/test_gpu_train_ops_edges.py::test_precision16_keeps_fp16_subnormals).

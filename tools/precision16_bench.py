@@ -5,6 +5,7 @@ geometry, alternating per repeat, HIP events around the work on the launch strea
     forward    one UNet forward at 4 x 96 x 96 (a window of --inner forwards per repeat, reported per forward)
     attention  cddpm_op_attention against cddpm_op_attention_p16 at (B, N, C) = (64, 1024, 256) and (4, 16384, 128)
                (a window of --inner launches per repeat, reported per launch)
+    attention_backward  cddpm_op_attention_backward against cddpm_op_attention_backward_p16 at the same two shapes, same protocol
 
 The experiment's descriptor (128 x (1, 2, 2), three ResBlocks, attention in the middle block), synthetic weights. Per item and
 precision: median, minimum and maximum over --reps repeats (at least 10) after a warm-up, and whether the two ranges overlap. Also
@@ -147,6 +148,24 @@ def main():
         rows.append(row)
         print(json.dumps(row), flush=True)
     result["attention"] = rows
+
+    # ---- their backward operators: 9 N x N x 64 products per head executed (the forward's 2 recomputed + 7)
+    rows = []
+    for (B, N, C) in ((64, 1024, 256), (4, 16384, 128)):
+        g = torch.Generator().manual_seed(N + C)
+        qkv = torch.randn(B, N, 3 * C, generator=g).cuda()
+        da = torch.randn(B, N, C, generator=g).cuda()
+
+        def att_bwd(bits):
+            for _ in range(a.inner):
+                e.op_attention_backward(qkv, da, precision=bits)
+        row = verdict(dict(B=B, N=N, C=C, unit="ms per call (two kernels)", flops=18.0 * B * N * N * C,
+                           **compare({"fp32": lambda: att_bwd(32), "p16": lambda: att_bwd(16)}, a.reps, scale=1.0 / a.inner)), "fp32", "p16")
+        for k in ("fp32", "p16"):
+            row[k]["tflops"] = row["flops"] / (row[k]["median_ms"] * 1e-3) / 1e12
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    result["attention_backward"] = rows
     for e in eng.values():
         e.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -1,9 +1,13 @@
 """Worst / median relative error of the training step's gradients against float64 autograd through the oracle, as JSON (one process per
 arithmetic: the families are chosen once per process from the environment, e.g. CDDPM_TRAIN_PRECISION=16).
-usage: python tools/train_grad_check.py [B H W [DESCRIPTOR]]
+usage: python tools/train_grad_check.py [--attention-precision 16|32] [--gradient NAME] [B H W [DESCRIPTOR]]
+--attention-precision: UNetTrainer's attention_precision (16: the fp16-MFMA attention forward and backward; default 32).
+--gradient NAME: also report "gradient_sha256", the digest of that parameter's gradient bits (to tell two arithmetics apart).
 DESCRIPTOR: a JSON object {"model_channels":, "channel_mult":, "num_res_blocks":, "cond_dim":, "attention_resolutions":} of another UNet
 than the experiment's (cond_dim 0: unconditioned; attention_resolutions absent: the experiment's (3, 6, 12), attention in the middle
 block only)"""
+import argparse
+import hashlib
 import importlib
 import json
 import os
@@ -18,6 +22,12 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 PKG = "conditioned-diffusion-models-uad_amd"
 import cddpm_oracle as oracle  # noqa: E402  (test infrastructure: this tool is a checker, not product code)
 
+_ap = argparse.ArgumentParser()
+_ap.add_argument("--attention-precision", default="32")
+_ap.add_argument("--gradient", default=None)
+_ap.add_argument("rest", nargs="*")
+_a = _ap.parse_args()
+sys.argv[1:] = _a.rest
 B, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (2, 32, 32)
 tr, synth, sched = (importlib.import_module(PKG + "." + m) for m in ("training", "synth", "schedule"))
 T = 1000
@@ -35,7 +45,8 @@ buf64 = oracle.to_float64(oracle.schedule_buffers(T))
 x0 = x01 * 2 - 1
 ref_out = oracle.unet_forward(oracle.q_sample(x0.double(), t, noise.double(), buf64), t, cond.double() if cond_dim else None, sd, **arch)
 dev = torch.device("cuda", 0)
-trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd_np.items()}, device=dev, cond_dim=cond_dim or None, **arch)
+trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd_np.items()}, device=dev, cond_dim=cond_dim or None,
+                         attention_precision=_a.attention_precision, **arch)
 buf = sched.schedule_buffers(T)
 xt = buf["sqrt_alphas_cumprod"][t].reshape(-1, 1, 1, 1) * x0 + buf["sqrt_one_minus_alphas_cumprod"][t].reshape(-1, 1, 1, 1) * noise
 out = trainer.forward(xt.to(dev), t.to(dev), cond.to(dev) if cond_dim else None)
@@ -48,5 +59,8 @@ errs = []
 for k, v in sd.items():
     g = grads[k].double().cpu().reshape(v.grad.shape) / S
     errs.append(float((g - v.grad).abs().max() / (v.grad.abs().max() + 1e-30)))
-print(json.dumps({"forward_max_abs_err": float((out.double().cpu() - ref_out.detach()).abs().max()), "worst": max(errs), "median": float(np.median(errs)),
-                  "finite": bool(np.isfinite(errs).all()), "n": len(errs)}))
+res = {"forward_max_abs_err": float((out.double().cpu() - ref_out.detach()).abs().max()), "worst": max(errs), "median": float(np.median(errs)),
+       "finite": bool(np.isfinite(errs).all()), "n": len(errs), "attention_precision": trainer.attention_precision}
+if _a.gradient:
+    res["gradient_sha256"] = hashlib.sha256(grads[_a.gradient].detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+print(json.dumps(res))

@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--attention-resolutions", default=None, metavar="DS[,DS...]",
                     help="down-sampling factors whose levels get attention behind every ResBlock (cfg.att_res), e.g. 1,2,4; default: the "
                          "experiment's 3,6,12 = attention in the middle block only")
+    ap.add_argument("--attention-precision", default="32",
+                    help="UNetTrainer's attention_precision: 16 = the fp16-MFMA attention forward and backward, 32 (default) = exact fp32")
     ap.add_argument("--phases", action="store_true", help="time forward / backward / adam separately (synchronises between them)")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without RANK in the environment: start the N ranks (torchrun child) and relay rank 0's line")
     a = ap.parse_args()
@@ -45,7 +47,8 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
     arch = {} if a.attention_resolutions is None else {"attention_resolutions": tuple(int(v) for v in a.attention_resolutions.split(","))}
     sd = synth.synth_state_dict(0, **arch)
-    trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd.items()}, device=dev, dropout=a.dropout, dropout_seed=1, **arch)
+    trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd.items()}, device=dev, dropout=a.dropout, dropout_seed=1,
+                             attention_precision=a.attention_precision, **arch)
     enc = None
     if a.encoder:
         et = importlib.import_module(PKG + ".encoder_training")
@@ -74,7 +77,7 @@ def main():
     bits = tr.get_precision()
     arith = "fp32-emulated convolutions" if bits == 32 else "fp16-operand convolutions (precision 16)"
     res = {"workload": f"training step {B}x1x{S}x{S} (noise-pred MSE, {arith}, Adam" + (", context encoder trained jointly)" if enc else ")"), "ms_per_step": dt * 1e3,
-           "precision": bits, "dropout": a.dropout, "attention_resolutions": list(trainer.att_res),
+           "precision": bits, "dropout": a.dropout, "attention_resolutions": list(trainer.att_res), "attention_precision": trainer.attention_precision,
            "slices_per_s": world * B / dt, "n_gpus": world, "losses": losses, "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
     if a.phases:
         buf = importlib.import_module(PKG + ".schedule").schedule_buffers(T)
