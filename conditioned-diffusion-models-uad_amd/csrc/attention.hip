@@ -1,147 +1,317 @@
-// Mid-block self-attention core for gfx950: softmax(q k^T / sqrt(d)) v, d = 64, exact fp32 on
-// v_mfma_f32_32x32x2_f32, flash-style (the N x N score matrix never leaves registers).
+// Self-attention core for gfx950: softmax(q k^T / sqrt(d)) v, d = 64, flash-style (the N x N score matrix never leaves registers),
+// forward and backward, in two arithmetics: exact fp32 on v_mfma_f32_32x32x2_f32 and plain fp16 operands on v_mfma_f32_32x32x16_f16.
 //
 // Replaces QKVAttention.forward (src/models/modules/OpenAI_Unet.py:457-476): q,k,v = chunk(qkv, 3);
 // heads are contiguous groups of 64 channels; w = softmax_fp32((q s)^T (k s)), s = 64^-1/4; a = w v^T.
 // The two s factors are applied as one exact 2^-3 scale of q.
 //
-// Work split: workgroup = (sample, head, 128 queries); wave = 32 queries; key tiles of 64 through LDS.
-//   S^T[key][query] = K . Q^T   : keys land in the 16 accumulator registers, the query on the lane, so the
-//                                 softmax row reduction is 32 in-lane values + one exchange with lane^32.
-//   O^T[c][query]  += V^T . P^T : the S^T accumulator IS the B operand (same lane = same query, register r of
-//                                 lane-half h = key (r&3) + 8 (r>>2) + 4 h), no LDS round trip; the matching A
-//                                 operand V[key(r,h)][c] is a conflict-free ds_read_b32 across 32 channels.
+// Six kernels behind four launchers; what they share exists once, as __device__ functions: the workgroup decode, the row store,
+// the online-softmax tile step, per arithmetic the stage / first-product / second-product pieces, and per arithmetic the forward
+// sweep over the key tiles, which is the forward kernel's body and sweep 1 of the bwd_q kernel. MFMA accumulators go through these
+// helpers by value and come back in small structs, and the two sub-tiles of a tile are a two-element array walked by an unrolled
+// loop: the same code with f32x16 (&)[2] parameters, or with the two sub-tiles spelled out as two calls, costs attention_kernel and
+// attention_p16_kernel a wave per SIMD (161 -> 186 / 171 and 127 -> 140 VGPRs) at unchanged instruction counts.
 #include "kernels.h"
 #include "conv_split.h"      // f32x16, f16x8, f16x4
 
 namespace cddpm {
+namespace {
+
+// Work split: workgroup = (sample, head, block of 128 rows); wave = 32 rows, one per lane li of lane-half lh; the other side of the
+// N x N matrix comes in tiles of 64 rows through LDS. The rows are queries in the forward and the bwd_q kernels, keys in bwd_kv.
+struct Wg {
+    int tid, li, lh;
+    int heads, hd, b, C3;
+    int row;             // this lane's query / key; past the end in the last block's tail (loads clamp it, stores skip it)
+    const float* base;   // qkv of sample b, [N][3C]
+};
+__device__ __forceinline__ Wg wg_decode(const float* qkv, int N, int C) {
+    Wg w;
+    w.tid = threadIdx.x;
+    const int lane = w.tid & 63, wave = w.tid >> 6;
+    w.li = lane & 31;
+    w.lh = lane >> 5;
+    w.heads = C >> 6;
+    const int nblk = (N + 127) >> 7;
+    int bid = blockIdx.x;
+    const int blk = bid % nblk;
+    bid /= nblk;
+    w.hd = bid % w.heads;
+    w.b = bid / w.heads;
+    w.C3 = 3 * C;
+    w.base = qkv + (size_t)w.b * N * w.C3;
+    w.row = blk * 128 + wave * 32 + w.li;
+    return w;
+}
+
+// A [64 channels][32 rows] fp32 accumulator (O^T, dQ^T, dK^T, dV^T): channel tiles 0 and 1, the row on the lane.
+struct Acc2 { f32x16 t[2]; };
+
+// An accumulator as 64 channels of its lane's global row: register 4 rq + x of tile ct = channel 32 ct + 8 rq + 4 lh + x.
+__device__ __forceinline__ void store_row(float* row, Acc2 acc, int lh) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq)
+            *reinterpret_cast<float4*>(row + 32 * ct + 8 * rq + 4 * lh) =
+                make_float4(acc.t[ct][4 * rq + 0], acc.t[ct][4 * rq + 1], acc.t[ct][4 * rq + 2], acc.t[ct][4 * rq + 3]);
+}
+__device__ __forceinline__ void store_row(float* row, Acc2 acc, float scale, int lh) {
+    acc.t[0] *= scale;
+    acc.t[1] *= scale;
+    store_row(row, acc, lh);
+}
+
+// Online softmax over one 64-key tile of S^T (keys k0 .. k0 + 63 in the registers of S0, S1; register r of lane-half h = key
+// (r & 3) + 8 (r >> 2) + 4 h of its 32-key sub-tile), fp32 VALU in both arithmetics: keys past N are masked, the row reduction is
+// 32 in-lane values + one exchange with lane^32. The caller folds alpha and psum into its running sum and rescales O by alpha.
+struct SoftmaxTile { f32x16 P[2]; float m_new, alpha, psum; };
+__device__ __forceinline__ SoftmaxTile softmax_tile(f32x16 S0, f32x16 S1, float m_run, int k0, int N, int lh) {
+    f32x16 P[2] = {S0, S1};
+    float psum = 0.f;
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (key >= N) P[kt][r] = -INFINITY;
+            tmax = fmaxf(tmax, P[kt][r]);
+        }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(m_run, tmax);
+    const float alpha = __expf(m_run - m_new);
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float p = __expf(P[kt][r] - m_new);
+            P[kt][r] = p;
+            psum += p;
+        }
+    psum += __shfl_xor(psum, 32, 64);
+    return SoftmaxTile{{P[0], P[1]}, m_new, alpha, psum};
+}
+
+// What a forward sweep leaves per query: O^T (not yet divided by l), the running max and the running sum.
+struct Sweep { Acc2 O; float m, l; };
+
+// ------------------------------------------------------------------------------------------------------------------
+// Exact fp32 on v_mfma_f32_32x32x2_f32.
+//   first product  S^T[key][query] = K . Q^T   : keys land in the 16 accumulator registers, the query on the lane.
+//   second product O^T[c][query]  += V^T . P^T : the S^T accumulator IS the B operand (same lane = same query, register r of
+//                                 lane-half h = key (r&3) + 8 (r>>2) + 4 h), no LDS round trip; the matching A
+//                                 operand V[key(r,h)][c] is a conflict-free ds_read_b32 across 32 channels.
+// The backward's products have the same two shapes with other matrices in the roles of K, Q, V and P.
+// ------------------------------------------------------------------------------------------------------------------
+
+// This lane's B operand of a first product: channels 8 g + 4 lh + {0..3} of a global row, EIGHTH: scaled by the exact 2^-3.
+template <bool EIGHTH>
+__device__ __forceinline__ void f32_fragment(float4 (&f)[8], const float* row, int lh) {
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        float4 v = *reinterpret_cast<const float4*>(row + 8 * g + 4 * lh);
+        if (EIGHTH) { v.x *= 0.125f; v.y *= 0.125f; v.z *= 0.125f; v.w *= 0.125f; }
+        f[g] = v;
+    }
+}
+
+// Stage rows r0 .. r0 + 63 (zero past N) of two matrices, 64 channels from pa / pb with row strides sa / sb, 256 threads x 4 float4
+// each: into a swizzled image [row][slot ^ (row & 15)] (A operand of a first product) and / or a plain image [row][64] (A operand of
+// a second product). A null image is skipped. EIGHTH_A: matrix a is scaled by the exact 2^-3.
+template <bool EIGHTH_A>
+__device__ __forceinline__ void f32_stage(int tid, int r0, int N, const float* pa, int sa, const float* pb, int sb,
+                                          float4* swz_a, float* plain_a, float4* swz_b, float* plain_b) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = tid + 256 * i;
+        const int row = e >> 4, slot = e & 15;
+        float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
+        if (r0 + row < N) {
+            av = *reinterpret_cast<const float4*>(pa + (size_t)(r0 + row) * sa + 4 * slot);
+            if (EIGHTH_A) { av.x *= 0.125f; av.y *= 0.125f; av.z *= 0.125f; av.w *= 0.125f; }
+            bv = *reinterpret_cast<const float4*>(pb + (size_t)(r0 + row) * sb + 4 * slot);
+        }
+        if (swz_a) swz_a[row * 16 + (slot ^ (row & 15))] = av;
+        if (swz_b) swz_b[row * 16 + (slot ^ (row & 15))] = bv;
+        if (plain_a) *reinterpret_cast<float4*>(&plain_a[row * 64 + 4 * slot]) = av;
+        if (plain_b) *reinterpret_cast<float4*>(&plain_b[row * 64 + 4 * slot]) = bv;
+    }
+}
+
+// swizzled image[row][64 channels] . frag: one 32 x 32 tile, image row `row` (32 sub + li) in this lane's A operand
+__device__ __forceinline__ f32x16 f32_first_product(const float4* swz, int row, int lh, const float4 (&frag)[8]) {
+    f32x16 acc = {};
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        const float4 a = swz[row * 16 + ((2 * g + lh) ^ (row & 15))];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, frag[g].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, frag[g].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, frag[g].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, frag[g].w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// acc += plain image[row][channels 32 ct + li] x bv for both channel tiles: one register's step of a second product
+__device__ __forceinline__ Acc2 f32_second_step(Acc2 acc, const float* plain, int row, int li, float bv) {
+    const float a0 = plain[row * 64 + li];
+    const float a1 = plain[row * 64 + 32 + li];
+    acc.t[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc.t[0], 0, 0, 0);
+    acc.t[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, acc.t[1], 0, 0, 0);
+    return acc;
+}
+// acc += image^T . bf over the 32 rows of a sub-tile whose first-product accumulator is bf; row0 = 32 sub + 4 lh
+__device__ __forceinline__ Acc2 f32_second_product(Acc2 acc, const float* plain, int li, int row0, f32x16 bf) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc = f32_second_step(acc, plain, row0 + (r & 3) + 8 * (r >> 2), li, bf[r]);
+    return acc;
+}
+
+// The forward over all key tiles for this lane's query (fragment qreg, pre-scaled by 1/8). ldsK: swizzled K tile, ldsV: plain V tile.
+__device__ __forceinline__ Sweep f32_forward_sweep(const Wg& w, const float4 (&qreg)[8], float4* ldsK, float* ldsV, int N, int C) {
+    const float* kp = w.base + C + w.hd * 64;
+    Sweep f = {{}, -INFINITY, 0.f};
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        __syncthreads();   // previous tile fully consumed
+        f32_stage<false>(w.tid, k0, N, kp, w.C3, kp + C, w.C3, ldsK, nullptr, nullptr, ldsV);
+        __syncthreads();
+        f32x16 S[2];
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) S[kt] = f32_first_product(ldsK, 32 * kt + w.li, w.lh, qreg);
+        const SoftmaxTile t = softmax_tile(S[0], S[1], f.m, k0, N, w.lh);
+        f.l = f.l * t.alpha + t.psum;
+        f.m = t.m_new;
+        f.O.t[0] *= t.alpha;
+        f.O.t[1] *= t.alpha;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) f.O = f32_second_product(f.O, ldsV, w.li, 32 * kt + 4 * w.lh, t.P[kt]);
+    }
+    return f;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Plain fp16 operands on v_mfma_f32_32x32x16_f16: the arithmetic of the reference under `precision: 16` (fp16 autocast over
+// QKVAttention.forward, OpenAI_Unet.py:457-476, and its backward) with fp32 accumulators.
+//   q (scaled by the exact 2^-3), k, v and dA are rounded to fp16 (RNE, gradual underflow) once, where they are staged; every product
+//   accumulates in fp32; the softmax, D and dS stay fp32 VALU work; P and dS are rounded to fp16 only as MFMA operands; outputs are fp32.
+//   first product  S^T[key][query] = K . Q^T   : 4 k-steps of 16 channels per 32-key sub-tile; A = a K row's 8 channels (ds_read_b128 of
+//                                 the row image [key][channel], rows padded to 144 B: 16 consecutive rows cover the 16 four-bank
+//                                 groups), B = the query's 8 channels, in registers for the whole kernel.
+//   second product O^T[c][query]  += V^T . P^T : registers 8s .. 8s+7 of the S^T accumulator, rounded to fp16, ARE the B operand of
+//                                 k-step s: element j of lane-half h is key 16 s + 8 (j >> 2) + 4 h + (j & 3). The A operand is
+//                                 V^T[c][those keys]: two 8-byte reads of the transposed image [channel][key] (rows padded to 136 B:
+//                                 32 consecutive rows cover the 32 bank pairs), which the staging threads write as 4-key columns.
+// One 64-key tile of the forward costs a wave 16 MFMAs of 32 cycles instead of 128 of 64.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int P16_RS = 72;   // fp16 elements of a row-image row (64 channels + 16 B)
+constexpr int P16_TS = 68;   // fp16 elements of a transposed-image row (64 rows + 8 B)
+
+__device__ __forceinline__ f16x4 p16_round4(float x, float y, float z, float w) {
+    return f16x4{(_Float16)x, (_Float16)y, (_Float16)z, (_Float16)w};
+}
+// 8 channels of a global row as one fp16 MFMA fragment, scaled by `scale` before rounding
+__device__ __forceinline__ f16x8 p16_fragment(const float* p, float scale) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    const float4 c = *reinterpret_cast<const float4*>(p + 4);
+    return f16x8{(_Float16)(a.x * scale), (_Float16)(a.y * scale), (_Float16)(a.z * scale), (_Float16)(a.w * scale),
+                 (_Float16)(c.x * scale), (_Float16)(c.y * scale), (_Float16)(c.z * scale), (_Float16)(c.w * scale)};
+}
+// this staging thread's 4 rows x 4 channels (rows r0 + 4 kq + i, zero past N; channels 4 cq + {0..3}) of two matrices, from pa / pb
+// with row strides sa / sb. EIGHTH_A: matrix a is scaled by the exact 2^-3.
+template <bool EIGHTH_A>
+__device__ __forceinline__ void p16_gather(float4 (&av)[4], float4 (&bv)[4], const float* pa, int sa, const float* pb, int sb,
+                                           int r0, int N, int kq, int cq) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = r0 + 4 * kq + i;
+        av[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        bv[i] = av[i];
+        if (row < N) {
+            av[i] = *reinterpret_cast<const float4*>(pa + (size_t)row * sa + 4 * cq);
+            if (EIGHTH_A) { av[i].x *= 0.125f; av[i].y *= 0.125f; av[i].z *= 0.125f; av[i].w *= 0.125f; }
+            bv[i] = *reinterpret_cast<const float4*>(pb + (size_t)row * sb + 4 * cq);
+        }
+    }
+}
+// ... rounded into a row image / a transposed image
+__device__ __forceinline__ void p16_stage_rows(_Float16* img, int kq, int cq, const float4 (&v)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<f16x4*>(&img[(4 * kq + i) * P16_RS + 4 * cq]) = p16_round4(v[i].x, v[i].y, v[i].z, v[i].w);
+}
+__device__ __forceinline__ void p16_stage_cols(_Float16* img, int kq, int cq, const float4 (&v)[4]) {
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 0) * P16_TS + 4 * kq]) = p16_round4(v[0].x, v[1].x, v[2].x, v[3].x);
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 1) * P16_TS + 4 * kq]) = p16_round4(v[0].y, v[1].y, v[2].y, v[3].y);
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 2) * P16_TS + 4 * kq]) = p16_round4(v[0].z, v[1].z, v[2].z, v[3].z);
+    *reinterpret_cast<f16x4*>(&img[(4 * cq + 3) * P16_TS + 4 * kq]) = p16_round4(v[0].w, v[1].w, v[2].w, v[3].w);
+}
+// row image[row][64 channels] . frag: one 32 x 32 tile, image row `row` (32 sub + li) in this lane's A operand
+__device__ __forceinline__ f32x16 p16_first_product(const _Float16* rimg, int row, int lh, const f16x8 (&frag)[4]) {
+    f32x16 acc = {};
+    const _Float16* rp = &rimg[row * P16_RS + 8 * lh];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(rp + 16 * s), frag[s], acc, 0, 0, 0);
+    return acc;
+}
+// registers 8s .. 8s+7 of a first product's accumulator as the B operand of k-step s of the second
+__device__ __forceinline__ f16x8 p16_operand(f32x16 acc, int s) {
+    f16x8 bf;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bf[j] = (_Float16)acc[8 * s + j];
+    return bf;
+}
+// acc[ct] += T^T-image[channel 32 ct + li][rows row0 + {0..3}, row0 + 8 + {0..3}] . bf for both channel tiles; row0 = 32 sub + 16 s + 4 lh
+__device__ __forceinline__ Acc2 p16_second_product(Acc2 acc, const _Float16* timg, int li, int row0, f16x8 bf) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+        const _Float16* tp = &timg[(32 * ct + li) * P16_TS + row0];
+        const f16x4 lo = *reinterpret_cast<const f16x4*>(tp);
+        const f16x4 hi = *reinterpret_cast<const f16x4*>(tp + 8);
+        acc.t[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7), bf, acc.t[ct], 0, 0, 0);
+    }
+    return acc;
+}
+
+// The forward over all key tiles for this lane's query (fragments qf, pre-scaled by 1/8). ldsK: K row image, ldsVt: V^T image.
+__device__ __forceinline__ Sweep p16_forward_sweep(const Wg& w, const f16x8 (&qf)[4], _Float16* ldsK, _Float16* ldsVt, int N, int C) {
+    const int cq = w.tid & 15, kq = w.tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
+    const float* kp = w.base + C + w.hd * 64;
+    Sweep f = {{}, -INFINITY, 0.f};
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        float4 kv[4], vv[4];
+        p16_gather<false>(kv, vv, kp, w.C3, kp + C, w.C3, k0, N, kq, cq);
+        __syncthreads();   // previous tile fully consumed
+        p16_stage_rows(ldsK, kq, cq, kv);
+        p16_stage_cols(ldsVt, kq, cq, vv);
+        __syncthreads();
+        f32x16 S[2];
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) S[kt] = p16_first_product(ldsK, 32 * kt + w.li, w.lh, qf);
+        const SoftmaxTile t = softmax_tile(S[0], S[1], f.m, k0, N, w.lh);
+        f.l = f.l * t.alpha + t.psum;
+        f.m = t.m_new;
+        f.O.t[0] *= t.alpha;
+        f.O.t[1] *= t.alpha;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) f.O = p16_second_product(f.O, ldsVt, w.li, 32 * kt + 16 * s + 4 * w.lh, p16_operand(t.P[kt], s));
+    }
+    return f;
+}
+}  // namespace
 
 __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                            int N, int C) {
     __shared__ float4 ldsK[64 * 16];   // [key][slot ^ (key & 15)]
     __shared__ float ldsV[64 * 64];    // [key][channel]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int heads = C >> 6;
-    const int nqb = (N + 127) >> 7;
-    int bid = blockIdx.x;
-    const int qb = bid % nqb;
-    bid /= nqb;
-    const int hd = bid % heads;
-    const int b = bid / heads;
-    const int C3 = 3 * C;
-    const float* base = qkv + (size_t)b * N * C3;
-
-    // Q fragment of this lane's query: channels 8g + 4 lh + {0..3}, pre-scaled by 1/8
-    const int query = qb * 128 + wave * 32 + li;
-    const int qrow = min(query, N - 1);
+    const Wg w = wg_decode(qkv, N, C);
     float4 qreg[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        float4 v = *reinterpret_cast<const float4*>(base + (size_t)qrow * C3 + hd * 64 + 8 * g + 4 * lh);
-        v.x *= 0.125f; v.y *= 0.125f; v.z *= 0.125f; v.w *= 0.125f;
-        qreg[g] = v;
-    }
-
-    f32x16 O[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) O[ct][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    for (int k0 = 0; k0 < N; k0 += 64) {
-        __syncthreads();   // previous tile fully consumed
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + 256 * i;
-            const int key = e >> 4, slot = e & 15;
-            float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-            if (k0 + key < N) {
-                const float* rowp = base + (size_t)(k0 + key) * C3 + hd * 64 + 4 * slot;
-                kv = *reinterpret_cast<const float4*>(rowp + C);
-                vv = *reinterpret_cast<const float4*>(rowp + 2 * C);
-            }
-            ldsK[key * 16 + (slot ^ (key & 15))] = kv;
-            *reinterpret_cast<float4*>(&ldsV[key * 64 + 4 * slot]) = vv;
-        }
-        __syncthreads();
-
-        // ---- S^T = K . Q^T for 2 sub-tiles of 32 keys
-        f32x16 S[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) S[kt][r] = 0.f;
-            const int row = 32 * kt + li;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const float4 kf = ldsK[row * 16 + ((2 * g + lh) ^ (row & 15))];
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qreg[g].x, S[kt], 0, 0, 0);
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qreg[g].y, S[kt], 0, 0, 0);
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qreg[g].z, S[kt], 0, 0, 0);
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qreg[g].w, S[kt], 0, 0, 0);
-            }
-        }
-
-        // ---- online softmax over keys (registers + lane^32)
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (key >= N) S[kt][r] = -INFINITY;
-                tmax = fmaxf(tmax, S[kt][r]);
-            }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = __expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __expf(S[kt][r] - m_new);
-                S[kt][r] = p;
-                psum += p;
-            }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) O[ct][r] *= alpha;
-
-        // ---- O^T += V^T . P^T
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const float v0 = ldsV[key * 64 + li];
-                const float v1 = ldsV[key * 64 + 32 + li];
-                O[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, S[kt][r], O[0], 0, 0, 0);
-                O[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, S[kt][r], O[1], 0, 0, 0);
-            }
-    }
-
-    if (query < N) {
-        const float inv = 1.0f / l_run;
-        float* orow = out + ((size_t)b * N + query) * C + hd * 64;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                float4 v;
-                v.x = O[ct][4 * rq + 0] * inv;
-                v.y = O[ct][4 * rq + 1] * inv;
-                v.z = O[ct][4 * rq + 2] * inv;
-                v.w = O[ct][4 * rq + 3] * inv;
-                *reinterpret_cast<float4*>(orow + 32 * ct + 8 * rq + 4 * lh) = v;
-            }
-    }
+    f32_fragment<true>(qreg, w.base + (size_t)min(w.row, N - 1) * w.C3 + w.hd * 64, w.lh);
+    const Sweep f = f32_forward_sweep(w, qreg, ldsK, ldsV, N, C);
+    if (w.row < N) store_row(out + ((size_t)w.b * N + w.row) * C + w.hd * 64, f.O, 1.0f / f.l, w.lh);
 }
 
 void launch_attention(const float* qkv, float* out, int B, int N, int C, hipStream_t stream) {
@@ -150,160 +320,17 @@ void launch_attention(const float* qkv, float* out, int B, int N, int C, hipStre
     hipLaunchKernelGGL(attention_kernel, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, stream, qkv, out, N, C);
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// The same forward with plain fp16 operands on v_mfma_f32_32x32x16_f16 (launch_attention_p16): the arithmetic of the reference's
-// evaluation under `precision: 16` (fp16 autocast over QKVAttention.forward, OpenAI_Unet.py:457-476) with fp32 accumulators.
-//   q (scaled by the exact 2^-3), k and v are rounded to fp16 (RNE) once, where they are staged; S and O accumulate in fp32; the
-//   running max / sum softmax stays in fp32; P is rounded to fp16 only as the MFMA operand; the output is fp32.
-// Work split and accumulator trick as above: workgroup = (sample, head, 128 queries), wave = 32 queries, key tiles of 64.
-//   S^T[key][query] = K . Q^T   : 4 k-steps of 16 channels per 32-key sub-tile; A = a K row's 8 channels (ds_read_b128 of the
-//                                 [key][channel] image, rows padded to 144 B: 16 consecutive rows cover the 16 four-bank groups),
-//                                 B = the query's 8 channels, in registers for the whole kernel.
-//   O^T[c][query]  += V^T . P^T : registers 8s .. 8s+7 of the S^T accumulator, rounded to fp16, ARE the B operand of k-step s:
-//                                 element j of lane-half h is key 16 s + 8 (j >> 2) + 4 h + (j & 3). The A operand is V^T[c][those
-//                                 keys]: two 8-byte reads of the transposed [channel][key] image (rows padded to 136 B: 32
-//                                 consecutive rows cover the 32 bank pairs), which the staging threads write as 4-key columns.
-// One 64-key tile costs a wave 16 MFMAs of 32 cycles instead of 128 of 64.
 __global__ __launch_bounds__(256, 2) void attention_p16_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                int N, int C) {
-    constexpr int KS = 72;   // fp16 elements of a K row (64 channels + 16 B)
-    constexpr int VS = 68;   // fp16 elements of a V^T row (64 keys + 8 B)
-    __shared__ __attribute__((aligned(16))) _Float16 ldsK[64 * KS];    // [key][channel]
-    __shared__ __attribute__((aligned(16))) _Float16 ldsVt[64 * VS];   // [channel][key]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int heads = C >> 6;
-    const int nqb = (N + 127) >> 7;
-    int bid = blockIdx.x;
-    const int qb = bid % nqb;
-    bid /= nqb;
-    const int hd = bid % heads;
-    const int b = bid / heads;
-    const int C3 = 3 * C;
-    const float* base = qkv + (size_t)b * N * C3;
-
+    __shared__ __attribute__((aligned(16))) _Float16 ldsK[64 * P16_RS];    // [key][channel]
+    __shared__ __attribute__((aligned(16))) _Float16 ldsVt[64 * P16_TS];   // [channel][key]
+    const Wg w = wg_decode(qkv, N, C);
     // Q fragments of this lane's query: k-step s = channels 16 s + 8 lh + {0..7}, pre-scaled by 1/8, fp16
-    const int query = qb * 128 + wave * 32 + li;
-    const int qrow = min(query, N - 1);
     f16x8 qf[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const float* qp = base + (size_t)qrow * C3 + hd * 64 + 16 * s + 8 * lh;
-        const float4 a = *reinterpret_cast<const float4*>(qp);
-        const float4 c = *reinterpret_cast<const float4*>(qp + 4);
-        qf[s] = f16x8{(_Float16)(a.x * 0.125f), (_Float16)(a.y * 0.125f), (_Float16)(a.z * 0.125f), (_Float16)(a.w * 0.125f),
-                      (_Float16)(c.x * 0.125f), (_Float16)(c.y * 0.125f), (_Float16)(c.z * 0.125f), (_Float16)(c.w * 0.125f)};
-    }
-
-    f32x16 O[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) O[ct][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    const int cq = tid & 15, kq = tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
-    for (int k0 = 0; k0 < N; k0 += 64) {
-        float4 kv[4], vv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int key = k0 + 4 * kq + i;
-            kv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            vv[i] = kv[i];
-            if (key < N) {
-                const float* rowp = base + (size_t)key * C3 + hd * 64 + 4 * cq;
-                kv[i] = *reinterpret_cast<const float4*>(rowp + C);
-                vv[i] = *reinterpret_cast<const float4*>(rowp + 2 * C);
-            }
-        }
-        __syncthreads();   // previous tile fully consumed
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            *reinterpret_cast<f16x4*>(&ldsK[(4 * kq + i) * KS + 4 * cq]) =
-                f16x4{(_Float16)kv[i].x, (_Float16)kv[i].y, (_Float16)kv[i].z, (_Float16)kv[i].w};
-        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 0) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].x, (_Float16)vv[1].x, (_Float16)vv[2].x, (_Float16)vv[3].x};
-        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 1) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].y, (_Float16)vv[1].y, (_Float16)vv[2].y, (_Float16)vv[3].y};
-        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 2) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].z, (_Float16)vv[1].z, (_Float16)vv[2].z, (_Float16)vv[3].z};
-        *reinterpret_cast<f16x4*>(&ldsVt[(4 * cq + 3) * VS + 4 * kq]) = f16x4{(_Float16)vv[0].w, (_Float16)vv[1].w, (_Float16)vv[2].w, (_Float16)vv[3].w};
-        __syncthreads();
-
-        // ---- S^T = K . Q^T for 2 sub-tiles of 32 keys
-        f32x16 S[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) S[kt][r] = 0.f;
-            const _Float16* krow = &ldsK[(32 * kt + li) * KS + 8 * lh];
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(krow + 16 * s), qf[s], S[kt], 0, 0, 0);
-        }
-
-        // ---- online softmax over keys (registers + lane^32), fp32
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (key >= N) S[kt][r] = -INFINITY;
-                tmax = fmaxf(tmax, S[kt][r]);
-            }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = __expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __expf(S[kt][r] - m_new);
-                S[kt][r] = p;
-                psum += p;
-            }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) O[ct][r] *= alpha;
-
-        // ---- O^T += V^T . P^T
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                f16x8 pf;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) pf[j] = (_Float16)S[kt][8 * s + j];
-                const int key0 = 32 * kt + 16 * s + 4 * lh;
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    const _Float16* vp = &ldsVt[(32 * ct + li) * VS + key0];
-                    const f16x4 lo = *reinterpret_cast<const f16x4*>(vp);
-                    const f16x4 hi = *reinterpret_cast<const f16x4*>(vp + 8);
-                    const f16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    O[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, O[ct], 0, 0, 0);
-                }
-            }
-    }
-
-    if (query < N) {
-        const float inv = 1.0f / l_run;
-        float* orow = out + ((size_t)b * N + query) * C + hd * 64;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                float4 v;
-                v.x = O[ct][4 * rq + 0] * inv;
-                v.y = O[ct][4 * rq + 1] * inv;
-                v.z = O[ct][4 * rq + 2] * inv;
-                v.w = O[ct][4 * rq + 3] * inv;
-                *reinterpret_cast<float4*>(orow + 32 * ct + 8 * rq + 4 * lh) = v;
-            }
-    }
+    for (int s = 0; s < 4; ++s) qf[s] = p16_fragment(w.base + (size_t)min(w.row, N - 1) * w.C3 + w.hd * 64 + 16 * s + 8 * w.lh, 0.125f);
+    const Sweep f = p16_forward_sweep(w, qf, ldsK, ldsVt, N, C);
+    if (w.row < N) store_row(out + ((size_t)w.b * N + w.row) * C + w.hd * 64, f.O, 1.0f / f.l, w.lh);
 }
 
 void launch_attention_p16(const float* qkv, float* out, int B, int N, int C, hipStream_t stream) {
@@ -332,197 +359,54 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_q_kernel(const float* __
     __shared__ float4 ldsK[64 * 16];   // K tile, [key][slot ^ (key & 15)]
     __shared__ float4 ldsV4[64 * 16];  // V tile, same layout (A operand of dP^T = V . dA^T)
     __shared__ float ldsP[64 * 64];    // plain [key][channel]: V in sweep 1 (O^T += V^T P^T), K in sweep 2 (dQ^T += K^T dS^T)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int heads = C >> 6;
-    const int nqb = (N + 127) >> 7;
-    int bid = blockIdx.x;
-    const int qb = bid % nqb;
-    bid /= nqb;
-    const int hd = bid % heads;
-    const int b = bid / heads;
-    const int C3 = 3 * C;
-    const float* base = qkv + (size_t)b * N * C3;
-    const int query = qb * 128 + wave * 32 + li;
-    const int qrow = min(query, N - 1);
+    const Wg w = wg_decode(qkv, N, C);
+    const int qrow = min(w.row, N - 1);
     float4 qreg[8], dareg[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        float4 v = *reinterpret_cast<const float4*>(base + (size_t)qrow * C3 + hd * 64 + 8 * g + 4 * lh);
-        v.x *= 0.125f; v.y *= 0.125f; v.z *= 0.125f; v.w *= 0.125f;
-        qreg[g] = v;
-        dareg[g] = *reinterpret_cast<const float4*>(da + ((size_t)b * N + qrow) * C + hd * 64 + 8 * g + 4 * lh);
-    }
-    float m_run = -INFINITY, l_run = 0.f, Dq = 0.f;
+    f32_fragment<true>(qreg, w.base + (size_t)qrow * w.C3 + w.hd * 64, w.lh);
+    f32_fragment<false>(dareg, da + ((size_t)w.b * N + qrow) * C + w.hd * 64, w.lh);
     // ---------------- sweep 1: the forward (running max / sum, O^T) -> D
-    {
-        f32x16 O[2];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) O[ct][r] = 0.f;
-        for (int k0 = 0; k0 < N; k0 += 64) {
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int e = tid + 256 * i;
-                const int key = e >> 4, slot = e & 15;
-                float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-                if (k0 + key < N) {
-                    const float* rowp = base + (size_t)(k0 + key) * C3 + hd * 64 + 4 * slot;
-                    kv = *reinterpret_cast<const float4*>(rowp + C);
-                    vv = *reinterpret_cast<const float4*>(rowp + 2 * C);
-                }
-                ldsK[key * 16 + (slot ^ (key & 15))] = kv;
-                *reinterpret_cast<float4*>(&ldsP[key * 64 + 4 * slot]) = vv;
-            }
-            __syncthreads();
-            f32x16 S[2];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) S[kt][r] = 0.f;
-                const int row = 32 * kt + li;
-#pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    const float4 kf = ldsK[row * 16 + ((2 * g + lh) ^ (row & 15))];
-                    S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qreg[g].x, S[kt], 0, 0, 0);
-                    S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qreg[g].y, S[kt], 0, 0, 0);
-                    S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qreg[g].z, S[kt], 0, 0, 0);
-                    S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qreg[g].w, S[kt], 0, 0, 0);
-                }
-            }
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= N) S[kt][r] = -INFINITY;
-                    tmax = fmaxf(tmax, S[kt][r]);
-                }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = __expf(m_run - m_new);
-            float psum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float pv = __expf(S[kt][r] - m_new);
-                    S[kt][r] = pv;
-                    psum += pv;
-                }
-            psum += __shfl_xor(psum, 32, 64);
-            l_run = l_run * alpha + psum;
-            m_run = m_new;
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) O[ct][r] *= alpha;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const float v0 = ldsP[key * 64 + li];
-                    const float v1 = ldsP[key * 64 + 32 + li];
-                    O[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, S[kt][r], O[0], 0, 0, 0);
-                    O[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, S[kt][r], O[1], 0, 0, 0);
-                }
-        }
-        // D = sum_c dA_c a_c, a = O / l. O^T[c][query]: register 4 rq + x of tile ct = channel 32 ct + 8 rq + 4 lh + x, i.e. dareg[4 ct + rq]
-        const float inv = 1.0f / l_run;
-        float dsum = 0.f;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const float4 d4 = dareg[4 * ct + rq];
-                dsum += d4.x * O[ct][4 * rq + 0] + d4.y * O[ct][4 * rq + 1] + d4.z * O[ct][4 * rq + 2] + d4.w * O[ct][4 * rq + 3];
-            }
-        dsum += __shfl_xor(dsum, 32, 64);
-        Dq = dsum * inv;
-    }
-    const float lse = m_run + __logf(l_run);
-    if (query < N && lh == 0) {
-        float* st = stats + (((size_t)b * heads + hd) * N + query) * 2;
-        st[0] = lse; st[1] = Dq;
-    }
-    // ---------------- sweep 2: dQ^T += K^T . dS^T
-    f32x16 dQ[2];
+    const Sweep f = f32_forward_sweep(w, qreg, ldsK, ldsP, N, C);
+    // D = sum_c dA_c a_c, a = O / l. O^T[c][query]: register 4 rq + x of tile ct = channel 32 ct + 8 rq + 4 lh + x, i.e. dareg[4 ct + rq]
+    float dsum = 0.f;
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dQ[ct][r] = 0.f;
+        for (int rq = 0; rq < 4; ++rq) {
+            const float4 d4 = dareg[4 * ct + rq];
+            dsum += d4.x * f.O.t[ct][4 * rq + 0] + d4.y * f.O.t[ct][4 * rq + 1] + d4.z * f.O.t[ct][4 * rq + 2] + d4.w * f.O.t[ct][4 * rq + 3];
+        }
+    dsum += __shfl_xor(dsum, 32, 64);
+    const float Dq = dsum * (1.0f / f.l);
+    const float lse = f.m + __logf(f.l);
+    if (w.row < N && w.lh == 0) {
+        float* st = stats + (((size_t)w.b * w.heads + w.hd) * N + w.row) * 2;
+        st[0] = lse; st[1] = Dq;
+    }
+    // ---------------- sweep 2: dQ^T += K^T . dS^T
+    const float* kp = w.base + C + w.hd * 64;
+    Acc2 dQ = {};
     for (int k0 = 0; k0 < N; k0 += 64) {
         __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + 256 * i;
-            const int key = e >> 4, slot = e & 15;
-            float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-            if (k0 + key < N) {
-                const float* rowp = base + (size_t)(k0 + key) * C3 + hd * 64 + 4 * slot;
-                kv = *reinterpret_cast<const float4*>(rowp + C);
-                vv = *reinterpret_cast<const float4*>(rowp + 2 * C);
-            }
-            ldsK[key * 16 + (slot ^ (key & 15))] = kv;
-            ldsV4[key * 16 + (slot ^ (key & 15))] = vv;
-            *reinterpret_cast<float4*>(&ldsP[key * 64 + 4 * slot]) = kv;
-        }
+        f32_stage<false>(w.tid, k0, N, kp, w.C3, kp + C, w.C3, ldsK, ldsP, ldsV4, nullptr);
         __syncthreads();
         f32x16 S[2], dP[2];
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { S[kt][r] = 0.f; dP[kt][r] = 0.f; }
-            const int row = 32 * kt + li;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const float4 kf = ldsK[row * 16 + ((2 * g + lh) ^ (row & 15))];
-                const float4 vf = ldsV4[row * 16 + ((2 * g + lh) ^ (row & 15))];
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qreg[g].x, S[kt], 0, 0, 0);
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qreg[g].y, S[kt], 0, 0, 0);
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qreg[g].z, S[kt], 0, 0, 0);
-                S[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qreg[g].w, S[kt], 0, 0, 0);
-                dP[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.x, dareg[g].x, dP[kt], 0, 0, 0);
-                dP[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.y, dareg[g].y, dP[kt], 0, 0, 0);
-                dP[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.z, dareg[g].z, dP[kt], 0, 0, 0);
-                dP[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf.w, dareg[g].w, dP[kt], 0, 0, 0);
-            }
+            S[kt] = f32_first_product(ldsK, 32 * kt + w.li, w.lh, qreg);
+            dP[kt] = f32_first_product(ldsV4, 32 * kt + w.li, w.lh, dareg);
         }
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * w.lh;
                 const float pv = (key < N) ? __expf(S[kt][r] - lse) : 0.f;
                 S[kt][r] = pv * (dP[kt][r] - Dq);            // dS^T
             }
 #pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const float k0v = ldsP[key * 64 + li];
-                const float k1v = ldsP[key * 64 + 32 + li];
-                dQ[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(k0v, S[kt][r], dQ[0], 0, 0, 0);
-                dQ[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(k1v, S[kt][r], dQ[1], 0, 0, 0);
-            }
+        for (int kt = 0; kt < 2; ++kt) dQ = f32_second_product(dQ, ldsP, w.li, 32 * kt + 4 * w.lh, S[kt]);
     }
-    if (query < N) {
-        float* orow = dqkv + ((size_t)b * N + query) * C3 + hd * 64;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                float4 v;
-                v.x = dQ[ct][4 * rq + 0] * 0.125f; v.y = dQ[ct][4 * rq + 1] * 0.125f;
-                v.z = dQ[ct][4 * rq + 2] * 0.125f; v.w = dQ[ct][4 * rq + 3] * 0.125f;
-                *reinterpret_cast<float4*>(orow + 32 * ct + 8 * rq + 4 * lh) = v;
-            }
-    }
+    if (w.row < N) store_row(dqkv + ((size_t)w.b * N + w.row) * w.C3 + w.hd * 64, dQ, 0.125f, w.lh);
 }
 
 __global__ __launch_bounds__(256, 2) void attention_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
@@ -532,101 +416,42 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_kv_kernel(const float* _
     __shared__ float ldsQp[64 * 64];    // plain [query][channel] copies: A operands of dK^T += Q^T dS and dV^T += dA^T P
     __shared__ float ldsAp[64 * 64];
     __shared__ float ldsL[64], ldsD[64];   // per query: m + log l, D
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int heads = C >> 6;
-    const int nkb = (N + 127) >> 7;
-    int bid = blockIdx.x;
-    const int kb = bid % nkb;
-    bid /= nkb;
-    const int hd = bid % heads;
-    const int b = bid / heads;
-    const int C3 = 3 * C;
-    const float* base = qkv + (size_t)b * N * C3;
-    const int keyi = kb * 128 + wave * 32 + li;
-    const int krow = min(keyi, N - 1);
+    const Wg w = wg_decode(qkv, N, C);
+    const float* krowp = w.base + (size_t)min(w.row, N - 1) * w.C3 + C + w.hd * 64;
     float4 kreg[8], vreg[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        kreg[g] = *reinterpret_cast<const float4*>(base + (size_t)krow * C3 + C + hd * 64 + 8 * g + 4 * lh);
-        vreg[g] = *reinterpret_cast<const float4*>(base + (size_t)krow * C3 + 2 * C + hd * 64 + 8 * g + 4 * lh);
-    }
-    f32x16 dK[2], dV[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dK[ct][r] = 0.f; dV[ct][r] = 0.f; }
-    const float* st = stats + ((size_t)b * heads + hd) * N * 2;
+    f32_fragment<false>(kreg, krowp, w.lh);
+    f32_fragment<false>(vreg, krowp + C, w.lh);
+    Acc2 dK = {}, dV = {};
+    const float* st = stats + ((size_t)w.b * w.heads + w.hd) * N * 2;
     for (int q0 = 0; q0 < N; q0 += 64) {
         __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + 256 * i;
-            const int qq = e >> 4, slot = e & 15;
-            float4 qv = make_float4(0.f, 0.f, 0.f, 0.f), av = qv;
-            if (q0 + qq < N) {
-                qv = *reinterpret_cast<const float4*>(base + (size_t)(q0 + qq) * C3 + hd * 64 + 4 * slot);
-                qv.x *= 0.125f; qv.y *= 0.125f; qv.z *= 0.125f; qv.w *= 0.125f;
-                av = *reinterpret_cast<const float4*>(da + ((size_t)b * N + q0 + qq) * C + hd * 64 + 4 * slot);
-            }
-            ldsQ4[qq * 16 + (slot ^ (qq & 15))] = qv;
-            ldsA4[qq * 16 + (slot ^ (qq & 15))] = av;
-            *reinterpret_cast<float4*>(&ldsQp[qq * 64 + 4 * slot]) = qv;
-            *reinterpret_cast<float4*>(&ldsAp[qq * 64 + 4 * slot]) = av;
-        }
-        if (tid < 64) {
-            const bool ok = q0 + tid < N;
-            ldsL[tid] = ok ? st[(size_t)(q0 + tid) * 2] : INFINITY;      // exp(S - inf) = 0: queries past the end contribute nothing
-            ldsD[tid] = ok ? st[(size_t)(q0 + tid) * 2 + 1] : 0.f;
+        f32_stage<true>(w.tid, q0, N, w.base + w.hd * 64, w.C3, da + (size_t)w.b * N * C + w.hd * 64, C, ldsQ4, ldsQp, ldsA4, ldsAp);
+        if (w.tid < 64) {
+            const bool ok = q0 + w.tid < N;
+            ldsL[w.tid] = ok ? st[(size_t)(q0 + w.tid) * 2] : INFINITY;      // exp(S - inf) = 0: queries past the end contribute nothing
+            ldsD[w.tid] = ok ? st[(size_t)(q0 + w.tid) * 2 + 1] : 0.f;
         }
         __syncthreads();
         // S[query][key] = (Q/8) . K^T and dP[query][key] = dA . V^T: queries in the accumulator registers, the key on the lane;
         // one 32-query sub-tile at a time (32 instead of 64 live accumulator registers for S and dP: no spills)
 #pragma unroll 1
         for (int qt = 0; qt < 2; ++qt) {
-            f32x16 S, dP;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
-            const int row = 32 * qt + li;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const float4 qf = ldsQ4[row * 16 + ((2 * g + lh) ^ (row & 15))];
-                const float4 af = ldsA4[row * 16 + ((2 * g + lh) ^ (row & 15))];
-                S = __builtin_amdgcn_mfma_f32_32x32x2f32(qf.x, kreg[g].x, S, 0, 0, 0);
-                S = __builtin_amdgcn_mfma_f32_32x32x2f32(qf.y, kreg[g].y, S, 0, 0, 0);
-                S = __builtin_amdgcn_mfma_f32_32x32x2f32(qf.z, kreg[g].z, S, 0, 0, 0);
-                S = __builtin_amdgcn_mfma_f32_32x32x2f32(qf.w, kreg[g].w, S, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, vreg[g].x, dP, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, vreg[g].y, dP, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, vreg[g].z, dP, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, vreg[g].w, dP, 0, 0, 0);
-            }
+            const f32x16 S = f32_first_product(ldsQ4, 32 * qt + w.li, w.lh, kreg);
+            const f32x16 dP = f32_first_product(ldsA4, 32 * qt + w.li, w.lh, vreg);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int qq = 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int qq = 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * w.lh;
                 const float pv = __expf(S[r] - ldsL[qq]);
                 const float ds = pv * (dP[r] - ldsD[qq]);
-                const float a0 = ldsAp[qq * 64 + li], a1 = ldsAp[qq * 64 + 32 + li];
-                const float x0 = ldsQp[qq * 64 + li], x1 = ldsQp[qq * 64 + 32 + li];
-                dV[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, pv, dV[0], 0, 0, 0);
-                dV[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, pv, dV[1], 0, 0, 0);
-                dK[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, ds, dK[0], 0, 0, 0);
-                dK[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, ds, dK[1], 0, 0, 0);
+                dV = f32_second_step(dV, ldsAp, qq, w.li, pv);
+                dK = f32_second_step(dK, ldsQp, qq, w.li, ds);
             }
         }
     }
-    if (keyi < N) {
-        float* krow_o = dqkv + ((size_t)b * N + keyi) * C3 + C + hd * 64;
-        float* vrow_o = krow_o + C;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                *reinterpret_cast<float4*>(krow_o + 32 * ct + 8 * rq + 4 * lh) =
-                    make_float4(dK[ct][4 * rq + 0], dK[ct][4 * rq + 1], dK[ct][4 * rq + 2], dK[ct][4 * rq + 3]);
-                *reinterpret_cast<float4*>(vrow_o + 32 * ct + 8 * rq + 4 * lh) =
-                    make_float4(dV[ct][4 * rq + 0], dV[ct][4 * rq + 1], dV[ct][4 * rq + 2], dV[ct][4 * rq + 3]);
-            }
+    if (w.row < N) {
+        float* krow_o = dqkv + ((size_t)w.b * N + w.row) * w.C3 + C + w.hd * 64;
+        store_row(krow_o, dK, w.lh);
+        store_row(krow_o + C, dV, w.lh);
     }
 }
 
@@ -639,198 +464,56 @@ void launch_attention_backward_flash(const float* qkv, const float* da, float* d
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The same backward with plain fp16 operands on v_mfma_f32_32x32x16_f16 (launch_attention_backward_p16): the arithmetic of fp16
-// autocast over QKVAttention.forward and its backward (the reference trains under `precision: 16`), with fp32 accumulators.
-//   q . 2^-3, k, v and dA are rounded to fp16 (RNE, gradual underflow) once, where they are staged; S, dP, dQ, dK and dV accumulate in
-//   fp32; the running max / sum, P = exp(S - lse), D_i = sum_c dA_ic a_ic (rounded dA, fp32 sweep-1 output) and dS = P (dP - D) are
-//   fp32 VALU work; P and dS are rounded to fp16 only as MFMA operands; dqkv is fp32. |dA| >= 65504 rounds to +-inf as under autocast
-//   and gives non-finite gradients of that sample (what the loss scale's device guard catches), never a finite wrong number.
-// Two kernels, work split, masking and row statistics as the fp32 pair above; LDS images as attention_p16_kernel:
-//   row images [row][channel], 144-B rows : A operands of the first products (ds_read_b128 of a row's 8 channels)
-//   transposed images [channel][row], 136-B rows, written as 4-row columns : A operands of the second products (2 x ds_read_b64);
-//   registers 8s .. 8s+7 of a first product's accumulator, rounded to fp16, are the B operand of k-step s of the second.
+// The same backward in the fp16 arithmetic (launch_attention_backward_p16): two kernels, work split, masking and row statistics as
+// the fp32 pair above. D_i = sum_c dA_ic a_ic takes the rounded dA and the fp32 sweep-1 output. |dA| >= 65504 rounds to +-inf as under
+// autocast and gives non-finite gradients of that sample (what the loss scale's device guard catches), never a finite wrong number.
 //   attention_bwd_q_p16_kernel  : sweep 1 = attention_p16_kernel (K rows, V^T); sweep 2: K rows, V rows, K^T (27 KB)
 //   attention_bwd_kv_p16_kernel : k, v fragments in registers; per 64-query tile Q/8 and dA rows, (Q/8)^T and dA^T (35 KB)
 // Per 64-row tile a wave issues 16 + 24 (q kernel, sweeps 1 + 2) and 32 (kv kernel) MFMAs of 32 cycles instead of 128 + 192 and 256 of 64.
 // ------------------------------------------------------------------------------------------------------------------
-namespace {
-constexpr int P16_RS = 72;   // fp16 elements of a row-image row (64 channels + 16 B)
-constexpr int P16_TS = 68;   // fp16 elements of a transposed-image row (64 rows + 8 B)
-
-__device__ __forceinline__ f16x4 p16_round4(float x, float y, float z, float w) {
-    return f16x4{(_Float16)x, (_Float16)y, (_Float16)z, (_Float16)w};
-}
-// this staging thread's 4 rows x 4 channels (rows 4 kq + i, channels 4 cq + {0..3}) into a row image / a transposed image
-__device__ __forceinline__ void p16_stage_rows(_Float16* img, int kq, int cq, const float4 (&v)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<f16x4*>(&img[(4 * kq + i) * P16_RS + 4 * cq]) = p16_round4(v[i].x, v[i].y, v[i].z, v[i].w);
-}
-__device__ __forceinline__ void p16_stage_cols(_Float16* img, int kq, int cq, const float4 (&v)[4]) {
-    *reinterpret_cast<f16x4*>(&img[(4 * cq + 0) * P16_TS + 4 * kq]) = p16_round4(v[0].x, v[1].x, v[2].x, v[3].x);
-    *reinterpret_cast<f16x4*>(&img[(4 * cq + 1) * P16_TS + 4 * kq]) = p16_round4(v[0].y, v[1].y, v[2].y, v[3].y);
-    *reinterpret_cast<f16x4*>(&img[(4 * cq + 2) * P16_TS + 4 * kq]) = p16_round4(v[0].z, v[1].z, v[2].z, v[3].z);
-    *reinterpret_cast<f16x4*>(&img[(4 * cq + 3) * P16_TS + 4 * kq]) = p16_round4(v[0].w, v[1].w, v[2].w, v[3].w);
-}
-// 8 channels of a global row as one fp16 MFMA fragment, scaled by `scale` before rounding
-__device__ __forceinline__ f16x8 p16_fragment(const float* p, float scale) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    const float4 c = *reinterpret_cast<const float4*>(p + 4);
-    return f16x8{(_Float16)(a.x * scale), (_Float16)(a.y * scale), (_Float16)(a.z * scale), (_Float16)(a.w * scale),
-                 (_Float16)(c.x * scale), (_Float16)(c.y * scale), (_Float16)(c.z * scale), (_Float16)(c.w * scale)};
-}
-// acc[ct] += T^T-image[channel 32 ct + li][rows row0 + {0..3}, row0 + 8 + {0..3}] . bf for both channel tiles
-__device__ __forceinline__ void p16_second_product(f32x16 (&acc)[2], const _Float16* timg, int li, int row0, f16x8 bf) {
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-        const _Float16* tp = &timg[(32 * ct + li) * P16_TS + row0];
-        const f16x4 lo = *reinterpret_cast<const f16x4*>(tp);
-        const f16x4 hi = *reinterpret_cast<const f16x4*>(tp + 8);
-        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7), bf, acc[ct], 0, 0, 0);
-    }
-}
-}  // namespace
-
 __global__ __launch_bounds__(256, 2) void attention_bwd_q_p16_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
                                                                      float* __restrict__ dqkv, float* __restrict__ stats /*[B][heads][N][2]*/,
                                                                      int N, int C) {
     __shared__ __attribute__((aligned(16))) _Float16 ldsK[64 * P16_RS];   // K rows [key][channel]
     __shared__ __attribute__((aligned(16))) _Float16 ldsV[64 * P16_RS];   // V rows [key][channel] (sweep 2: A operand of dP^T = V . dA^T)
     __shared__ __attribute__((aligned(16))) _Float16 ldsT[64 * P16_TS];   // [channel][key]: V^T in sweep 1, K^T in sweep 2
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int heads = C >> 6;
-    const int nqb = (N + 127) >> 7;
-    int bid = blockIdx.x;
-    const int qb = bid % nqb;
-    bid /= nqb;
-    const int hd = bid % heads;
-    const int b = bid / heads;
-    const int C3 = 3 * C;
-    const float* base = qkv + (size_t)b * N * C3;
-    const int query = qb * 128 + wave * 32 + li;
-    const int qrow = min(query, N - 1);
-    const float* darow = da + ((size_t)b * N + qrow) * C + hd * 64;
+    const Wg w = wg_decode(qkv, N, C);
+    const int qrow = min(w.row, N - 1);
+    const float* darow = da + ((size_t)w.b * N + qrow) * C + w.hd * 64;
     // fragments of this lane's query: k-step s = channels 16 s + 8 lh + {0..7}; q pre-scaled by 1/8
     f16x8 qf[4], daf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        qf[s] = p16_fragment(base + (size_t)qrow * C3 + hd * 64 + 16 * s + 8 * lh, 0.125f);
-        daf[s] = p16_fragment(darow + 16 * s + 8 * lh, 1.0f);
+        qf[s] = p16_fragment(w.base + (size_t)qrow * w.C3 + w.hd * 64 + 16 * s + 8 * w.lh, 0.125f);
+        daf[s] = p16_fragment(darow + 16 * s + 8 * w.lh, 1.0f);
     }
-    const int cq = tid & 15, kq = tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
-    float m_run = -INFINITY, l_run = 0.f, Dq = 0.f;
     // ---------------- sweep 1: the p16 forward (running max / sum, O^T) -> D
-    {
-        f32x16 O[2];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) O[ct][r] = 0.f;
-        for (int k0 = 0; k0 < N; k0 += 64) {
-            float4 kv[4], vv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int key = k0 + 4 * kq + i;
-                kv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                vv[i] = kv[i];
-                if (key < N) {
-                    const float* rowp = base + (size_t)key * C3 + hd * 64 + 4 * cq;
-                    kv[i] = *reinterpret_cast<const float4*>(rowp + C);
-                    vv[i] = *reinterpret_cast<const float4*>(rowp + 2 * C);
-                }
-            }
-            __syncthreads();   // previous tile fully consumed
-            p16_stage_rows(ldsK, kq, cq, kv);
-            p16_stage_cols(ldsT, kq, cq, vv);
-            __syncthreads();
-            f32x16 S[2];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) S[kt][r] = 0.f;
-                const _Float16* krow = &ldsK[(32 * kt + li) * P16_RS + 8 * lh];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    S[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(krow + 16 * s), qf[s], S[kt], 0, 0, 0);
-            }
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= N) S[kt][r] = -INFINITY;
-                    tmax = fmaxf(tmax, S[kt][r]);
-                }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = __expf(m_run - m_new);
-            float psum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float pv = __expf(S[kt][r] - m_new);
-                    S[kt][r] = pv;
-                    psum += pv;
-                }
-            psum += __shfl_xor(psum, 32, 64);
-            l_run = l_run * alpha + psum;
-            m_run = m_new;
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) O[ct][r] *= alpha;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    f16x8 pf;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[j] = (_Float16)S[kt][8 * s + j];
-                    p16_second_product(O, ldsT, li, 32 * kt + 16 * s + 4 * lh, pf);
-                }
-        }
-        // D = sum_c dA_c a_c, a = O / l, with the fp16-rounded dA. O^T[c][query]: register 4 rq + x of tile ct = channel
-        // 32 ct + 8 rq + 4 lh + x -- not the channels of this lane's MFMA fragments, so those 32 values are read again
-        const float inv = 1.0f / l_run;
-        float dsum = 0.f;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const float4 d4 = *reinterpret_cast<const float4*>(darow + 32 * ct + 8 * rq + 4 * lh);
-                dsum += (float)(_Float16)d4.x * O[ct][4 * rq + 0] + (float)(_Float16)d4.y * O[ct][4 * rq + 1] +
-                        (float)(_Float16)d4.z * O[ct][4 * rq + 2] + (float)(_Float16)d4.w * O[ct][4 * rq + 3];
-            }
-        dsum += __shfl_xor(dsum, 32, 64);
-        Dq = dsum * inv;
-    }
-    const float lse = m_run + __logf(l_run);
-    if (query < N && lh == 0) {
-        float* st = stats + (((size_t)b * heads + hd) * N + query) * 2;
-        st[0] = lse; st[1] = Dq;
-    }
-    // ---------------- sweep 2: S^T = K . Q^T, dP^T = V . dA^T, dQ^T += K^T . dS^T
-    f32x16 dQ[2];
+    const Sweep f = p16_forward_sweep(w, qf, ldsK, ldsT, N, C);
+    // D = sum_c dA_c a_c, a = O / l, with the fp16-rounded dA. O^T[c][query]: register 4 rq + x of tile ct = channel
+    // 32 ct + 8 rq + 4 lh + x -- not the channels of this lane's MFMA fragments, so those 32 values are read again
+    float dsum = 0.f;
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dQ[ct][r] = 0.f;
+        for (int rq = 0; rq < 4; ++rq) {
+            const float4 d4 = *reinterpret_cast<const float4*>(darow + 32 * ct + 8 * rq + 4 * w.lh);
+            dsum += (float)(_Float16)d4.x * f.O.t[ct][4 * rq + 0] + (float)(_Float16)d4.y * f.O.t[ct][4 * rq + 1] +
+                    (float)(_Float16)d4.z * f.O.t[ct][4 * rq + 2] + (float)(_Float16)d4.w * f.O.t[ct][4 * rq + 3];
+        }
+    dsum += __shfl_xor(dsum, 32, 64);
+    const float Dq = dsum * (1.0f / f.l);
+    const float lse = f.m + __logf(f.l);
+    if (w.row < N && w.lh == 0) {
+        float* st = stats + (((size_t)w.b * w.heads + w.hd) * N + w.row) * 2;
+        st[0] = lse; st[1] = Dq;
+    }
+    // ---------------- sweep 2: S^T = K . Q^T, dP^T = V . dA^T, dQ^T += K^T . dS^T
+    const int cq = w.tid & 15, kq = w.tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
+    const float* kp = w.base + C + w.hd * 64;
+    Acc2 dQ = {};
     for (int k0 = 0; k0 < N; k0 += 64) {
         float4 kv[4], vv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int key = k0 + 4 * kq + i;
-            kv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            vv[i] = kv[i];
-            if (key < N) {
-                const float* rowp = base + (size_t)key * C3 + hd * 64 + 4 * cq;
-                kv[i] = *reinterpret_cast<const float4*>(rowp + C);
-                vv[i] = *reinterpret_cast<const float4*>(rowp + 2 * C);
-            }
-        }
+        p16_gather<false>(kv, vv, kp, w.C3, kp + C, w.C3, k0, N, kq, cq);
         __syncthreads();   // previous tile (or sweep 1's last) fully consumed
         p16_stage_rows(ldsK, kq, cq, kv);
         p16_stage_rows(ldsV, kq, cq, vv);
@@ -838,43 +521,19 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_q_p16_kernel(const float
         __syncthreads();
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
-            f32x16 S, dP;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
-            const _Float16* krow = &ldsK[(32 * kt + li) * P16_RS + 8 * lh];
-            const _Float16* vrow = &ldsV[(32 * kt + li) * P16_RS + 8 * lh];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                S = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(krow + 16 * s), qf[s], S, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(vrow + 16 * s), daf[s], dP, 0, 0, 0);
-            }
+            f32x16 S = p16_first_product(ldsK, 32 * kt + w.li, w.lh, qf);
+            const f32x16 dP = p16_first_product(ldsV, 32 * kt + w.li, w.lh, daf);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * w.lh;
                 const float pv = (key < N) ? __expf(S[r] - lse) : 0.f;
                 S[r] = pv * (dP[r] - Dq);            // dS^T
             }
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                f16x8 dsf;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) dsf[j] = (_Float16)S[8 * s + j];
-                p16_second_product(dQ, ldsT, li, 32 * kt + 16 * s + 4 * lh, dsf);
-            }
+            for (int s = 0; s < 2; ++s) dQ = p16_second_product(dQ, ldsT, w.li, 32 * kt + 16 * s + 4 * w.lh, p16_operand(S, s));
         }
     }
-    if (query < N) {
-        float* orow = dqkv + ((size_t)b * N + query) * C3 + hd * 64;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                float4 v;
-                v.x = dQ[ct][4 * rq + 0] * 0.125f; v.y = dQ[ct][4 * rq + 1] * 0.125f;
-                v.z = dQ[ct][4 * rq + 2] * 0.125f; v.w = dQ[ct][4 * rq + 3] * 0.125f;
-                *reinterpret_cast<float4*>(orow + 32 * ct + 8 * rq + 4 * lh) = v;
-            }
-    }
+    if (w.row < N) store_row(dqkv + ((size_t)w.b * N + w.row) * w.C3 + w.hd * 64, dQ, 0.125f, w.lh);
 }
 
 __global__ __launch_bounds__(256, 2) void attention_bwd_kv_p16_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
@@ -884,101 +543,57 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_kv_p16_kernel(const floa
     __shared__ __attribute__((aligned(16))) _Float16 ldsQt[64 * P16_TS];   // [channel][query] images: A operands of dK^T += (Q/8)^T dS
     __shared__ __attribute__((aligned(16))) _Float16 ldsAt[64 * P16_TS];   //                          and dV^T += dA^T P
     __shared__ float ldsL[64], ldsD[64];   // per query: m + log l, D
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int heads = C >> 6;
-    const int nkb = (N + 127) >> 7;
-    int bid = blockIdx.x;
-    const int kb = bid % nkb;
-    bid /= nkb;
-    const int hd = bid % heads;
-    const int b = bid / heads;
-    const int C3 = 3 * C;
-    const float* base = qkv + (size_t)b * N * C3;
-    const int keyi = kb * 128 + wave * 32 + li;
-    const int krow = min(keyi, N - 1);
+    const Wg w = wg_decode(qkv, N, C);
+    const float* krowp = w.base + (size_t)min(w.row, N - 1) * w.C3 + C + w.hd * 64;
     // fragments of this lane's key: k-step s = channels 16 s + 8 lh + {0..7}
     f16x8 kf[4], vf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        kf[s] = p16_fragment(base + (size_t)krow * C3 + C + hd * 64 + 16 * s + 8 * lh, 1.0f);
-        vf[s] = p16_fragment(base + (size_t)krow * C3 + 2 * C + hd * 64 + 16 * s + 8 * lh, 1.0f);
+        kf[s] = p16_fragment(krowp + 16 * s + 8 * w.lh, 1.0f);
+        vf[s] = p16_fragment(krowp + C + 16 * s + 8 * w.lh, 1.0f);
     }
-    f32x16 dK[2], dV[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dK[ct][r] = 0.f; dV[ct][r] = 0.f; }
-    const float* st = stats + ((size_t)b * heads + hd) * N * 2;
-    const int cq = tid & 15, kq = tid >> 4;     // staging: this thread's 4 channels x 4 queries of the tile
+    Acc2 dK = {}, dV = {};
+    const float* st = stats + ((size_t)w.b * w.heads + w.hd) * N * 2;
+    const int cq = w.tid & 15, kq = w.tid >> 4;     // staging: this thread's 4 channels x 4 queries of the tile
     for (int q0 = 0; q0 < N; q0 += 64) {
         float4 qv[4], av[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int qq = q0 + 4 * kq + i;
-            qv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            av[i] = qv[i];
-            if (qq < N) {
-                qv[i] = *reinterpret_cast<const float4*>(base + (size_t)qq * C3 + hd * 64 + 4 * cq);
-                qv[i].x *= 0.125f; qv[i].y *= 0.125f; qv[i].z *= 0.125f; qv[i].w *= 0.125f;
-                av[i] = *reinterpret_cast<const float4*>(da + ((size_t)b * N + qq) * C + hd * 64 + 4 * cq);
-            }
-        }
+        p16_gather<true>(qv, av, w.base + w.hd * 64, w.C3, da + (size_t)w.b * N * C + w.hd * 64, C, q0, N, kq, cq);
         float lq = INFINITY, dq_ = 0.f;      // exp(S - inf) = 0: queries past the end contribute nothing
-        if (tid < 64 && q0 + tid < N) {
-            lq = st[(size_t)(q0 + tid) * 2];
-            dq_ = st[(size_t)(q0 + tid) * 2 + 1];
+        if (w.tid < 64 && q0 + w.tid < N) {
+            lq = st[(size_t)(q0 + w.tid) * 2];
+            dq_ = st[(size_t)(q0 + w.tid) * 2 + 1];
         }
         __syncthreads();   // previous tile fully consumed
         p16_stage_rows(ldsQ, kq, cq, qv);
         p16_stage_rows(ldsA, kq, cq, av);
         p16_stage_cols(ldsQt, kq, cq, qv);
         p16_stage_cols(ldsAt, kq, cq, av);
-        if (tid < 64) { ldsL[tid] = lq; ldsD[tid] = dq_; }
+        if (w.tid < 64) { ldsL[w.tid] = lq; ldsD[w.tid] = dq_; }
         __syncthreads();
         // S[query][key] = (Q/8) . K^T and dP[query][key] = dA . V^T: queries in the accumulator registers, the key on the lane
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
-            f32x16 S, dP;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
-            const _Float16* qrow = &ldsQ[(32 * qt + li) * P16_RS + 8 * lh];
-            const _Float16* arow = &ldsA[(32 * qt + li) * P16_RS + 8 * lh];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                S = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(qrow + 16 * s), kf[s], S, 0, 0, 0);
-                dP = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(arow + 16 * s), vf[s], dP, 0, 0, 0);
-            }
+            f32x16 S = p16_first_product(ldsQ, 32 * qt + w.li, w.lh, kf);
+            f32x16 dP = p16_first_product(ldsA, 32 * qt + w.li, w.lh, vf);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int qq = 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int qq = 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * w.lh;
                 const float pv = __expf(S[r] - ldsL[qq]);
                 S[r] = pv;
                 dP[r] = pv * (dP[r] - ldsD[qq]);     // dS
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                f16x8 pf, dsf;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { pf[j] = (_Float16)S[8 * s + j]; dsf[j] = (_Float16)dP[8 * s + j]; }
-                const int row0 = 32 * qt + 16 * s + 4 * lh;
-                p16_second_product(dV, ldsAt, li, row0, pf);
-                p16_second_product(dK, ldsQt, li, row0, dsf);
+                const int row0 = 32 * qt + 16 * s + 4 * w.lh;
+                dV = p16_second_product(dV, ldsAt, w.li, row0, p16_operand(S, s));
+                dK = p16_second_product(dK, ldsQt, w.li, row0, p16_operand(dP, s));
             }
         }
     }
-    if (keyi < N) {
-        float* krow_o = dqkv + ((size_t)b * N + keyi) * C3 + C + hd * 64;
-        float* vrow_o = krow_o + C;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                *reinterpret_cast<float4*>(krow_o + 32 * ct + 8 * rq + 4 * lh) =
-                    make_float4(dK[ct][4 * rq + 0], dK[ct][4 * rq + 1], dK[ct][4 * rq + 2], dK[ct][4 * rq + 3]);
-                *reinterpret_cast<float4*>(vrow_o + 32 * ct + 8 * rq + 4 * lh) =
-                    make_float4(dV[ct][4 * rq + 0], dV[ct][4 * rq + 1], dV[ct][4 * rq + 2], dV[ct][4 * rq + 3]);
-            }
+    if (w.row < N) {
+        float* krow_o = dqkv + ((size_t)w.b * N + w.row) * w.C3 + C + w.hd * 64;
+        store_row(krow_o, dK, w.lh);
+        store_row(krow_o + C, dV, w.lh);
     }
 }
 

@@ -13,8 +13,10 @@ import arch_cases as A
 pytestmark = pytest.mark.gpu
 
 # (B, N, C): `attn_levels` level 0 (16 x 24 tokens, two heads); 12 x 20 tokens (a multiple of neither the 128-query workgroup nor the
-# 64-key tile); four heads with 12 query tiles each
-SHAPES = [(2, 384, 128), (2, 240, 128), (1, 1536, 256)]
+# 64-key tile); four heads with 12 query tiles each. Then the edges of the staging, masking and row-store code that the fp32 and the
+# fp16 kernels share: below one tile with N % 4 != 0; one key into the second tile (a fully masked 32-key sub-tile); the same with
+# N % 4 != 0; a second workgroup with a single live query (the clamped row). fp32-vs-float64 yardsticks there: 2.8e-7 ... 1.2e-6
+SHAPES = [(2, 384, 128), (2, 240, 128), (1, 1536, 256), (2, 15, 256), (1, 65, 64), (2, 67, 128), (1, 129, 128)]
 
 
 @pytest.fixture(scope="module")
