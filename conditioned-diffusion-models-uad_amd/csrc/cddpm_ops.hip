@@ -607,7 +607,8 @@ int cddpm_op_attention_p16(cddpm_handle h, const float* qkv_dev, float* out_dev,
 }
 
 int cddpm_op_attention(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream) {
-    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, !(C % 64 || N < 1), "cddpm_op_attention: C must be a multiple of 64")
+    OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention: C must be a multiple of 64")
+    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && out_dev, "cddpm_op_attention: NULL argument")
     launch_attention(qkv_dev, out_dev, B, N, C, s);
     OP_EPILOGUE()
 }

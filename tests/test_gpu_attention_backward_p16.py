@@ -13,14 +13,17 @@ import torch
 
 import precision16_cases as P
 from conftest import load_pkg
-from test_gpu_attention_shapes import _nlc, _reference      # d64 of _reference: float64 autograd of its _attention
+from attention_cases import nlc as _nlc, reference      # d64: float64 autograd of attention_cases.attention
 from test_gpu_precision16 import SWITCH
 
 pytestmark = pytest.mark.gpu
 
 # (B, N, C): N below one key tile; N a multiple of neither 128 nor 64; two heads, three query tiles; four heads, twelve query tiles; one
-# head with two queries past a 128-query workgroup and two keys past a key tile
-SHAPES = [(2, 15, 256), (2, 240, 128), (2, 384, 128), (1, 1536, 256), (1, 130, 64)]
+# head with two queries past a 128-query workgroup and two keys past a key tile. Then the tile boundaries, where the fp16 staging (4-key
+# columns of the transposed images, zero rows past N) has the most to get wrong: one short of a tile and of a workgroup, exactly one and
+# two tiles, one past each, N % 4 != 0 in a second tile. tests/test_attention_cases_host.py admits every one (none dropped)
+SHAPES = [(2, 15, 256), (2, 240, 128), (2, 384, 128), (1, 1536, 256), (1, 130, 64),
+          (1, 63, 64), (1, 64, 64), (1, 127, 64), (1, 128, 64), (1, 65, 64), (2, 67, 128), (1, 129, 128)]
 _id = lambda s: "x".join(map(str, s))
 
 
@@ -29,28 +32,12 @@ def eng(engine_factory):
     return engine_factory(timesteps=50, max_batch=2, max_h=16, max_w=24)
 
 
-def _attention_autocast(qkv, ch=64):
-    """_attention as the reference writes it for autocast: the softmax in fp32, cast back to the weights' dtype"""
-    B, C3, N = qkv.shape
-    heads = C3 // 3 // ch
-    q, k, v = qkv.chunk(3, dim=1)
-    s = 1 / (ch ** 0.25)
-    w = torch.einsum("bct,bcs->bts", (q * s).reshape(B * heads, ch, N), (k * s).reshape(B * heads, ch, N))
-    w = torch.softmax(w.float(), dim=-1).type(w.dtype)
-    return torch.einsum("bts,bcs->bct", w, v.reshape(B * heads, ch, N)).reshape(B, -1, N)
+_reference = functools.partial(reference, "flat")
 
 
-@functools.lru_cache(maxsize=None)
 def _yardstick(shape):
     """dL/dqkv [B, 3C, N] of fp16 autocast on the CPU for the inputs of _reference(shape), computed once per shape"""
-    ref = _reference(shape)
-    x = ref["qkv"].detach().clone().requires_grad_(True)       # _reference made its fp32 input a leaf of its own graph
-    with torch.autocast("cpu", dtype=torch.float16):
-        a = _attention_autocast(x)
-    assert a.dtype == torch.float16
-    a.backward(ref["da"].half())
-    assert bool(torch.isfinite(x.grad).all())
-    return x.grad.float()
+    return _reference(shape)["amp_d"]
 
 
 def _parts(C):

@@ -16,6 +16,7 @@ Measured on an MI355X (rms ratio / max ratio against the yardstick; switch = p16
     re-run slice         max 1.96e-7 rms 4.6e-8 against the fp32 oracle's 2.03e-7 / 6.0e-8
     validation_step      loss 0.53495288 at precision 16, 0.53493118 at 32
 """
+import functools
 import os
 import subprocess
 import sys
@@ -28,14 +29,18 @@ import torch
 import arch_cases as A
 import precision16_cases as P
 from conftest import ROOT, load_pkg
-from test_gpu_attention_shapes import _attention, _nlc, _reference
+from attention_cases import attention as _attention, nlc as _nlc, reference
 from test_gpu_conv_family import SCALE, explicit_noise, overflowing_batch
 
 pytestmark = pytest.mark.gpu
 
 SWITCH = 10.0         # a precision-16 result is at least this many times as far from float64 (rms) as the precision-32 one
 # (B, N, C): N below one 64-key tile; N a multiple of neither the 128-query workgroup nor the key tile; two heads; four heads x 12 query tiles
-ATTN_SHAPES = [(2, 15, 256), (2, 240, 128), (2, 384, 128), (1, 1536, 256)]
+# then the tile boundaries: one short of a tile and of a workgroup, exactly one and two tiles, one and two past each, N % 4 != 0 in a
+# second tile (tests/test_attention_cases_host.py admits every one: none dropped)
+ATTN_SHAPES = [(2, 15, 256), (2, 240, 128), (2, 384, 128), (1, 1536, 256),
+               (1, 63, 64), (1, 64, 64), (1, 127, 64), (1, 128, 64), (1, 65, 64), (2, 67, 128), (1, 129, 128), (1, 130, 64)]
+_reference = functools.partial(reference, "flat")
 
 
 @pytest.fixture(scope="module")
