@@ -1,11 +1,9 @@
 """CPU: what the evaluation-metric fixtures rest on (tools/make_golden_metrics.py, tests/golden/eval_metrics.json) and the
 host-only parts of the native _test_end (utils_eval.py of this package): the aggregates and the test stage's `del threshold`."""
-import itertools
 import json
 import math
 import os
 import sys
-from collections import deque
 
 import numpy as np
 import pytest
@@ -15,33 +13,13 @@ from conftest import GOLD, ROOT, load_pkg
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import make_golden_metrics as MG  # noqa: E402
 import eval_cases as EC  # noqa: E402
+from metric_shape_cases import brute_force_components  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def fixture():
     with open(os.path.join(GOLD, "eval_metrics.json")) as f:
         return json.load(f)
-
-
-def brute_force_components(v):
-    """26-connected components by breadth-first search: list of voxel sets"""
-    seen, comps = np.zeros(v.shape, bool), []
-    offs = [o for o in itertools.product((-1, 0, 1), repeat=3) if o != (0, 0, 0)]
-    for start in zip(*np.nonzero(v)):
-        if seen[start]:
-            continue
-        comp, q = set(), deque([start])
-        seen[start] = True
-        while q:
-            p = q.popleft()
-            comp.add(p)
-            for o in offs:
-                n = tuple(a + b for a, b in zip(p, o))
-                if all(0 <= c < s for c, s in zip(n, v.shape)) and v[n] and not seen[n]:
-                    seen[n] = True
-                    q.append(n)
-        comps.append(comp)
-    return comps
 
 
 def test_skimage_restatement_against_brute_force_labelling():
