@@ -126,6 +126,19 @@ SYMBOLS = {
     "cddpm_op_enc_maxpool": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _vp]),
     "cddpm_op_enc_avgpool": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "cddpm_op_set_scratch": (_i, [_vp, _sz]),
+    "cddpm_op_conv_wgrad_scratch": (_sz, [_i] * 9),
+    "cddpm_op_gn_coef_scratch": (_sz, [_i] * 5),
+    "cddpm_op_gn_silu_backward_scratch": (_sz, [_i] * 4),
+    "cddpm_op_attention_backward_scratch": (_sz, [_i] * 3),
+    "cddpm_op_linear_backward_scratch": (_sz, [_i] * 4),
+    "cddpm_op_head_scratch": (_sz, [_i] * 4),
+    "cddpm_op_bias_grad_scratch": (_sz, [_i64, _i]),
+    "cddpm_op_chan_image_corr_scratch": (_sz, [_i] * 4),
+    "cddpm_op_enc_conv_scratch": (_sz, [_i] * 8),
+    "cddpm_op_enc_conv_wgrad_scratch": (_sz, [_i] * 7),
+    "cddpm_op_enc_stem_wgrad_scratch": (_sz, [_i] * 3),
+    "cddpm_op_enc_bn_forward_scratch": (_sz, [_i64, _i, _i]),
+    "cddpm_op_enc_bn_backward_scratch": (_sz, [_i64, _i, _i]),
     "cddpm_op_absmax": (_i, [_vp, _fp, _i64, _fp, _vp]),
     "cddpm_op_pack_conv": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _vp, _vp]),
     "cddpm_op_pack_conv_batch": (_i, [_vp, _vp, _i, _i64, _vp]),
@@ -168,3 +181,22 @@ def load_library(path: str = LIB_PATH):
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def scratch_query(op, *args):
+    """bytes ONE call of cddpm_op_<op> takes from its handle's arena: the library's own answer (cddpm_op_<op>_scratch of include/cddpm.h,
+    host code: the function through which the operator takes its temporaries, run on a counting scratch). No device is needed."""
+    return int(getattr(load_library(), f"cddpm_op_{op}_scratch")(*args))
+
+
+def largest_calls(calls):
+    """-> (main, side) over (operator, query arguments) pairs: the largest single call, which is what the main handle's arena must hold
+    (every call takes its temporaries from the arena's start), and the largest weight gradient (cddpm_op_conv_wgrad,
+    cddpm_op_enc_conv_wgrad), all that runs on the side-stream handle. A weight gradient's k-images are part of its call."""
+    main = side = 0
+    for op, args in calls:
+        n = scratch_query(op, *args)
+        main = max(main, n)
+        if op in ("conv_wgrad", "enc_conv_wgrad"):
+            side = max(side, n)
+    return main, side

@@ -200,6 +200,9 @@ struct Prof {
 // on ONE stream are ordered, nothing synchronises -- what the training step runs on); without an arena, or for a `per_call` scratch
 // (the kernel-test convolutions, which synchronise anyway and must not depend on how a trainer sized the arena), they are
 // hipMalloc'ed for the call and freed after a stream synchronisation.
+// A scratch without a handle only COUNTS: every request adds its rounded size to `off` and returns nullptr, nothing is allocated and
+// nothing fails. An operator states its requests once, in a function of (OpScratch&, shape); run on a counting scratch that function
+// is the operator's size query (cddpm_op_*_scratch), run on the real one it hands out the pointers.
 struct OpScratch {
     cddpm_ctx* h;
     hipStream_t s;
@@ -207,9 +210,11 @@ struct OpScratch {
     std::vector<void*> owned;
     size_t off = 0;
     bool failed = false;
+    OpScratch() : h(nullptr), s(nullptr), per_call(false) {}
     OpScratch(cddpm_ctx* h_, hipStream_t s_, bool per_call_ = false) : h(h_), s(s_), per_call(per_call_) {}
     void* get(size_t bytes) {
         bytes = (bytes + 255) & ~(size_t)255;
+        if (!h) { off += bytes; return nullptr; }
         if (h->arena && !per_call) {
             if (off + bytes > h->arena_bytes) { failed = true; off += bytes; return nullptr; }
             void* p = static_cast<char*>(h->arena) + off;
@@ -223,8 +228,9 @@ struct OpScratch {
     }
     template <class T> T* n(size_t count) { return static_cast<T*>(get(count * sizeof(T))); }
     // a parameter vector given in host OR device memory: device pointers are used where they lie, host ones are staged (the copy is
-    // asynchronous: the host array must stay valid until the stream has run it)
+    // asynchronous: the host array must stay valid until the stream has run it). A counting scratch takes them to be on the device.
     const float* param(const float* p, size_t count) {
+        if (!h) return p;
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice) return p;
         (void)hipGetLastError();

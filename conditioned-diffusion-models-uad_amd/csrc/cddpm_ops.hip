@@ -1,12 +1,21 @@
 // The standalone operators of libcddpm_hip.so's C ABI (cddpm_op_* of include/cddpm.h): single kernels and small kernel groups behind
 // argument checks, what the training step (training.py, encoder_training.py) is sequenced from and what the kernel tests call. Host
 // code only. Every operator has one form: OP_CHECK (once per message), OP_PROLOGUE, temporaries from an OpScratch, launches,
-// OP_EPILOGUE (cddpm_ctx.h). The handle, the forward program and the reverse loop are in cddpm_api.hip.
+// OP_EPILOGUE (cddpm_ctx.h). An operator with shape-dependent temporaries states them ONCE, in a static *_scratch function over an
+// OpScratch: the operator runs it on its real scratch and gets the pointers, its exported size query (cddpm_op_*_scratch) runs it on a
+// counting scratch and returns the bytes. The handle, the forward program and the reverse loop are in cddpm_api.hip.
 #include "cddpm_ctx.h"
 
 #include <cmath>
 
 using namespace cddpm;
+
+// a size query: the operator's own request function, run on a scratch that only counts
+template <class Request> static size_t counted(Request&& request) {
+    OpScratch sc;
+    request(sc);
+    return sc.off;
+}
 
 extern "C" {
 
@@ -187,6 +196,15 @@ int cddpm_op_conv_gn(cddpm_handle h, const float* src0, int C0, const float* w_h
     OP_EPILOGUE_SYNC()
 }
 
+static void gn_coef_scratch(OpScratch& sc, int C0, bool two, int C1, int B, int HW, float*& rec0, float*& rec1) {
+    const int ns = gn_nsplit(B, HW);
+    rec0 = sc.n<float>((size_t)B * ns * C0 * 2);
+    rec1 = two ? sc.n<float>((size_t)B * ns * C1 * 2) : nullptr;
+}
+size_t cddpm_op_gn_coef_scratch(int C0, int has_src1, int C1, int B, int HW) {
+    float *rec0, *rec1;
+    return counted([&](OpScratch& sc) { gn_coef_scratch(sc, C0, has_src1 != 0, C1, B, HW, rec0, rec1); });
+}
 int cddpm_op_gn_coef(cddpm_handle h, const float* src0, int C0, const float* src1, int C1, const float* gamma_host,
                      const float* beta_host, const float* film_dev, float* coef_dev, int B, int HW, void* stream) {
     const int C = C0 + C1;
@@ -194,8 +212,8 @@ int cddpm_op_gn_coef(cddpm_handle h, const float* src0, int C0, const float* src
                 "cddpm_op_gn_coef: unsupported channels (each source <= 1024, together <= %d)", MAX_CONCAT_CHANNELS)
     const int ns = gn_nsplit(B, HW);
     OpScratch sc(h, s);
-    float* rec0 = sc.n<float>((size_t)B * ns * C0 * 2);
-    float* rec1 = src1 ? sc.n<float>((size_t)B * ns * C1 * 2) : nullptr;
+    float *rec0, *rec1;
+    gn_coef_scratch(sc, C0, src1 != nullptr, C1, B, HW, rec0, rec1);
     const float* g = sc.param(gamma_host, C);
     const float* bt = sc.param(beta_host, C);
     SCRATCH_CHECK(sc)
@@ -229,40 +247,58 @@ int cddpm_op_conv_dgrad(cddpm_handle h, const float* dy_dev, int Cout, const flo
     OP_EPILOGUE_SYNC()
 }
 
+static double* bias_grad_scratch(OpScratch& sc, int C) { return sc.n<double>((size_t)512 * C); }
+size_t cddpm_op_bias_grad_scratch(int64_t, int C) { return counted([&](OpScratch& sc) { bias_grad_scratch(sc, C); }); }
 int cddpm_op_bias_grad(cddpm_handle h, const float* dy_dev, int64_t npix, int C, float* db_dev, void* stream) {
     OP_PROLOGUE(PC_OTHER, 0.0, 0.0, !(!dy_dev || !db_dev || npix < 1 || C % 4 || C > 1024), "cddpm_op_bias_grad: bad arguments")
     OpScratch sc(h, s);
-    double* part = sc.n<double>((size_t)512 * C);
+    double* part = bias_grad_scratch(sc, C);
     SCRATCH_CHECK(sc)
     launch_bias_grad(dy_dev, npix, C, db_dev, part, s);
     OP_EPILOGUE()
 }
 
+static bool wgrad_shape_ok(int C0, int C1, int upsample, int Cout, int ksize, int B, int H, int W) {
+    const int Cin = C0 + C1;
+    return !((ksize != 1 && ksize != 3) || C0 <= 0 || C1 < 0 || Cin % 32 || (C1 > 0 && C0 % 32) || Cout <= 0 || Cout % 64 || H < 1 || W < 1 || B < 1 ||
+             (upsample && (C1 > 0 || (W & 1) || (H & 1))));
+}
+static float* wgrad_scratch(OpScratch& sc, const WgradPlan& pl, void*& images) {
+    float* part = sc.n<float>(pl.part_floats);
+    images = pl.image_units ? sc.get(pl.image_units * 16) : nullptr;
+    return part;
+}
+size_t cddpm_op_conv_wgrad_scratch(int C0, int C1, int upsample, int Cout, int ksize, int B, int H, int W, int precision) {
+    if (!wgrad_shape_ok(C0, C1, upsample, Cout, ksize, B, H, W) || (precision != 0 && precision != 16 && precision != 32)) return 0;
+    void* images;
+    const WgradPlan pl = conv_wgrad_plan(B, H, W, C0 + C1, Cout, ksize * ksize, precision ? precision : train_precision());
+    return counted([&](OpScratch& sc) { wgrad_scratch(sc, pl, images); });
+}
 int cddpm_op_conv_wgrad(cddpm_handle h, const float* x0_dev, int C0, const float* x1_dev, int C1, const float* coef_dev, int silu,
                         int upsample, const float* dy_dev, int Cout, int ksize, float* dw_dev, float* db_dev, int B, int H, int W,
                         void* stream) {
     const int Cin = C0 + C1, taps = ksize * ksize;
-    OP_CHECK(!((ksize != 1 && ksize != 3) || C0 <= 0 || C1 < 0 || Cin % 32 || (C1 > 0 && C0 % 32) || Cout <= 0 || Cout % 64 || H < 1 ||
-               W < 1 || B < 1 || (C1 > 0 && !x1_dev) || (upsample && (C1 > 0 || (W & 1) || (H & 1)))),
+    OP_CHECK(wgrad_shape_ok(C0, C1, upsample, Cout, ksize, B, H, W) && !(C1 > 0 && !x1_dev),
              "cddpm_op_conv_wgrad: unsupported shape (k %d, C0 %d, C1 %d, Cout %d, H %d)", ksize, C0, C1, Cout, H)
     OP_PROLOGUE(PC_WGRAD, 2.0 * B * H * W * (double)Cout * Cin * taps, 4.0 * B * (double)H * W * (Cin + Cout), x0_dev && dy_dev && dw_dev,
                 "cddpm_op_conv_wgrad: NULL argument")
-    const int P = conv_wgrad_parts(B, H, W, Cin, Cout, taps);
+    const WgradPlan pl = conv_wgrad_plan(B, H, W, Cin, Cout, taps, train_precision());
     OpScratch sc(h, s);
-    float* part = sc.n<float>((size_t)P * Cout * Cin * taps);
-    const size_t iu = conv_wgrad_image_units(B, H, W, Cin, Cout, taps);
-    void* images = iu ? sc.get(iu * 16) : nullptr;
+    void* images;
+    float* part = wgrad_scratch(sc, pl, images);
     SCRATCH_CHECK(sc)
-    launch_conv_wgrad(x0_dev, C0, x1_dev, C1, coef_dev, silu, upsample ? 1 : 0, dy_dev, B, H, W, Cout, taps, part, P, images, dw_dev, db_dev, s);
+    launch_conv_wgrad(x0_dev, C0, x1_dev, C1, coef_dev, silu, upsample ? 1 : 0, dy_dev, B, H, W, Cout, taps, pl, part, images, dw_dev, db_dev, s);
     OP_EPILOGUE()
 }
 
+static float* attention_backward_scratch(OpScratch& sc, int B, int N, int C) { return sc.n<float>((size_t)B * (C / 64) * N * 2); }
+size_t cddpm_op_attention_backward_scratch(int B, int N, int C) { return counted([&](OpScratch& sc) { attention_backward_scratch(sc, B, N, C); }); }
 int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
                                 void* stream) {
     OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_backward: C must be a multiple of 64")
     OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && da_dev && dqkv_dev, "cddpm_op_attention_backward: NULL argument")
     OpScratch sc(h, s);
-    float* stats = sc.n<float>((size_t)B * (C / 64) * N * 2);
+    float* stats = attention_backward_scratch(sc, B, N, C);
     SCRATCH_CHECK(sc)
     launch_attention_backward_flash(qkv_dev, da_dev, dqkv_dev, stats, B, N, C, s);
     OP_EPILOGUE()
@@ -273,18 +309,24 @@ int cddpm_op_attention_backward_p16(cddpm_handle h, const float* qkv_dev, const 
     OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_backward_p16: C must be a multiple of 64")
     OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && da_dev && dqkv_dev, "cddpm_op_attention_backward_p16: NULL argument")
     OpScratch sc(h, s);
-    float* stats = sc.n<float>((size_t)B * (C / 64) * N * 2);
+    float* stats = attention_backward_scratch(sc, B, N, C);
     SCRATCH_CHECK(sc)
     launch_attention_backward_p16(qkv_dev, da_dev, dqkv_dev, stats, B, N, C, s);
     OP_EPILOGUE()
 }
 
+static float* linear_backward_scratch(OpScratch& sc, int M, int N, int K, int silu_in) {
+    const size_t nscr = linear_backward_scratch_floats(M, N, K, silu_in);
+    return nscr ? sc.n<float>(nscr) : nullptr;
+}
+size_t cddpm_op_linear_backward_scratch(int M, int N, int K, int silu_in) {
+    return counted([&](OpScratch& sc) { linear_backward_scratch(sc, M, N, K, silu_in); });
+}
 int cddpm_op_linear_backward(cddpm_handle h, const float* x_dev, const float* w_dev, const float* dy_dev, int M, int N, int K,
                              int silu_in, float* dw_dev, float* db_dev, float* dx_dev, void* stream) {
     OP_PROLOGUE(PC_OTHER, 0.0, 0.0, M >= 1 && N >= 1 && K >= 1 && x_dev && w_dev && dy_dev && dw_dev, "cddpm_op_linear_backward: bad arguments")
     OpScratch sc(h, s);
-    const size_t nscr = linear_backward_scratch_floats(M, N, K, silu_in);
-    float* a = nscr ? sc.n<float>(nscr) : nullptr;
+    float* a = linear_backward_scratch(sc, M, N, K, silu_in);
     SCRATCH_CHECK(sc)
     launch_linear_backward(x_dev, w_dev, dy_dev, M, N, K, silu_in, a, dw_dev, db_dev, dx_dev, s);
     OP_EPILOGUE()
@@ -302,11 +344,13 @@ int cddpm_op_conv_in1(cddpm_handle h, const float* x_dev, const float* w_dev, co
     launch_conv_in1(x_dev, w_dev, b_dev, out_dev, B, H, W, C, s);
     OP_EPILOGUE()
 }
+static float* head_scratch(OpScratch& sc, int B, int H, int W) { return sc.n<float>((size_t)B * H * W * 9); }
+size_t cddpm_op_head_scratch(int B, int H, int W, int) { return counted([&](OpScratch& sc) { head_scratch(sc, B, H, W); }); }
 int cddpm_op_head(cddpm_handle h, const float* x_dev, const float* coef_dev, const float* w9_dev, float bias, const float* bias_dev,
                   float* out_dev, int B, int H, int W, int C, void* stream) {
     OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && coef_dev && w9_dev && out_dev && C % 32 == 0, "cddpm_op_head: bad arguments")
     OpScratch sc(h, s);
-    float* P = sc.n<float>((size_t)B * H * W * 9);
+    float* P = head_scratch(sc, B, H, W);
     SCRATCH_CHECK(sc)
     launch_head_dots(x_dev, coef_dev, w9_dev, P, B, H * W, C, s);
     launch_head_gather(P, bias, bias_dev, out_dev, B, H, W, s);
@@ -358,11 +402,13 @@ int cddpm_op_dropout_scale(cddpm_handle h, float* da_dev, uint64_t seed, uint32_
     OP_EPILOGUE()
 }
 
+static double* chan_image_corr_scratch(OpScratch& sc, int C) { return sc.n<double>((size_t)256 * C * 9); }
+size_t cddpm_op_chan_image_corr_scratch(int, int, int, int C) { return counted([&](OpScratch& sc) { chan_image_corr_scratch(sc, C); }); }
 int cddpm_op_chan_image_corr(cddpm_handle h, const float* t_dev, const float* coef_dev, int silu, const float* s_dev, int sign, float* dw_dev,
                              int B, int H, int W, int C, void* stream) {
     OP_PROLOGUE(PC_OTHER, 0.0, 0.0, t_dev && s_dev && dw_dev && C % 64 == 0 && (sign == 1 || sign == -1), "cddpm_op_chan_image_corr: bad arguments")
     OpScratch sc(h, s);
-    double* part = sc.n<double>((size_t)256 * C * 9);
+    double* part = chan_image_corr_scratch(sc, C);
     SCRATCH_CHECK(sc)
     launch_chan_image_corr(t_dev, coef_dev, silu, s_dev, sign, B, H, W, C, part, dw_dev, s);
     OP_EPILOGUE()
@@ -470,31 +516,50 @@ int cddpm_op_enc_pack_w(cddpm_handle h, const float* w_dev, int Cout, int Cin, i
     launch_enc_pack_w(w_dev, Cout, Cin, K * K, wf_dev, wd_dev, s);
     OP_EPILOGUE()
 }
+static bool enc_conv_shape_ok(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed) {
+    return B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (K == 1 || K == 3) && (stride == 1 || stride == 2) &&
+           (transposed ? (Cout % 16 == 0 && Cin % 64 == 0) : (Cin % 16 == 0 && Cout % 64 == 0));
+}
+static float* enc_conv_scratch(OpScratch& sc, int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed) {
+    const int Z = enc_conv_split(B, H, W, Cin, Cout, K, stride, transposed);      // split-K planes (1: the kernel writes dst itself)
+    if (Z == 1) return nullptr;
+    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+    return sc.n<float>((size_t)Z * B * (transposed ? (size_t)H * W * Cin : (size_t)Ho * Wo * Cout));
+}
+size_t cddpm_op_enc_conv_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed) {
+    if (!enc_conv_shape_ok(B, H, W, Cin, Cout, K, stride, transposed)) return 0;
+    return counted([&](OpScratch& sc) { enc_conv_scratch(sc, B, H, W, Cin, Cout, K, stride, transposed); });
+}
 int cddpm_op_enc_conv(cddpm_handle h, const float* src_dev, const float* w_img_dev, float* dst_dev, int B, int H, int W, int Cin, int Cout, int K,
                       int stride, int transposed, void* stream) {
     OP_PROLOGUE(PC_ENC, 0.0, 0.0,
-                src_dev && w_img_dev && dst_dev && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (K == 1 || K == 3) && (stride == 1 || stride == 2) &&
-                    (transposed ? (Cout % 16 == 0 && Cin % 64 == 0) : (Cin % 16 == 0 && Cout % 64 == 0)),
+                src_dev && w_img_dev && dst_dev && enc_conv_shape_ok(B, H, W, Cin, Cout, K, stride, transposed),
                 "cddpm_op_enc_conv: unsupported shape (contraction channels a multiple of 16, produced channels of 64; K 1|3, stride 1|2)")
-    const int Z = enc_conv_split(B, H, W, Cin, Cout, K, stride, transposed);
     OpScratch sc(h, s);
-    float* part = nullptr;
-    if (Z > 1) {
-        const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-        part = sc.n<float>((size_t)Z * B * (transposed ? (size_t)H * W * Cin : (size_t)Ho * Wo * Cout));
-        SCRATCH_CHECK(sc)
-    }
+    float* part = enc_conv_scratch(sc, B, H, W, Cin, Cout, K, stride, transposed);
+    SCRATCH_CHECK(sc)
     launch_enc_conv(src_dev, w_img_dev, dst_dev, B, H, W, Cin, Cout, K, stride, transposed, part, s);
     OP_EPILOGUE()
 }
+static bool enc_wgrad_shape_ok(int B, int H, int W, int Cin, int Cout, int K, int stride) {
+    return B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 64 == 0 && (K == 1 || K == 3) && (stride == 1 || stride == 2);
+}
+static float* enc_wgrad_scratch(OpScratch& sc, int B, int H, int W, int Cin, int Cout, int K, int stride, int& P) {
+    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+    P = enc_wgrad_parts(B, Ho, Wo, Cin, Cout, K);
+    return sc.n<float>((size_t)P * K * K * Cin * Cout);
+}
+size_t cddpm_op_enc_conv_wgrad_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride) {
+    if (!enc_wgrad_shape_ok(B, H, W, Cin, Cout, K, stride)) return 0;
+    int P;
+    return counted([&](OpScratch& sc) { enc_wgrad_scratch(sc, B, H, W, Cin, Cout, K, stride, P); });
+}
 int cddpm_op_enc_conv_wgrad(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, int Cin, int Cout, int K,
                             int stride, void* stream) {
-    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && dz_dev && dw_dev && B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 64 == 0 && (K == 1 || K == 3) &&
-                    (stride == 1 || stride == 2), "cddpm_op_enc_conv_wgrad: unsupported shape")
-    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-    const int P = enc_wgrad_parts(B, Ho, Wo, Cin, Cout, K);
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && dz_dev && dw_dev && enc_wgrad_shape_ok(B, H, W, Cin, Cout, K, stride), "cddpm_op_enc_conv_wgrad: unsupported shape")
     OpScratch sc(h, s);
-    float* part = sc.n<float>((size_t)P * K * K * Cin * Cout);
+    int P;
+    float* part = enc_wgrad_scratch(sc, B, H, W, Cin, Cout, K, stride, P);
     SCRATCH_CHECK(sc)
     launch_enc_wgrad(x_dev, dz_dev, part, P, dw_dev, B, H, W, Cin, Cout, K, stride, s);
     OP_EPILOGUE()
@@ -504,21 +569,31 @@ int cddpm_op_enc_stem(cddpm_handle h, const float* x_dev, const float* w_dev, fl
     launch_enc_stem_fwd(x_dev, w_dev, z_dev, B, H, W, s);
     OP_EPILOGUE()
 }
+static double* enc_stem_wgrad_scratch(OpScratch& sc) { return sc.n<double>((size_t)32 * 49 * 64); }
+size_t cddpm_op_enc_stem_wgrad_scratch(int, int, int) { return counted([](OpScratch& sc) { enc_stem_wgrad_scratch(sc); }); }
 int cddpm_op_enc_stem_wgrad(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, void* stream) {
     OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && dz_dev && dw_dev && B > 0 && H > 0 && W > 0, "cddpm_op_enc_stem_wgrad: bad arguments")
     OpScratch sc(h, s);
-    double* part = sc.n<double>((size_t)32 * 49 * 64);
+    double* part = enc_stem_wgrad_scratch(sc);
     SCRATCH_CHECK(sc)
     launch_enc_stem_wgrad(x_dev, dz_dev, part, dw_dev, B, H, W, s);
     OP_EPILOGUE()
 }
+static double* enc_bn_scratch(OpScratch& sc, int64_t N, int C, bool backward, float*& k) {
+    double* part = sc.n<double>((size_t)enc_bn_chunks(N) * 2 * C);
+    k = backward ? sc.n<float>((size_t)2 * C) : nullptr;
+    return part;
+}
+size_t cddpm_op_enc_bn_forward_scratch(int64_t N, int, int C) { float* k; return counted([&](OpScratch& sc) { enc_bn_scratch(sc, N, C, false, k); }); }
+size_t cddpm_op_enc_bn_backward_scratch(int64_t N, int, int C) { float* k; return counted([&](OpScratch& sc) { enc_bn_scratch(sc, N, C, true, k); }); }
 int cddpm_op_enc_bn_forward(cddpm_handle h, const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* sample_scale_dev,
                             const float* res_dev, int relu, float eps, float momentum, float* run_mean_dev, float* run_var_dev, float* mean_rstd_dev,
                             float* y_dev, int64_t N, int HW, int C, void* stream) {
     OP_PROLOGUE(PC_ENC, 0.0, 0.0, z_dev && gamma_dev && beta_dev && mean_rstd_dev && y_dev && N > 0 && HW > 0 && C > 0 && C % 64 == 0 && (!run_mean_dev == !run_var_dev),
                 "cddpm_op_enc_bn_forward: bad arguments (C a multiple of 64)")
     OpScratch sc(h, s);
-    double* part = sc.n<double>((size_t)enc_bn_chunks(N) * 2 * C);
+    float* k;
+    double* part = enc_bn_scratch(sc, N, C, false, k);
     SCRATCH_CHECK(sc)
     launch_enc_bn_forward(z_dev, gamma_dev, beta_dev, sample_scale_dev, res_dev, relu, eps, momentum, run_mean_dev, run_var_dev, mean_rstd_dev, y_dev,
                           part, N, HW, C, s);
@@ -530,8 +605,8 @@ int cddpm_op_enc_bn_backward(cddpm_handle h, const float* z_dev, const float* y_
     OP_PROLOGUE(PC_ENC, 0.0, 0.0, z_dev && dy_dev && mean_rstd_dev && gamma_dev && dz_dev && dgamma_dev && dbeta_dev && (!relu || y_dev) && N > 0 && HW > 0 && C > 0 &&
                     C % 64 == 0, "cddpm_op_enc_bn_backward: bad arguments (C a multiple of 64)")
     OpScratch sc(h, s);
-    double* part = sc.n<double>((size_t)enc_bn_chunks(N) * 2 * C);
-    float* k = sc.n<float>((size_t)2 * C);
+    float* k;
+    double* part = enc_bn_scratch(sc, N, C, true, k);
     SCRATCH_CHECK(sc)
     launch_enc_bn_backward(z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, sample_scale_dev, relu, dz_dev, dres_dev, dgamma_dev, dbeta_dev, k, part, N,
                            HW, C, s);
@@ -552,6 +627,24 @@ int cddpm_op_enc_avgpool(cddpm_handle h, const float* x_dev, float* g_dev, int B
     OP_EPILOGUE()
 }
 
+// the statistics records of x (swept here when the call brings none), the parameter vectors when they come from the host, planes,
+// per-(sample, channel) sums, fp64 partial sums
+static void gn_silu_backward_scratch(OpScratch& sc, bool has_rec, int B, int HW, int C, const float*& gamma, const float*& beta, float*& rec,
+                                     float*& planes, float*& out_bc, double*& part) {
+    const int ns = gn_nsplit(B, HW);
+    rec = has_rec ? nullptr : sc.n<float>((size_t)B * ns * C * 2);
+    gamma = sc.param(gamma, C);
+    beta = sc.param(beta, C);
+    planes = sc.n<float>((size_t)4 * B * C);
+    out_bc = sc.n<float>((size_t)4 * B * C);
+    part = sc.n<double>((size_t)B * ns * C * 2);
+}
+size_t cddpm_op_gn_silu_backward_scratch(int has_rec, int B, int HW, int C) {
+    const float *g = nullptr, *bt = nullptr;
+    float *rec, *planes, *out_bc;
+    double* part;
+    return counted([&](OpScratch& sc) { gn_silu_backward_scratch(sc, has_rec != 0, B, HW, C, g, bt, rec, planes, out_bc, part); });
+}
 int cddpm_op_gn_silu_backward(cddpm_handle h, const float* x_dev, const float* x1_dev, int C1, const float* da_dev, const float* gamma_host,
                               const float* beta_host, const float* film_dev, int silu, float* dx_dev, float* dx1_dev, float* dgamma_dev,
                               float* dbeta_dev, float* dfilm_dev, const float* rec_dev, int nrec, const float* add_dev, int B, int HW, int C,
@@ -564,12 +657,10 @@ int cddpm_op_gn_silu_backward(cddpm_handle h, const float* x_dev, const float* x
                 "cddpm_op_gn_silu_backward: NULL argument")
     const int ns = gn_nsplit(B, HW);
     OpScratch sc(h, s);
-    float* rec = rec_dev ? nullptr : sc.n<float>((size_t)B * ns * C * 2);
-    const float* g = sc.param(gamma_host, C);
-    const float* bt = sc.param(beta_host, C);
-    float* planes = sc.n<float>((size_t)4 * B * C);
-    float* out_bc = sc.n<float>((size_t)4 * B * C);
-    double* part = sc.n<double>((size_t)B * ns * C * 2);
+    const float *g = gamma_host, *bt = beta_host;
+    float *rec, *planes, *out_bc;
+    double* part;
+    gn_silu_backward_scratch(sc, rec_dev != nullptr, B, HW, C, g, bt, rec, planes, out_bc, part);
     SCRATCH_CHECK(sc)
     if (!rec_dev) launch_gn_partial(x_dev, C, B, HW, ns, rec, s);      // statistics records of x: given (kept from the forward pass) or swept here
     launch_gn_bwd_planes(rec_dev ? rec_dev : rec, rec_dev ? nrec : ns, g, bt, film_dev, B, C, HW, planes, s);

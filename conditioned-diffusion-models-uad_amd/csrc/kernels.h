@@ -194,14 +194,22 @@ void launch_simplex(unsigned short* out, long long seed, int B, int H, int W, in
 // ------------------------------------------------------------------------------------------------
 void launch_gn_bwd_planes(const float* rec, int nrec, const float* gamma, const float* beta, const float* film, int B, int C, int HW,
                           float* planes, hipStream_t stream);
-// conv wgrad (3x3 pad 1, or 1x1): dw [Cout][Cin][k][k] (PyTorch layout), db [Cout] or nullptr; input = cat[x0 (C0), x1 (C1)];
-// part: scratch of conv_wgrad_parts() * Cout * Cin * taps floats. Cin (and C0 when C1 > 0) multiple of 32, Cout of 64
+// conv wgrad (3x3 pad 1, or 1x1): dw [Cout][Cin][k][k] (PyTorch layout), db [Cout] or nullptr; input = cat[x0 (C0), x1 (C1)].
+// Cin (and C0 when C1 > 0) multiple of 32, Cout of 64. conv_wgrad_plan states ONCE what a call runs and takes (precision: 16 | 32):
+// `part` holds part_floats floats, `images` image_units 16-byte units (0: the call has none) = the activation's k-image, dy's, the
+// bias gradient's bias_rows partial rows of Cout floats and their bias_rows2 second-level rows.
 int train_precision();                 // 32 (default) or 16: see train_kernels.hip
 int set_train_precision(int bits);    // returns the previous value
-int conv_wgrad_parts(int B, int H, int W, int Cin, int Cout, int taps);
-size_t conv_wgrad_image_units(int B, int H, int W, int Cin, int Cout, int taps);   // 16-byte units of `images` (0: not used by this call)
+struct WgradPlan {
+    bool img;                          // the two-pass kernels over k-images; else the single-pass 1x1 kernel (Cin % 64 == 32)
+    int CK, NS, G, P;                  // input channels per tile, fp16 terms per operand, batch groups of 8, partial tiles
+    size_t part_floats;
+    size_t act_units, dy_units, image_units;
+    int bias_rows, bias_rows2;
+};
+WgradPlan conv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int taps, int precision);
 void launch_conv_wgrad(const float* x0, int C0, const float* x1, int C1, const float* coef, int silu, int up, const float* dy, int B, int H,
-                       int W, int Cout, int taps, float* part, int P, void* images, float* dw, float* db, hipStream_t stream);
+                       int W, int Cout, int taps, const WgradPlan& pl, float* part, void* images, float* dw, float* db, hipStream_t stream);
 void launch_bias_grad(const float* dy, long long npix, int C, float* db, double* scratch /* 512 * C doubles */, hipStream_t stream);
 // QKVAttention backward (attention.hip, flash-style): qkv [B][N][3C] (q | k | v), da [B][N][C] -> dqkv [B][N][3C];
 // stats = B * heads * N * 2 floats of scratch

@@ -254,7 +254,7 @@ struct WgradArgs {
     int up;                // 1: the conv input is the nearest x2 upsampling of act(x): x is [B,H/2,W/2,C], read at (y >> 1, x >> 1)
     const float* dy;       // NHWC [B,H,W,Cout]
     int B, H, W, Cout;
-    float* part;           // [P][Cout/64][Cin/CK][64 co][TAPS][CK ci]
+    float* part;           // [P][Cout/64][Cin/32][64 co][32 ci]
     int P;
 };
 
@@ -271,20 +271,18 @@ __device__ __forceinline__ float silu_t(float v) { return v * sigmoid_t(v); }
 // float4 rows, one per sample), applies GroupNorm / FiLM / SiLU, splits, and writes for each of its 4 channels ONE 16-byte unit
 // [8 samples] to LDS at [channel][pixel]: no scattered 2-byte stores, no shuffles, and a tap is a plain (aligned) pixel offset.
 // Channel rows are padded by one unit so that the 16 channels a fragment read touches fall into distinct bank groups.
-// Workgroup = 4 waves on a 64 co x 32 ci (x 9 taps) tile, pixel tile 2 x 8 (+ halo), one batch group at a time: 80 KB of LDS, two
-// workgroups per CU -- one stages while the other multiplies. Wave = (co 32-block) x (taps 0..4 | 5..8) [3x3] or (ci 16-half) [1x1].
+// conv_wgrad_x_kernel is the single-pass form of this, for what the image kernels below do not serve: the 1x1 convolution whose Cin
+// is an odd multiple of 32. Workgroup = 4 waves on a 64 co x 32 ci tile, pixel tile 2 x 8, one batch group at a time, two
+// workgroups per CU -- one stages while the other multiplies. Wave = (co 32-block) x (ci 16-half).
 // ------------------------------------------------------------------------------------------------------------------
 typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
 typedef float wg_v4f __attribute__((ext_vector_type(4)));
 
-template <int TAPS, int NS>
+template <int NS>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_x_kernel(const WgradArgs a, int G) {
-    constexpr int PAD = (TAPS == 9) ? 1 : 0;
     constexpr int TX = 8, TY = 2, NPX = TX * TY;
-    constexpr int PW = TX + 2 * PAD, PH = TY + 2 * PAD, NHP = PW * PH;          // 10 x 4 = 40 halo pixels | 16
     constexpr int CK = 32;
-    constexpr int APITCH = NHP + 1, DPITCH = NPX + 1;                           // 16-byte units per channel row
-    constexpr int NT = (TAPS == 9) ? 5 : 1, NJ = (TAPS == 9) ? 2 : 1;          // taps and ci 16-blocks per wave
+    constexpr int APITCH = NPX + 1, DPITCH = NPX + 1;                           // 16-byte units per channel row
     __shared__ uint4 actL[NS][CK * APITCH];
     __shared__ uint4 dyL[NS][64 * DPITCH];
     __shared__ float coefL[3][8][CK];
@@ -299,18 +297,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x_kernel(const WgradArgs a,
     const int tilesX = (a.W + TX - 1) / TX, tilesY = (a.H + TY - 1) / TY, tpg = tilesX * tilesY;
     const int ntile = G * tpg;
     const int t0 = (int)((long long)ntile * p / a.P), t1 = (int)((long long)ntile * (p + 1) / a.P);
-    const int tapbase = (TAPS == 9) ? tg * 5 : 0, ntap = (TAPS == 9) ? (tg ? 4 : 5) : 1;
     const int ch0 = chunk * CK;
     const float* xsrc = (ch0 < a.C0) ? a.x0 : a.x1;
     const int Cs = (ch0 < a.C0) ? a.C0 : a.C1, cs0 = (ch0 < a.C0) ? ch0 : ch0 - a.C0;
     const int sH = a.up ? a.H >> 1 : a.H, sW = a.up ? a.W >> 1 : a.W;
-    wg_v4f acc[2][NJ][NT];
+    wg_v4f acc[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[i][j][t] = wg_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 2; ++i) acc[i] = wg_v4f{0.f, 0.f, 0.f, 0.f};
     int cur_grp = -1;
     for (int tile = t0; tile < t1; ++tile) {
         const int grp = tile / tpg, tt = tile - grp * tpg;
@@ -349,11 +342,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x_kernel(const WgradArgs a,
                 if (NS == 2) dyL[NS - 1][(4 * q + c) * DPITCH + n] = __builtin_bit_cast(uint4, m);
             }
         }
-        // activated patch: NHP pixels x 8 channel quads
-        for (int task = tid; task < NHP * 8; task += 256) {
+        // activated tile: 16 pixels x 8 channel quads
+        for (int task = tid; task < NPX * 8; task += 256) {
             const int hp = task >> 3, q = task & 7;
-            const int gy = y0 - PAD + hp / PW, gx = x0 - PAD + hp % PW;
-            const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+            const int gy = y0 + hp / TX, gx = x0 + hp % TX;
+            const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;       // (the lower bounds always hold: kept, so that the kernel compiles to what it was)
             const int sy = a.up ? gy >> 1 : gy, sx = a.up ? gx >> 1 : gx;
             float4 v[8];
 #pragma unroll
@@ -370,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x_kernel(const WgradArgs a,
                     float f = c == 0 ? v[i].x : c == 1 ? v[i].y : c == 2 ? v[i].z : v[i].w;
                     f = (f - coefL[0][i][4 * q + c]) * coefL[1][i][4 * q + c] + coefL[2][i][4 * q + c];
                     if (a.silu) f = silu_t(f);
-                    if (!(in && grp * 8 + i < a.B)) f = 0.f;          // padding pixels and samples past the batch contribute nothing
+                    if (!(in && grp * 8 + i < a.B)) f = 0.f;          // pixels past the image and samples past the batch contribute nothing
                     h[i] = (_Float16)f;
                     m[i] = (_Float16)(f - (float)h[i]);
                 }
@@ -379,56 +372,35 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x_kernel(const WgradArgs a,
             }
         }
         __syncthreads();
-        // 4 k-steps of 4 pixels x 8 samples; A = dy[co][k], B = act[k + tap][ci]
+        // 4 k-steps of 4 pixels x 8 samples; A = dy[co][k], B = act[k][ci]
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int ty = ks >> 1, tx = 4 * (ks & 1) + g;
-            wg_f16x8 fa[NS][2];
+            wg_f16x8 fa[NS][2], fb[NS];
 #pragma unroll
             for (int s2 = 0; s2 < NS; ++s2)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) fa[s2][i] = __builtin_bit_cast(wg_f16x8, dyL[s2][(cw * 32 + i * 16 + r) * DPITCH + ty * TX + tx]);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                if (t < ntap) {
-                    const int tap = tapbase + t, ky = (TAPS == 9) ? tap / 3 : 0, kx = (TAPS == 9) ? tap - 3 * ky : 0;
-                    wg_f16x8 fb[NS][NJ];
+            for (int s2 = 0; s2 < NS; ++s2) fb[s2] = __builtin_bit_cast(wg_f16x8, actL[s2][(tg * 16 + r) * APITCH + ty * TX + tx]);
 #pragma unroll
-                    for (int s2 = 0; s2 < NS; ++s2)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) {
-                            const int ci = (TAPS == 9) ? j * 16 + r : tg * 16 + r;
-                            fb[s2][j] = __builtin_bit_cast(wg_f16x8, actL[s2][ci * APITCH + (ty + ky) * PW + tx + kx]);
-                        }
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) {
-                            if (NS == 2) {
-                                acc[i][j][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[NS - 1][i], fb[0][j], acc[i][j][t], 0, 0, 0);
-                                acc[i][j][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[0][i], fb[NS - 1][j], acc[i][j][t], 0, 0, 0);
-                            }
-                            acc[i][j][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[0][i], fb[0][j], acc[i][j][t], 0, 0, 0);
-                        }
+            for (int i = 0; i < 2; ++i) {
+                if (NS == 2) {
+                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[NS - 1][i], fb[0], acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[0][i], fb[NS - 1], acc[i], 0, 0, 0);
                 }
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[0][i], fb[0], acc[i], 0, 0, 0);
             }
         }
     }
-    // partial tile [64 co][TAPS][32 ci]; D row = co = 4 g + e, column = ci = r
-    float* o = a.part + ((((size_t)p * ncb + cb) * nchunk + chunk) * 64) * TAPS * CK;
+    // partial tile [64 co][32 ci]; D row = co = 4 g + e, column = ci = r
+    float* o = a.part + ((((size_t)p * ncb + cb) * nchunk + chunk) * 64) * CK;
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
-        if (t < ntap) {
-            const int tap = tapbase + t;
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int co = cw * 32 + i * 16 + 4 * g + e, ci = (TAPS == 9) ? j * 16 + r : tg * 16 + r;
-                        o[((size_t)co * TAPS + tap) * CK + ci] = acc[i][j][t][e];
-                    }
+        for (int e = 0; e < 4; ++e) {
+            const int co = cw * 32 + i * 16 + 4 * g + e, ci = tg * 16 + r;
+            o[(size_t)co * CK + ci] = acc[i][e];
         }
 }
 
@@ -731,14 +703,13 @@ __global__ __launch_bounds__(256) void bias_fold_f32_kernel(const float* __restr
     }
 }
 // rows -> db in one launch (few rows) or two (row ranges of 128 across workgroups first: a 4096-row fold on C / 16 workgroups took 30 us);
-// `rows` is overwritten by the intermediate partial rows (its first ceil(nrow / 128) rows)
-static void bias_fold_rows(float* rows, int nrow, int C, float* db, hipStream_t stream) {
+// `rows` is followed by room for the nr2 = ceil(nrow / 128) intermediate partial rows (conv_wgrad_plan counts them)
+static void bias_fold_rows(float* rows, int nrow, int nr2, int C, float* db, hipStream_t stream) {
     if (nrow > 256) {
-        const int nr = (nrow + 127) / 128;
         // (the ranges run concurrently: the partial rows go BEHIND the input rows, not over them)
         float* tmp = rows + (size_t)nrow * C;
-        hipLaunchKernelGGL(bias_fold_f32_kernel, dim3((C + 15) / 16, nr), dim3(256), 0, stream, rows, nrow, 128, C, tmp);
-        hipLaunchKernelGGL(bias_fold_f32_kernel, dim3((C + 15) / 16, 1), dim3(256), 0, stream, tmp, nr, nr, C, db);
+        hipLaunchKernelGGL(bias_fold_f32_kernel, dim3((C + 15) / 16, nr2), dim3(256), 0, stream, rows, nrow, 128, C, tmp);
+        hipLaunchKernelGGL(bias_fold_f32_kernel, dim3((C + 15) / 16, 1), dim3(256), 0, stream, tmp, nr2, nr2, C, db);
     } else {
         hipLaunchKernelGGL(bias_fold_f32_kernel, dim3((C + 15) / 16, 1), dim3(256), 0, stream, rows, nrow, nrow, C, db);
     }
@@ -755,77 +726,79 @@ static void bias_grad_run(const float* dy, long long npix, int C, float* db, dou
     hipLaunchKernelGGL(bias_grad_fold_kernel, dim3((C + 15) / 16), dim3(256), 0, stream, scratch, nchunk, C, db);
 }
 
-int conv_wgrad_parts(int B, int H, int W, int Cin, int Cout, int taps) {
-    // enough workgroups for two per CU, at most one tile each, at least 1
-    // mirrors launch_conv_wgrad's choice of kernel: tiles of (8 samples) x (2 x 8 pixels); chunks of 32 input channels (3x3, and the
-    // single-pass 1x1 fallback) or 64 (1x1 over images)
-    const bool img = (taps == 9 || Cin % 64 == 0);
-    const int ntile = ((B + 7) / 8) * ((H + 1) / 2) * ((W + 7) / 8);
-    const int per = (Cout / 64) * (Cin / ((taps == 9 || !img) ? 32 : 64));
+// The one plan of a weight gradient: which kernel, how many partial tiles, what the call takes from its scratch and where each piece
+// lies. cddpm_op_conv_wgrad, its size query and launch_conv_wgrad all read it; nothing else decides any of it.
+WgradPlan conv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int taps, int precision) {
+    WgradPlan pl;
+    // two passes over k-images (every 3x3, and the 1x1 whose Cin is a multiple of 64), else the single-pass 1x1 kernel
+    pl.img = (taps == 9 || Cin % 64 == 0);
+    pl.CK = (taps == 1 && pl.img) ? 64 : 32;       // input channels of a workgroup's tile
+    pl.NS = precision == 16 ? 1 : 2;                // fp16 terms per operand: plain fp16 (precision 16) or the two-term split
+    pl.G = (B + 7) / 8;                             // batch groups of 8 samples
+    // enough workgroups for two per CU, at most one (8 samples) x (2 x 8 pixels) tile each, at least 1
+    const int ntile = pl.G * ((H + 1) / 2) * ((W + 7) / 8);
+    const int per = (Cout / 64) * (Cin / pl.CK);
     int P = (512 + per - 1) / per;
     if (P > ntile) P = ntile;
     if (P > 64) P = 64;
     if (P < 1) P = 1;
-    if (img) P = (P + 7) & ~7;      // the two-pass kernel spreads its pixel ranges over the 8 XCDs
-    return P;
-}
-
-// scratch of the two-pass 3x3 family beyond the partial tiles: the two k-images, in 16-byte units (0: this call does not use them)
-size_t conv_wgrad_image_units(int B, int H, int W, int Cin, int Cout, int taps) {
-    if (taps == 1 && Cin % 64) return 0;
-    // + the bias gradient's partial rows written by the dy image pass: [(HW / 8 rounded up) * G][Cout] floats
-    const size_t bias_rows = (size_t)((H * W + 7) / 8) * ((B + 7) / 8);
-    const size_t bias_units = ((bias_rows + (bias_rows + 127) / 128) * Cout + 3) / 4;       // + the second-level partial rows behind them
-    return (size_t)(train_precision() == 16 ? 1 : 2) * ((B + 7) / 8) * (size_t)(Cin + Cout) * H * W + bias_units;
+    if (pl.img) P = (P + 7) & ~7;      // the two-pass kernel spreads its pixel ranges over the 8 XCDs
+    pl.P = P;
+    pl.part_floats = (size_t)P * Cout * Cin * taps;
+    pl.act_units = pl.dy_units = pl.image_units = 0;
+    pl.bias_rows = pl.bias_rows2 = 0;
+    if (pl.img) {
+        pl.act_units = (size_t)pl.NS * pl.G * Cin * H * W;
+        pl.dy_units = (size_t)pl.NS * pl.G * Cout * H * W;
+        // behind the two images: the bias gradient's partial rows written by the dy image pass, [(HW / 8 rounded up) * G][Cout]
+        // floats, and the second-level partial rows behind them
+        pl.bias_rows = ((H * W + 7) / 8) * pl.G;
+        pl.bias_rows2 = (pl.bias_rows + 127) / 128;
+        pl.image_units = pl.act_units + pl.dy_units + ((size_t)(pl.bias_rows + pl.bias_rows2) * Cout + 3) / 4;
+    }
+    return pl;
 }
 
 void launch_conv_wgrad(const float* x0, int C0, const float* x1, int C1, const float* coef, int silu, int up, const float* dy, int B, int H,
-                       int W, int Cout, int taps, float* part, int P, void* images, float* dw, float* db, hipStream_t stream) {
-    WgradArgs a;
-    a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.coef = coef; a.silu = silu; a.up = up; a.dy = dy; a.B = B; a.H = H; a.W = W; a.Cout = Cout;
-    a.part = part; a.P = P;
+                       int W, int Cout, int taps, const WgradPlan& pl, float* part, void* images, float* dw, float* db, hipStream_t stream) {
     const int Cin = C0 + C1;
-    const int NS = train_precision() == 16 ? 1 : 2;     // fp16 terms per operand: plain fp16 (precision 16) or the two-term split
-    const int G = (B + 7) / 8;
-    int CK = 32;
-    if (taps == 9 || Cin % 64 == 0) {
+    const unsigned grid = (unsigned)(pl.P * (Cout / 64) * (Cin / pl.CK));
+    if (pl.img) {
         // pass 1: the two k-images; pass 2: the GEMM over them
         uint4* aimg = static_cast<uint4*>(images);
-        uint4* dimg = aimg + (size_t)NS * G * Cin * H * W;
+        uint4* dimg = aimg + pl.act_units;
         ImageArgs ia;
-        ia.x0 = x0; ia.x1 = x1; ia.C0 = C0; ia.C1 = C1; ia.coef = coef; ia.silu = silu; ia.up = up; ia.B = B; ia.H = H; ia.W = W; ia.G = G;
-        ia.img = aimg; ia.NS = NS; ia.bsum = nullptr;
-        hipLaunchKernelGGL(wgrad_image_kernel, dim3((H * W + 7) / 8, (Cin + 127) / 128, G), dim3(256), 0, stream, ia);
+        ia.x0 = x0; ia.x1 = x1; ia.C0 = C0; ia.C1 = C1; ia.coef = coef; ia.silu = silu; ia.up = up; ia.B = B; ia.H = H; ia.W = W; ia.G = pl.G;
+        ia.img = aimg; ia.NS = pl.NS; ia.bsum = nullptr;
+        hipLaunchKernelGGL(wgrad_image_kernel, dim3((H * W + 7) / 8, (Cin + 127) / 128, pl.G), dim3(256), 0, stream, ia);
         ia.x0 = dy; ia.x1 = nullptr; ia.C0 = Cout; ia.C1 = 0; ia.coef = nullptr; ia.silu = 0; ia.up = 0; ia.img = dimg;
-        float* bsum = reinterpret_cast<float*>(dimg + (size_t)NS * G * Cout * H * W);       // behind the two images (conv_wgrad_image_units)
+        float* bsum = reinterpret_cast<float*>(dimg + pl.dy_units);
         ia.bsum = db ? bsum : nullptr;
-        hipLaunchKernelGGL(wgrad_image_kernel, dim3((H * W + 7) / 8, (Cout + 127) / 128, G), dim3(256), 0, stream, ia);
+        hipLaunchKernelGGL(wgrad_image_kernel, dim3((H * W + 7) / 8, (Cout + 127) / 128, pl.G), dim3(256), 0, stream, ia);
         if (db) {       // the bias gradient from the rows the pass just wrote: dy is not read again
-            bias_fold_rows(bsum, ((H * W + 7) / 8) * G, Cout, db, stream);
+            bias_fold_rows(bsum, pl.bias_rows, pl.bias_rows2, Cout, db, stream);
             db = nullptr;
         }
         WgradImgArgs w;
-        w.act = aimg; w.dy = dimg; w.Cin = Cin; w.Cout = Cout; w.H = H; w.W = W; w.G = G; w.part = part; w.P = P;
-        CK = taps == 9 ? 32 : 64;
-        const unsigned grid = (unsigned)(P * (Cout / 64) * (Cin / CK));
+        w.act = aimg; w.dy = dimg; w.Cin = Cin; w.Cout = Cout; w.H = H; w.W = W; w.G = pl.G; w.part = part; w.P = pl.P;
         if (taps == 9) {
-            if (NS == 2) hipLaunchKernelGGL((conv_wgrad_img_kernel<9, 2>), dim3(grid), dim3(256), 0, stream, w);
-            else         hipLaunchKernelGGL((conv_wgrad_img_kernel<9, 1>), dim3(grid), dim3(256), 0, stream, w);
+            if (pl.NS == 2) hipLaunchKernelGGL((conv_wgrad_img_kernel<9, 2>), dim3(grid), dim3(256), 0, stream, w);
+            else            hipLaunchKernelGGL((conv_wgrad_img_kernel<9, 1>), dim3(grid), dim3(256), 0, stream, w);
         } else {
-            if (NS == 2) hipLaunchKernelGGL((conv_wgrad_img_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, w);
-            else         hipLaunchKernelGGL((conv_wgrad_img_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, w);
+            if (pl.NS == 2) hipLaunchKernelGGL((conv_wgrad_img_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, w);
+            else            hipLaunchKernelGGL((conv_wgrad_img_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, w);
         }
     } else {
-        const unsigned grid = (unsigned)(P * (Cout / 64) * (Cin / 32));
-        if (NS == 1) hipLaunchKernelGGL((conv_wgrad_x_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, a, G);
-        else           hipLaunchKernelGGL((conv_wgrad_x_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, a, G);
+        WgradArgs a;
+        a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.coef = coef; a.silu = silu; a.up = up; a.dy = dy; a.B = B; a.H = H; a.W = W; a.Cout = Cout;
+        a.part = part; a.P = pl.P;
+        if (pl.NS == 1) hipLaunchKernelGGL((conv_wgrad_x_kernel<1>), dim3(grid), dim3(256), 0, stream, a, pl.G);
+        else            hipLaunchKernelGGL((conv_wgrad_x_kernel<2>), dim3(grid), dim3(256), 0, stream, a, pl.G);
     }
     const long long n = (long long)Cout * Cin * taps;
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, part, P, Cout, Cin, taps, CK, dw);
-    if (db) {   // the partial tiles are folded by now (stream order): their memory serves as the bias sum's scratch
-        const size_t part_floats = (size_t)P * Cout * Cin * taps;
-        bias_grad_run(dy, (long long)B * H * W, Cout, db, reinterpret_cast<double*>(part), bias_grad_chunks((long long)B * H * W, Cout, part_floats), stream);
-    }
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, part, pl.P, Cout, Cin, taps, pl.CK, dw);
+    if (db)     // the partial tiles are folded by now (stream order): their memory serves as the bias sum's scratch
+        bias_grad_run(dy, (long long)B * H * W, Cout, db, reinterpret_cast<double*>(part), bias_grad_chunks((long long)B * H * W, Cout, pl.part_floats), stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

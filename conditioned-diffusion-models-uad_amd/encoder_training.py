@@ -6,7 +6,8 @@ training_step (src/models/DDPM_2D.py:114-135; Adam over self.parameters(), :305-
 
 Same construction as training.UNetTrainer: Python sequencing C-ABI operators (include/cddpm.h, "training-mode operators of the context
 encoder"; csrc/encoder_train.hip), one flat fp32 parameter buffer / gradient buffer / Adam state, weight images re-packed on the device
-after every update. Parity: unpinned like the encoder's forward (timm is not in the image): checked against float64 autograd through
+after every update. The operators run on the UNet trainer's handles; what they take from its arenas is a function of the geometry
+(operator_scratch_bytes), which that trainer sizes its arenas for. Parity: unpinned like the encoder's forward (timm is not in the image): checked against float64 autograd through
 oracle/encoder_oracle.py's restatement (tests/test_gpu_encoder_training.py)."""
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ from typing import Dict, Optional
 
 import torch
 
+from ._lib import largest_calls
 from .engine import _stream_ptr
 
 STAGES = ((64, 3), (128, 4), (256, 6), (512, 3))
@@ -25,10 +27,46 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def operator_calls(B, H, W, cond_dim=128):
+    """the operator calls of the ResNet-50's training step (EncoderTrainer.forward / backward) on a [B, 1, H, W] batch that take
+    temporaries from an arena, as (operator, arguments of its size query cddpm_op_<operator>_scratch, include/cddpm.h). The network
+    is fixed, so they are a function of the geometry."""
+    def bn(c, h, w):
+        yield "enc_bn_forward", (B * h * w, h * w, c)
+        yield "enc_bn_backward", (B * h * w, h * w, c)
+
+    yield "enc_stem_wgrad", (B, H, W)
+    h, w = (H + 1) // 2, (W + 1) // 2              # the stem's stride
+    yield from bn(64, h, w)
+    h, w = (h + 1) // 2, (w + 1) // 2              # the max pool's
+    cin = 64
+    for s, (planes, nblocks) in enumerate(STAGES):
+        for i in range(nblocks):
+            st = 2 if (i == 0 and s > 0) else 1
+            ho, wo = (h + st - 1) // st, (w + st - 1) // st
+            convs = [(planes, cin, 1, 1, h, w), (planes, planes, 3, st, h, w), (4 * planes, planes, 1, 1, ho, wo)]
+            if i == 0:
+                convs.append((4 * planes, cin, 1, st, h, w))      # downsample.0
+            for co, ci, kk, cs, hi, wi in convs:
+                yield "enc_conv", (B, hi, wi, ci, co, kk, cs, 0)
+                yield "enc_conv", (B, hi, wi, ci, co, kk, cs, 1)          # the input gradient: the transposed operator
+                yield "enc_conv_wgrad", (B, hi, wi, ci, co, kk, cs)
+                yield from bn(co, (hi + cs - 1) // cs, (wi + cs - 1) // cs)
+            cin, h, w = 4 * planes, ho, wo
+    if cond_dim:
+        yield "linear_backward", (B, cond_dim, cin, 0)                    # fc
+
+
+def operator_scratch_bytes(B, H, W, cond_dim=128):
+    """-> (main, side): the largest single call of operator_calls, and the largest cddpm_op_enc_conv_wgrad (what runs on the
+    side-stream handle of the trainer whose handles the encoder uses). training.UNetTrainer._fit sizes its arenas for these too."""
+    return largest_calls(operator_calls(B, H, W, cond_dim))
+
+
 class EncoderTrainer:
     """params: timm state_dict of the ResNet-50 (names conv1.weight, bn1.*, layerS.I.convJ.weight, layerS.I.bnJ.*, layerS.0.downsample.*,
     fc.*; running_mean / running_var included). `ops`: an object with `.lib`, `.h`, `.dev` (a training.UNetTrainer: the operators run on
-    its handle and scratch arena)."""
+    its handles and scratch arenas, which it sizes for the encoder's calls as well as its own: operator_scratch_bytes)."""
 
     def __init__(self, params: Dict[str, torch.Tensor], ops, drop_path_rate: float = 0.0):
         self.ops, self.dev = ops, ops.dev

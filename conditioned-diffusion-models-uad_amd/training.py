@@ -8,7 +8,8 @@ and of the backward runs in csrc/*.hip; torch is used for device memory, views, 
 (the gradient all-reduce). fp32 throughout (the gradients carry fp32 accuracy and are checked against autograd on the oracle).
 
 State: device-resident (flat parameter / gradient / Adam buffers, weight images re-packed on the device after every update, operator
-temporaries from one scratch arena, no synchronisation inside a step); loss and all gradients checked against float64 autograd through the
+temporaries from one scratch arena per handle, sized as the largest single call by the operators' own size queries -- arena_bytes --, no
+synchronisation inside a step); loss and all gradients checked against float64 autograd through the
 oracle, three complete steps against float64 autograd + torch Adam (tests/test_gpu_training.py); the context encoder is trained jointly by
 encoder_training.EncoderTrainer. Convolutions keep the inference path's fp32-grade arithmetic (fp16 two-term splits) by default; the
 reference trainer's `precision: 16` arithmetic (plain fp16 operands, fp32 accumulation) is selected per process (CDDPM_TRAIN_PRECISION=16,
@@ -32,6 +33,8 @@ import torch
 
 from . import schedule as _schedule
 from . import synth as _synth
+from . import encoder_training as _encoder_training
+from ._lib import largest_calls, scratch_query
 from .engine import CddpmEngine, _stream_ptr, check_boxes, precision_bits
 
 
@@ -140,6 +143,9 @@ def unsupported_blocks(names, program):
     return missing
 
 
+ARENA_FLOOR = 192 << 20      # the least a handle's operator arena holds; no call's fit depends on it (arena_bytes)
+
+
 def attention_scratch_bytes(program, B, H, W):
     """what cddpm_op_attention_backward takes from the operator arena at the largest attention block of `program` on a B x H x W batch:
     B x (C / 64) heads x N tokens x 2 floats of row statistics (include/cddpm.h), rounded up to the arena's 256-byte granule"""
@@ -148,54 +154,68 @@ def attention_scratch_bytes(program, B, H, W):
         if kind == "res":
             lv += 1 if a["kind"] == "down" else -1 if a["kind"] == "up" else 0
         elif kind == "attn":
-            worst = max(worst, B * (a["c"] // 64) * (H >> lv) * (W >> lv) * 2 * 4)
-    return (worst + 255) // 256 * 256
+            worst = max(worst, scratch_query("attention_backward", B, (H >> lv) * (W >> lv), a["c"]))
+    return worst
 
 
-ARENA_FLOOR = 192 << 20      # what every handle's operator arena holds besides the weight gradient's k-images, at the least
+def operator_calls(program, B, H, W, emb_dim=2048, cond_dim=128):
+    """the operator calls of one training step (UNetTrainer.forward / backward over `program`) on a B x H x W batch that take
+    temporaries from an arena, as (operator, arguments of its size query). Each call at the most it can take: a GroupNorm without
+    kept statistics (swept), a weight gradient at training precision 32 (two fp16 planes per k-image; precision 16 writes one), the
+    embedding Linears batched and one by one."""
+    C_ = program[1][2]["cin"]
 
+    def gn(c, c1, h, w):                 # GroupNorm over cat[c - c1, c1] channels: the coefficient sweep, and the backward
+        yield "gn_coef", (c - c1, int(c1 > 0), c1, B, h * w)
+        yield "gn_silu_backward", (0, B, h * w, c)
 
-def operator_scratch_bytes(program, B, H, W, emb_dim=2048):
-    """-> (main, wgrad): the largest temporaries ONE operator call of the training step takes from its handle's arena on a B x H x W
-    batch, the weight gradient's two k-images aside (UNetTrainer._fit adds those) -- a host restatement of the OpScratch requests of
-    csrc/cddpm_ops.hip, every request rounded up to the arena's 256-byte granule. `wgrad`: cddpm_op_conv_wgrad alone (partial tiles as
-    conv_wgrad_parts plans them + the bias gradient's partial rows), what the side-stream handle runs; `main`: that and every other
-    operator -- the head's nine partial dot products per pixel (B H W 9 floats: the one that grows fastest with the geometry), the
-    GroupNorm backward's planes and partial sums and a swept GroupNorm's records (B x pixel ranges x C), the attention backward's row
-    statistics (attention_scratch_bytes), the batched embedding Linear's backward (33 x B x emb_dim), the input convolution's and the
-    head's weight-gradient partials. UNetTrainer._fit sizes the arena as max(ARENA_FLOOR, this) + the k-images."""
-    r = lambda n: (n + 255) // 256 * 256
-    G = (B + 7) // 8
+    def wg(co, c0, c1, k, h, w, up=0):
+        yield "conv_wgrad", (c0, c1, up, co, k, B, h, w, 32)
 
-    def gn(c, h, w):
-        ns = -(-(h * w) // (256 if h * w >= 4096 else 64))
-        return r(B * ns * c * 8) + 2 * r(16 * B * c) + r(B * ns * c * 16)
-
-    def wg(co, ci, taps, h, w):
-        img = taps == 9 or ci % 64 == 0
-        per = (co // 64) * (ci // (64 if taps == 1 and img else 32))
-        P = max(1, min(-(-512 // per), G * ((h + 1) // 2) * ((w + 7) // 8), 64))
-        P = (P + 7) // 8 * 8 if img else P
-        rows = -(-(h * w) // 8) * G
-        return r(P * co * ci * taps * 4) + (r(((rows + -(-rows // 128)) * co + 3) // 4 * 16) if img else 0)
-
-    main = max(r(33 * B * emb_dim * 4), attention_scratch_bytes(program, B, H, W))
-    wgrad, lv = 0, 0
+    yield "linear_backward", (B, sum(2 * a["cout"] for kind, _n, a in program if kind == "res"), emb_dim, 1)
+    for n, k, silu in ((4 * C_, 4 * C_, 1), (4 * C_, C_, 0), (4 * C_, cond_dim, 0)):          # time_embed.2 / label_emb.2, .0 of either
+        if k:
+            yield "linear_backward", (B, n, k, silu)
+    lv = 0
     for kind, _name, a in program:
         h, w = H >> lv, W >> lv
-        if kind in ("in", "head"):
-            c = a["c"] if a else program[1][2]["cin"]
-            main = max(main, r(256 * c * 9 * 8), r(512 * c * 8), r(B * H * W * 9 * 4) if kind == "head" else 0, gn(c, h, w) if kind == "head" else 0)
+        if kind == "in":
+            yield "chan_image_corr", (B, H, W, C_)
+            yield "bias_grad", (B * H * W, C_)
+        elif kind == "head":
+            yield from gn(a["c"], 0, h, w)
+            yield "head", (B, H, W, a["c"])
+            yield "chan_image_corr", (B, H, W, a["c"])
         elif kind == "attn":
-            main = max(main, gn(a["c"], h, w))
-            wgrad = max(wgrad, wg(3 * a["c"], a["c"], 1, h, w), wg(a["c"], a["c"], 1, h, w))
+            yield from gn(a["c"], 0, h, w)
+            yield "attention_backward", (B, h * w, a["c"])
+            yield from wg(3 * a["c"], a["c"], 0, 1, h, w)
+            yield from wg(a["c"], a["c"], 0, 1, h, w)
         else:
             lv += 1 if a["kind"] == "down" else -1 if a["kind"] == "up" else 0
             ho, wo = H >> lv, W >> lv                          # the ResBlock's output resolution: where its convolutions run
-            main = max(main, gn(a["cin"], h, w), gn(a["cout"], ho, wo))
-            wgrad = max(wgrad, wg(a["cout"], a["cin"], 9, ho, wo), wg(a["cout"], a["cout"], 9, ho, wo),
-                        wg(a["cout"], a["cin"], 1, ho, wo) if a["cin"] != a["cout"] else 0)
-    return max(main, wgrad), wgrad
+            c1 = a.get("concat", 0)
+            yield from gn(a["cin"], c1, h, w)
+            yield from gn(a["cout"], 0, ho, wo)
+            yield "linear_backward", (B, 2 * a["cout"], emb_dim, 1)
+            yield from wg(a["cout"], a["cin"] - c1, c1, 3, ho, wo, int(a["kind"] == "up"))
+            yield from wg(a["cout"], a["cout"], 0, 3, ho, wo)
+            if a["cin"] != a["cout"]:
+                yield from wg(a["cout"], a["cin"] - c1, c1, 1, ho, wo)
+
+
+def operator_scratch_bytes(program, B, H, W, emb_dim=2048, cond_dim=128):
+    """-> (main, side) of `program`'s training step on a B x H x W batch: largest_calls over operator_calls"""
+    return largest_calls(operator_calls(program, B, H, W, emb_dim, cond_dim))
+
+
+def arena_bytes(program, B, H, W, emb_dim=2048, cond_dim=128):
+    """-> (main, side): what UNetTrainer._fit gives cddpm_op_set_scratch on its two handles for a B x H x W batch -- the largest call of
+    the UNet's step (`program` None: a trainer without a UNet's parameters) and of the context encoder's, which runs on the same handles
+    whenever one is trained jointly (encoder_training.operator_scratch_bytes: a function of the geometry), and never below ARENA_FLOOR"""
+    unet = operator_scratch_bytes(program, B, H, W, emb_dim, cond_dim) if program else (0, 0)
+    enc = _encoder_training.operator_scratch_bytes(B, H, W, cond_dim)
+    return max(ARENA_FLOOR, unet[0], enc[0]), max(ARENA_FLOOR, unet[1], enc[1])
 
 
 class UNetTrainer:
@@ -291,32 +311,25 @@ class UNetTrainer:
     # ------------------------------------------------------------------ handle, packed weights
     def _fit(self, B, H, W):
         """the handle the operators run on; its scratch arena is sized for the batch. Every operator takes its temporaries from the
-        arena's start, so the arena holds the largest single call (operator_scratch_bytes: the attention backward's row statistics, B x
-        heads x N x 2 floats -- the N x N matrices stay in registers --, the head's partial products, the GroupNorm backward's partial
-        sums, the weight gradient's partial tiles, ...; at least ARENA_FLOOR) and the weight gradient's two k-images"""
+        arena's start, so the arena holds the largest single call, and what a call takes is asked of the library (arena_bytes: the
+        operators' own size queries over the calls of the step -- the weight gradient's partial tiles and k-images, the head's partial
+        products, the GroupNorm backward's partial sums, the attention backward's row statistics, ...)"""
         e = self.eng
         if e is None or e.max_batch < B or e.max_h < H or e.max_w < W:
             if e is not None:
                 torch.cuda.synchronize(self.dev)
                 e.close()
             self.eng = CddpmEngine(timesteps=2, max_batch=B, max_h=H, max_w=W, device=self.dev, **self._cfg)
-            main, side = operator_scratch_bytes(self.program, B, H, W, 8 * self.C) if self._convs else (0, 0)
-            # the 3x3 weight gradient's two k-images (fp16 hi | mid, batch padded to groups of 8): the largest (Cin + Cout) x pixels of the net
-            lv, worst = 0, 0
-            for kind, _name, a_ in self.program:
-                if kind == "res":
-                    worst = max(worst, (a_["cin"] + a_["cout"]) * (H >> lv) * (W >> lv), 2 * a_["cout"] * (H >> lv) * (W >> lv))
-                    lv += 1 if a_["kind"] == "down" else -1 if a_["kind"] == "up" else 0
-            images = 2 * ((B + 7) // 8) * worst * 16
-            rc = self.eng.lib.cddpm_op_set_scratch(self.eng._h, max(ARENA_FLOOR, main) + images)
+            main, side = arena_bytes(self.program if self._convs else None, B, H, W, 8 * self.C, self.cond_dim or 0)
+            rc = self.eng.lib.cddpm_op_set_scratch(self.eng._h, main)
             if rc != 0:
                 raise RuntimeError("cddpm_op_set_scratch failed: " + self.eng.lib.cddpm_last_error(self.eng._h).decode())
             if self.overlap_wgrad:
                 if self.eng_w is not None:
                     self.eng_w.close()
-                # the weight-gradient handle: only its operator arena is used (k-images + partial tiles); smallest geometry
+                # the weight-gradient handle: only its operator arena is used (partial tiles + k-images); smallest geometry
                 self.eng_w = CddpmEngine(timesteps=2, max_batch=1, max_h=16, max_w=16, device=self.dev, **self._cfg)
-                if self.eng_w.lib.cddpm_op_set_scratch(self.eng_w._h, max(ARENA_FLOOR, side) + images) != 0:
+                if self.eng_w.lib.cddpm_op_set_scratch(self.eng_w._h, side) != 0:
                     raise RuntimeError("cddpm_op_set_scratch failed: " + self.eng_w.lib.cddpm_last_error(self.eng_w._h).decode())
                 if self.side is None:
                     self.side = torch.cuda.Stream(device=self.dev)

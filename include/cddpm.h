@@ -550,6 +550,28 @@ int cddpm_op_scaler_update(cddpm_handle h, const int32_t* ctrl_dev, int32_t* sca
  * cddpm_op_conv_packed: cddpm_op_conv / cddpm_op_conv_skip on such images: out = conv_k(act(cat[src0, src1])) [+ conv1x1(skip)] + bias
  * [+ res]; bias_dev NULL = none; skip_dev NULL = no skip segment (its image shares scale_exp); folded_up: src0 is at H/2 x W/2. */
 int cddpm_op_set_scratch(cddpm_handle h, size_t bytes);
+/* What ONE call of an operator takes from the arena, in bytes (every temporary rounded up to 256): host functions without a handle, a
+ * stream or a device, run by the very code through which the operator takes its temporaries, so a caller sizes the arena as the
+ * largest of them over the calls it will make on the handle. Arguments: the operator's own shape arguments, in the operator's order;
+ * where a NULL pointer of the operator changes what it takes, a flag stands in for the pointer (has_src1: src1 given; has_rec: rec_dev
+ * given). GroupNorm parameter vectors are taken to be on the device, as the trainers pass them (a vector given in HOST memory is
+ * staged through the arena: 256-byte-rounded C floats more for each). A shape the operator refuses gives 0.
+ * cddpm_op_conv_wgrad_scratch: precision 16 | 32 = the process-wide training precision to plan for, 0 = the current one
+ * (cddpm_get_train_precision); 32 takes the most, so an arena sized for it serves either. db_dev does not change the request.
+ * cddpm_op_attention_backward_scratch serves cddpm_op_attention_backward and cddpm_op_attention_backward_p16. */
+size_t cddpm_op_conv_wgrad_scratch(int C0, int C1, int upsample, int Cout, int ksize, int B, int H, int W, int precision);
+size_t cddpm_op_gn_coef_scratch(int C0, int has_src1, int C1, int B, int HW);
+size_t cddpm_op_gn_silu_backward_scratch(int has_rec, int B, int HW, int C);
+size_t cddpm_op_attention_backward_scratch(int B, int N, int C);
+size_t cddpm_op_linear_backward_scratch(int M, int N, int K, int silu_in);
+size_t cddpm_op_head_scratch(int B, int H, int W, int C);
+size_t cddpm_op_bias_grad_scratch(int64_t npix, int C);
+size_t cddpm_op_chan_image_corr_scratch(int B, int H, int W, int C);
+size_t cddpm_op_enc_conv_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);
+size_t cddpm_op_enc_conv_wgrad_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride);
+size_t cddpm_op_enc_stem_wgrad_scratch(int B, int H, int W);
+size_t cddpm_op_enc_bn_forward_scratch(int64_t N, int HW, int C);
+size_t cddpm_op_enc_bn_backward_scratch(int64_t N, int HW, int C);
 int cddpm_op_absmax(cddpm_handle h, const float* x_dev, int64_t n, float* out_dev, void* stream);
 int cddpm_op_pack_conv(cddpm_handle h, const float* w_dev, int Cout, int Cin, int ksize, int mode, int scale_exp, void* packed_dev,
                        void* stream);

@@ -332,7 +332,7 @@ def p16_wgrad_ref(x, coef, silu, up, dy, k):
 @pytest.mark.parametrize("case", P16_WGRAD, ids=[c[0] for c in P16_WGRAD])
 def test_precision16_conv_wgrad_is_fp16_operands(eng, case):
     """cddpm_op_conv_wgrad under precision 16 against its definition (p16_wgrad_ref): the image kernels <9, 1> and <1, 1> (3x3; 1x1 with
-    Cin % 64 == 0), conv_wgrad_x_kernel<1, 1> (1x1 with Cin % 64 == 32, with its bias_grad_run branch), an upsampled input and a batch that
+    Cin % 64 == 0), conv_wgrad_x_kernel<1> (1x1 with Cin % 64 == 32, with its bias_grad_run branch), an upsampled input and a batch that
     does not fill its last group of 8. db: the fp32 sums of the raw dy (bound 2^-20 sum |dy|)"""
     name, B, C0, C1, Cout, k, H, W, use_coef, silu, up = case
     torch.manual_seed(B + C0 + C1 + Cout + H)

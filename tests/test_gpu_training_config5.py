@@ -279,7 +279,7 @@ def test_a_repeated_step_is_bitwise_identical(hip):
 @pytest.mark.gpu
 def test_serial_weight_gradients_are_bitwise_identical(hip):
     """overlap_wgrad=False: the weight gradients on the main stream and its handle instead of the side stream and the second handle. The
-    kernels and their plans depend on the call, not the handle (conv_wgrad_parts), so the bits are the same"""
+    kernels and their plans depend on the call, not the handle (conv_wgrad_plan), so the bits are the same"""
     trainer, enc, loss = run_step(overlap_wgrad=False)
     assert trainer.side is None
     same = {k: torch.equal(v, hip["bits"][k]) for k, v in _bits(trainer, enc).items()}
