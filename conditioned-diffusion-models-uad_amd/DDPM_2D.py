@@ -19,6 +19,9 @@ Added, behind a cfg switch that is absent (= reference behaviour) by default:
                                      kernels (UNetTrainer's attention_precision: the arithmetic of the reference's `precision: 16`
                                      autocast over QKVAttention; unset or 32: exact fp32 attention, today's behaviour). Independent of
                                      the Trainer's precision, which selects the convolutions' arithmetic; 'bf16' is a ValueError.
+    cfg.evalHausdorff: true      ->  the standalone metric pass (utils_eval._test_step, which reads this cfg like `evalSeg`) fills HausPerVol
+                                     with the device Hausdorff distance (CddpmEngine.hausdorff) instead of NaN (unset: NaN, dropped by
+                                     _test_end). Pinned to scipy, unpinned to monai.
 
 `test_step` follows the reference's evaluation call (:171-286): 4 centre slices, `noise_ensemble` / `step_ensemble`
 averaging, a fresh `gen_noise` (device simplex) field per reconstruction.

@@ -14,7 +14,8 @@ cddpm_box_q_sample, the loss is cddpm_op_loss_box); test_step does the reference
 mirrors share (trainer aliasing, checkpoint hooks, precision, loss-scale logging, evaluation bookkeeping) is mirror_common.HipMirror.
 The cfg keys `conv_family`, `conv_fallback`, `eval_precision` and `train_attention_precision` (absent in the reference; unset = nothing
 changes) mean what they mean in DDPM_2D.py: `eval_precision: 16` evaluates (test_step, validation_step) with plain fp16 operands in the
-UNet's engine; `train_attention_precision: 16` trains the attention cores on the fp16-MFMA kernels.
+UNet's engine; `train_attention_precision: 16` trains the attention cores on the fp16-MFMA kernels. `evalHausdorff: true` reaches the
+standalone metric pass with the rest of the cfg, like `evalSeg`: HausPerVol gets the device Hausdorff distance instead of NaN.
 """
 from __future__ import annotations
 

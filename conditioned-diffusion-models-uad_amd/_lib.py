@@ -58,6 +58,8 @@ SYMBOLS = {
     "cddpm_eval_workspace_bytes": (_sz, [_i64, _i]),
     "cddpm_eval_volume": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_double, _vp, _sz, _fp, _fp, _fp, _fp, _fp, _vp]),
     "cddpm_eval_set": (_i, [_vp, _fp, _fp, _i64, _i, _vp, _sz, _fp, _vp]),
+    "cddpm_hausdorff_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cddpm_eval_hausdorff": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _fp, _fp, _fp, _vp]),
     "cddpm_q_sample": (_i, [_vp, _fp, _fp, _fp, _i, _fp, _fp, _i, _fp, _i, _i, _i, _vp]),
     "cddpm_set_clip_denoised": (_i, [_vp, _i]),
     "cddpm_set_accumulation_switch": (_i, [_vp, _i]),

@@ -1084,6 +1084,33 @@ int cddpm_eval_set(cddpm_handle h, const float* x_dev, const int8_t* y_dev, int6
     return 0;
 }
 
+static bool hausdorff_in_range(int R, int D1, int D2) {
+    return R >= 1 && D1 >= 1 && D2 >= 1 && R <= CDDPM_HAUSDORFF_MAX_AXIS && D1 <= CDDPM_HAUSDORFF_MAX_AXIS && D2 <= CDDPM_HAUSDORFF_MAX_AXIS;
+}
+
+size_t cddpm_hausdorff_workspace_bytes(int R, int D1, int D2) {
+    if (!hausdorff_in_range(R, D1, D2)) {
+        fail(nullptr, "cddpm_hausdorff_workspace_bytes: volume %dx%dx%d outside 1 ... %d per axis", R, D1, D2, CDDPM_HAUSDORFF_MAX_AXIS);
+        return 0;
+    }
+    return hausdorff_workspace_bytes(R, D1, D2);
+}
+
+int cddpm_eval_hausdorff(cddpm_handle h, const uint8_t* pred_dev, const float* seg_dev, int R, int D1, int D2, int flags,
+                         void* ws_dev, size_t ws_bytes, double* out_dev, uint8_t* edges_dev, int32_t* dist2_dev, void* stream) {
+    if (!h) return -1;
+    if (!pred_dev || !seg_dev || !ws_dev || !out_dev) return fail(h, "cddpm_eval_hausdorff: NULL argument");
+    if (!hausdorff_in_range(R, D1, D2))
+        return fail(h, "cddpm_eval_hausdorff: volume %dx%dx%d outside 1 ... %d per axis", R, D1, D2, CDDPM_HAUSDORFF_MAX_AXIS);
+    if (flags & ~CDDPM_HAUSDORFF_SQUEEZE) return fail(h, "cddpm_eval_hausdorff: unknown flags 0x%x", flags);
+    const size_t need = hausdorff_workspace_bytes(R, D1, D2);
+    if (ws_bytes < need) return fail(h, "cddpm_eval_hausdorff: workspace of %zu bytes, need %zu", ws_bytes, need);
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, launch_eval_hausdorff(pred_dev, seg_dev, R, D1, D2, (flags & CDDPM_HAUSDORFF_SQUEEZE) ? 1 : 0, ws_dev, ws_bytes,
+                                      out_dev, edges_dev, dist2_dev, (hipStream_t)stream));
+    return 0;
+}
+
 int cddpm_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev, const int32_t* t_dev, int t_uniform,
                    const float* sqrt_ac_host, const float* sqrt_1mac_host, int T, float* out_dev, int B, int H, int W,
                    void* stream) {

@@ -276,6 +276,11 @@ hipError_t launch_eval_volume(const float* recon, const float* orig, const float
 hipError_t launch_eval_set(const float* x, const int8_t* y, int n, int healthy, void* ws, size_t ws_bytes, double* out,
                            hipStream_t s);
 
+// Hausdorff distance of the evaluation step (eval_hausdorff.hip; src/utils/utils_eval.py:131-135)
+size_t hausdorff_workspace_bytes(int R, int D1, int D2);
+hipError_t launch_eval_hausdorff(const uint8_t* pred, const float* seg, int R, int D1, int D2, int squeeze, void* ws, size_t ws_bytes,
+                                 double* out, uint8_t* edges_out, int32_t* dist2_out, hipStream_t s);
+
 // ---- training-mode kernels of the context encoder (encoder_train.hip)
 int enc_conv_split(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);     // planes of `part` (1: not used)
 void launch_enc_conv(const float* src, const float* w_img, float* dst, int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed,

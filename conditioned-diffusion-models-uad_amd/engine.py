@@ -577,6 +577,45 @@ class CddpmEngine:
                                          out.data_ptr(), _stream_ptr(self.device)), "cddpm_eval_set")
         return out
 
+    # ------------------------------------------------------------------ Hausdorff distance (eval_hausdorff.hip)
+    HAUSDORFF_SQUEEZE, HAUSDORFF_RESULT, HAUSDORFF_FAR = 1, 8, 1 << 28     # include/cddpm.h
+
+    def _hausdorff_workspace(self, R: int, D1: int, D2: int) -> torch.Tensor:
+        """caller-side workspace of cddpm_eval_hausdorff: sized by cddpm_hausdorff_workspace_bytes, grown on demand, its own buffer"""
+        need = int(self.lib.cddpm_hausdorff_workspace_bytes(int(R), int(D1), int(D2)))
+        if need == 0:
+            raise RuntimeError(f"cddpm_hausdorff_workspace_bytes: {self.lib.cddpm_last_error(None).decode()}")
+        ws = getattr(self, "_hausdorff_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._hausdorff_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def hausdorff(self, pred: torch.Tensor, seg: torch.Tensor, *, squeeze: bool = True, fields: bool = False) -> Dict[str, torch.Tensor]:
+        """The undirected Hausdorff distance between the surfaces of pred != 0 and seg != 0 (cddpm_eval_hausdorff; HausPerVol of
+        _test_step, utils_eval.py:131-135). pred: [R, D1, D2] uint8, the `pred` of eval_volume; seg: [R, D1, D2] fp32, raw data_seg.
+        squeeze: erode along the axes where the union's bounding box is wider than one voxel only (monai's crop + np.squeeze).
+        Returns device tensors: record [HAUSDORFF_RESULT] float64 (distance, the two directed squared distances, the two edge counts,
+        the three active-axis flags); with fields=True also edges [R, D1, D2] uint8 (bit 0: pred's edge, bit 1: seg's) and dist2
+        [2, R, D1, D2] int32 (squared distance of every voxel to pred's edge, to seg's edge; HAUSDORFF_FAR for an empty edge set)."""
+        if not isinstance(pred, torch.Tensor) or not pred.is_cuda or pred.device != self.device or pred.dtype != torch.uint8:
+            raise RuntimeError(f"pred must be a uint8 tensor on {self.device} (got {getattr(pred, 'dtype', type(pred).__name__)})")
+        seg = _check_dev(seg, "seg", self.device)
+        if pred.dim() != 3 or seg.shape != pred.shape:
+            raise RuntimeError(f"pred and seg must be [R, D1, D2] volumes of one shape, got {tuple(pred.shape)} and {tuple(seg.shape)}")
+        pred = pred.contiguous()
+        R, D1, D2 = pred.shape
+        ws = self._hausdorff_workspace(R, D1, D2)
+        out = dict(record=torch.empty(self.HAUSDORFF_RESULT, dtype=torch.float64, device=self.device))
+        if fields:
+            out["edges"] = torch.empty(R, D1, D2, dtype=torch.uint8, device=self.device)
+            out["dist2"] = torch.empty(2, R, D1, D2, dtype=torch.int32, device=self.device)
+        self._ck(self.lib.cddpm_eval_hausdorff(self._h, pred.data_ptr(), seg.data_ptr(), R, D1, D2,
+                                               self.HAUSDORFF_SQUEEZE if squeeze else 0, ws.data_ptr(), ws.numel(),
+                                               out["record"].data_ptr(), out["edges"].data_ptr() if fields else None,
+                                               out["dist2"].data_ptr() if fields else None, _stream_ptr(self.device)),
+                 "cddpm_eval_hausdorff")
+        return out
+
     def simplex_noise(self, B: int, H: int, W: int, *, seed: int, octaves: int = 6, persistence: float = 0.8,
                       frequency: float = 64.0) -> torch.Tensor:
         """gen_noise for noisetype 'simplex': float16 [B,1,H,W], the same field for every batch item, bit-exact

@@ -17,8 +17,11 @@ DDPM_2D mirror uses standalone, with the reference's names and arguments:
 
 They follow the reference as its environment ran it (numpy 1.22, scikit-learn 1.0.1, scikit-image 0.18.3), quirks included:
 the swapped confusion-matrix names, fpr = fp / (fp + tp), NaN AUROC / AUPRC for a volume without lesion, "per-slice" metrics
-over axis 0 of the [H, W, D] volume. Not built: image grids (log_images), the Hausdorff distance (monai; HausPerVol gets NaN,
-which _test_end drops), calc_thresh, the KLDBackprop branches, resizedEvaluation = False (NotImplementedError).
+over axis 0 of the [H, W, D] volume. The Hausdorff distance (utils_eval.py:131-135, monai's compute_hausdorff_distance in the
+reference) is computed on the device (csrc/eval_hausdorff.hip through CddpmEngine.hausdorff) when cfg.evalHausdorff is true: pinned to
+scipy bit for bit, unpinned to monai (its rules are restated in include/cddpm.h; monai reads a non-boolean ground truth as == 1, this
+pass as != 0). Without the key HausPerVol gets NaN, which _test_end drops, as before.
+Not built: image grids (log_images), calc_thresh, the KLDBackprop branches, resizedEvaluation = False (NotImplementedError).
 No CPU fallback: the functions need an engine (a loaded libcddpm_hip.so) and HIP tensors.
 """
 import math
@@ -199,7 +202,10 @@ def _test_step(self, final_volume, data_orig, data_seg, data_mask, batch_idx, ID
         ed["PrecisionPerVol"].append(p1s1 / pred1 if pred1 else 0.0)
         ed["RecallPerVol"].append(p1s1 / L if L else 0.0)
         ed["SpecificityPerVol"].append(p1s0 / (p1s0 + p0s1 + 0.0000001))
-        ed["HausPerVol"].append(math.nan)                   # monai's Hausdorff distance: not built
+        if self.cfg.get("evalHausdorff"):                   # :131-135: filtered prediction (unfiltered for 'node' sets) against data_seg
+            ed["HausPerVol"].append(float(eng.hausdorff(res["pred"], seg)["record"][0]))
+        else:
+            ed["HausPerVol"].append(math.nan)               # the default: _test_end drops it
         counts = res["row_counts"].cpu().numpy()
         for r in np.nonzero(row_label)[0]:                  # rows with lesion, unfiltered prediction (:137-144)
             p, pg, g = (int(v) for v in counts[r])

@@ -289,6 +289,54 @@ int cddpm_eval_volume(cddpm_handle h, const float* recon_dev, const float* orig_
 int cddpm_eval_set(cddpm_handle h, const float* x_dev, const int8_t* y_dev, int64_t n, int healthy, void* ws_dev,
                    size_t ws_bytes, double* out_dev, void* stream);
 
+/* ---- Hausdorff distance (csrc/eval_hausdorff.hip) -------------------------------------------------------
+ * Replaces the HausPerVol entry of _test_step (src/utils/utils_eval.py:131-135; aggregated :240-241), which the reference
+ * takes from monai.metrics.compute_hausdorff_distance(diffs_thresholded, data_seg, include_background=False,
+ * distance_metric='euclidean', percentile=None, directed=False) on the CPU. Status: PINNED TO SCIPY, UNPINNED TO MONAI. The
+ * rules below restate monai 1.0.1's get_mask_edges / get_surface_distance / compute_hausdorff_distance; monai itself was not
+ * available to compare with, scipy was, and every result equals the scipy restatement bit for bit.
+ * Volumes are flat [R][D1][D2] (R = axis 0 of the reference's [H, W, D]), unit spacing.
+ *   masks    P = pred != 0 (uint8: the pred_dev of cddpm_eval_volume, which is what the reference hands to monai);
+ *            G = seg != 0 (raw fp32 data_seg). monai, as recalled, reads a non-boolean ground truth as == 1: the two agree
+ *            on binary segmentations and differ where a label map holds other values.
+ *   axes     U = P | G. With CDDPM_HAUSDORFF_SQUEEZE the ACTIVE axes are those along which U's bounding box is wider than
+ *            one voxel (monai crops to the box and np.squeeze's it, so a flat union is eroded with a 2-D cross); without
+ *            the flag all three are active.
+ *   edges    edge(M) = M & ~erode(M); erode keeps a voxel only if both neighbours along every active axis are in M, and a
+ *            neighbour outside the volume is not in M (scipy.ndimage.binary_erosion, border_value = 0). A non-empty mask
+ *            always has an edge: when no axis is active (U is one voxel) that voxel is its own edge.
+ *   d2       d2(v, E) = min over e in E of the squared index distance (an exact integer);
+ *            directed(A -> B) = max over a in edge(A) of d2(a, edge(B)).
+ *   result   NaN when both masks are empty, +inf when exactly one is, otherwise
+ *            sqrt((double) max(directed(P -> G), directed(G -> P))): equal to
+ *            scipy.ndimage.distance_transform_edt(~edge)[other_edge].max() bit for bit.
+ * Supported range: every axis 1 ... CDDPM_HAUSDORFF_MAX_AXIS (3 * 1023^2 + CDDPM_HAUSDORFF_FAR fits an int32). */
+#define CDDPM_HAUSDORFF_SQUEEZE 1        /* flags: derive the active axes from the bounding box of U (what the mirrors set) */
+#define CDDPM_HAUSDORFF_MAX_AXIS 1024
+#define CDDPM_HAUSDORFF_FAR (1 << 28)    /* dist2_dev of an EMPTY edge set holds this value at every voxel */
+/* slots of the result (float64) */
+#define CDDPM_HAUSDORFF_DISTANCE 0
+#define CDDPM_HAUSDORFF_D2_PRED_TO_SEG 1 /* directed(P -> G) and directed(G -> P), squared; NaN unless both masks are non-empty */
+#define CDDPM_HAUSDORFF_D2_SEG_TO_PRED 2
+#define CDDPM_HAUSDORFF_EDGES_PRED 3     /* #edge(P), #edge(G) */
+#define CDDPM_HAUSDORFF_EDGES_SEG 4
+#define CDDPM_HAUSDORFF_ACTIVE_AXIS0 5   /* 1.0 / 0.0 per axis (R, D1, D2); with the flag all 0.0 when U is empty or one voxel */
+#define CDDPM_HAUSDORFF_ACTIVE_AXIS1 6
+#define CDDPM_HAUSDORFF_ACTIVE_AXIS2 7
+#define CDDPM_HAUSDORFF_RESULT 8
+
+/* workspace bytes of cddpm_eval_hausdorff; host arithmetic, callable without a GPU. Outside the supported range: 0, with the
+ * reason in cddpm_last_error(NULL). */
+size_t cddpm_hausdorff_workspace_bytes(int R, int D1, int D2);
+
+/* out_dev [CDDPM_HAUSDORFF_RESULT] float64. edges_dev [R*D1*D2] uint8 (may be NULL): bit 0 = edge(P), bit 1 = edge(G).
+ * dist2_dev [2][R*D1*D2] int32 (may be NULL): the squared distance of every voxel of the VOLUME to edge(P) ([0]) and to
+ * edge(G) ([1]). The two exist for tests: the distance is a maximum, which a transform that is wrong at most voxels can
+ * still get right. Integer arithmetic and integer atomics throughout: bitwise reproducible. Nothing allocates or
+ * synchronises inside; the bounding box and the active axes stay on the device. */
+int cddpm_eval_hausdorff(cddpm_handle h, const uint8_t* pred_dev, const float* seg_dev, int R, int D1, int D2, int flags,
+                         void* ws_dev, size_t ws_bytes, double* out_dev, uint8_t* edges_dev, int32_t* dist2_dev, void* stream);
+
 /* Replaces q_sample (src/models/modules/cond_DDPM.py:548-554) fused with normalize_to_neg_one_to_one (:75):
  * out = sqrt_ac[t_b] * (2 x01 - 1) + sqrt_1mac[t_b] * noise; coefficient tables are host arrays [T]
  * uploaded on first use. Used by the single-step reconstruction (GaussianDiffusion.forward, :647-655). */
