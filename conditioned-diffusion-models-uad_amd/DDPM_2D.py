@@ -19,6 +19,13 @@ Added, behind a cfg switch that is absent (= reference behaviour) by default:
                                      kernels (UNetTrainer's attention_precision: the arithmetic of the reference's `precision: 16`
                                      autocast over QKVAttention; unset or 32: exact fp32 attention, today's behaviour). Independent of
                                      the Trainer's precision, which selects the convolutions' arithmetic; 'bf16' is a ValueError.
+    cfg.train_encoder_precision: 16 -> training_step runs the context encoder's convolutions (all but the 7x7 stem), forward, input gradient
+                                     and weight gradient, on the fp16-MFMA kernels (EncoderTrainer's precision: the arithmetic of the
+                                     reference's `precision: 16` autocast over self.encoder; unset or 32: fp32 FMA kernels, today's
+                                     behaviour). Independent of the Trainer's precision, which selects the UNet convolutions'
+                                     arithmetic, like the attention switch; 'bf16' is a ValueError. Operands are rounded as they are:
+                                     without loss scaling (a precision-32 Trainer has none) the fp16 `dz` operand of the backward
+                                     underflows, as torch's would under autocast without a GradScaler.
     cfg.evalHausdorff: true      ->  the standalone metric pass (utils_eval._test_step, which reads this cfg like `evalSeg`) fills HausPerVol
                                      with the device Hausdorff distance (CddpmEngine.hausdorff) instead of NaN (unset: NaN, dropped by
                                      _test_end). Pinned to scipy, unpinned to monai.
@@ -243,7 +250,8 @@ class DDPM_2D(HipMirror, _Base):
             # SparK_2D_encoder: build_encoder(..., drop_path_rate=cfg.get('dp', 0)) overrides timm's kwarg only when non-zero, the
             # resnet50 default of pre_train_d is 0.05 (spark/Spark_2D.py:277-282, spark/models.py:50, :91-93); plain timm resnet50: 0
             dp = float(_cfg_get(self.cfg, "dp", 0) or 0)
-            self._hip_enc_trainer = EncoderTrainer(sd, self.hip_trainer(device), drop_path_rate=(dp if dp != 0 else 0.05) if spark else 0.0)
+            self._hip_enc_trainer = EncoderTrainer(sd, self.hip_trainer(device), drop_path_rate=(dp if dp != 0 else 0.05) if spark else 0.0,
+                                                   precision=_cfg_get(self.cfg, "train_encoder_precision", 32))
             self.__dict__["_enc_core"] = core          # NOT a registered submodule: state_dict() must keep the reference's key set
             self._alias_encoder()
             self._load_pending_optimizer_state()

@@ -121,6 +121,9 @@ SYMBOLS = {
     "cddpm_op_enc_pack_w": (_i, [_vp, _fp, _i, _i, _i, _fp, _fp, _vp]),
     "cddpm_op_enc_conv": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "cddpm_op_enc_conv_wgrad": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cddpm_op_enc_pack_w_p16": (_i, [_vp, _fp, _i, _i, _i, _vp, _vp, _vp]),
+    "cddpm_op_enc_conv_p16": (_i, [_vp, _fp, _vp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cddpm_op_enc_conv_wgrad_p16": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "cddpm_op_enc_stem": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_enc_stem_wgrad": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_enc_bn_forward": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, C.c_float, C.c_float, _fp, _fp, _fp, _fp, _i64, _i, _i, _vp]),
@@ -138,6 +141,8 @@ SYMBOLS = {
     "cddpm_op_chan_image_corr_scratch": (_sz, [_i] * 4),
     "cddpm_op_enc_conv_scratch": (_sz, [_i] * 8),
     "cddpm_op_enc_conv_wgrad_scratch": (_sz, [_i] * 7),
+    "cddpm_op_enc_conv_p16_scratch": (_sz, [_i] * 8),
+    "cddpm_op_enc_conv_wgrad_p16_scratch": (_sz, [_i] * 7),
     "cddpm_op_enc_stem_wgrad_scratch": (_sz, [_i] * 3),
     "cddpm_op_enc_bn_forward_scratch": (_sz, [_i64, _i, _i]),
     "cddpm_op_enc_bn_backward_scratch": (_sz, [_i64, _i, _i]),
@@ -194,11 +199,11 @@ def scratch_query(op, *args):
 def largest_calls(calls):
     """-> (main, side) over (operator, query arguments) pairs: the largest single call, which is what the main handle's arena must hold
     (every call takes its temporaries from the arena's start), and the largest weight gradient (cddpm_op_conv_wgrad,
-    cddpm_op_enc_conv_wgrad), all that runs on the side-stream handle. A weight gradient's k-images are part of its call."""
+    cddpm_op_enc_conv_wgrad, cddpm_op_enc_conv_wgrad_p16), all that runs on the side-stream handle. A weight gradient's k-images are part of its call."""
     main = side = 0
     for op, args in calls:
         n = scratch_query(op, *args)
         main = max(main, n)
-        if op in ("conv_wgrad", "enc_conv_wgrad"):
+        if op in ("conv_wgrad", "enc_conv_wgrad", "enc_conv_wgrad_p16"):
             side = max(side, n)
     return main, side

@@ -564,6 +564,60 @@ int cddpm_op_enc_conv_wgrad(cddpm_handle h, const float* x_dev, const float* dz_
     launch_enc_wgrad(x_dev, dz_dev, part, P, dw_dev, B, H, W, Cin, Cout, K, stride, s);
     OP_EPILOGUE()
 }
+// the same three operators in precision 16 (encoder_train_p16.hip): what configs/trainer/default.yaml:7 makes of self.encoder's convolutions
+// (src/models/DDPM_2D.py:114-135) -- fp16 operands rounded to nearest, fp32 accumulation, fp32 NHWC results
+int cddpm_op_enc_pack_w_p16(cddpm_handle h, const float* w_dev, int Cout, int Cin, int K, void* wf16_dev, void* wd16_dev, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, w_dev && (wf16_dev || wd16_dev) && Cout > 0 && Cout % 64 == 0 && Cin > 0 && Cin % 64 == 0 && (K == 1 || K == 3),
+                "cddpm_op_enc_pack_w_p16: bad arguments (Cin, Cout multiples of 64; K 1|3)")
+    launch_enc_pack_w_p16(w_dev, Cout, Cin, K * K, wf16_dev, wd16_dev, s);
+    OP_EPILOGUE()
+}
+static bool enc_conv_p16_shape_ok(int B, int H, int W, int Cin, int Cout, int K, int stride) {
+    return B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 64 == 0 && Cin <= 2048 && Cout > 0 && Cout % 64 == 0 && Cout <= 2048 && (K == 1 || K == 3) &&
+           (stride == 1 || stride == 2);
+}
+static float* enc_conv_p16_scratch(OpScratch& sc, int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed) {
+    const int Z = enc_conv_p16_split(B, H, W, Cin, Cout, K, stride, transposed);      // split-K planes (1: the kernel writes dst itself)
+    if (Z == 1) return nullptr;
+    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+    return sc.n<float>((size_t)Z * B * (transposed ? (size_t)H * W * Cin : (size_t)Ho * Wo * Cout));
+}
+size_t cddpm_op_enc_conv_p16_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed) {
+    if (!enc_conv_p16_shape_ok(B, H, W, Cin, Cout, K, stride)) return 0;
+    return counted([&](OpScratch& sc) { enc_conv_p16_scratch(sc, B, H, W, Cin, Cout, K, stride, transposed ? 1 : 0); });
+}
+int cddpm_op_enc_conv_p16(cddpm_handle h, const float* src_dev, const void* w_img16_dev, float* dst_dev, int B, int H, int W, int Cin, int Cout,
+                          int K, int stride, int transposed, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, src_dev && w_img16_dev && dst_dev && enc_conv_p16_shape_ok(B, H, W, Cin, Cout, K, stride),
+                "cddpm_op_enc_conv_p16: unsupported shape (Cin, Cout multiples of 64 up to 2048; K 1|3, stride 1|2)")
+    OpScratch sc(h, s);
+    float* part = enc_conv_p16_scratch(sc, B, H, W, Cin, Cout, K, stride, transposed ? 1 : 0);
+    SCRATCH_CHECK(sc)
+    launch_enc_conv_p16(src_dev, w_img16_dev, dst_dev, B, H, W, Cin, Cout, K, stride, transposed ? 1 : 0, part, s);
+    OP_EPILOGUE()
+}
+static float* enc_wgrad_p16_scratch(OpScratch& sc, int B, int H, int W, int Cin, int Cout, int K, int stride, int& P) {
+    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+    P = enc_wgrad_p16_parts(B, Ho, Wo, Cin, Cout, K);
+    if (K == 1 && P == 1) return nullptr;             // one pixel range of a 1x1: the kernel writes dw itself
+    return sc.n<float>((size_t)P * K * K * Cin * Cout);
+}
+size_t cddpm_op_enc_conv_wgrad_p16_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride) {
+    if (!enc_conv_p16_shape_ok(B, H, W, Cin, Cout, K, stride)) return 0;
+    int P;
+    return counted([&](OpScratch& sc) { enc_wgrad_p16_scratch(sc, B, H, W, Cin, Cout, K, stride, P); });
+}
+int cddpm_op_enc_conv_wgrad_p16(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, int Cin, int Cout,
+                                int K, int stride, void* stream) {
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && dz_dev && dw_dev && enc_conv_p16_shape_ok(B, H, W, Cin, Cout, K, stride),
+                "cddpm_op_enc_conv_wgrad_p16: unsupported shape (Cin, Cout multiples of 64 up to 2048; K 1|3, stride 1|2)")
+    OpScratch sc(h, s);
+    int P;
+    float* part = enc_wgrad_p16_scratch(sc, B, H, W, Cin, Cout, K, stride, P);
+    SCRATCH_CHECK(sc)
+    launch_enc_wgrad_p16(x_dev, dz_dev, part, P, dw_dev, B, H, W, Cin, Cout, K, stride, s);
+    OP_EPILOGUE()
+}
 int cddpm_op_enc_stem(cddpm_handle h, const float* x_dev, const float* w_dev, float* z_dev, int B, int H, int W, void* stream) {
     OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && w_dev && z_dev && B > 0 && H > 0 && W > 0, "cddpm_op_enc_stem: bad arguments")
     launch_enc_stem_fwd(x_dev, w_dev, z_dev, B, H, W, s);

@@ -2,9 +2,9 @@
 // builds it (src/models/modules/DDPM_encoder.py:21-23; spark/models.py:89-109) and trains it jointly with the UNet
 // (src/models/DDPM_2D.py:114-135: features = self(input) carries a gradient, :305-306 Adam over self.parameters()).
 //
-// Everything NHWC fp32, plain FMA tiles: the encoder is ~5 % of a training step's FLOPs (0.45 GFLOP per 128 x 128 slice forward) and
-// its layers are small (64 ... 2048 channels over 64 x 64 ... 4 x 4 pixels), so these kernels are written for correctness and
-// coalescing, not for the matrix pipe. Pieces:
+// Everything NHWC fp32. The convolutions here are plain FMA tiles, the encoder's default arithmetic (precision 32): its layers are small
+// (64 ... 2048 channels over 64 x 64 ... 4 x 4 pixels) and these kernels are written for correctness and coalescing; the matrix-pipe
+// convolutions of the opt-in precision 16 (EncoderTrainer(precision=16)) are in encoder_train_p16.hip and share the plane fold below. Pieces:
 //   enc_gemm_conv_kernel   one 64 x 64-tile direct convolution in two roles: forward (rows = output pixels, gathered input rows
 //                          yo * stride + ky - pad) and input gradient (rows = INPUT pixels, gathered dz rows (yi + pad - ky) / stride
 //                          where that division is exact): K in {1, 3}, stride in {1, 2}, weights as [taps][K-dim][N-dim] images
@@ -108,6 +108,9 @@ __global__ __launch_bounds__(256) void enc_fold_planes_kernel(const float* __res
     }
     reinterpret_cast<float4*>(dst)[e] = s;
 }
+void launch_enc_fold_planes(const float* part, int Z, long long n4, float* dst, hipStream_t s) {
+    hipLaunchKernelGGL(enc_fold_planes_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, part, Z, n4, dst);
+}
 // layers that give the chip fewer than 128 workgroups (the 8 x 8 and 4 x 4 stages at batch 16) split their contraction
 int enc_conv_split(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed) {
     const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
@@ -127,10 +130,7 @@ void launch_enc_conv(const float* src, const float* w, float* dst, int B, int H,
     a.Kdim = transposed ? Cout : Cin; a.Ndim = transposed ? Cin : Cout; a.K = K; a.stride = stride; a.transposed = transposed;
     const long long M = (long long)B * (transposed ? H * W : a.Ho * a.Wo);
     hipLaunchKernelGGL(enc_gemm_conv_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(a.Ndim / 64), a.Z), dim3(256), 0, s, a);
-    if (a.Z > 1) {
-        const long long n4 = M * a.Ndim / 4;
-        hipLaunchKernelGGL(enc_fold_planes_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, part, a.Z, n4, dst);
-    }
+    if (a.Z > 1) launch_enc_fold_planes(part, a.Z, M * a.Ndim / 4, dst, s);
 }
 
 // weight images of one convolution from the PyTorch tensor w [Cout][Cin][K][K]: wf [taps][Cin][Cout] (forward), wd [taps][Cout][Cin]

@@ -289,6 +289,17 @@ void launch_enc_pack_w(const float* w, int Cout, int Cin, int taps, float* wf, f
 int enc_wgrad_parts(int B, int Ho, int Wo, int Cin, int Cout, int K);
 void launch_enc_wgrad(const float* x, const float* dz, float* part, int P, float* dw, int B, int H, int W, int Cin, int Cout, int K, int stride,
                       hipStream_t s);
+void launch_enc_fold_planes(const float* part, int Z, long long n4, float* dst, hipStream_t s);                 // dst = sum of Z planes of n4 float4, in order
+// the same three roles on plain fp16 operands, v_mfma_f32_16x16x32_f16 with fp32 accumulation (encoder_train_p16.hip): Cin, Cout multiples of 64.
+// Images: wf [taps][Cin / 32][Cout][32], wd [taps][Cout / 32][Cin][32] fp16 (either may be nullptr); `part`: enc_conv_p16_split() planes of the result
+// (nullptr: no split), enc_wgrad_p16_parts() planes of dw
+int enc_conv_p16_split(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);
+void launch_enc_conv_p16(const float* src, const void* w_img, float* dst, int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed,
+                         float* part, hipStream_t s);
+void launch_enc_pack_w_p16(const float* w, int Cout, int Cin, int taps, void* wf, void* wd, hipStream_t s);
+int enc_wgrad_p16_parts(int B, int Ho, int Wo, int Cin, int Cout, int K);
+void launch_enc_wgrad_p16(const float* x, const float* dz, float* part, int P, float* dw, int B, int H, int W, int Cin, int Cout, int K, int stride,
+                          hipStream_t s);
 void launch_enc_stem_fwd(const float* x, const float* w, float* z, int B, int H, int W, hipStream_t s);
 void launch_enc_stem_wgrad(const float* x, const float* dz, double* part /* 32 * 49 * 64 */, float* dw, int B, int H, int W, hipStream_t s);
 int enc_bn_chunks(long long N);

@@ -5,9 +5,14 @@ forward with saved activations and the backward of every operator, what `loss.ba
 training_step (src/models/DDPM_2D.py:114-135; Adam over self.parameters(), :305-306).
 
 Same construction as training.UNetTrainer: Python sequencing C-ABI operators (include/cddpm.h, "training-mode operators of the context
-encoder"; csrc/encoder_train.hip), one flat fp32 parameter buffer / gradient buffer / Adam state, weight images re-packed on the device
+encoder"; csrc/encoder_train.hip, csrc/encoder_train_p16.hip), one flat fp32 parameter buffer / gradient buffer / Adam state, weight images re-packed on the device
 after every update. The operators run on the UNet trainer's handles; what they take from its arenas is a function of the geometry
-(operator_scratch_bytes), which that trainer sizes its arenas for. Parity: unpinned like the encoder's forward (timm is not in the image): checked against float64 autograd through
+(operator_scratch_bytes), which that trainer sizes its arenas for.
+
+Arithmetic of the convolutions (all but the 7x7 stem): `EncoderTrainer(..., precision=32)` (default) runs the fp32 FMA kernels;
+`precision=16` (the spellings of engine.precision_bits; the mirrors' `cfg.train_encoder_precision`) runs forward, input gradient and
+weight gradient on plain fp16 operands with fp32 accumulation (cddpm_op_enc_*_p16), what the reference's `precision: 16` autocast computes
+for self.encoder. BatchNorm, ReLU, pooling, fc, Adam and the master weights are fp32 in both. Measured: DESIGN.md section 4b. Parity: unpinned like the encoder's forward (timm is not in the image): checked against float64 autograd through
 oracle/encoder_oracle.py's restatement (tests/test_gpu_encoder_training.py)."""
 from __future__ import annotations
 
@@ -17,7 +22,7 @@ from typing import Dict, Optional
 import torch
 
 from ._lib import largest_calls
-from .engine import _stream_ptr
+from .engine import _stream_ptr, precision_bits
 
 STAGES = ((64, 3), (128, 4), (256, 6), (512, 3))
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
@@ -30,7 +35,8 @@ def _p(t: Optional[torch.Tensor]):
 def operator_calls(B, H, W, cond_dim=128):
     """the operator calls of the ResNet-50's training step (EncoderTrainer.forward / backward) on a [B, 1, H, W] batch that take
     temporaries from an arena, as (operator, arguments of its size query cddpm_op_<operator>_scratch, include/cddpm.h). The network
-    is fixed, so they are a function of the geometry."""
+    is fixed, so they are a function of the geometry. Every convolution is listed in both arithmetics (enc_conv / enc_conv_p16, ...): an
+    arena sized over these calls serves an EncoderTrainer of either precision."""
     def bn(c, h, w):
         yield "enc_bn_forward", (B * h * w, h * w, c)
         yield "enc_bn_backward", (B * h * w, h * w, c)
@@ -51,6 +57,9 @@ def operator_calls(B, H, W, cond_dim=128):
                 yield "enc_conv", (B, hi, wi, ci, co, kk, cs, 0)
                 yield "enc_conv", (B, hi, wi, ci, co, kk, cs, 1)          # the input gradient: the transposed operator
                 yield "enc_conv_wgrad", (B, hi, wi, ci, co, kk, cs)
+                yield "enc_conv_p16", (B, hi, wi, ci, co, kk, cs, 0)
+                yield "enc_conv_p16", (B, hi, wi, ci, co, kk, cs, 1)
+                yield "enc_conv_wgrad_p16", (B, hi, wi, ci, co, kk, cs)
                 yield from bn(co, (hi + cs - 1) // cs, (wi + cs - 1) // cs)
             cin, h, w = 4 * planes, ho, wo
     if cond_dim:
@@ -58,7 +67,7 @@ def operator_calls(B, H, W, cond_dim=128):
 
 
 def operator_scratch_bytes(B, H, W, cond_dim=128):
-    """-> (main, side): the largest single call of operator_calls, and the largest cddpm_op_enc_conv_wgrad (what runs on the
+    """-> (main, side): the largest single call of operator_calls, and the largest cddpm_op_enc_conv_wgrad / _wgrad_p16 (what runs on the
     side-stream handle of the trainer whose handles the encoder uses). training.UNetTrainer._fit sizes its arenas for these too."""
     return largest_calls(operator_calls(B, H, W, cond_dim))
 
@@ -66,9 +75,11 @@ def operator_scratch_bytes(B, H, W, cond_dim=128):
 class EncoderTrainer:
     """params: timm state_dict of the ResNet-50 (names conv1.weight, bn1.*, layerS.I.convJ.weight, layerS.I.bnJ.*, layerS.0.downsample.*,
     fc.*; running_mean / running_var included). `ops`: an object with `.lib`, `.h`, `.dev` (a training.UNetTrainer: the operators run on
-    its handles and scratch arenas, which it sizes for the encoder's calls as well as its own: operator_scratch_bytes)."""
+    its handles and scratch arenas, which it sizes for the encoder's calls as well as its own: operator_scratch_bytes).
+    precision: 32 (default) = fp32 FMA convolutions; 16 (the spellings of engine.precision_bits) = fp16 operands, fp32 accumulation."""
 
-    def __init__(self, params: Dict[str, torch.Tensor], ops, drop_path_rate: float = 0.0):
+    def __init__(self, params: Dict[str, torch.Tensor], ops, drop_path_rate: float = 0.0, *, precision=32):
+        self.precision = precision_bits(precision)            # parsed before a device is touched: a bad value is a ValueError here
         self.ops, self.dev = ops, ops.dev
         train_names = [k for k in params if not (k.endswith("running_mean") or k.endswith("running_var") or k.endswith("num_batches_tracked"))]
         sizes = [(int(params[k].numel()) + 63) // 64 * 64 for k in train_names]
@@ -101,8 +112,10 @@ class EncoderTrainer:
             self.convs[n + ".conv3"] = (4 * pl, pl, 1, 1)
             if bk["down"]:
                 self.convs[n + ".downsample.0"] = (4 * pl, bk["cin"], 1, bk["stride"])
-        self.wf = {k: torch.empty(co * ci * kk * kk, dtype=torch.float32, device=self.dev) for k, (co, ci, kk, _s) in self.convs.items()}
-        self.wd = {k: torch.empty(co * ci * kk * kk, dtype=torch.float32, device=self.dev) for k, (co, ci, kk, _s) in self.convs.items()}
+        # one image per role: fp32 [taps][K-dim][N-dim], or at precision 16 the fp16 images of cddpm_op_enc_pack_w_p16 (include/cddpm.h)
+        img = torch.float16 if self.precision == 16 else torch.float32
+        self.wf = {k: torch.empty(co * ci * kk * kk, dtype=img, device=self.dev) for k, (co, ci, kk, _s) in self.convs.items()}
+        self.wd = {k: torch.empty(co * ci * kk * kk, dtype=img, device=self.dev) for k, (co, ci, kk, _s) in self.convs.items()}
         self.state: Dict[str, object] = {}
         self.repack()
 
@@ -126,8 +139,9 @@ class EncoderTrainer:
         return torch.empty(shape, dtype=torch.float32, device=self.dev)
 
     def repack(self):
+        pack = self.lib.cddpm_op_enc_pack_w_p16 if self.precision == 16 else self.lib.cddpm_op_enc_pack_w
         for k, (co, ci, kk, _s) in self.convs.items():
-            self._ck(self.lib.cddpm_op_enc_pack_w(self.h, _p(self.p[k + ".weight"]), co, ci, kk, _p(self.wf[k]), _p(self.wd[k]), self._s()),
+            self._ck(pack(self.h, _p(self.p[k + ".weight"]), co, ci, kk, _p(self.wf[k]), _p(self.wd[k]), self._s()),
                      "op_enc_pack_w")
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -148,26 +162,27 @@ class EncoderTrainer:
             H, W = in_hw
             out = self._new(B, H, W, ci)
             img = self.wd[name]
-        self._ck(self.lib.cddpm_op_enc_conv(self.h, _p(x), _p(img), _p(out), B, H, W, ci, co, kk, st, int(transposed), self._s()), "op_enc_conv")
+        op = self.lib.cddpm_op_enc_conv_p16 if self.precision == 16 else self.lib.cddpm_op_enc_conv
+        self._ck(op(self.h, _p(x), _p(img), _p(out), B, H, W, ci, co, kk, st, int(transposed), self._s()), "op_enc_conv")
         return out
 
     def wgrad(self, name, x, dz):
         co, ci, kk, st = self.convs[name]
         B, H, W, _c = x.shape
         ops = self.ops
+        op = self.lib.cddpm_op_enc_conv_wgrad_p16 if self.precision == 16 else self.lib.cddpm_op_enc_conv_wgrad
         if getattr(ops, "overlap_wgrad", False) and getattr(ops, "side", None) is not None:
             # as the UNet's weight gradients (training.UNetTrainer.wgrad): on the side stream and its handle, beside the main stream's chain
             # of small BatchNorm / input-gradient kernels
             ops.side.wait_stream(torch.cuda.current_stream(self.dev))
-            rc = self.lib.cddpm_op_enc_conv_wgrad(ops.eng_w._h, _p(x), _p(dz), _p(self.g[name + ".weight"]), B, H, W, ci, co, kk, st, ops.side.cuda_stream)
+            rc = op(ops.eng_w._h, _p(x), _p(dz), _p(self.g[name + ".weight"]), B, H, W, ci, co, kk, st, ops.side.cuda_stream)
             if rc != 0:
                 raise RuntimeError("op_enc_conv_wgrad failed: " + self.lib.cddpm_last_error(ops.eng_w._h).decode())
             x.record_stream(ops.side)
             dz.record_stream(ops.side)
             ops._side_busy = True
             return
-        self._ck(self.lib.cddpm_op_enc_conv_wgrad(self.h, _p(x), _p(dz), _p(self.g[name + ".weight"]), B, H, W, ci, co, kk, st, self._s()),
-                 "op_enc_conv_wgrad")
+        self._ck(op(self.h, _p(x), _p(dz), _p(self.g[name + ".weight"]), B, H, W, ci, co, kk, st, self._s()), "op_enc_conv_wgrad")
 
     def bn(self, name, z, relu, res=None, sscale=None):
         B, H, W, Cc = z.shape

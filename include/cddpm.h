@@ -563,7 +563,9 @@ int cddpm_op_adam(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev
  * (configs/trainer/default.yaml:7) computes under autocast; GroupNorm, embeddings, Adam and the master weights stay fp32 in both, and so
  * does attention unless the trainer asks otherwise: the training step calls cddpm_op_attention / cddpm_op_attention_backward at either
  * value, and cddpm_op_attention_p16 / cddpm_op_attention_backward_p16 only where its caller selects them (UNetTrainer's
- * attention_precision=16), independently of this setting.
+ * attention_precision=16), independently of this setting. The context encoder's convolutions likewise: cddpm_op_enc_conv /
+ * cddpm_op_enc_conv_wgrad are fp32 at either value, and cddpm_op_enc_conv_p16 / cddpm_op_enc_conv_wgrad_p16 run only where the caller
+ * selects them (EncoderTrainer's precision=16).
  * Precision 16 rounds each operand to fp16 to nearest even with gradual underflow, as torch's .half(): measured on gfx950, the 16-bit
  * MFMA inputs keep fp16 subnormals (|x| < 2^-14 is carried to 2^-25, not flushed), in both operators and on either operand
  * (tests/test_gpu_train_ops_edges.py::test_precision16_keeps_fp16_subnormals).
@@ -617,6 +619,8 @@ size_t cddpm_op_bias_grad_scratch(int64_t npix, int C);
 size_t cddpm_op_chan_image_corr_scratch(int B, int H, int W, int C);
 size_t cddpm_op_enc_conv_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);
 size_t cddpm_op_enc_conv_wgrad_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride);
+size_t cddpm_op_enc_conv_p16_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);
+size_t cddpm_op_enc_conv_wgrad_p16_scratch(int B, int H, int W, int Cin, int Cout, int K, int stride);
 size_t cddpm_op_enc_stem_wgrad_scratch(int B, int H, int W);
 size_t cddpm_op_enc_bn_forward_scratch(int64_t N, int HW, int C);
 size_t cddpm_op_enc_bn_backward_scratch(int64_t N, int HW, int C);
@@ -640,8 +644,9 @@ int cddpm_op_conv_packed(cddpm_handle h, const float* src0_dev, int C0, const fl
 int cddpm_op_gn_coef_rec(cddpm_handle h, const float* rec0_dev, int n0, int C0, const float* rec1_dev, int n1, int C1, const float* gamma_host,
                          const float* beta_host, const float* film_dev, float* coef_dev, int B, int HW, void* stream);
 /* ---- training-mode operators of the context encoder (timm ResNet-50, in_chans = 1; reference src/models/modules/DDPM_encoder.py:21-23,
- * trained jointly with the UNet by src/models/DDPM_2D.py:114-135 / :305-306). NHWC fp32 device tensors, plain fp32 FMA kernels (the encoder is
- * ~5 % of a training step's FLOPs). Strided operators map n -> ceil(n / stride).
+ * trained jointly with the UNet by src/models/DDPM_2D.py:114-135 / :305-306). NHWC fp32 device tensors. The convolutions come in two
+ * arithmetics: plain fp32 FMA kernels (cddpm_op_enc_pack_w / _conv / _conv_wgrad: the default), and precision 16 on the matrix pipe
+ * (the *_p16 entry points below), chosen per call by the caller (EncoderTrainer's precision). Strided operators map n -> ceil(n / stride).
  * cddpm_op_enc_pack_w: PyTorch weight [Cout][Cin][K][K] -> the images the convolution reads: wf [K*K][Cin][Cout] (forward) and, when wd_dev is
  *   given, wd [K*K][Cout][Cin] (input gradient).
  * cddpm_op_enc_conv: transposed = 0: z [B,Ho,Wo,Cout] = conv_K,stride,pad K/2 (x [B,H,W,Cin]) with wf; transposed = 1: dx [B,H,W,Cin] from
@@ -660,6 +665,24 @@ int cddpm_op_enc_conv(cddpm_handle h, const float* src_dev, const float* w_img_d
                       int stride, int transposed, void* stream);
 int cddpm_op_enc_conv_wgrad(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, int Cin, int Cout, int K,
                             int stride, void* stream);
+/* Precision 16 of the three convolution operators: what the reference trainer's `precision: 16` (configs/trainer/default.yaml:7) computes for
+ * self.encoder, whose forward and backward lie inside the LightningModule's autocast (src/models/DDPM_2D.py:114-135). The convention of
+ * "Arithmetic of the training operators" above: every operand element (forward x, w; input gradient dz, w; weight gradient x, dz) is rounded to
+ * fp16 to nearest even with gradual underflow, as torch's .half() (|v| > 65504 -> inf: the result is then non-finite, which cddpm_op_grad_check
+ * sees in the gradient buffer; range is the loss scaler's job, there are no pre-scales), products are accumulated in fp32
+ * (v_mfma_f32_16x16x32_f16), results are fp32 NHWC / PyTorch layout as the fp32 operators'. Bit-identical from run to run (contraction splits
+ * are folded in a fixed order). BatchNorm, ReLU, pooling, fc, the 7x7 stem (K = 49), Adam and the master weights have no precision-16 form.
+ * Shapes: Cin and Cout multiples of 64 up to 2048, K 1|3, stride 1|2, B, H, W >= 1; anything else is refused with a message.
+ * cddpm_op_enc_pack_w_p16: PyTorch weight [Cout][Cin][K][K] (fp32) -> fp16 images, rounded once here; either pointer may be NULL:
+ *   wf16 [K*K][Cin / 32][Cout][32]: element (t, ci, co) at ((t (Cin / 32) + ci / 32) Cout + co) 32 + ci % 32   (forward, transposed = 0)
+ *   wd16 [K*K][Cout / 32][Cin][32]: element (t, ci, co) at ((t (Cout / 32) + co / 32) Cin + ci) 32 + co % 32   (input gradient, transposed = 1)
+ *   i.e. [tap][32-chunk of the contraction][produced channel][position in the chunk], Cout Cin K K 2 bytes each; taps in the weight's own order.
+ * cddpm_op_enc_conv_p16 / cddpm_op_enc_conv_wgrad_p16: cddpm_op_enc_conv / cddpm_op_enc_conv_wgrad with those images and that arithmetic. */
+int cddpm_op_enc_pack_w_p16(cddpm_handle h, const float* w_dev, int Cout, int Cin, int K, void* wf16_dev, void* wd16_dev, void* stream);
+int cddpm_op_enc_conv_p16(cddpm_handle h, const float* src_dev, const void* w_img16_dev, float* dst_dev, int B, int H, int W, int Cin, int Cout,
+                          int K, int stride, int transposed, void* stream);
+int cddpm_op_enc_conv_wgrad_p16(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, int Cin, int Cout,
+                                int K, int stride, void* stream);
 int cddpm_op_enc_stem(cddpm_handle h, const float* x_dev, const float* w_dev, float* z_dev, int B, int H, int W, void* stream);
 int cddpm_op_enc_stem_wgrad(cddpm_handle h, const float* x_dev, const float* dz_dev, float* dw_dev, int B, int H, int W, void* stream);
 int cddpm_op_enc_bn_forward(cddpm_handle h, const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* sample_scale_dev,

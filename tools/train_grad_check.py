@@ -1,7 +1,11 @@
 """Worst / median relative error of the training step's gradients against float64 autograd through the oracle, as JSON (one process per
 arithmetic: the families are chosen once per process from the environment, e.g. CDDPM_TRAIN_PRECISION=16).
-usage: python tools/train_grad_check.py [--attention-precision 16|32] [--gradient NAME] [B H W [DESCRIPTOR]]
+usage: python tools/train_grad_check.py [--attention-precision 16|32] [--gradient NAME] [--encoder-precision 16|32 --joint-steps N]
+                                        [B H W [DESCRIPTOR]]
 --attention-precision: UNetTrainer's attention_precision (16: the fp16-MFMA attention forward and backward; default 32).
+--joint-steps N: instead of the gradient check, N joint optimisation steps (training_step(..., encoder=enc)) on one fixed batch with the
+context encoder built at --encoder-precision (EncoderTrainer's precision) and dynamic loss scaling on; reports each step's loss, which
+steps the guard skipped, skipped_steps and the final loss_scale.
 --gradient NAME: also report "gradient_sha256", the digest of that parameter's gradient bits (to tell two arithmetics apart).
 DESCRIPTOR: a JSON object {"model_channels":, "channel_mult":, "num_res_blocks":, "cond_dim":, "attention_resolutions":} of another UNet
 than the experiment's (cond_dim 0: unconditioned; attention_resolutions absent: the experiment's (3, 6, 12), attention in the middle
@@ -25,6 +29,8 @@ import cddpm_oracle as oracle  # noqa: E402  (test infrastructure: this tool is 
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--attention-precision", default="32")
 _ap.add_argument("--gradient", default=None)
+_ap.add_argument("--encoder-precision", default="32")
+_ap.add_argument("--joint-steps", type=int, default=0)
 _ap.add_argument("rest", nargs="*")
 _a = _ap.parse_args()
 sys.argv[1:] = _a.rest
@@ -35,6 +41,26 @@ desc = json.loads(sys.argv[4]) if len(sys.argv) >= 5 else {}
 arch = {k: (tuple(desc[k]) if k in ("channel_mult", "attention_resolutions") else desc[k])
         for k in ("model_channels", "channel_mult", "num_res_blocks", "attention_resolutions") if k in desc}
 cond_dim = desc.get("cond_dim", 128)
+encoder_precision = importlib.import_module(PKG + ".engine").precision_bits(_a.encoder_precision)
+if _a.joint_steps > 0:
+    et = importlib.import_module(PKG + ".encoder_training")
+    dev = torch.device("cuda", 0)
+    trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in synth.synth_state_dict(0, **arch).items()}, device=dev,
+                             attention_precision=_a.attention_precision, **arch)
+    trainer.enable_loss_scaling()
+    enc = et.EncoderTrainer({k: torch.from_numpy(v) for k, v in synth.synth_encoder_state_dict(0).items()}, trainer, precision=encoder_precision)
+    x01 = torch.from_numpy(synth.synth_slices(3, 0, B, H, W)).reshape(B, 1, H, W).to(dev)
+    noise = torch.from_numpy(synth.noise_xT(3, 0, B, H, W)).reshape(B, 1, H, W).to(dev)
+    t = torch.tensor([(137 * (i + 1) + 3) % T for i in range(B)], dtype=torch.long, device=dev)
+    losses, skipped = [], []
+    for _ in range(_a.joint_steps):
+        before = trainer.skipped_steps
+        losses.append(float(tr.training_step(trainer, x01, None, t=t, noise=noise, objective="pred_noise", loss_type="l2", encoder=enc)))
+        skipped.append(trainer.skipped_steps > before)
+    print(json.dumps({"losses": losses, "skipped": skipped, "skipped_steps": trainer.skipped_steps, "step_count": trainer.step_count,
+                      "loss_scale": trainer.loss_scale, "precision": tr.get_precision(), "attention_precision": trainer.attention_precision,
+                      "encoder_precision": enc.precision, "finite_parameters": bool(torch.isfinite(enc.flat).all() and torch.isfinite(trainer.flat).all())}))
+    sys.exit(0)
 sd_np = synth.synth_state_dict(0, num_classes=cond_dim or None, **arch)
 x01 = torch.from_numpy(synth.synth_slices(3, 0, B, H, W)).reshape(B, 1, H, W)
 cond = torch.from_numpy(synth.synth_cond(3, 0, B, cond_dim)) if cond_dim else None
@@ -60,7 +86,8 @@ for k, v in sd.items():
     g = grads[k].double().cpu().reshape(v.grad.shape) / S
     errs.append(float((g - v.grad).abs().max() / (v.grad.abs().max() + 1e-30)))
 res = {"forward_max_abs_err": float((out.double().cpu() - ref_out.detach()).abs().max()), "worst": max(errs), "median": float(np.median(errs)),
-       "finite": bool(np.isfinite(errs).all()), "n": len(errs), "attention_precision": trainer.attention_precision}
+       "finite": bool(np.isfinite(errs).all()), "n": len(errs), "attention_precision": trainer.attention_precision,
+       "encoder_precision": encoder_precision}
 if _a.gradient:
     res["gradient_sha256"] = hashlib.sha256(grads[_a.gradient].detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 print(json.dumps(res))

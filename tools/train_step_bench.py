@@ -28,6 +28,9 @@ def main():
                          "experiment's 3,6,12 = attention in the middle block only")
     ap.add_argument("--attention-precision", default="32",
                     help="UNetTrainer's attention_precision: 16 = the fp16-MFMA attention forward and backward, 32 (default) = exact fp32")
+    ap.add_argument("--encoder-precision", default="32",
+                    help="EncoderTrainer's precision (with --encoder): 16 = its convolutions on fp16 operands (fp16-MFMA kernels), 32 (default) = "
+                         "fp32 FMA kernels")
     ap.add_argument("--phases", action="store_true", help="time forward / backward / adam separately (synchronises between them)")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without RANK in the environment: start the N ranks (torchrun child) and relay rank 0's line")
     a = ap.parse_args()
@@ -52,7 +55,8 @@ def main():
     enc = None
     if a.encoder:
         et = importlib.import_module(PKG + ".encoder_training")
-        enc = et.EncoderTrainer({k: torch.from_numpy(v) for k, v in synth.synth_encoder_state_dict(0).items()}, trainer, drop_path_rate=0.05)
+        enc = et.EncoderTrainer({k: torch.from_numpy(v) for k, v in synth.synth_encoder_state_dict(0).items()}, trainer, drop_path_rate=0.05,
+                                precision=a.encoder_precision)
     B, S, T = a.batch, a.size, 1000
     x01 = torch.from_numpy(synth.synth_slices(1, rank * B, B, S, S)).reshape(B, 1, S, S).to(dev)      # each rank its own slices
     cond = torch.from_numpy(synth.synth_cond(1, rank * B, B)).to(dev)
@@ -78,6 +82,7 @@ def main():
     arith = "fp32-emulated convolutions" if bits == 32 else "fp16-operand convolutions (precision 16)"
     res = {"workload": f"training step {B}x1x{S}x{S} (noise-pred MSE, {arith}, Adam" + (", context encoder trained jointly)" if enc else ")"), "ms_per_step": dt * 1e3,
            "precision": bits, "dropout": a.dropout, "attention_resolutions": list(trainer.att_res), "attention_precision": trainer.attention_precision,
+           "encoder_precision": enc.precision if enc else None,
            "slices_per_s": world * B / dt, "n_gpus": world, "losses": losses, "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
     if a.phases:
         buf = importlib.import_module(PKG + ".schedule").schedule_buffers(T)
