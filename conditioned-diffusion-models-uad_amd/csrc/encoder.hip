@@ -220,8 +220,9 @@ int cddpm_encoder_create(cddpm_encoder_handle* out, int num_classes, int max_bat
     if (device < 0 || device >= ndev) return efail(nullptr, "device %d out of range (%d devices)", device, ndev);
     cddpm_encoder_ctx* h = new cddpm_encoder_ctx;
     h->device = device; h->num_classes = num_classes; h->max_batch = max_batch; h->max_h = max_h; h->max_w = max_w;
-    // largest activation: stem output [B, H/2, W/2, 64] = layer1 output [B, H/4, W/4, 256]
-    h->buf_elems = (size_t)max_batch * ((max_h + 1) / 2) * ((max_w + 1) / 2) * 64;
+    // largest activation: stem output [B, H2, W2, 64] or layer1 output [B, H4, W4, 256] (n -> ceil(n / 2) twice: the larger one when H2 or W2 is odd)
+    const size_t h2 = (max_h + 1) / 2, w2 = (max_w + 1) / 2, h4 = (h2 + 1) / 2, w4 = (w2 + 1) / 2;
+    h->buf_elems = (size_t)max_batch * (h2 * w2 * 64 > h4 * w4 * 256 ? h2 * w2 * 64 : h4 * w4 * 256);
     *out = h;
     return 0;
 }

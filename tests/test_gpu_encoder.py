@@ -26,7 +26,8 @@ def enc_and_weights(synth):
     enc.close()
 
 
-@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 96, 96), (1, 128, 128), (2, 80, 96)])
+@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (3, 96, 96), (1, 128, 128), (2, 80, 96),
+                                   (2, 72, 88), (1, 33, 47)])          # feature maps that turn odd: 36x44 ... 9x11, 5x6, 3x3 and 17x24, 9x12, 5x6, 3x3, 2x2
 def test_encoder_forward_vs_oracle(enc_and_weights, synth, B, H, W):
     import encoder_oracle as EO
     enc, sdt = enc_and_weights
@@ -43,6 +44,36 @@ def test_encoder_forward_vs_oracle(enc_and_weights, synth, B, H, W):
     e_ref, e_hip = float((ref.double() - ref64).abs().max()), float((out.double() - ref64).abs().max())
     print(f"   vs float64: torch fp32 {e_ref:.3e}, HIP {e_hip:.3e}")
     assert e_hip < 10 * e_ref + 1e-6
+
+
+def test_encoder_handle_created_for_exactly_an_odd_half_size(synth):
+    """ResNet50Encoder sizes its handle for at least 64 x 128 x 128, so the module never runs a handle at its limit. Here the handle is
+    created for exactly 1 x 34 x 34 through the C ABI: the stem's output is 17 x 17 x 64 = 18496 floats and layer1's 9 x 9 x 256 = 20736,
+    the larger of the two because 17 is odd -- the handle's activation buffers must hold it (cddpm_encoder_create sized them for the
+    stem's output alone once: 18496 floats)."""
+    import ctypes as C
+    import encoder_oracle as EO
+    lib = load_pkg("_lib").load_library()
+    w = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in synth.synth_encoder_state_dict(0, 128).items() if not k.endswith("num_batches_tracked")}
+    B, H, W = 1, 34, 34
+    h = C.c_void_p()
+    assert lib.cddpm_encoder_create(C.byref(h), 128, B, H, W, 0) == 0, lib.cddpm_encoder_last_error(None)
+    try:
+        names = (C.c_char_p * len(w))(*[k.encode() for k in w])
+        ptrs = (C.c_void_p * len(w))(*[a.ctypes.data for a in w.values()])
+        nums = (C.c_int64 * len(w))(*[a.size for a in w.values()])
+        assert lib.cddpm_encoder_load_weights(h, names, ptrs, nums, len(w)) == 0, lib.cddpm_encoder_last_error(h)
+        x = torch.from_numpy(synth.synth_slices(4, 0, B, H, W))
+        xg, out = x.cuda().contiguous(), torch.empty(B, 128, device="cuda")
+        assert lib.cddpm_encoder_forward(h, xg.data_ptr(), out.data_ptr(), B, H, W, None) == 0, lib.cddpm_encoder_last_error(h)
+        assert lib.cddpm_encoder_forward(h, xg.data_ptr(), out.data_ptr(), B, H + 1, W, None) != 0          # beyond the handle's limits: refused
+        torch.cuda.synchronize()
+    finally:
+        lib.cddpm_encoder_destroy(h)
+    ref = EO.resnet50_forward(x, {k: torch.from_numpy(v) for k, v in w.items()})
+    scale, err = float(ref.abs().max()), float((out.cpu() - ref).abs().max())
+    print(f"encoder {B}x{H}x{W} at the handle's limit: max|delta| {err:.3e} (|ref| max {scale:.3e})")
+    assert err < 1e-4 * max(1.0, scale)
 
 
 def test_encoder_in_ddpm2d(enc_and_weights, synth):

@@ -12,71 +12,10 @@ import sys
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from conftest import load_pkg
+from encoder_step_calls import build, check, record
 
 pytestmark = pytest.mark.gpu
-
-LIMIT = 5e-6
-
-
-def rounded(t):
-    return t.float().half().double().cpu()
-
-
-def nchw(t):
-    return t.permute(0, 3, 1, 2).contiguous()
-
-
-def record(enc):
-    """wraps enc.conv and enc.wgrad (the only two places convolutions are issued): each call's inputs and output are kept"""
-    calls = []
-    conv0, wgrad0 = enc.conv, enc.wgrad
-
-    def conv(name, x, transposed=False, in_hw=None):
-        out = conv0(name, x, transposed=transposed, in_hw=in_hw)
-        calls.append(("dx" if transposed else "y", name, x.clone(), enc.p[name + ".weight"].clone(), in_hw, out.clone()))
-        return out
-
-    def wgrad(name, x, dz):
-        wgrad0(name, x, dz)
-        calls.append(("dw", name, x.clone(), dz.clone(), None, enc.g[name + ".weight"].clone()))
-
-    enc.conv, enc.wgrad = conv, wgrad
-    return calls
-
-
-def check(enc, calls):
-    """every recorded call against float64 on its own rounded inputs -> {role: (count, worst error)}"""
-    torch.cuda.synchronize()
-    seen = {}
-    for role, name, a, b, in_hw, out in calls:
-        co, ci, k, st = enc.convs[name]
-        if role == "y":
-            ref = F.conv2d(nchw(rounded(a)), rounded(b), None, stride=st, padding=k // 2)
-            got = nchw(out.double().cpu())
-        elif role == "dx":
-            ref = torch.nn.grad.conv2d_input((a.shape[0], ci, in_hw[0], in_hw[1]), rounded(b), nchw(rounded(a)), stride=st, padding=k // 2)
-            got = nchw(out.double().cpu())
-        else:
-            ref = torch.nn.grad.conv2d_weight(nchw(rounded(a)), (co, ci, k, k), nchw(rounded(b)), stride=st, padding=k // 2)
-            got = out.double().cpu()
-        assert got.shape == ref.shape, (role, name)
-        assert torch.isfinite(got).all(), (role, name)
-        e = float((got - ref).abs().max() / (ref.abs().max() + 1e-300))
-        assert e < LIMIT, (role, name, e)
-        n, worst = seen.get(role, (0, 0.0))
-        seen[role] = (n + 1, max(worst, e))
-    return seen
-
-
-def build(synth, B, H, W, **kw):
-    tr, et = load_pkg("training"), load_pkg("encoder_training")
-    ops = tr.UNetTrainer({"w": torch.zeros(64)}, device=torch.device("cuda", 0))
-    ops._fit(B, H, W)
-    ops.overlap_wgrad = False
-    return et.EncoderTrainer({k: torch.from_numpy(v) for k, v in synth.synth_encoder_state_dict(0).items()}, ops, **kw)
 
 
 @pytest.mark.parametrize("B,H,W,drop", [(4, 64, 64, False), (3, 64, 96, True)])
