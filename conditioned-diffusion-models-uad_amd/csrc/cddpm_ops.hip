@@ -334,13 +334,20 @@ int cddpm_op_linear_backward(cddpm_handle h, const float* x_dev, const float* w_
 
 int cddpm_op_linear(cddpm_handle h, const float* x_dev, const float* w_dev, const float* b_dev, int M, int N, int K, int silu_in,
                     float* y_dev, void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && w_dev && y_dev && M > 0 && N > 0 && K > 0, "cddpm_op_linear: bad arguments")
+    // linear_kernel reads x and w in quads of K (float4 at k = 4 * lane while k < K): a K that is no multiple of 4 would read the last quad
+    // of a row out of the next row, or past the end of the last one, and leave the rows unaligned
+    OP_CHECK(M >= 1 && N >= 1 && K >= 1 && K % 4 == 0, "cddpm_op_linear: unsupported shape (M %d, N %d, K %d: all >= 1, K a multiple of 4)", M, N, K)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && w_dev && y_dev && !(((uintptr_t)x_dev | (uintptr_t)w_dev) & 15),
+                "cddpm_op_linear: NULL argument, or x_dev / w_dev not 16-byte aligned")
     launch_linear(x_dev, K, w_dev, K, 0, b_dev, y_dev, N, M, N, K, silu_in, s);
     OP_EPILOGUE()
 }
 int cddpm_op_conv_in1(cddpm_handle h, const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int B, int H, int W,
                       int C, void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && w_dev && b_dev && out_dev && C % 64 == 0 && C <= 512, "cddpm_op_conv_in1: bad arguments")
+    // conv_in1_kernel walks the B * H * W pixels as one flat 32-bit range
+    OP_CHECK(B >= 1 && H >= 1 && W >= 1 && (long long)B * H * W < (1ll << 31) && C >= 64 && C % 64 == 0 && C <= 512,
+             "cddpm_op_conv_in1: unsupported shape (B %d, H %d, W %d: all >= 1, B * H * W < 2^31; C %d: a multiple of 64, at most 512)", B, H, W, C)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && w_dev && b_dev && out_dev, "cddpm_op_conv_in1: NULL argument")
     launch_conv_in1(x_dev, w_dev, b_dev, out_dev, B, H, W, C, s);
     OP_EPILOGUE()
 }
@@ -348,7 +355,12 @@ static float* head_scratch(OpScratch& sc, int B, int H, int W) { return sc.n<flo
 size_t cddpm_op_head_scratch(int B, int H, int W, int) { return counted([&](OpScratch& sc) { head_scratch(sc, B, H, W); }); }
 int cddpm_op_head(cddpm_handle h, const float* x_dev, const float* coef_dev, const float* w9_dev, float bias, const float* bias_dev,
                   float* out_dev, int B, int H, int W, int C, void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && coef_dev && w9_dev && out_dev && C % 32 == 0, "cddpm_op_head: bad arguments")
+    // head_dots_kernel keeps 64 pixel rows and the weight image in LDS (head_dots_lds_bytes, kernels.h): C is bounded by a workgroup's LDS
+    static_assert(head_dots_lds_bytes(head_max_channels()) <= LDS_BYTES_PER_WORKGROUP && head_dots_lds_bytes(head_max_channels() + 32) > LDS_BYTES_PER_WORKGROUP,
+                  "the widest head");
+    OP_CHECK(B >= 1 && H >= 1 && W >= 1 && C >= 32 && C % 32 == 0 && C <= head_max_channels(),
+             "cddpm_op_head: unsupported shape (B %d, H %d, W %d: all >= 1; C %d: a multiple of 32, at most %d)", B, H, W, C, head_max_channels())
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && coef_dev && w9_dev && out_dev, "cddpm_op_head: NULL argument")
     OpScratch sc(h, s);
     float* P = head_scratch(sc, B, H, W);
     SCRATCH_CHECK(sc)
@@ -356,19 +368,24 @@ int cddpm_op_head(cddpm_handle h, const float* x_dev, const float* coef_dev, con
     launch_head_gather(P, bias, bias_dev, out_dev, B, H, W, s);
     OP_EPILOGUE()
 }
+// the 2x2 resampling operators: a full-resolution [B,H,W,C] tensor next to its [B,H/2,W/2,C] half (an empty grid is a launch error)
+static bool resample_shape_ok(int B, int H, int W, int C) { return B >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && C >= 4 && C % 4 == 0; }
 int cddpm_op_pool_act(cddpm_handle h, const float* x_dev, const float* coef_dev, float* hp_dev, float* xp_dev, int B, int H, int W, int C,
                       void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && coef_dev && hp_dev && xp_dev && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "cddpm_op_pool_act: bad arguments")
+    OP_CHECK(resample_shape_ok(B, H, W, C), "cddpm_op_pool_act: unsupported shape (B %d >= 1; H %d, W %d: even, >= 2; C %d: a multiple of 4, >= 4)", B, H, W, C)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, x_dev && coef_dev && hp_dev && xp_dev, "cddpm_op_pool_act: NULL argument")
     launch_pool_act(x_dev, coef_dev, hp_dev, xp_dev, B, H, W, C, s);
     OP_EPILOGUE()
 }
 int cddpm_op_unpool2(cddpm_handle h, const float* dyp_dev, float* dx_dev, int B, int H, int W, int C, float scale, int accumulate, void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dyp_dev && dx_dev && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "cddpm_op_unpool2: bad arguments")
+    OP_CHECK(resample_shape_ok(B, H, W, C), "cddpm_op_unpool2: unsupported shape (B %d >= 1; H %d, W %d: even, >= 2; C %d: a multiple of 4, >= 4)", B, H, W, C)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dyp_dev && dx_dev, "cddpm_op_unpool2: NULL argument")
     launch_unpool2(dyp_dev, dx_dev, B, H, W, C, scale, accumulate, s);
     OP_EPILOGUE()
 }
 int cddpm_op_sumpool2(cddpm_handle h, const float* dy_dev, float* dxp_dev, int B, int H, int W, int C, int accumulate, void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dy_dev && dxp_dev && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "cddpm_op_sumpool2: bad arguments")
+    OP_CHECK(resample_shape_ok(B, H, W, C), "cddpm_op_sumpool2: unsupported shape (B %d >= 1; H %d, W %d: even, >= 2; C %d: a multiple of 4, >= 4)", B, H, W, C)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dy_dev && dxp_dev, "cddpm_op_sumpool2: NULL argument")
     launch_sumpool2(dy_dev, dxp_dev, B, H, W, C, accumulate, s);
     OP_EPILOGUE()
 }
@@ -406,7 +423,9 @@ static double* chan_image_corr_scratch(OpScratch& sc, int C) { return sc.n<doubl
 size_t cddpm_op_chan_image_corr_scratch(int, int, int, int C) { return counted([&](OpScratch& sc) { chan_image_corr_scratch(sc, C); }); }
 int cddpm_op_chan_image_corr(cddpm_handle h, const float* t_dev, const float* coef_dev, int silu, const float* s_dev, int sign, float* dw_dev,
                              int B, int H, int W, int C, void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, t_dev && s_dev && dw_dev && C % 64 == 0 && (sign == 1 || sign == -1), "cddpm_op_chan_image_corr: bad arguments")
+    OP_CHECK(B >= 1 && H >= 1 && W >= 1 && C >= 64 && C % 64 == 0 && (sign == 1 || sign == -1),
+             "cddpm_op_chan_image_corr: unsupported arguments (B %d, H %d, W %d: all >= 1; C %d: a multiple of 64; sign %d: +1 or -1)", B, H, W, C, sign)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, t_dev && s_dev && dw_dev, "cddpm_op_chan_image_corr: NULL argument")
     OpScratch sc(h, s);
     double* part = chan_image_corr_scratch(sc, C);
     SCRATCH_CHECK(sc)
@@ -414,7 +433,8 @@ int cddpm_op_chan_image_corr(cddpm_handle h, const float* t_dev, const float* co
     OP_EPILOGUE()
 }
 int cddpm_op_head_dgrad(cddpm_handle h, const float* dout_dev, const float* w9_dev, float* dact_dev, int B, int H, int W, int C, void* stream) {
-    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dout_dev && w9_dev && dact_dev && C % 4 == 0, "cddpm_op_head_dgrad: bad arguments")
+    OP_CHECK(B >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, "cddpm_op_head_dgrad: unsupported shape (B %d, H %d, W %d: all >= 1; C %d: a multiple of 4)", B, H, W, C)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, dout_dev && w9_dev && dact_dev, "cddpm_op_head_dgrad: NULL argument")
     launch_head_dgrad(dout_dev, w9_dev, dact_dev, B, H, W, C, s);
     OP_EPILOGUE()
 }

@@ -116,6 +116,15 @@ void launch_gn_finalize(const float* rec0, int C0, int n0, const float* rec1, in
 void launch_conv_in1(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int C,
                      hipStream_t stream);
 // head: per pixel 9 partial dot products of act(x) with w[tap][C] -> P[B,HW,9]; then gather to out [B,H,W]
+// head_dots stages 64 pixel rows of C + 4 floats and the [9][C] weight image in dynamic LDS: the widest C is what a gfx950
+// workgroup's 160 KB holds (cddpm_op_head refuses more)
+constexpr size_t LDS_BYTES_PER_WORKGROUP = 160 * 1024;
+constexpr size_t head_dots_lds_bytes(int C) { return ((size_t)64 * (C + 4) + (size_t)9 * C) * sizeof(float); }
+constexpr int head_max_channels() {
+    int C = 32;
+    while (head_dots_lds_bytes(C + 32) <= LDS_BYTES_PER_WORKGROUP) C += 32;
+    return C;
+}
 void launch_head_dots(const float* x, const float* coef, const float* w9 /*[9][C]*/, float* P, int B, int HW, int C,
                       hipStream_t stream);
 void launch_head_gather(const float* P, float bias, const float* bias_ptr /* device, overrides bias */, float* out, int B, int H, int W,

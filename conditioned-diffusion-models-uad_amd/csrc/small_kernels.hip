@@ -132,7 +132,13 @@ __global__ __launch_bounds__(256) void head_dots_kernel(const float* __restrict_
 void launch_head_dots(const float* x, const float* coef, const float* w9, float* P, int B, int HW, int C,
                       hipStream_t stream) {
     const long long total = (long long)B * HW;
-    const size_t lds = (size_t)(64 * (C + 4) + 9 * C) * sizeof(float);
+    const size_t lds = head_dots_lds_bytes(C);      // above 64 KB from C = 224
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_dots_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)LDS_BYTES_PER_WORKGROUP);
+        attr = true;
+    }
     hipLaunchKernelGGL(head_dots_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), lds, stream, x, coef, w9, P, B,
                        HW, C);
 }

@@ -1164,7 +1164,7 @@ __global__ void corr_reduce_kernel(const double* __restrict__ part, int nsplit, 
     for (int p = 0; p < nsplit; ++p) s += part[(size_t)p * n + i];
     dw[i] = (float)s;
 }
-// part: scratch of 64 * C * 9 doubles;  dw [C][9]
+// part: scratch of 256 * C * 9 doubles (one [C][9] plane per pixel split);  dw [C][9]
 void launch_chan_image_corr(const float* T, const float* coef, int silu, const float* simg, int sign, int B, int H, int W, int C,
                             double* part, float* dw, hipStream_t stream) {
     const int nsplit = 256;      // x C / 64 workgroups (128 of them took 0.5 ms per launch at 16 x 128 x 128)

@@ -488,7 +488,13 @@ int cddpm_op_linear_backward(cddpm_handle h, const float* x_dev, const float* w_
                              int silu_in, float* dw_dev, float* db_dev, float* dx_dev, void* stream);
 /* small forward operators of the UNet as stand-alone entry points (the training step's host code sequences them; every pointer is a
  * device pointer, NHWC fp32): y[M,N] = [SiLU](x[M,K]) w[N,K]^T + b (torch.nn.Linear); input_blocks.0 Conv2d(1 -> C, 3x3) with w [C][9];
- * the head out.2 Conv2d(C -> 1, 3x3) on act(x) with w9 [9][C]; the down-ResBlock front end (hp = avgpool2(act(x)), xp = avgpool2(x)). */
+ * the head out.2 Conv2d(C -> 1, 3x3) on act(x) with w9 [9][C]; the down-ResBlock front end (hp = avgpool2(act(x)), xp = avgpool2(x)).
+ * Each entry refuses, with a message (cddpm_last_error) and before anything is launched, what its kernel cannot compute:
+ *   cddpm_op_linear   : M, N, K >= 1; K a multiple of 4 and x_dev, w_dev 16-byte aligned (the rows are read in quads of K);
+ *   cddpm_op_conv_in1 : B, H, W >= 1 and B * H * W < 2^31 (one flat 32-bit pixel range); C a multiple of 64, at most 512;
+ *   cddpm_op_head     : B, H, W >= 1; C a multiple of 32, at most the C whose 64 (C + 4) + 9 C staged floats fit a gfx950 workgroup's
+ *                       160 KB of LDS (544);
+ *   cddpm_op_pool_act : B >= 1; H, W even and >= 2; C a multiple of 4. */
 int cddpm_op_linear(cddpm_handle h, const float* x_dev, const float* w_dev, const float* b_dev, int M, int N, int K, int silu_in,
                     float* y_dev, void* stream);
 int cddpm_op_conv_in1(cddpm_handle h, const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int B, int H, int W,
@@ -498,7 +504,8 @@ int cddpm_op_head(cddpm_handle h, const float* x_dev, const float* coef_dev, con
 int cddpm_op_pool_act(cddpm_handle h, const float* x_dev, const float* coef_dev, float* hp_dev, float* xp_dev, int B, int H, int W, int C,
                       void* stream);
 /* resampling backward and accumulation: dx[B,H,W,C] (+)= scale * dyp[B,H/2,W/2,C] at (y/2, x/2) (AvgPool2d(2) backward: scale 1/4);
- * dxp[B,H/2,W/2,C] (+)= 2x2 block sums of dy (nearest x2 upsample backward); a += b (n floats, multiple of 4). */
+ * dxp[B,H/2,W/2,C] (+)= 2x2 block sums of dy (nearest x2 upsample backward); a += b (n floats, multiple of 4).
+ * unpool2 / sumpool2: B >= 1, H and W even and >= 2, C a multiple of 4; anything else is refused with a message. */
 int cddpm_op_unpool2(cddpm_handle h, const float* dyp_dev, float* dx_dev, int B, int H, int W, int C, float scale, int accumulate, void* stream);
 int cddpm_op_sumpool2(cddpm_handle h, const float* dy_dev, float* dxp_dev, int B, int H, int W, int C, int accumulate, void* stream);
 int cddpm_op_add_inplace(cddpm_handle h, float* a_dev, const float* b_dev, int64_t n, void* stream);
@@ -517,7 +524,8 @@ int cddpm_op_dropout_scale(cddpm_handle h, float* da_dev, uint64_t seed, uint32_
                            int HW, int C, void* stream);
 /* weight gradients of the two single-channel convolutions: dw_dev [C][9] = sum_{b,q} act(T)[b,q,c] * s[b, q + sign * tap]
  * (input conv: T = dL/d(output), s = the image, sign +1; head conv: T = the head's input, act = its GroupNorm + SiLU, s = dL/d(out),
- * sign -1), and the head's input gradient dact[b,q,c] = sum_tap w9[tap][c] dout[b, q - tap]. */
+ * sign -1), and the head's input gradient dact[b,q,c] = sum_tap w9[tap][c] dout[b, q - tap].
+ * Both refuse B, H or W < 1 with a message; chan_image_corr: C a multiple of 64, sign +1 or -1; head_dgrad: C a multiple of 4. */
 int cddpm_op_chan_image_corr(cddpm_handle h, const float* t_dev, const float* coef_dev, int silu, const float* s_dev, int sign, float* dw_dev,
                              int B, int H, int W, int C, void* stream);
 int cddpm_op_head_dgrad(cddpm_handle h, const float* dout_dev, const float* w9_dev, float* dact_dev, int B, int H, int W, int C, void* stream);
