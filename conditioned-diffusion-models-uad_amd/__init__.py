@@ -5,7 +5,7 @@ Import this package with importlib (the directory name carries a hyphen):
 Submodules: synth (counter RNG + synthetic weights), schedule, engine (ctypes owner of the HIP handle),
 OpenAI_Unet / cond_DDPM / DDPM_2D / DDPM_2D_patched (host-side mirrors of the reference classes; the patched DDPM's class is
 DDPM_2D_patched.DDPM_2D, its box sampler patch_sampling.BoxSampler -- both also reachable as pkg.DDPM_2D_patched / pkg.BoxSampler),
-sharding, config, build.
+Spark_2D (the mirror of the SparK pre-training LightningModule) over spark_training, sharding, config, build.
 Nothing here imports oracle/ and nothing computes on the CPU: without the HIP library the path raises.
 """
 __all__ = ["synth", "schedule", "engine", "build", "DDPM_2D_patched", "BoxSampler"]

@@ -146,6 +146,19 @@ SYMBOLS = {
     "cddpm_op_enc_stem_wgrad_scratch": (_sz, [_i] * 3),
     "cddpm_op_enc_bn_forward_scratch": (_sz, [_i64, _i, _i]),
     "cddpm_op_enc_bn_backward_scratch": (_sz, [_i64, _i, _i]),
+    "cddpm_op_spark_bn_forward": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, C.c_float, C.c_float, _fp, _fp, _fp, _fp, _i64, _i, _i, _vp, _i, _i, _i, _fp, _i,
+                                       _vp]),
+    "cddpm_op_spark_bn_backward": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i64, _i, _i, _vp, _i, _i, _i, _fp, _i, _vp]),
+    "cddpm_op_spark_mask_mul": (_i, [_vp, _fp, _vp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "cddpm_op_spark_conv": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cddpm_op_spark_conv_wgrad": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cddpm_op_spark_loss": (_i, [_vp, _fp, _fp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _fp, _fp, _vp]),
+    "cddpm_op_adamw_guarded": (_i, [_vp, _fp, _fp, _fp, _fp, _i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    "cddpm_op_spark_bn_forward_scratch": (_sz, [_i64, _i, _i]),
+    "cddpm_op_spark_bn_backward_scratch": (_sz, [_i64, _i, _i]),
+    "cddpm_op_spark_conv_scratch": (_sz, [_i] * 8),
+    "cddpm_op_spark_conv_wgrad_scratch": (_sz, [_i] * 8),
+    "cddpm_op_spark_loss_scratch": (_sz, [_i] * 4),
     "cddpm_op_absmax": (_i, [_vp, _fp, _i64, _fp, _vp]),
     "cddpm_op_pack_conv": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _vp, _vp]),
     "cddpm_op_pack_conv_batch": (_i, [_vp, _vp, _i, _i64, _vp]),

@@ -102,10 +102,15 @@ def compose(config_dir: str, experiment: str = "cDDPM/DDPM_cond_spark_2D", overr
 
 
 def instantiate_model(cfg: Dict[str, Any], encoder=None):
-    """what `hydra.utils.instantiate(cfg.model)` does for `_target_: src.models.DDPM_2D.DDPM_2D` and
-    `src.models.DDPM_2D_patched.DDPM_2D` (reference src/train.py:98), bound to this package's mirrors."""
-    cls, patched = model_class(cfg["model"].get("_target_", ""))
+    """what `hydra.utils.instantiate(cfg.model)` does for `_target_: src.models.DDPM_2D.DDPM_2D`,
+    `src.models.DDPM_2D_patched.DDPM_2D` and `src.models.Spark_2D.Spark_2D` (reference src/train.py:98), bound to this package's mirrors."""
+    target = cfg["model"].get("_target_", "")
+    cls, patched = model_class(target)
     from .mirror_common import AttrDict
+    if target.endswith("Spark_2D.Spark_2D"):
+        if encoder is not None:
+            raise ValueError("SparK pre-training builds its own sparse encoder: it takes none")
+        return cls(AttrDict(cfg["model"]["cfg"]), prefix=None)
     if patched:
         if encoder is not None:
             raise ValueError("the patched DDPM is unconditioned: it takes no encoder")
@@ -115,12 +120,16 @@ def instantiate_model(cfg: Dict[str, Any], encoder=None):
 
 def model_class(target: str):
     """the mirror class a Hydra `_target_` names -> (class, is the patched DDPM): `src.models.DDPM_2D.DDPM_2D` (experiments
-    DDPM_cond_spark_2D and DDPM) or `src.models.DDPM_2D_patched.DDPM_2D` (experiment DDPM_patched); anything else is refused"""
+    DDPM_cond_spark_2D and DDPM), `src.models.DDPM_2D_patched.DDPM_2D` (experiment DDPM_patched) or `src.models.Spark_2D.Spark_2D`
+    (experiment Spark_2D_pretrain, the encoder's masked pre-training; not patched); anything else is refused"""
+    if target.endswith("Spark_2D.Spark_2D"):
+        from .Spark_2D import Spark_2D
+        return Spark_2D, False
     if target.endswith("DDPM_2D_patched.DDPM_2D"):
         from .DDPM_2D_patched import DDPM_2D as Patched
         return Patched, True
     if target.endswith("DDPM_2D.DDPM_2D"):
         from .DDPM_2D import DDPM_2D
         return DDPM_2D, False
-    raise NotImplementedError("only the targets src.models.DDPM_2D.DDPM_2D and src.models.DDPM_2D_patched.DDPM_2D are provided, "
+    raise NotImplementedError("only the targets src.models.DDPM_2D.DDPM_2D, src.models.DDPM_2D_patched.DDPM_2D and src.models.Spark_2D.Spark_2D are provided, "
                               f"got {target!r}")

@@ -509,13 +509,13 @@ int cddpm_op_guard_commit(cddpm_handle h, int32_t* ctrl_dev, float beta1, float 
 int cddpm_op_adam_guarded(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1,
                           float beta2, float eps, float grad_unscale, const int32_t* ctrl_dev, void* stream) {
     OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && ctrl_dev && n > 0, "cddpm_op_adam_guarded: bad arguments")
-    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, grad_unscale, ctrl_dev, nullptr, s);
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, grad_unscale, 0.0f, ctrl_dev, nullptr, s);
     OP_EPILOGUE()
 }
 int cddpm_op_adam_scaled(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1,
                          float beta2, float eps, float extra_unscale, const int32_t* ctrl_dev, const int32_t* scaler_dev, void* stream) {
     OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && ctrl_dev && scaler_dev && n > 0, "cddpm_op_adam_scaled: bad arguments")
-    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, extra_unscale, ctrl_dev, scaler_dev, s);
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, extra_unscale, 0.0f, ctrl_dev, scaler_dev, s);
     OP_EPILOGUE()
 }
 static bool power_of_two(float x) {
@@ -775,6 +775,197 @@ int cddpm_op_attention(cddpm_handle h, const float* qkv_dev, float* out_dev, int
     OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention: C must be a multiple of 64")
     OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && out_dev, "cddpm_op_attention: NULL argument")
     launch_attention(qkv_dev, out_dev, B, N, C, s);
+    OP_EPILOGUE()
+}
+
+// ---- SparK masked pre-training (spark_train.hip; reference src/models/Spark_2D.py, src/models/modules/spark/): NHWC fp32 device tensors ----
+static bool spark_aligned(std::initializer_list<const void*> ps) {
+    uintptr_t u = 0;
+    for (const void* p : ps) u |= (uintptr_t)p;
+    return (u & 15) == 0;
+}
+static bool spark_bn_shape_ok(int64_t N, int HW, int C, bool masked, int f, int H, int W) {
+    return N > 0 && N <= 0x7FFFFFFF && H > 0 && W > 0 && HW > 0 && (int64_t)H * W == HW && N % HW == 0 && C >= 4 && C % 4 == 0 && C <= 65536 &&
+           (!masked || (f >= 1 && H % f == 0 && W % f == 0 && (N / HW) * f * f <= 0x7FFFFFFF));
+}
+static double* spark_bn_scratch(OpScratch& sc, int64_t N, int C, bool backward, float*& k, int*& status) {
+    double* part = sc.n<double>((size_t)spark_bn_chunks(N, C) * (backward ? 3 : 2) * C);
+    k = backward ? sc.n<float>((size_t)2 * C) : nullptr;
+    status = backward ? nullptr : sc.n<int>(2);
+    return part;
+}
+size_t cddpm_op_spark_bn_forward_scratch(int64_t N, int HW, int C) {
+    if (N <= 0 || N > 0x7FFFFFFF || HW <= 0 || N % HW || C < 4 || C % 4 || C > 65536) return 0;
+    float* k; int* st;
+    return counted([&](OpScratch& sc) { spark_bn_scratch(sc, N, C, false, k, st); });
+}
+size_t cddpm_op_spark_bn_backward_scratch(int64_t N, int HW, int C) {
+    if (N <= 0 || N > 0x7FFFFFFF || HW <= 0 || N % HW || C < 4 || C % 4 || C > 65536) return 0;
+    float* k; int* st;
+    return counted([&](OpScratch& sc) { spark_bn_scratch(sc, N, C, true, k, st); });
+}
+int cddpm_op_spark_bn_forward(cddpm_handle h, const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* sample_scale_dev,
+                              const float* res_dev, int act, float eps, float momentum, float* run_mean_dev, float* run_var_dev, float* mean_rstd_dev,
+                              float* y_dev, int64_t N, int HW, int C, const uint8_t* active_dev, int f, int H, int W, const float* fill_dev, int training,
+                              void* stream) {
+    OP_CHECK(spark_bn_shape_ok(N, HW, C, active_dev != nullptr, f, H, W) && act >= 0 && act <= 2,
+             "cddpm_op_spark_bn_forward: unsupported arguments (N %lld = B H W, HW %d = H %d x W %d, C %d a multiple of 4, f %d dividing H and W, act %d in 0..2)",
+             (long long)N, HW, H, W, C, f, act)
+    OP_CHECK(training ? (!run_mean_dev == !run_var_dev) : (run_mean_dev && run_var_dev),
+             "cddpm_op_spark_bn_forward: running statistics come as a pair, and evaluation mode (training = 0) needs them")
+    OP_CHECK(!training || active_dev || N >= 2, "cddpm_op_spark_bn_forward: training-mode BatchNorm needs more than one value per channel (N = %lld)", (long long)N)
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0,
+                z_dev && gamma_dev && beta_dev && mean_rstd_dev && y_dev && spark_aligned({z_dev, gamma_dev, beta_dev, res_dev, mean_rstd_dev, y_dev, fill_dev}),
+                "cddpm_op_spark_bn_forward: NULL argument or a tensor that is not 16-byte aligned")
+    const int B = (int)(N / HW);
+    OpScratch sc(h, s);
+    float* k; int* status;
+    double* part = spark_bn_scratch(sc, N, C, false, k, status);
+    SCRATCH_CHECK(sc)
+    if (training) {
+        launch_spark_bn_stats(z_dev, active_dev, f, B, H, W, C, eps, momentum, run_mean_dev, run_var_dev, mean_rstd_dev, part, status, s);
+        if (active_dev) {        // n_act is the device's count: read its verdict back before anything is written from statistics of one row
+            int st[2] = {0, 0};
+            HIPCHECK(h, hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s));
+            HIPCHECK(h, hipStreamSynchronize(s));
+            if (st[0])
+                return fail(h, "cddpm_op_spark_bn_forward: %d active pixel(s): training-mode BatchNorm needs more than one value per channel "
+                               "(torch's BatchNorm1d raises here)", st[1]);
+        }
+    } else {
+        launch_spark_bn_eval_stats(run_mean_dev, run_var_dev, eps, C, mean_rstd_dev, s);
+    }
+    launch_spark_bn_act(z_dev, mean_rstd_dev, gamma_dev, beta_dev, sample_scale_dev, res_dev, active_dev, f, fill_dev, act, y_dev, B, H, W, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_spark_bn_backward(cddpm_handle h, const float* z_dev, const float* y_dev, const float* dy_dev, const float* mean_rstd_dev,
+                               const float* gamma_dev, const float* sample_scale_dev, int act, float* dz_dev, float* dres_dev, float* dgamma_dev,
+                               float* dbeta_dev, int64_t N, int HW, int C, const uint8_t* active_dev, int f, int H, int W, float* dfill_dev, int training,
+                               void* stream) {
+    OP_CHECK(spark_bn_shape_ok(N, HW, C, active_dev != nullptr, f, H, W) && act >= 0 && act <= 2,
+             "cddpm_op_spark_bn_backward: unsupported arguments (N %lld = B H W, HW %d = H %d x W %d, C %d a multiple of 4, f %d dividing H and W, act %d in 0..2)",
+             (long long)N, HW, H, W, C, f, act)
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0,
+                z_dev && dy_dev && mean_rstd_dev && gamma_dev && dz_dev && dgamma_dev && dbeta_dev && (!act || y_dev) &&
+                    spark_aligned({z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, dz_dev, dres_dev}),
+                "cddpm_op_spark_bn_backward: NULL argument (y_dev is needed with an activation) or a tensor that is not 16-byte aligned")
+    OpScratch sc(h, s);
+    float* k; int* status;
+    double* part = spark_bn_scratch(sc, N, C, true, k, status);
+    SCRATCH_CHECK(sc)
+    launch_spark_bn_backward(z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, sample_scale_dev, act, active_dev, f, training, dz_dev, dres_dev, dgamma_dev,
+                             dbeta_dev, dfill_dev, k, part, (int)(N / HW), H, W, C, s);
+    OP_EPILOGUE()
+}
+int cddpm_op_spark_mask_mul(cddpm_handle h, const float* x_dev, const uint8_t* active_dev, float* y_dev, int B, int H, int W, int C, int f, void* stream) {
+    OP_CHECK(B >= 1 && H >= 1 && W >= 1 && C >= 1 && f >= 1 && H % f == 0 && W % f == 0 && (int64_t)B * H * W <= 0x7FFFFFFF,
+             "cddpm_op_spark_mask_mul: unsupported shape (B %d, H %d, W %d, C %d, f %d dividing H and W)", B, H, W, C, f)
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && active_dev && y_dev, "cddpm_op_spark_mask_mul: NULL argument")
+    launch_spark_mask_mul(x_dev, active_dev, y_dev, B, H, W, C, f, s);
+    OP_EPILOGUE()
+}
+
+// Conv2d (K 1 | 3, stride 1, pad K / 2) and ConvTranspose2d (K 4, stride 2, pad 1), forward and input gradient, as one gather over the layer's
+// own weight tensor. H, W: the LAYER's input size (a ConvTranspose2d's output is 2H x 2W)
+static bool spark_conv_geom(int B, int H, int W, int Cin, int Cout, int K, int tconv, int backward, SparkConv& a) {
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || Cin > 65536 || Cout > 65536 || (int64_t)B * H * W * 4 > 0x7FFFFFFF) return false;
+    if (tconv ? K != 4 : (K != 1 && K != 3)) return false;
+    const long long KK = (long long)K * K;
+    a.B = B; a.K = K; a.stride = tconv ? 2 : 1; a.pad = tconv ? 1 : K / 2;
+    const int Ho = tconv ? 2 * H : H, Wo = tconv ? 2 * W : W;
+    if (!backward) { a.Hs = H; a.Ws = W; a.Hd = Ho; a.Wd = Wo; a.Cs = Cin; a.Cd = Cout; }
+    else { a.Hs = Ho; a.Ws = Wo; a.Hd = H; a.Wd = W; a.Cs = Cout; a.Cd = Cin; }
+    a.form = (tconv != 0) == (backward != 0) ? 0 : 1;
+    // Conv2d [Cout][Cin][K][K]; ConvTranspose2d [Cin][Cout][K][K]
+    const long long s_in = tconv ? Cout * KK : KK, s_out = tconv ? KK : Cin * KK;
+    a.wsd = backward ? s_in : s_out; a.wss = backward ? s_out : s_in;
+    return true;
+}
+static float* spark_conv_scratch(OpScratch& sc, const SparkConv& a) {
+    const long long M = (long long)a.B * a.Hd * a.Wd;
+    const int Z = spark_conv_split(M, a.Cd, a.Cs, a.K);
+    return Z == 1 ? nullptr : sc.n<float>((size_t)Z * M * a.Cd);
+}
+size_t cddpm_op_spark_conv_scratch(int B, int H, int W, int Cin, int Cout, int K, int transposed_conv, int backward) {
+    SparkConv a;
+    if (!spark_conv_geom(B, H, W, Cin, Cout, K, transposed_conv, backward, a)) return 0;
+    return counted([&](OpScratch& sc) { spark_conv_scratch(sc, a); });
+}
+int cddpm_op_spark_conv(cddpm_handle h, const float* src_dev, const float* w_dev, const float* bias_dev, float* dst_dev, int B, int H, int W, int Cin,
+                        int Cout, int K, int transposed_conv, int backward, void* stream) {
+    SparkConv a;
+    OP_CHECK(spark_conv_geom(B, H, W, Cin, Cout, K, transposed_conv, backward, a),
+             "cddpm_op_spark_conv: unsupported shape (B %d, H %d, W %d, Cin %d, Cout %d; K %d: 1 | 3 for a convolution, 4 for a transposed one)", B, H, W, Cin,
+             Cout, K)
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, src_dev && w_dev && dst_dev && src_dev != dst_dev && spark_aligned({src_dev, dst_dev}),
+                "cddpm_op_spark_conv: NULL argument, src = dst, or a tensor that is not 16-byte aligned")
+    OpScratch sc(h, s);
+    a.part = spark_conv_scratch(sc, a);
+    SCRATCH_CHECK(sc)
+    a.src = src_dev; a.w = w_dev; a.bias = bias_dev; a.dst = dst_dev;
+    launch_spark_conv(a, s);
+    OP_EPILOGUE()
+}
+static bool spark_wgrad_geom(int B, int H, int W, int Cin, int Cout, int K, int tconv, SparkWgrad& a) {
+    SparkConv c;
+    if (!spark_conv_geom(B, H, W, Cin, Cout, K, tconv, 0, c)) return false;
+    a.B = B; a.Hq = H; a.Wq = W; a.Hg = tconv ? 2 * H : H; a.Wg = tconv ? 2 * W : W; a.K = K; a.stride = c.stride; a.pad = c.pad;
+    a.Cd = tconv ? Cin : Cout; a.Cg = tconv ? Cout : Cin;
+    a.P = spark_wgrad_parts((long long)B * H * W, a.Cd, a.Cg, K);
+    return true;
+}
+static float* spark_wgrad_scratch(OpScratch& sc, const SparkWgrad& a, bool has_db, int Cout, long long Mdy, double*& bpart) {
+    float* part = sc.n<float>((size_t)a.P * a.Cd * a.Cg * a.K * a.K);
+    bpart = has_db ? sc.n<double>((size_t)spark_chan_sum_chunks(Mdy, Cout) * Cout) : nullptr;
+    return part;
+}
+size_t cddpm_op_spark_conv_wgrad_scratch(int B, int H, int W, int Cin, int Cout, int K, int transposed_conv, int has_db) {
+    SparkWgrad a;
+    if (!spark_wgrad_geom(B, H, W, Cin, Cout, K, transposed_conv, a) || (has_db && Cout > 256)) return 0;
+    double* bpart;
+    return counted([&](OpScratch& sc) { spark_wgrad_scratch(sc, a, has_db != 0, Cout, (long long)B * a.Hg * a.Wg, bpart); });
+}
+int cddpm_op_spark_conv_wgrad(cddpm_handle h, const float* x_dev, const float* dy_dev, float* dw_dev, float* db_dev, int B, int H, int W, int Cin, int Cout,
+                              int K, int transposed_conv, void* stream) {
+    SparkWgrad a;
+    OP_CHECK(spark_wgrad_geom(B, H, W, Cin, Cout, K, transposed_conv, a) && (!db_dev || Cout <= 256),
+             "cddpm_op_spark_conv_wgrad: unsupported shape (B %d, H %d, W %d, Cin %d, Cout %d (<= 256 with a bias gradient); K %d: 1 | 3, or 4 transposed)", B,
+             H, W, Cin, Cout, K)
+    OP_PROLOGUE(PC_ENC, 0.0, 0.0, x_dev && dy_dev && dw_dev && spark_aligned({x_dev, dy_dev}),
+                "cddpm_op_spark_conv_wgrad: NULL argument or a tensor that is not 16-byte aligned")
+    OpScratch sc(h, s);
+    double* bpart;
+    const long long Mdy = (long long)B * a.Hg * a.Wg;          // pixels of dy: the layer's output
+    a.part = spark_wgrad_scratch(sc, a, db_dev != nullptr, Cout, Mdy, bpart);
+    SCRATCH_CHECK(sc)
+    a.d = transposed_conv ? x_dev : dy_dev; a.g = transposed_conv ? dy_dev : x_dev;
+    launch_spark_wgrad(a, dw_dev, s);
+    if (db_dev) launch_spark_chan_sum(dy_dev, Mdy, Cout, bpart, db_dev, s);
+    OP_EPILOGUE()
+}
+static bool spark_loss_shape_ok(int B, int H, int W, int f) {
+    return B >= 1 && H >= 1 && W >= 1 && f >= 1 && H % f == 0 && W % f == 0 && (int64_t)B * H * W <= 0x7FFFFFFF;
+}
+static double* spark_loss_scratch(OpScratch& sc, int B, int H, int W) { return sc.n<double>((size_t)spark_loss_chunks((long long)B * H * W) * 2); }
+size_t cddpm_op_spark_loss_scratch(int B, int H, int W, int f) {
+    if (!spark_loss_shape_ok(B, H, W, f)) return 0;
+    return counted([&](OpScratch& sc) { spark_loss_scratch(sc, B, H, W); });
+}
+int cddpm_op_spark_loss(cddpm_handle h, const float* rec_dev, const float* inp_dev, const uint8_t* active_dev, int f, int B, int H, int W, float w_mask,
+                        float w_l1, float* loss_dev, float* drec_dev, void* stream) {
+    OP_CHECK(spark_loss_shape_ok(B, H, W, f), "cddpm_op_spark_loss: unsupported shape (B %d, H %d, W %d, f %d dividing H and W)", B, H, W, f)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, rec_dev && inp_dev && active_dev && loss_dev, "cddpm_op_spark_loss: NULL argument")
+    OpScratch sc(h, s);
+    double* part = spark_loss_scratch(sc, B, H, W);
+    SCRATCH_CHECK(sc)
+    launch_spark_loss(rec_dev, inp_dev, active_dev, f, B, H, W, w_mask, w_l1, loss_dev, drec_dev, part, s);
+    OP_EPILOGUE()
+}
+// torch.optim.AdamW (src/models/Spark_2D.py:123-124): cddpm_op_adam_guarded with the decoupled decay p <- p (1 - lr weight_decay) before the update
+int cddpm_op_adamw_guarded(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, float grad_unscale, const int32_t* ctrl_dev, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && ctrl_dev && n > 0 && weight_decay >= 0.0f, "cddpm_op_adamw_guarded: bad arguments")
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, grad_unscale, weight_decay, ctrl_dev, nullptr, s);
     OP_EPILOGUE()
 }
 

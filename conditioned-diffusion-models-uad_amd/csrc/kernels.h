@@ -256,7 +256,7 @@ void launch_grad_check(const float* g, long long n, int* ctrl, hipStream_t strea
 void launch_guard_commit(int* ctrl, float b1, float b2, hipStream_t stream);
 // scaler: nullptr = gradient g * grad_unscale; else g * grad_unscale / (the device loss scale)
 void launch_adam_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float grad_unscale,
-                         const int* ctrl, const int* scaler, hipStream_t stream);
+                         float weight_decay /* 0: Adam; else AdamW's decoupled decay */, const int* ctrl, const int* scaler, hipStream_t stream);
 // scaler = int32[4] {bits of the loss scale, growth tracker, consecutive skips, -}: torch._amp_update_scale_ from ctrl's skip decision
 void launch_scaler_update(const int* ctrl, int* scaler, float growth, float backoff, int interval, hipStream_t stream);
 void launch_gn_silu_backward(const float* x, const float* x1 /* second source of a concatenated input or nullptr */, int C0, float* dx1,
@@ -322,5 +322,37 @@ void launch_enc_maxpool(const float* x, float* y, int B, int H, int W, int C, hi
 void launch_enc_maxpool_backward(const float* x, const float* dy, float* dx, int B, int H, int W, int C, hipStream_t s);
 void launch_enc_avgpool(const float* x, float* g, int B, int HW, int C, hipStream_t s);
 void launch_enc_avgpool_backward(const float* dg, float* dx, int B, int HW, int C, hipStream_t s);
+
+// ---- SparK masked pre-training (spark_train.hip): sparse / dense BatchNorm with a fill value and ReLU6, the mask multiply, the
+// small-channel convolution family (gather kernel in two index forms + weight gradient), the masked loss
+struct SparkConv {
+    const float* src; const float* w; const float* bias; float* dst;
+    float* part;               // [Z][pixels][Cd] contraction-split planes, or nullptr (no split)
+    int B, Hs, Ws, Hd, Wd;     // source and destination geometry
+    int Cs, Cd, K, stride, pad;
+    int form;                  // 0: ys = y stride + ky - pad; 1: ys = (y + pad - ky) / stride where exact
+    long long wsd, wss;        // weight strides of the destination / source channel (the K K taps are contiguous)
+    int Z;                     // set by the launcher
+};
+struct SparkWgrad { const float* d; const float* g; float* part; int B, Hq, Wq, Hg, Wg, Cd, Cg, K, stride, pad, P; };
+int spark_bn_chunks(long long N, int C);
+void launch_spark_bn_stats(const float* z, const unsigned char* active, int f, int B, int H, int W, int C, float eps, float momentum, float* run_mean,
+                           float* run_var, float* mr, double* part, int* status, hipStream_t s);
+void launch_spark_bn_eval_stats(const float* run_mean, const float* run_var, float eps, int C, float* mr, hipStream_t s);
+void launch_spark_bn_act(const float* z, const float* mr, const float* gamma, const float* beta, const float* sscale, const float* res,
+                         const unsigned char* active, int f, const float* fill, int act, float* y, int B, int H, int W, int C, hipStream_t s);
+void launch_spark_bn_backward(const float* z, const float* y, const float* dy, const float* mr, const float* gamma, const float* sscale, int act,
+                              const unsigned char* active, int f, int training, float* dz, float* dres, float* dgamma, float* dbeta, float* dfill,
+                              float* k, double* part, int B, int H, int W, int C, hipStream_t s);
+void launch_spark_mask_mul(const float* x, const unsigned char* active, float* y, int B, int H, int W, int C, int f, hipStream_t s);
+int spark_conv_split(long long M, int Cd, int Cs, int K);
+void launch_spark_conv(SparkConv a, hipStream_t s);
+int spark_wgrad_parts(long long M, int Cd, int Cg, int K);
+void launch_spark_wgrad(SparkWgrad a, float* dw, hipStream_t s);
+int spark_chan_sum_chunks(long long M, int C);
+void launch_spark_chan_sum(const float* x, long long M, int C, double* part, float* out, hipStream_t s);
+int spark_loss_chunks(long long total);
+void launch_spark_loss(const float* rec, const float* inp, const unsigned char* active, int f, int B, int H, int W, float w_mask, float w_l1,
+                       float* loss, float* drec, double* part, hipStream_t s);
 
 }  // namespace cddpm

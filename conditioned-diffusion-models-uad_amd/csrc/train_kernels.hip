@@ -1333,8 +1333,9 @@ __global__ void guard_commit_kernel(int* __restrict__ ctrl, float b1, float b2) 
 }
 __global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
-                                                           float unscale, const int* __restrict__ ctrl, const int* __restrict__ scaler) {
-    if (ctrl[2]) return;                                   // uniform over the grid
+                                                           float unscale, float wd, const int* __restrict__ ctrl,
+                                                           const int* __restrict__ scaler) {
+    if (ctrl[2]) return;                                   // uniform over the grid: a skipped step moves nothing and decays nothing
     const float bc1 = reinterpret_cast<const float*>(ctrl)[4], bc2 = reinterpret_cast<const float*>(ctrl)[5];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -1345,7 +1346,9 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p
     const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
     m[i] = mi; v[i] = vi;
     const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
+    // wd != 0: torch.optim.AdamW's decoupled decay, p <- p (1 - lr wd) before the update
+    const float pi = wd != 0.0f ? p[i] * (1.0f - lr * wd) : p[i];
+    p[i] = pi - (lr / bc1) * (mi / denom);
 }
 void launch_grad_check(const float* g, long long n, int* ctrl, hipStream_t stream) {
     const unsigned blocks = (unsigned)((n / 4 + 255) / 256 < 2048 ? ((n / 4 + 255) / 256 > 0 ? (n / 4 + 255) / 256 : 1) : 2048);
@@ -1355,9 +1358,9 @@ void launch_guard_commit(int* ctrl, float b1, float b2, hipStream_t stream) {
     hipLaunchKernelGGL(guard_commit_kernel, dim3(1), dim3(64), 0, stream, ctrl, b1, b2);
 }
 void launch_adam_guarded(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps,
-                         float grad_unscale, const int* ctrl, const int* scaler, hipStream_t stream) {
-    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, m, v, n, lr, b1, b2, eps, grad_unscale, ctrl,
-                       scaler);
+                         float grad_unscale, float weight_decay, const int* ctrl, const int* scaler, hipStream_t stream) {
+    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, m, v, n, lr, b1, b2, eps, grad_unscale,
+                       weight_decay, ctrl, scaler);
 }
 
 // ---- dynamic loss scaling: torch's GradScaler.update (torch._amp_update_scale_) on the device, after the step's Adam updates, from the skip

@@ -66,6 +66,21 @@ def operator_calls(B, H, W, cond_dim=128):
         yield "linear_backward", (B, cond_dim, cin, 0)                    # fc
 
 
+def pyramid_operator_calls(B, H, W):
+    """the calls of EncoderTrainer.forward_pyramid / backward_pyramid (the sparse encoder of SparK pre-training, precision 32) on a
+    [B, 1, H, W] batch that take temporaries from an arena, in the form of operator_calls"""
+    def bn(c, h, w):
+        yield "spark_bn_forward", (B * h * w, h * w, c)
+        yield "spark_bn_backward", (B * h * w, h * w, c)
+
+    for op, args in operator_calls(B, H, W, 0):
+        if op in ("enc_bn_forward", "enc_bn_backward"):
+            if op == "enc_bn_forward":
+                yield from bn(args[2], 1, args[1])
+        elif not op.endswith("_p16"):
+            yield op, args
+
+
 def operator_scratch_bytes(B, H, W, cond_dim=128):
     """-> (main, side): the largest single call of operator_calls, and the largest cddpm_op_enc_conv_wgrad / _wgrad_p16 (what runs on the
     side-stream handle of the trainer whose handles the encoder uses). training.UNetTrainer._fit sizes its arenas for these too."""
@@ -303,6 +318,145 @@ class EncoderTrainer:
         if hasattr(self.ops, "join_side"):
             self.ops.join_side()
         self.saved = None
+        return g
+
+    # ------------------------------------------------------------------ SparK pre-training: the sparse encoder's pyramid
+    # The ResNet-50 after SparseEncoder.dense_model_to_sparse (reference spark/encoder.py:163-204): every BatchNorm is a BatchNorm1d over the
+    # ACTIVE pixels that writes zeros elsewhere, every convolution and pooling output is multiplied by the mask at its resolution. A
+    # convolution is always followed by such a BatchNorm, which neither reads the inactive pixels nor lets a gradient through to them, so
+    # the convolutions run unmasked (cddpm_op_enc_conv as it is); the input and the max-pool output are masked by cddpm_op_spark_mask_mul.
+    def sbn(self, name, z, act, active=None, f=1, res=None, sscale=None, fill=None, training=True):
+        """cddpm_op_spark_bn_forward on parameter group `name`: sparse (active uint8 [B,f,f]) or dense BatchNorm; -> y, (mean | rstd)"""
+        B, H, W, Cc = z.shape
+        mr, y = self._new(2, Cc), torch.empty_like(z)
+        self._ck(self.lib.cddpm_op_spark_bn_forward(self.h, _p(z), _p(self.p[name + ".weight"]), _p(self.p[name + ".bias"]), _p(sscale), _p(res), int(act),
+                                                    C.c_float(BN_EPS), C.c_float(BN_MOMENTUM), _p(self.buf[name + ".running_mean"]),
+                                                    _p(self.buf[name + ".running_var"]), _p(mr), _p(y), B * H * W, H * W, Cc, _p(active), f, H, W,
+                                                    _p(fill), int(training), self._s()), "op_spark_bn_forward")
+        return y, mr
+
+    def sbn_bwd(self, name, z, y, dy, mr, act, active=None, f=1, sscale=None, want_dres=False, dfill=None):
+        B, H, W, Cc = z.shape
+        dz = torch.empty_like(z)
+        dres = torch.empty_like(z) if want_dres else None
+        self._ck(self.lib.cddpm_op_spark_bn_backward(self.h, _p(z), _p(y), _p(dy), _p(mr), _p(self.p[name + ".weight"]), _p(sscale), int(act), _p(dz),
+                                                     _p(dres), _p(self.g[name + ".weight"]), _p(self.g[name + ".bias"]), B * H * W, H * W, Cc,
+                                                     _p(active), f, H, W, _p(dfill), 1, self._s()), "op_spark_bn_backward")
+        return dz, dres
+
+    def mask_mul_(self, x, active, f):
+        """x [B,H,W,C] *= the mask dilated to H x W, in place"""
+        B, H, W, Cc = x.shape
+        self._ck(self.lib.cddpm_op_spark_mask_mul(self.h, _p(x), _p(active), _p(x), B, H, W, Cc, f, self._s()), "op_spark_mask_mul")
+        return x
+
+    def _stage_end(self):
+        """name of each stage's last block -> index of its map among the four of forward_pyramid"""
+        ends = [bk["name"] for i, bk in enumerate(self.blocks) if i + 1 == len(self.blocks) or self.blocks[i + 1]["down"]]
+        return {n: i for i, n in enumerate(ends)}
+
+    def forward_pyramid(self, x: torch.Tensor, active: torch.Tensor, drop_scales: Optional[Dict[str, torch.Tensor]] = None, *, training=True):
+        """x [B,1,H,W] (H, W multiples of 32), active bool / uint8 [B,f,f] or [B,1,f,f] with f = H / 32, both on the device -> the masked
+        outputs of layer1..4 as NHWC tensors [B,8f,8f,256], [B,4f,4f,512], [B,2f,2f,1024], [B,f,f,2048] (forward_features with pyramid = 4,
+        reference spark/resnet.py:13-34) and latent [B,2048] = the layer4 map's mean over its pixels (src/models/Spark_2D.py:32).
+        training False: running statistics, no stochastic depth, nothing kept for a backward. drop_scales: as forward()."""
+        B, _c, H, W = x.shape
+        active = active.reshape(B, -1)
+        f = int(round(active.shape[1] ** 0.5))
+        if f * f != active.shape[1] or H != 32 * f or W != 32 * f:
+            raise ValueError(f"forward_pyramid: a {H} x {W} input needs a [{B}, {H // 32}, {H // 32}] mask (side / 32), got {active.shape[1]} cells")
+        active = active.to(self.dev, torch.uint8).contiguous()
+        xm = x.float().reshape(B, H, W, 1).clone()
+        self.mask_mul_(xm, active, f)
+        kw = dict(active=active, f=f, training=training)
+        H1, W1 = H // 2, W // 2
+        z0 = self._new(B, H1, W1, 64)
+        self._ck(self.lib.cddpm_op_enc_stem(self.h, _p(xm), _p(self.p["conv1.weight"]), _p(z0), B, H, W, self._s()), "op_enc_stem")
+        a0, mr0 = self.sbn("bn1", z0, 1, **kw)
+        cur = self._new(B, H1 // 2, W1 // 2, 64)
+        self._ck(self.lib.cddpm_op_enc_maxpool(self.h, _p(a0), _p(cur), B, H1, W1, 64, 0, None, None, self._s()), "op_enc_maxpool")
+        self.mask_mul_(cur, active, f)
+        sv: Dict[str, object] = dict(x=xm, z0=z0, a0=a0, mr0=mr0, active=active, f=f)
+        feats = []
+        for bk in self.blocks:
+            n = bk["name"]
+            ss = None
+            if training and drop_scales is not None:
+                ss = drop_scales.get(n)
+                ss = None if ss is None else ss.to(self.dev, torch.float32).contiguous()
+            elif training and bk["drop"] > 0:
+                keep = 1.0 - bk["drop"]
+                ss = (torch.floor(keep + torch.rand(B, device=self.dev)) / keep).contiguous()     # timm.layers.drop_path
+            z1 = self.conv(n + ".conv1", cur)
+            a1, mr1 = self.sbn(n + ".bn1", z1, 1, **kw)
+            z2 = self.conv(n + ".conv2", a1)
+            a2, mr2 = self.sbn(n + ".bn2", z2, 1, **kw)
+            z3 = self.conv(n + ".conv3", a2)
+            r = dict(inp=cur, z1=z1, a1=a1, mr1=mr1, z2=z2, a2=a2, mr2=mr2, z3=z3, ss=ss)
+            sc = cur
+            if bk["down"]:
+                zd = self.conv(n + ".downsample.0", cur)
+                sc, mrd = self.sbn(n + ".downsample.1", zd, 0, **kw)
+                r.update(zd=zd, mrd=mrd)
+            out, mr3 = self.sbn(n + ".bn3", z3, 1, res=sc, sscale=ss, **kw)
+            r.update(mr3=mr3, out=out)
+            sv[n] = r
+            cur = out
+            if n in self._stage_end():
+                feats.append(out)
+        Bc, Hc, Wc, Cc = cur.shape
+        latent = self._new(B, Cc)
+        self._ck(self.lib.cddpm_op_enc_avgpool(self.h, _p(cur), _p(latent), B, Hc * Wc, Cc, 0, self._s()), "op_enc_avgpool")
+        self.saved_pyramid = sv if training else None
+        return feats, latent
+
+    def backward_pyramid(self, dfeats) -> Dict[str, torch.Tensor]:
+        """dfeats: dL/d(the four maps of forward_pyramid), NHWC, layer1..4 (None: no gradient into that map) -> the gradient of every
+        parameter (no gradient flows through latent: the pre-training loss does not read it)"""
+        sv, g = self.saved_pyramid, self.g
+        if sv is None:
+            raise RuntimeError("backward_pyramid: no training-mode forward_pyramid to differentiate")
+        active, f = sv["active"], sv["f"]
+        kw = dict(active=active, f=f)
+        stage_end = self._stage_end()
+        d = None
+        for bk in reversed(self.blocks):
+            n, r = bk["name"], sv[bk["name"]]
+            if n in stage_end and dfeats[stage_end[n]] is not None:
+                df = dfeats[stage_end[n]].float().contiguous()
+                d = df.clone() if d is None else self.ops.add_(d, df)
+            if d is None:
+                raise ValueError("backward_pyramid: the gradient of the layer4 map is needed")
+            inp = r["inp"]
+            hw = (inp.shape[1], inp.shape[2])
+            dz3, dsc = self.sbn_bwd(n + ".bn3", r["z3"], r["out"], d, r["mr3"], 1, sscale=r["ss"], want_dres=True, **kw)
+            da2 = self.conv(n + ".conv3", dz3, transposed=True, in_hw=(r["a2"].shape[1], r["a2"].shape[2]))
+            self.wgrad(n + ".conv3", r["a2"], dz3)
+            dz2, _ = self.sbn_bwd(n + ".bn2", r["z2"], r["a2"], da2, r["mr2"], 1, **kw)
+            da1 = self.conv(n + ".conv2", dz2, transposed=True, in_hw=hw)
+            self.wgrad(n + ".conv2", r["a1"], dz2)
+            dz1, _ = self.sbn_bwd(n + ".bn1", r["z1"], r["a1"], da1, r["mr1"], 1, **kw)
+            dinp = self.conv(n + ".conv1", dz1, transposed=True, in_hw=hw)
+            self.wgrad(n + ".conv1", inp, dz1)
+            if bk["down"]:
+                dzd, _ = self.sbn_bwd(n + ".downsample.1", r["zd"], None, dsc, r["mrd"], 0, **kw)
+                self.ops.add_(dinp, self.conv(n + ".downsample.0", dzd, transposed=True, in_hw=hw))
+                self.wgrad(n + ".downsample.0", inp, dzd)
+            else:
+                self.ops.add_(dinp, dsc)
+            d = dinp
+        self.mask_mul_(d, active, f)                                   # the masked max-pool output (SparseMaxPooling, encoder.py:42-43)
+        a0, z0 = sv["a0"], sv["z0"]
+        B, H1, W1, _c = a0.shape
+        da0 = torch.empty_like(a0)
+        self._ck(self.lib.cddpm_op_enc_maxpool(self.h, _p(a0), None, B, H1, W1, 64, 1, _p(d), _p(da0), self._s()), "op_enc_maxpool (backward)")
+        dz0, _ = self.sbn_bwd("bn1", z0, a0, da0, sv["mr0"], 1, **kw)
+        x = sv["x"]
+        self._ck(self.lib.cddpm_op_enc_stem_wgrad(self.h, _p(x), _p(dz0), _p(g["conv1.weight"]), B, x.shape[1], x.shape[2], self._s()),
+                 "op_enc_stem_wgrad")
+        if hasattr(self.ops, "join_side"):
+            self.ops.join_side()
+        self.saved_pyramid = None
         return g
 
     def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=None, guarded=False, extra_unscale=None):

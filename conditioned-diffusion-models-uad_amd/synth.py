@@ -316,3 +316,75 @@ def synth_encoder_state_dict(seed: int = 0, num_classes: int = 128):
             v = (np.float32(2.0) * uniform_quads(nq, 0, 0, stream, seed)[:n] - np.float32(1.0)) * bound
         sd[name] = np.ascontiguousarray(v.astype(np.float32).reshape(shape))
     return sd
+
+
+# ----------------------------------------------------------------------------------------------
+STREAM_SPARK_WEIGHT = 0x5000   # + tensor ordinal (tensors outside the ResNet-50)
+SPARK_ENC_PREFIX = "model.sparse_encoder.sp_cnn."
+
+
+def spark_param_shapes(dec_dim: int = 128, input_size: int = 96):
+    """name -> shape of the state dict of the reference's Spark_2D LightningModule (src/models/Spark_2D.py: `model` = SparK_2D with a
+    resnet50 backbone, pyramid 4, double = True, heavy [0, 1], cmid 0), in state_dict order. num_batches_tracked entries are 0-d int64."""
+    shapes = {"model.imn_m": (1, 3, 1, 1), "model.imn_s": (1, 3, 1, 1), "model.norm_black": (1, 3, input_size, input_size)}
+
+    def bn(p, c):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            shapes[f"{p}.{k}"] = (c,)
+        shapes[f"{p}.num_batches_tracked"] = ()
+    for name, shape in encoder_param_shapes().items():
+        if name.startswith("fc."):
+            continue                                   # num_classes = 0: timm's fc is an Identity
+        shapes[SPARK_ENC_PREFIX + name] = shape
+        if name.endswith("running_var"):
+            shapes[SPARK_ENC_PREFIX + name[:-len("running_var")] + "num_batches_tracked"] = ()
+    for i in range(5):
+        c, p = dec_dim >> i, f"model.dense_decoder.dec.{i}"
+        shapes[p + ".up.weight"] = (c, c, 4, 4); shapes[p + ".up.bias"] = (c,)
+        shapes[p + ".conv.0.b.0.weight"] = (c, c, 3, 3); bn(p + ".conv.0.b.1", c)
+        shapes[p + ".conv.0.b.3.weight"] = (c // 2, c, 3, 3); bn(p + ".conv.0.b.4", c // 2)
+    shapes["model.dense_decoder.proj.weight"] = (1, dec_dim >> 5, 1, 1); shapes["model.dense_decoder.proj.bias"] = (1,)
+    for i in range(4):
+        bn(f"model.en_de_norms.{i}", 2048 >> i)
+    for i in range(4):
+        k = 1 if i == 0 else 3
+        shapes[f"model.en_de_lins.{i}.weight"] = (dec_dim >> i, 2048 >> i, k, k); shapes[f"model.en_de_lins.{i}.bias"] = (dec_dim >> i,)
+    for i in range(4):
+        shapes[f"model.mask_tokens.{i}"] = (1, 2048 >> i, 1, 1)
+    return shapes
+
+
+def synth_spark_state_dict(seed: int = 0, dec_dim: int = 128, input_size: int = 96):
+    """Synthetic SparK weights (numpy; about 100 MB, regenerated wherever they are needed): the ResNet-50 of synth_encoder_state_dict(seed);
+    convolutions ~ U(+-sqrt(3 / fan_in)) (a transposed 4/2/1 convolution sums 4 taps per output: fan_in = 4 Cin), biases and mask tokens
+    0.1 n, BatchNorm gamma = 1 + 0.1 n, beta = 0.1 n, running_mean = 0.1 n, running_var = 1 + 0.2 u, num_batches_tracked = 0, the
+    image-norm buffers as the reference registers them (spark/Spark_2D.py:112-117)."""
+    shapes = spark_param_shapes(dec_dim, input_size)
+    enc = synth_encoder_state_dict(seed)
+    sd = {}
+    for ordinal, (name, shape) in enumerate(shapes.items()):
+        leaf = name.rsplit(".", 1)[1]
+        if leaf == "num_batches_tracked":
+            sd[name] = np.zeros((), dtype=np.int64)
+            continue
+        if name.startswith(SPARK_ENC_PREFIX):
+            sd[name] = enc[name[len(SPARK_ENC_PREFIX):]]
+            continue
+        if name in ("model.imn_m", "model.imn_s", "model.norm_black"):
+            v = {"model.imn_m": (0.485, 0.456, 0.406), "model.imn_s": (0.229, 0.224, 0.225)}.get(name)
+            sd[name] = np.zeros(shape, dtype=np.float32) if v is None else np.asarray(v, dtype=np.float32).reshape(shape)
+            continue
+        n = int(np.prod(shape))
+        nq = (n + 3) // 4
+        stream = STREAM_SPARK_WEIGHT + ordinal
+        if len(shape) == 4 and "mask_tokens" not in name:
+            fan_in = 4 * shape[0] if name.endswith(".up.weight") else int(np.prod(shape[1:]))
+            v = (np.float32(2.0) * uniform_quads(nq, 0, 0, stream, seed)[:n] - np.float32(1.0)) * np.float32(math.sqrt(3.0 / fan_in))
+        elif leaf == "running_var":
+            v = np.float32(1.0) + np.float32(0.2) * uniform_quads(nq, 0, 0, stream, seed)[:n]
+        else:
+            z = normal_quads(nq, 0, 0, stream, seed)[:n]
+            is_gamma = leaf == "weight" and len(shape) == 1
+            v = (np.float32(1.0) + np.float32(0.1) * z) if is_gamma else np.float32(0.1) * z
+        sd[name] = np.ascontiguousarray(v.astype(np.float32).reshape(shape))
+    return sd

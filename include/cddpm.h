@@ -703,6 +703,59 @@ int cddpm_op_enc_maxpool(cddpm_handle h, const float* x_dev, float* y_dev, int B
                          void* stream);
 int cddpm_op_enc_avgpool(cddpm_handle h, const float* x_dev, float* g_dev, int B, int HW, int C, int backward, void* stream);
 
+/* ---- operators of SparK masked pre-training (csrc/spark_train.hip): what reference src/models/Spark_2D.py trains beside the ResNet-50 --
+ * the sparse BatchNorm of the converted encoder (src/models/modules/spark/encoder.py:25-35, :183-190), densify (spark/Spark_2D.py:157-171),
+ * the LightDecoder (spark/decoder.py:17-76), spatial_loss (spark/Spark_2D.py:180-199) and AdamW (src/models/Spark_2D.py:123-124). NHWC fp32
+ * device tensors; nothing uses float atomics, two calls give the same bits.
+ * The cell mask active_dev: uint8 [B][f][f]; pixel (b, y, x) of an H x W tensor is active iff active[b][y f / H][x f / W] (H and W multiples
+ * of f: the mask dilated to the tensor's resolution, encoder.py:13-16).
+ * cddpm_op_spark_bn_forward / _backward: cddpm_op_enc_bn_forward / _backward, sparse or dense, with a fill value and ReLU6:
+ *   y = act((active ? ((z - mean_c) rstd_c gamma_c + beta_c) : fill_c) s_b + res), act 0 none | 1 ReLU | 2 ReLU6 (decoder.py:26).
+ *   active_dev NULL = dense (nn.BatchNorm2d); given = BatchNorm1d over the active pixels only (sp_bn_forward): batch statistics in fp64 over the
+ *   n_act active pixels, n_act counted on the device, running mean / unbiased variance updated with n_act. fill_dev [C] or NULL = 0: what
+ *   inactive pixels get -- the mask token of densify (torch.where, spark/Spark_2D.py:165-168), 0 in the encoder. training = 0: the running
+ *   statistics are used and left alone. Training with fewer than 2 values per channel is refused (torch's BatchNorm1d raises); with a mask
+ *   the operator reads the device's count back to say so, which synchronises the stream once per call.
+ *   Backward: dz = 0 at inactive pixels; dgamma, dbeta sum over the active pixels; dfill_dev (or NULL) [C] = sum over the inactive pixels
+ *   of dy act' s_b; dres_dev (or NULL) = dy act'; ReLU6's gradient flows where 0 < y < 6. training = 0: the backward of the evaluation form.
+ *   C: a multiple of 4, >= 4; N = B H W, HW = H W.
+ * cddpm_op_spark_mask_mul: y = x * active_ex on [B,H,W,C], C >= 1; y_dev may be x_dev (Spark_2D.py:150-151; encoder.py:19-22).
+ * cddpm_op_spark_conv: the small-channel convolution family on the layer's own PyTorch weight tensor, read in place:
+ *   transposed_conv 0: nn.Conv2d(Cin, Cout, K, 1, K / 2), K 1 | 3, weight [Cout][Cin][K][K]  (en_de_lins, decoder.py:26-27, proj :66)
+ *   transposed_conv 1: nn.ConvTranspose2d(Cin, Cout, 4, 2, 1), weight [Cin][Cout][4][4]       (DecoderConv.up, decoder.py:37)
+ *   backward 0: dst = layer(src) + bias (bias_dev [Cout] or NULL); backward 1: dst = the input gradient from src = dy (bias_dev NULL).
+ *   H, W: the LAYER's input size; a transposed convolution's output is [B,2H,2W,Cout]. Any Cin, Cout >= 1.
+ * cddpm_op_spark_conv_wgrad: dw_dev in the weight's own layout and (db_dev given, Cout <= 256) the bias gradient, from the layer's input
+ *   x_dev [B,H,W,Cin] and its output gradient dy_dev. Pixel ranges are folded in a fixed order.
+ * cddpm_op_spark_loss: rec_dev, inp_dev [B][H][W] (one channel). loss_dev[0] = sum over the pixels of masked (not active) cells of
+ *   (rec - inp)^2 / (p^2 (n_masked + 1e-8)), p^2 = (H / f)(W / f) (spatial_loss, pix_norm 0; 0 when nothing is masked); loss_dev[1] = mean |rec - inp|
+ *   (L1_AE's recon_error); drec_dev (or NULL) = the gradient of w_mask loss[0] + w_l1 loss[1].
+ * cddpm_op_adamw_guarded: cddpm_op_adam_guarded with torch.optim.AdamW's decoupled decay, p <- p (1 - lr weight_decay) before the update;
+ *   the same control block, so a skipped step decays nothing. */
+int cddpm_op_spark_bn_forward(cddpm_handle h, const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* sample_scale_dev,
+                              const float* res_dev, int act, float eps, float momentum, float* run_mean_dev, float* run_var_dev, float* mean_rstd_dev,
+                              float* y_dev, int64_t N, int HW, int C, const uint8_t* active_dev, int f, int H, int W, const float* fill_dev, int training,
+                              void* stream);
+int cddpm_op_spark_bn_backward(cddpm_handle h, const float* z_dev, const float* y_dev, const float* dy_dev, const float* mean_rstd_dev,
+                               const float* gamma_dev, const float* sample_scale_dev, int act, float* dz_dev, float* dres_dev, float* dgamma_dev,
+                               float* dbeta_dev, int64_t N, int HW, int C, const uint8_t* active_dev, int f, int H, int W, float* dfill_dev, int training,
+                               void* stream);
+int cddpm_op_spark_mask_mul(cddpm_handle h, const float* x_dev, const uint8_t* active_dev, float* y_dev, int B, int H, int W, int C, int f, void* stream);
+int cddpm_op_spark_conv(cddpm_handle h, const float* src_dev, const float* w_dev, const float* bias_dev, float* dst_dev, int B, int H, int W, int Cin,
+                        int Cout, int K, int transposed_conv, int backward, void* stream);
+int cddpm_op_spark_conv_wgrad(cddpm_handle h, const float* x_dev, const float* dy_dev, float* dw_dev, float* db_dev, int B, int H, int W, int Cin, int Cout,
+                              int K, int transposed_conv, void* stream);
+int cddpm_op_spark_loss(cddpm_handle h, const float* rec_dev, const float* inp_dev, const uint8_t* active_dev, int f, int B, int H, int W, float w_mask,
+                        float w_l1, float* loss_dev, float* drec_dev, void* stream);
+int cddpm_op_adamw_guarded(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, float grad_unscale, const int32_t* ctrl_dev, void* stream);
+/* their size queries (the convention of cddpm_op_set_scratch above; has_db: db_dev given) */
+size_t cddpm_op_spark_bn_forward_scratch(int64_t N, int HW, int C);
+size_t cddpm_op_spark_bn_backward_scratch(int64_t N, int HW, int C);
+size_t cddpm_op_spark_conv_scratch(int B, int H, int W, int Cin, int Cout, int K, int transposed_conv, int backward);
+size_t cddpm_op_spark_conv_wgrad_scratch(int B, int H, int W, int Cin, int Cout, int K, int transposed_conv, int has_db);
+size_t cddpm_op_spark_loss_scratch(int B, int H, int W, int f);
+
 /* backward of a = act(GroupNorm32(x) * (1 + scale) + shift), act = SiLU (silu != 0) or identity (OpenAI_Unet.py:284-338, :325-330):
  * given da_dev [B,HW,C] writes dx_dev [B,HW,C] (with x1_dev: x = cat[x_dev [.., C - C1], x1_dev [.., C1]], the input gradient split the same
  * way into dx_dev / dx1_dev; needs rec_dev), dgamma_dev / dbeta_dev [C] and, when film_dev ([B][2C] scale | shift) is given,
