@@ -1007,7 +1007,11 @@ int cddpm_reverse(cddpm_handle h, float* img, const float* noise_dev, uint64_t s
 int cddpm_noise_fill(cddpm_handle h, float* out_dev, uint64_t seed, uint32_t stream_id, int t, uint64_t slice0, int B,
                      int H, int W, void* stream) {
     if (!h) return -1;
-    if (!out_dev || B < 1 || H < 1 || W < 1 || (H * W) % 4) return fail(h, "bad arguments to cddpm_noise_fill");
+    if (!out_dev) return fail(h, "cddpm_noise_fill: out_dev is NULL");
+    if (B < 1 || H < 1 || W < 1 || ((long long)H * W) % 4)
+        return fail(h, "cddpm_noise_fill: B=%d H=%d W=%d unsupported (B, H, W >= 1, H * W a multiple of 4)", B, H, W);
+    if ((long long)B * H * W >= (1ll << 31)) return fail(h, "cddpm_noise_fill: B * H * W = %lld, must be below 2^31", (long long)B * H * W);
+    if (reinterpret_cast<uintptr_t>(out_dev) % 16) return fail(h, "cddpm_noise_fill: out_dev must be 16-byte aligned");
     HIPCHECK(h, hipSetDevice(h->device));
     launch_noise_fill(out_dev, seed, stream_id, t, slice0, B, H * W, (hipStream_t)stream);
     HIPCHECK(h, hipGetLastError());
@@ -1116,8 +1120,12 @@ int cddpm_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev,
                    void* stream) {
     if (!h) return -1;
     if (T != h->d.timesteps) return fail(h, "T mismatch");
-    if (B < 1 || B > h->d.max_batch || (H * W) % 4) return fail(h, "bad B/H/W");
+    if (B < 1 || B > h->d.max_batch || H < 1 || W < 1 || ((long long)H * W) % 4 || (long long)B * H * W >= (1ll << 31))
+        return fail(h, "cddpm_q_sample: B=%d H=%d W=%d unsupported (1 <= B <= max_batch=%d, H * W a multiple of 4, B * H * W below 2^31)", B, H, W,
+                    h->d.max_batch);
     if (!x01_dev || !noise_dev || !out_dev || !sqrt_ac_host || !sqrt_1mac_host) return fail(h, "cddpm_q_sample: NULL argument");
+    if (reinterpret_cast<uintptr_t>(x01_dev) % 16 || reinterpret_cast<uintptr_t>(noise_dev) % 16 || reinterpret_cast<uintptr_t>(out_dev) % 16)
+        return fail(h, "cddpm_q_sample: x01_dev, noise_dev and out_dev must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(h, hipSetDevice(h->device));
     if (stage_t(h, t_dev, t_uniform, B, s)) return -1;      // first: a bad t_uniform is refused before anything is enqueued

@@ -417,6 +417,10 @@ void launch_noise_fill(float* out, uint64_t seed, uint32_t stream_id, int t, uin
 __device__ __forceinline__ float clamp11(float v) { return (v != v) ? v : fminf(fmaxf(v, -1.f), 1.f); }
 
 __global__ __launch_bounds__(256) void step_kernel(const StepArgs a) {
+    // Every product and sum of this kernel is rounded on its own, as the reference's tensor expressions are. __fmul_rn / __fadd_rn do not
+    // give that: they are plain operators inside header functions, which carry the translation unit's contraction (HIP's default allows it)
+    // and were fused into FMAs. Plain operators written HERE, with contraction switched off for this body, are not.
+#pragma clang fp contract(off)
     const int nq = a.HW >> 2;
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)a.B * nq) return;
@@ -445,19 +449,19 @@ __global__ __launch_bounds__(256) void step_kernel(const StepArgs a) {
     const float c1 = a.coef1[t], c2 = a.coef2[t];
     // separate roundings of the two products, as the reference's tensor expression does
     float4 r;
-    r.x = __fadd_rn(__fmul_rn(c1, x0.x), __fmul_rn(c2, x.x));
-    r.y = __fadd_rn(__fmul_rn(c1, x0.y), __fmul_rn(c2, x.y));
-    r.z = __fadd_rn(__fmul_rn(c1, x0.z), __fmul_rn(c2, x.z));
-    r.w = __fadd_rn(__fmul_rn(c1, x0.w), __fmul_rn(c2, x.w));
+    r.x = c1 * x0.x + c2 * x.x;
+    r.y = c1 * x0.y + c2 * x.y;
+    r.z = c1 * x0.z + c2 * x.z;
+    r.w = c1 * x0.w + c2 * x.w;
     if (t > 0) {
         const float sigma = expf(0.5f * a.logvar[t]);
         float4 z;
         if (a.noise) z = *reinterpret_cast<const float4*>(a.noise + (size_t)t * a.noise_t_stride + off);
         else z = normal4((uint32_t)q, (uint32_t)t, (uint32_t)(a.slice0 + b), 0x1002u, a.seed);
-        r.x = __fadd_rn(r.x, __fmul_rn(sigma, z.x));
-        r.y = __fadd_rn(r.y, __fmul_rn(sigma, z.y));
-        r.z = __fadd_rn(r.z, __fmul_rn(sigma, z.z));
-        r.w = __fadd_rn(r.w, __fmul_rn(sigma, z.w));
+        r.x = r.x + sigma * z.x;
+        r.y = r.y + sigma * z.y;
+        r.z = r.z + sigma * z.z;
+        r.w = r.w + sigma * z.w;
     }
     if (a.finalize < 0 ? (t == 0) : (a.finalize != 0)) {
         r.x = (r.x + 1.f) * 0.5f; r.y = (r.y + 1.f) * 0.5f; r.z = (r.z + 1.f) * 0.5f; r.w = (r.w + 1.f) * 0.5f;
@@ -476,6 +480,7 @@ void launch_step(const StepArgs& a, hipStream_t stream) {
 // order of the reference's tensor expression.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ddim_step_kernel(const DdimArgs a) {
+#pragma clang fp contract(off)      // as in step_kernel: plain operators in this body, each rounded on its own; the division is correctly rounded
     const int nq = a.HW >> 2;
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)a.B * nq) return;
@@ -498,14 +503,14 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const DdimArgs a) {
         float x0, eps;
         if (a.objective == 0) {      // pred_x0
             x0 = ms[i];
-            eps = __fdiv_rn(__fsub_rn(__fmul_rn(sr, xs[i]), x0), srm1);
+            eps = __fdiv_rn(sr * xs[i] - x0, srm1);
         } else {                     // pred_noise
             eps = ms[i];
-            x0 = __fsub_rn(__fmul_rn(sr, xs[i]), __fmul_rn(srm1, eps));
+            x0 = sr * xs[i] - srm1 * eps;
         }
         if (a.clip) x0 = clamp11(x0);          // clip_denoised (cond_DDPM.py:493-494)
-        float r = __fadd_rn(__fmul_rn(x0, a.coef_x0), __fmul_rn(a.coef_eps, eps));
-        r = __fadd_rn(r, __fmul_rn(a.sigma, zs[i]));
+        float r = x0 * a.coef_x0 + a.coef_eps * eps;
+        r = r + a.sigma * zs[i];
         if (a.finalize) r = (r + 1.f) * 0.5f;
         rs[i] = r;
     }

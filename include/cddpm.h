@@ -200,7 +200,11 @@ int cddpm_ddim_step(cddpm_handle h, float* img_inout_dev, const float* z_dev, ui
                     int B, int H, int W, void* stream);
 
 /* Replaces torch.randn(shape) / torch.randn_like (src/models/modules/cond_DDPM.py:454, :440) with the
- * counter RNG: out_dev [B,1,H,W] ~ N(0,1); stream_id 0x1001 = x_T, 0x1002 = z_t. */
+ * counter RNG: out_dev [B,1,H,W] ~ N(0,1); stream_id 0x1001 = x_T, 0x1002 = z_t. Philox4x32-10, key = the two 32-bit halves of
+ * `seed`, counter = (element quad within the slice, t, slice0 + b, stream_id) with t and slice0 + b taken modulo 2^32: slice b of a
+ * batch holds the bits a one-slice call at slice0 + b gives. Not bound by the handle's max_batch.
+ * Preconditions, each refused with a message before anything is launched: out_dev not NULL and 16-byte aligned; B, H, W >= 1;
+ * H * W a multiple of 4; B * H * W < 2^31. */
 int cddpm_noise_fill(cddpm_handle h, float* out_dev, uint64_t seed, uint32_t stream_id, int t,
                      uint64_t slice0, int B, int H, int W, void* stream);
 
@@ -339,7 +343,11 @@ int cddpm_eval_hausdorff(cddpm_handle h, const uint8_t* pred_dev, const float* s
 
 /* Replaces q_sample (src/models/modules/cond_DDPM.py:548-554) fused with normalize_to_neg_one_to_one (:75):
  * out = sqrt_ac[t_b] * (2 x01 - 1) + sqrt_1mac[t_b] * noise; coefficient tables are host arrays [T]
- * uploaded on first use. Used by the single-step reconstruction (GaussianDiffusion.forward, :647-655). */
+ * uploaded on first use. Used by the single-step reconstruction (GaussianDiffusion.forward, :647-655). t_b = t_dev[b] kept inside
+ * [0, T) when t_dev is given, else t_uniform for every slice. One fused multiply-add over the rounded second product per element.
+ * Preconditions, each refused with a message before anything is enqueued: T the handle's timesteps; 1 <= B <= max_batch; H, W >= 1;
+ * H * W a multiple of 4; B * H * W < 2^31; no NULL argument; x01_dev, noise_dev and out_dev 16-byte aligned; t_uniform inside
+ * [0, T) when t_dev is NULL. */
 int cddpm_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev, const int32_t* t_dev, int t_uniform,
                    const float* sqrt_ac_host, const float* sqrt_1mac_host, int T,
                    float* out_dev, int B, int H, int W, void* stream);

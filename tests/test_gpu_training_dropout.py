@@ -39,6 +39,18 @@ def test_mask_bits_and_dropout_scale_equal_the_host_restatement(eng, synth, shap
     assert torch.equal(eng.op_dropout_scale(x.cuda(), **kw).cpu(), x * keep)     # one fp32 product per kept element: exact
 
 
+@pytest.mark.parametrize("seed", [(1 << 32) + SEED, (1 << 64) - 1], ids=["2^32+seed", "2^64-1"])
+def test_mask_reads_the_high_word_of_a_64_bit_seed(eng, synth, seed):
+    """the Philox key is (seed mod 2^32, seed >> 32): every other seed of this file is below 2^32 and leaves the second word zero"""
+    shape, p, step, layer, slice0 = MASK_SHAPES[1], 0.5, 3, 7, 5
+    kw = dict(step=step, slice0=slice0, stream_id=synth.STREAM_DROPOUT + layer, p=p)
+    keep = torch.from_numpy(synth.dropout_mask(seed, step, layer, slice0, *shape, p).astype(np.float32) * synth.dropout_scale(p))
+    got = eng.op_act_dropout(torch.ones(shape, device="cuda"), None, False, seed=seed, **kw).cpu()
+    assert torch.equal(got, keep)
+    low = eng.op_act_dropout(torch.ones(shape, device="cuda"), None, False, seed=seed & 0xFFFFFFFF, **kw).cpu()
+    assert not torch.equal(got, low) and 0 < int((got == 0).sum()) < got.numel()
+
+
 @pytest.mark.parametrize("shape", MASK_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_act_dropout_with_coefficients_and_silu_vs_float64(eng, synth, shape):
     """out = mask s SiLU((x - m) a + d) with s = fp32(1 / (1 - p)), against float64 on the SAME fp32 coefficient plane. Bound, from the
