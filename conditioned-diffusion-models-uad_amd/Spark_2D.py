@@ -14,7 +14,14 @@ SparK_2D.mask draws it (spark/Spark_2D.py:139-141): under torch.manual_seed the 
 Built: the experiment's configuration. Refused with NotImplementedError (the convention of DDPM_encoder.py): a missing `backbone` or one
 other than resnet50, mask_ratio != mask_ratio2, uniform, pe, pix_norm other than 0, dense_loss, loss_l2 False, pyramid != 4, double
 False, hea != [0, 1], cmid != 0, a dec_dim that is no multiple of 128, an input side that is no multiple of 32. `en_de_norm` and `sbn`
-are ignored, as SparK_2D.__init__ hard-codes 'bn' and False over them (spark/Spark_2D.py:31-33). Precision 32 only.
+are ignored, as SparK_2D.__init__ hard-codes 'bn' and False over them (spark/Spark_2D.py:31-33).
+Precision: `cfg.precision`, or the attached Lightning trainer's `precision` (the experiment inherits `precision: 16` from
+configs/trainer/default.yaml:7), in the spellings and with the mapping of training.set_precision (unset: 32). It is
+the SparKTrainer's own precision, read when the trainer is created; the process-wide training precision is not touched. At 16 the sparse
+ResNet-50's convolutions run on the fp16-MFMA operators under a dynamic loss scale on the device, as Lightning's native AMP trains the
+reference: `train/loss_scale` and `train/skipped_steps` are logged from device tensors, the consecutive skips are read once every 50
+steps (30 or more: one RuntimeWarning), the scaler travels in the checkpoint with AdamW's state, and a reference checkpoint's
+`native_amp_scaling_state` seeds scale and growth tracker.
 Initialisation follows the reference's distributions (timm's ResNet init with zero_init_last, PyTorch's Conv2d default for en_de_lins,
 LightDecoder.initialize, trunc_normal_ tokens) drawn from torch's generator; it is not the reference's random stream (timm is not here to
 consume it in its order). `test_step`: not built -- the experiment sets `test_after_training: False`."""
@@ -25,7 +32,9 @@ import math
 import torch
 import torch.nn as nn
 
-from .mirror_common import AttrDict, _Base, _cfg_get, _to_cpu
+import warnings
+
+from .mirror_common import AttrDict, HipMirror, _Base, _cfg_get, _to_cpu
 from .synth import SPARK_ENC_PREFIX, spark_param_shapes
 
 BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked")
@@ -145,6 +154,12 @@ class Spark_2D(_Base):
             raise ValueError(f"lossStrategy {strat!r}: 'mean' or 'sum'")
         return float(_cfg_get(self.cfg, "delta_mask", 0)), (1.0 if strat == "mean" else float(self.input_size * self.input_size))
 
+    def precision_bits(self) -> int:
+        """16 | 32 from cfg.precision or the attached Lightning trainer's precision (HipMirror._train_precision), through
+        training.set_precision's mapping; neither given: 32"""
+        from .training import lightning_precision_bits
+        return lightning_precision_bits(HipMirror._train_precision(self))
+
     def hip_trainer(self, device):
         """spark_training.SparKTrainer with this module's tensors; from here on the module's parameters and running statistics ARE the
         trainer's buffers (state_dict() / checkpoints see the trained values)"""
@@ -152,11 +167,12 @@ class Spark_2D(_Base):
             from .spark_training import SparKTrainer
             sd = {k[len("model."):]: v for k, v in self.state_dict().items()}
             self._hip_spark_trainer = SparKTrainer(sd, device, dec_dim=self.dec_dim, drop_path_rate=self.drop_path_rate, loss_weights=self.loss_weights(),
-                                                   precision=_cfg_get(self.cfg, "precision", 32))
+                                                   precision=self.precision_bits())
             st = getattr(self, "_pending_opt_state", None)
             if st:
                 self._hip_spark_trainer.load_optimizer_state(st)
                 self._pending_opt_state = None
+            self._seed_loss_scaling()
         self._alias()
         return self._hip_spark_trainer
 
@@ -241,7 +257,31 @@ class Spark_2D(_Base):
         tr_.adamw_step(lr=float(self.cfg.lr), weight_decay=float(_cfg_get(self.cfg, "weight_decay", 0.05)), betas=(0.9, 0.95))
         self._param_versions = tuple(p._version for p in self.model.parameters())
         self._log(f"{self.prefix}train/Loss_comb", loss, input.shape[0])
+        if tr_.loss_scaling:
+            self._watch_loss_scale(tr_)
         return {"loss": loss}
+
+    def _watch_loss_scale(self, tr_):
+        """HipMirror._watch_loss_scale for this trainer: the loss scale and the skipped steps are logged from device tensors (no read-back);
+        every SCALER_CHECK_EVERY steps the consecutive skips are read once, and SCALER_STALL_SKIPS of them in a row -- gradients that are
+        non-finite at any scale -- give one RuntimeWarning"""
+        for name, value in (("train/loss_scale", tr_.scaler[:1].view(torch.float32)[0].clone()), ("train/skipped_steps", tr_.ctrl[3].float())):
+            self.logged[name] = value
+            if hasattr(self, "log") and _Base is not nn.Module:
+                try:
+                    self.log(f"{self.prefix}{name}", value, on_step=True, on_epoch=False)
+                except Exception:
+                    pass
+        self._scaler_steps = getattr(self, "_scaler_steps", 0) + 1
+        if self._scaler_steps % HipMirror.SCALER_CHECK_EVERY:
+            return
+        skips = tr_.consecutive_skips
+        if skips < HipMirror.SCALER_STALL_SKIPS:
+            self._scaler_warned = False
+        elif not getattr(self, "_scaler_warned", False):
+            self._scaler_warned = True
+            warnings.warn(f"{skips} training steps in a row were skipped for non-finite gradients (loss scale now {tr_.loss_scale:g}): "
+                          "the gradients are not finite at any scale -- a NaN / inf input or a diverged run?", RuntimeWarning, stacklevel=2)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx: int):
@@ -282,6 +322,23 @@ class Spark_2D(_Base):
             checkpoint["hip_optimizer_state"] = {k: _to_cpu(v) for k, v in st.items()}
 
     def on_load_checkpoint(self, checkpoint):
+        """restores hip_optimizer_state (AdamW's moments, the step count, the loss scaler); a checkpoint without it but with Lightning 1.5's
+        `native_amp_scaling_state` (a reference checkpoint trained at precision 16: GradScaler.state_dict()) seeds the scale and growth
+        tracker of a precision-16 trainer"""
         st = checkpoint.get("hip_optimizer_state")
         if st is not None:
             self.load_hip_optimizer_state(st)
+        elif checkpoint.get("native_amp_scaling_state"):
+            from .training import loss_scaling_from_grad_scaler
+            self._pending_amp_scaler = loss_scaling_from_grad_scaler(checkpoint["native_amp_scaling_state"])
+            self._seed_loss_scaling()
+
+    def _seed_loss_scaling(self):
+        """a seed from a reference checkpoint restarts the scaler of a precision-16 trainer (now, or once the trainer exists); at 32 it
+        is dropped: there the scaler is off, as a precision-32 Lightning run has none"""
+        tr_, seed = self._hip_spark_trainer, getattr(self, "_pending_amp_scaler", None)
+        if tr_ is None or seed is None:
+            return
+        self._pending_amp_scaler = None
+        if tr_.precision == 16:
+            tr_.enable_loss_scaling(**seed)

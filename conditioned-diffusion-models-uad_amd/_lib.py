@@ -154,6 +154,8 @@ SYMBOLS = {
     "cddpm_op_spark_conv_wgrad": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "cddpm_op_spark_loss": (_i, [_vp, _fp, _fp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _fp, _fp, _vp]),
     "cddpm_op_adamw_guarded": (_i, [_vp, _fp, _fp, _fp, _fp, _i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    "cddpm_op_spark_loss_scaled": (_i, [_vp, _fp, _fp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _vp, _fp, _fp, _vp]),
+    "cddpm_op_adamw_scaled": (_i, [_vp, _fp, _fp, _fp, _fp, _i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp]),
     "cddpm_op_spark_bn_forward_scratch": (_sz, [_i64, _i, _i]),
     "cddpm_op_spark_bn_backward_scratch": (_sz, [_i64, _i, _i]),
     "cddpm_op_spark_conv_scratch": (_sz, [_i] * 8),

@@ -958,7 +958,18 @@ int cddpm_op_spark_loss(cddpm_handle h, const float* rec_dev, const float* inp_d
     OpScratch sc(h, s);
     double* part = spark_loss_scratch(sc, B, H, W);
     SCRATCH_CHECK(sc)
-    launch_spark_loss(rec_dev, inp_dev, active_dev, f, B, H, W, w_mask, w_l1, loss_dev, drec_dev, part, s);
+    launch_spark_loss(rec_dev, inp_dev, active_dev, f, B, H, W, w_mask, w_l1, nullptr, loss_dev, drec_dev, part, s);
+    OP_EPILOGUE()
+}
+// cddpm_op_spark_loss under the dynamic loss scale: drec carries the device scale, the two terms do not (step (a) of "Dynamic loss scaling")
+int cddpm_op_spark_loss_scaled(cddpm_handle h, const float* rec_dev, const float* inp_dev, const uint8_t* active_dev, int f, int B, int H, int W,
+                               float w_mask, float w_l1, const int32_t* scaler_dev, float* loss_dev, float* drec_dev, void* stream) {
+    OP_CHECK(spark_loss_shape_ok(B, H, W, f), "cddpm_op_spark_loss_scaled: unsupported shape (B %d, H %d, W %d, f %d dividing H and W)", B, H, W, f)
+    OP_PROLOGUE(PC_OTHER, 0.0, 0.0, rec_dev && inp_dev && active_dev && loss_dev && scaler_dev, "cddpm_op_spark_loss_scaled: NULL argument")
+    OpScratch sc(h, s);
+    double* part = spark_loss_scratch(sc, B, H, W);
+    SCRATCH_CHECK(sc)
+    launch_spark_loss(rec_dev, inp_dev, active_dev, f, B, H, W, w_mask, w_l1, scaler_dev, loss_dev, drec_dev, part, s);
     OP_EPILOGUE()
 }
 // torch.optim.AdamW (src/models/Spark_2D.py:123-124): cddpm_op_adam_guarded with the decoupled decay p <- p (1 - lr weight_decay) before the update
@@ -966,6 +977,14 @@ int cddpm_op_adamw_guarded(cddpm_handle h, float* p_dev, const float* g_dev, flo
                            float eps, float weight_decay, float grad_unscale, const int32_t* ctrl_dev, void* stream) {
     OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && ctrl_dev && n > 0 && weight_decay >= 0.0f, "cddpm_op_adamw_guarded: bad arguments")
     launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, grad_unscale, weight_decay, ctrl_dev, nullptr, s);
+    OP_EPILOGUE()
+}
+// cddpm_op_adamw_guarded under the dynamic loss scale, in the form of cddpm_op_adam_scaled: gradient = g extra_unscale / the device scale
+int cddpm_op_adamw_scaled(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, float extra_unscale, const int32_t* ctrl_dev, const int32_t* scaler_dev, void* stream) {
+    OP_PROLOGUE(PC_OPT, 0.0, 0.0, p_dev && g_dev && m_dev && v_dev && ctrl_dev && scaler_dev && n > 0 && weight_decay >= 0.0f,
+                "cddpm_op_adamw_scaled: bad arguments")
+    launch_adam_guarded(p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps, extra_unscale, weight_decay, ctrl_dev, scaler_dev, s);
     OP_EPILOGUE()
 }
 

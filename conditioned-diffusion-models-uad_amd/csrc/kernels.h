@@ -353,6 +353,6 @@ int spark_chan_sum_chunks(long long M, int C);
 void launch_spark_chan_sum(const float* x, long long M, int C, double* part, float* out, hipStream_t s);
 int spark_loss_chunks(long long total);
 void launch_spark_loss(const float* rec, const float* inp, const unsigned char* active, int f, int B, int H, int W, float w_mask, float w_l1,
-                       float* loss, float* drec, double* part, hipStream_t s);
+                       const int* scaler, float* loss, float* drec, double* part, hipStream_t s);
 
 }  // namespace cddpm

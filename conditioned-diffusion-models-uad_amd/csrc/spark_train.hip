@@ -506,13 +506,19 @@ void launch_spark_chan_sum(const float* x, long long M, int C, double* part, flo
 // ---------------------------------------------------------------------------------------------------------------- loss
 // masked = sum over pixels of masked cells of (rec - inp)^2 / (p^2 (n_masked + 1e-8)), l1 = mean |rec - inp|;
 // drec = w_mask d masked / d rec + w_l1 d l1 / d rec. One channel: rec, inp [B][H][W]; p^2 = (H / f)(W / f) pixels per cell.
+// scaler given (the device block of the dynamic loss scaling, include/cddpm.h): both weights are multiplied by its scale first, a power of
+// two, so drec carries the bits the plain call gives for weights S w_mask, S w_l1; the two loss terms are never scaled.
 __global__ __launch_bounds__(256) void spark_loss_partial_kernel(const float* __restrict__ rec, const float* __restrict__ inp,
                                                                  const unsigned char* __restrict__ active, int f, int ncell, int H, int W, int ch, int cw,
-                                                                 long long total, float w_mask, float w_l1, float* __restrict__ drec,
-                                                                 double* __restrict__ part) {
+                                                                 long long total, float w_mask, float w_l1, const int* __restrict__ scaler,
+                                                                 float* __restrict__ drec, double* __restrict__ part) {
     __shared__ int cnt[256];
     __shared__ double red[2][256];
     const int n_masked = ncell - spark_count_active(active, ncell, cnt);
+    if (scaler) {
+        const float scale = reinterpret_cast<const float*>(scaler)[0];
+        w_mask *= scale; w_l1 *= scale;
+    }
     const float km = w_mask * 2.f / ((float)(ch * cw) * ((float)n_masked + 1e-8f)), kl = w_l1 / (float)total;
     const long long per = (total + gridDim.x - 1) / gridDim.x, e0 = per * blockIdx.x, e1 = e0 + per < total ? e0 + per : total;
     double sm = 0, sl = 0;
@@ -550,11 +556,11 @@ int spark_loss_chunks(long long total) {
     return n < 1 ? 1 : (int)n;
 }
 void launch_spark_loss(const float* rec, const float* inp, const unsigned char* active, int f, int B, int H, int W, float w_mask, float w_l1,
-                       float* loss, float* drec, double* part, hipStream_t s) {
+                       const int* scaler, float* loss, float* drec, double* part, hipStream_t s) {
     const long long total = (long long)B * H * W;
     const int nchunk = spark_loss_chunks(total);
     hipLaunchKernelGGL(spark_loss_partial_kernel, dim3(nchunk), dim3(256), 0, s, rec, inp, active, f, B * f * f, H, W, H / f, W / f, total, w_mask, w_l1,
-                       drec, part);
+                       scaler, drec, part);
     hipLaunchKernelGGL(spark_loss_fold_kernel, dim3(1), dim3(256), 0, s, part, nchunk, active, B * f * f, (H / f) * (W / f), total, loss);
 }
 

@@ -66,9 +66,12 @@ def operator_calls(B, H, W, cond_dim=128):
         yield "linear_backward", (B, cond_dim, cin, 0)                    # fc
 
 
-def pyramid_operator_calls(B, H, W):
-    """the calls of EncoderTrainer.forward_pyramid / backward_pyramid (the sparse encoder of SparK pre-training, precision 32) on a
-    [B, 1, H, W] batch that take temporaries from an arena, in the form of operator_calls"""
+def pyramid_operator_calls(B, H, W, precision=32):
+    """the calls of EncoderTrainer.forward_pyramid / backward_pyramid (the sparse encoder of SparK pre-training) on a [B, 1, H, W] batch
+    that take temporaries from an arena, in the form of operator_calls. precision (the spellings of engine.precision_bits): 32 lists
+    the fp32 convolutions, 16 their _p16 forms in their place -- the arena serves an EncoderTrainer of that precision"""
+    p16 = precision_bits(precision) == 16
+
     def bn(c, h, w):
         yield "spark_bn_forward", (B * h * w, h * w, c)
         yield "spark_bn_backward", (B * h * w, h * w, c)
@@ -77,7 +80,7 @@ def pyramid_operator_calls(B, H, W):
         if op in ("enc_bn_forward", "enc_bn_backward"):
             if op == "enc_bn_forward":
                 yield from bn(args[2], 1, args[1])
-        elif not op.endswith("_p16"):
+        elif not op.startswith("enc_conv") or op.endswith("_p16") == p16:
             yield op, args
 
 

@@ -11,7 +11,16 @@ the library's size queries (operator_calls).
 
 Built: the configuration of the reference experiment -- resnet50, four pyramid levels, BatchNorm densify norms, double = True (ConvTranspose2d
 4/2/1), heavy [0, 1], cmid 0, no positional embedding, pix_norm 0, loss on the masked cells. dec_dim must be a multiple of 128 (the last
-decoder BatchNorm then has 4 channels, the least cddpm_op_spark_bn_forward takes). Precision 32 only."""
+decoder BatchNorm then has 4 channels, the least cddpm_op_spark_bn_forward takes).
+
+Precision (the trainer's own: `SparKTrainer(..., precision=16)`, the spellings of engine.precision_bits; the process-wide
+cddpm_set_train_precision is neither read nor set): at 16 -- what the reference's `precision: 16` (configs/trainer/default.yaml:7, which
+Spark_2D_pretrain inherits) computes under autocast -- every convolution of the sparse ResNet-50 but the 7x7 stem runs forward, input
+gradient and weight gradient on the fp16-MFMA operators (EncoderTrainer(precision=16): fp16 operands, fp32 accumulation), in training and
+in evaluation forwards. The sparse and dense BatchNorms, mask multiply, max pool, stem, en_de_lins, the LightDecoder, the loss, AdamW and
+the master weights are fp32 at either precision (launch- and memory-bound at 4 to 128 channels: DESIGN.md section 4b-g). Precision 16
+trains under a dynamic loss scale on the device (enable_loss_scaling; torch GradScaler's rule and default start 65536), as Lightning's
+native AMP does for the reference: unscaled, most of the gradient inside layer3 / layer4 lies below fp16's smallest normal."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +34,7 @@ from .engine import _stream_ptr, precision_bits
 
 ENC_PREFIX = "sparse_encoder.sp_cnn."
 ENC_DIMS = (2048, 1024, 512, 256)            # channels of the maps densify reads, smallest map first
+DEFAULT_INIT_SCALE = 65536.0                 # torch.cuda.amp.GradScaler()'s init_scale: where the reference's Trainer starts
 
 
 def decoder_layers(dec_dim=128):
@@ -40,10 +50,11 @@ def decoder_layers(dec_dim=128):
     return out
 
 
-def operator_calls(B, H, W, dec_dim=128):
+def operator_calls(B, H, W, dec_dim=128, precision=32):
     """the calls of SparKTrainer.forward / backward on a [B, 1, H, W] batch that take temporaries from the arena, as (operator, arguments of
-    its size query): the sparse encoder's (encoder_training.pyramid_operator_calls) and those of densify, decoder and loss"""
-    yield from pyramid_operator_calls(B, H, W)
+    its size query): the sparse encoder's at `precision` (encoder_training.pyramid_operator_calls) and those of densify, decoder and loss
+    (cddpm_op_spark_loss_scaled takes what cddpm_op_spark_loss takes)"""
+    yield from pyramid_operator_calls(B, H, W, precision)
     f = H // 32
     res = {}
     for i in range(4):
@@ -65,27 +76,35 @@ def operator_calls(B, H, W, dec_dim=128):
     yield "spark_loss", (B, H, W, f)
 
 
-def arena_bytes(B, H, W, dec_dim=128):
-    return largest_calls(operator_calls(B, H, W, dec_dim))[0]
+def arena_bytes(B, H, W, dec_dim=128, precision=32):
+    return largest_calls(operator_calls(B, H, W, dec_dim, precision))[0]
 
 
 class SparKTrainer:
     """params: the reference's state dict of SparK_2D without the `model.` prefix (sparse_encoder.sp_cnn.*, en_de_norms.*, en_de_lins.*,
     mask_tokens.*, dense_decoder.*; running statistics included, num_batches_tracked and the image-norm buffers ignored).
     loss_weights (w_mask, w_l1): loss = w_mask * masked L2 + w_l1 * mean |reco - x| -- (1, 0) is `loss_on_mask: True`, (delta_mask, 1) the
-    other branch of Spark_2D.forward (src/models/Spark_2D.py:28-31)."""
+    other branch of Spark_2D.forward (src/models/Spark_2D.py:28-31).
+    precision: 32 (default) | 16, the spellings of engine.precision_bits ("bf16" and anything else: ValueError) -- the arithmetic of the
+    sparse ResNet-50's convolutions (module docstring). 16 turns dynamic loss scaling on (enable_loss_scaling's defaults) and needs a
+    GPU device: with any other it is a ValueError, raised like a bad precision before a device is touched."""
 
     def __init__(self, params: Dict[str, torch.Tensor], device=None, *, dec_dim=128, drop_path_rate=0.05, loss_weights=(1.0, 0.0), precision=32):
-        if precision_bits(precision) != 32:
-            raise ValueError(f"SparKTrainer: precision {precision!r} is not built; the pre-training step runs in precision 32 only")
+        self.precision = precision_bits(precision)            # parsed before a device is touched: a bad value is a ValueError here
         if dec_dim < 128 or dec_dim % 128:
             raise NotImplementedError(f"SparKTrainer: dec_dim {dec_dim} must be a multiple of 128")
         from .training import UNetTrainer
         self.dev = torch.device(device) if device is not None else next(iter(params.values())).device
+        if self.precision == 16 and self.dev.type != "cuda":
+            # checked like the precision itself, before a device is touched: a precision-16 request that names no GPU keeps the answer it
+            # had before the fp16-MFMA step was built (a ValueError that says "precision 32 only"), not the handle's "no HIP device"
+            raise ValueError(f"SparKTrainer: precision {precision!r} is not built for device '{self.dev}': its convolutions are the fp16-MFMA "
+                             "kernels of a GPU; off a GPU the request is refused as before (precision 32 only)")
         self.dec_dim, self.loss_weights = int(dec_dim), (float(loss_weights[0]), float(loss_weights[1]))
         # the handle the operators run on (no UNet is trained on it; overlap off: every call of this step runs on the one stream)
         self.ops = UNetTrainer({"w": torch.zeros(64)}, device=self.dev, overlap_wgrad=False)
-        self.enc = EncoderTrainer({k[len(ENC_PREFIX):]: v for k, v in params.items() if k.startswith(ENC_PREFIX)}, self.ops, drop_path_rate)
+        self.enc = EncoderTrainer({k[len(ENC_PREFIX):]: v for k, v in params.items() if k.startswith(ENC_PREFIX)}, self.ops, drop_path_rate,
+                                  precision=self.precision)
         skip = ("num_batches_tracked", "running_mean", "running_var")
         own = {k: v for k, v in params.items() if not k.startswith(ENC_PREFIX) and k.split(".")[0] in ("en_de_norms", "en_de_lins", "mask_tokens", "dense_decoder")}
         names = [k for k in own if not k.endswith(skip)]
@@ -111,6 +130,50 @@ class SparKTrainer:
         self.ctrl = torch.zeros(8, dtype=torch.int32, device=self.dev)
         self._arena = (0, 0, 0)
         self.saved = None
+        self.loss_scaling = False           # dynamic loss scaling (enable_loss_scaling): on by default at precision 16, available at 32
+        self.scaler: Optional[torch.Tensor] = None
+        if self.precision == 16:
+            self.enable_loss_scaling()
+
+    # ------------------------------------------------------------------ dynamic loss scaling (torch's GradScaler, the scale on the device)
+    def enable_loss_scaling(self, init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, growth_tracker=0):
+        """UNetTrainer.enable_loss_scaling for this step: torch.cuda.amp.GradScaler's rule on the device block of include/cddpm.h ("Dynamic
+        loss scaling") -- a skipped step multiplies the scale by backoff_factor, growth_interval clean steps in a row by growth_factor.
+        init_scale None: 65536, GradScaler's own start and so the reference Trainer's (measured inside the
+        stages: at most 0.001 % of the dz operands stay below fp16's smallest normal, the largest is 1.3e4 at 3x96x96 and falls with the
+        batch; a batch that overflows there backs off in its first steps). Scale and factors must be powers of two (ValueError
+        otherwise): the unscale is then exact. Starts a fresh scaler state at once; no step reads the scale back."""
+        from .training import _scaler_block, loss_scaling_settings
+        cfg = loss_scaling_settings(DEFAULT_INIT_SCALE if init_scale is None else init_scale, growth_factor, backoff_factor, growth_interval,
+                                    growth_tracker)
+        self.scaler_init = cfg["init_scale"]
+        self.scaler_cfg = (cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"])
+        self.scaler_tracker0 = cfg["growth_tracker"]
+        self.scaler = _scaler_block(self.scaler_init, self.scaler_tracker0, 0, self.dev)
+        self.loss_scaling = True
+
+    def disable_loss_scaling(self):
+        """back to unscaled gradients and the plain guarded update (what precision 32 runs by default). At precision 16 this trains the
+        encoder on flushed gradients unless the loss weights carry a scale themselves."""
+        self.loss_scaling, self.scaler = False, None
+
+    def _scaler_read(self, i):
+        return self.scaler[:1].view(torch.float32).item() if i == 0 else int(self.scaler[i].item())
+
+    @property
+    def loss_scale(self) -> Optional[float]:
+        """the scale the next loss gradient is formed with (reads the device block: synchronises); None with loss scaling off"""
+        return self._scaler_read(0) if self.loss_scaling else None
+
+    @property
+    def growth_tracker(self) -> int:
+        """clean steps since the scale last changed (reads the device counter)"""
+        return self._scaler_read(1) if self.loss_scaling else 0
+
+    @property
+    def consecutive_skips(self) -> int:
+        """skipped steps in a row up to now (reads the device counter)"""
+        return self._scaler_read(2) if self.loss_scaling else 0
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -137,7 +200,7 @@ class SparKTrainer:
             return
         B, H, W = max(B, self._arena[0]), max(H, self._arena[1]), max(W, self._arena[2])
         torch.cuda.synchronize(self.dev)
-        self._ck(self.lib.cddpm_op_set_scratch(self.h, arena_bytes(B, H, W, self.dec_dim)), "op_set_scratch")
+        self._ck(self.lib.cddpm_op_set_scratch(self.h, arena_bytes(B, H, W, self.dec_dim, self.precision)), "op_set_scratch")
         self._arena = (B, H, W)
 
     def close(self):
@@ -224,8 +287,12 @@ class SparKTrainer:
         sv["last"] = h
         terms, drec = self._new(2), (torch.empty_like(rec) if training else None)
         wm, wl = self.loss_weights
-        self._ck(self.lib.cddpm_op_spark_loss(self.h, _p(rec), _p(x), _p(active), f, B, H, W, C.c_float(wm), C.c_float(wl), _p(terms), _p(drec), self._s()),
-                 "op_spark_loss")
+        if self.loss_scaling:               # drec carries the device scale; the terms, and so the loss returned, do not
+            self._ck(self.lib.cddpm_op_spark_loss_scaled(self.h, _p(rec), _p(x), _p(active), f, B, H, W, C.c_float(wm), C.c_float(wl), _p(self.scaler),
+                                                         _p(terms), _p(drec), self._s()), "op_spark_loss_scaled")
+        else:
+            self._ck(self.lib.cddpm_op_spark_loss(self.h, _p(rec), _p(x), _p(active), f, B, H, W, C.c_float(wm), C.c_float(wl), _p(terms), _p(drec),
+                                                  self._s()), "op_spark_loss")
         sv["drec"] = drec
         self.saved = sv if training else None
         self.terms = terms
@@ -233,6 +300,7 @@ class SparKTrainer:
         return loss, rec.view(B, 1, H, W), latent
 
     # ------------------------------------------------------------------ backward: the gradient of `loss` w.r.t. every parameter
+    # (with dynamic loss scaling on: times the device scale the forward's loss gradient was formed with; adamw_step divides it out)
     def backward(self):
         sv = self.saved
         if sv is None:
@@ -267,7 +335,9 @@ class SparKTrainer:
     def adamw_step(self, lr=1e-4, weight_decay=0.05, betas=(0.9, 0.95), eps=1e-8):
         """torch.optim.AdamW(self.parameters(), lr, weight_decay, betas) of Spark_2D.configure_optimizers: decoupled decay, then Adam, on
         the encoder's and on this trainer's flat buffers under one control block -- a step with a non-finite gradient anywhere moves and
-        decays nothing and does not count."""
+        decays nothing and does not count. With dynamic loss scaling on, the order of include/cddpm.h: the checks, one commit,
+        cddpm_op_adamw_scaled on both buffers (the gradient buffers hold scale x the gradient; the scale of this step's loss is divided
+        out on the device), one cddpm_op_scaler_update."""
         lib, ctrl = self.lib, self.ctrl
         bufs = (self, self.enc)
         for t in bufs:
@@ -276,9 +346,17 @@ class SparKTrainer:
             self._ck(lib.cddpm_op_grad_check(self.h, _p(t.gflat), t.gflat.numel(), _p(ctrl), self._s()), "op_grad_check")
         self._ck(lib.cddpm_op_guard_commit(self.h, _p(ctrl), C.c_float(betas[0]), C.c_float(betas[1]), self._s()), "op_guard_commit")
         for t in bufs:
-            self._ck(lib.cddpm_op_adamw_guarded(self.h, _p(t.flat), _p(t.gflat), _p(t.state["m"]), _p(t.state["v"]), t.flat.numel(), C.c_float(lr),
-                                                C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(weight_decay), C.c_float(1.0),
-                                                _p(ctrl), self._s()), "op_adamw_guarded")
+            if self.loss_scaling:
+                self._ck(lib.cddpm_op_adamw_scaled(self.h, _p(t.flat), _p(t.gflat), _p(t.state["m"]), _p(t.state["v"]), t.flat.numel(), C.c_float(lr),
+                                                   C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(weight_decay), C.c_float(1.0),
+                                                   _p(ctrl), _p(self.scaler), self._s()), "op_adamw_scaled")
+            else:
+                self._ck(lib.cddpm_op_adamw_guarded(self.h, _p(t.flat), _p(t.gflat), _p(t.state["m"]), _p(t.state["v"]), t.flat.numel(), C.c_float(lr),
+                                                    C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(weight_decay), C.c_float(1.0),
+                                                    _p(ctrl), self._s()), "op_adamw_guarded")
+        if self.loss_scaling:
+            g, b, n = self.scaler_cfg
+            self._ck(lib.cddpm_op_scaler_update(self.h, _p(ctrl), _p(self.scaler), C.c_float(g), C.c_float(b), n, self._s()), "op_scaler_update")
         self.enc.repack()
 
     @property
@@ -297,9 +375,14 @@ class SparKTrainer:
         for t in (self, self.enc):
             if "m" not in t.state:
                 t.state["m"], t.state["v"] = torch.zeros_like(t.flat), torch.zeros_like(t.flat)
-        return {"m": torch.cat([self.enc.state["m"], self.state["m"]]).detach().clone(),
-                "v": torch.cat([self.enc.state["v"], self.state["v"]]).detach().clone(), "layout": self._layout(),
-                "step": self.step_count, "skipped": self.skipped_steps}
+        out = {"m": torch.cat([self.enc.state["m"], self.state["m"]]).detach().clone(),
+               "v": torch.cat([self.enc.state["v"], self.state["v"]]).detach().clone(), "layout": self._layout(),
+               "step": self.step_count, "skipped": self.skipped_steps}
+        if self.loss_scaling:               # UNetTrainer.optimizer_state's layout: the settings and the device block
+            g, b, n = self.scaler_cfg
+            out["scaler"] = {"init_scale": self.scaler_init, "growth_factor": g, "backoff_factor": b, "growth_interval": n,
+                             "growth_tracker": self.scaler_tracker0, "state": self.scaler.detach().clone()}
+        return out
 
     def load_optimizer_state(self, state) -> None:
         if [tuple(x) for x in state["layout"]] != self._layout():
@@ -311,6 +394,12 @@ class SparKTrainer:
         self.ctrl.zero_()
         self.ctrl[1], self.ctrl[3] = int(state.get("step", 0)), int(state.get("skipped", 0))
         # the bias corrections of the control block are rewritten by the next cddpm_op_guard_commit before any update reads them
+        sc = state.get("scaler")            # absent: saved without dynamic loss scaling -- the scaler is left as it is
+        if sc is not None:
+            self.enable_loss_scaling(init_scale=sc["init_scale"], growth_factor=sc["growth_factor"], backoff_factor=sc["backoff_factor"],
+                                     growth_interval=sc["growth_interval"], growth_tracker=sc["growth_tracker"])
+            if sc.get("state") is not None:
+                self.scaler = sc["state"].to(self.dev, torch.int32).clone()
 
     def parameters_changed(self) -> None:
         self.enc.repack()

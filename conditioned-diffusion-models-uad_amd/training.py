@@ -1049,6 +1049,17 @@ def loss_scaling_from_grad_scaler(state) -> Dict[str, object]:
                                  state.get("growth_interval", 2000), state.get("_growth_tracker", 0))
 
 
+def lightning_precision_bits(precision) -> int:
+    """set_precision's mapping of a Lightning-style precision value onto 16 | 32, on its own (nothing is set, no library is needed): what a
+    trainer with a precision of its own (the Spark_2D mirror's SparKTrainer) is built with. ValueError for anything else."""
+    key = str(precision).lower() if precision is not None else "32"
+    if key in ("32", "32-true", "64", "64-true", "none"):
+        return 32
+    if key in ("16", "16-mixed", "16-true", "bf16", "bf16-mixed", "bf16-true"):
+        return 16
+    raise ValueError(f"unknown precision {precision!r}")
+
+
 def set_precision(precision) -> int:
     """selects the arithmetic of the training operators from a Lightning-style precision value: 32 / "32" / "32-true" / None -> fp32-grade
     (two-term fp16 operand splits); 16 / "16" / "16-mixed" -> plain fp16 operands with fp32 accumulation, the arithmetic of the reference
@@ -1056,13 +1067,7 @@ def set_precision(precision) -> int:
     fp16-operand kernels: 11 significand bits instead of bf16's 8, the exponent range covered by the per-tensor power-of-two pre-scales, the
     loss scale and the non-finite-step guard. Process-wide (include/cddpm.h: cddpm_set_train_precision). Returns the bits in effect."""
     from . import _lib
-    key = str(precision).lower() if precision is not None else "32"
-    if key in ("32", "32-true", "64", "64-true", "none"):
-        bits = 32
-    elif key in ("16", "16-mixed", "16-true", "bf16", "bf16-mixed", "bf16-true"):
-        bits = 16
-    else:
-        raise ValueError(f"unknown precision {precision!r}")
+    bits = lightning_precision_bits(precision)
     lib = _lib.load_library()
     if lib.cddpm_set_train_precision(bits) < 0:
         raise RuntimeError("cddpm_set_train_precision failed")

@@ -739,7 +739,19 @@ int cddpm_op_enc_avgpool(cddpm_handle h, const float* x_dev, float* g_dev, int B
  *   (rec - inp)^2 / (p^2 (n_masked + 1e-8)), p^2 = (H / f)(W / f) (spatial_loss, pix_norm 0; 0 when nothing is masked); loss_dev[1] = mean |rec - inp|
  *   (L1_AE's recon_error); drec_dev (or NULL) = the gradient of w_mask loss[0] + w_l1 loss[1].
  * cddpm_op_adamw_guarded: cddpm_op_adam_guarded with torch.optim.AdamW's decoupled decay, p <- p (1 - lr weight_decay) before the update;
- *   the same control block, so a skipped step decays nothing. */
+ *   the same control block, so a skipped step decays nothing.
+ * Under "Dynamic loss scaling" above (scaler_dev: that int32[4] block, required), the pre-training step's forms of steps (a) and (c):
+ * cddpm_op_spark_loss_scaled: cddpm_op_spark_loss whose drec_dev is the gradient of w_mask loss[0] + w_l1 loss[1] TIMES the device scale;
+ *   loss_dev[0..1] are the unscaled terms. With the scale a power of two S and no under- or overflow it is bit-identical to
+ *   cddpm_op_spark_loss called with S w_mask, S w_l1. Temporaries: cddpm_op_spark_loss_scratch.
+ * cddpm_op_adamw_scaled: cddpm_op_adamw_guarded with gradient g_dev * extra_unscale / scale, in the form of cddpm_op_adam_scaled:
+ *   bit-identical to cddpm_op_adamw_guarded with grad_unscale = extra_unscale / S.
+ * Precision 16 of the pre-training step (SparKTrainer's precision=16; the trainer's own choice, cddpm_set_train_precision is neither read
+ * nor set): the rule of "Precision 16 of the three convolution operators" -- every convolution of the sparse ResNet-50 but the 7x7 stem,
+ * forward, input gradient and weight gradient, runs on cddpm_op_enc_conv_p16 / cddpm_op_enc_conv_wgrad_p16 and the images of
+ * cddpm_op_enc_pack_w_p16 (operands rounded as .half(), fp32 accumulation). The sparse and dense BatchNorms, the mask multiply and max
+ * pool, the stem, the densify convolutions (en_de_lins), the LightDecoder, the loss, AdamW and the master weights are fp32 at either
+ * precision: those layers are launch- and memory-bound at 4 to 128 channels, fp16 operands buy nothing there. */
 int cddpm_op_spark_bn_forward(cddpm_handle h, const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* sample_scale_dev,
                               const float* res_dev, int act, float eps, float momentum, float* run_mean_dev, float* run_var_dev, float* mean_rstd_dev,
                               float* y_dev, int64_t N, int HW, int C, const uint8_t* active_dev, int f, int H, int W, const float* fill_dev, int training,
@@ -757,6 +769,10 @@ int cddpm_op_spark_loss(cddpm_handle h, const float* rec_dev, const float* inp_d
                         float w_l1, float* loss_dev, float* drec_dev, void* stream);
 int cddpm_op_adamw_guarded(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
                            float eps, float weight_decay, float grad_unscale, const int32_t* ctrl_dev, void* stream);
+int cddpm_op_spark_loss_scaled(cddpm_handle h, const float* rec_dev, const float* inp_dev, const uint8_t* active_dev, int f, int B, int H, int W,
+                               float w_mask, float w_l1, const int32_t* scaler_dev, float* loss_dev, float* drec_dev, void* stream);
+int cddpm_op_adamw_scaled(cddpm_handle h, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, float extra_unscale, const int32_t* ctrl_dev, const int32_t* scaler_dev, void* stream);
 /* their size queries (the convention of cddpm_op_set_scratch above; has_db: db_dev given) */
 size_t cddpm_op_spark_bn_forward_scratch(int64_t N, int HW, int C);
 size_t cddpm_op_spark_bn_backward_scratch(int64_t N, int HW, int C);
