@@ -19,6 +19,11 @@ Added, behind a cfg switch that is absent (= reference behaviour) by default:
                                      kernels (UNetTrainer's attention_precision: the arithmetic of the reference's `precision: 16`
                                      autocast over QKVAttention; unset or 32: exact fp32 attention, today's behaviour). Independent of
                                      the Trainer's precision, which selects the convolutions' arithmetic; 'bf16' is a ValueError.
+    cfg.attention_family: h3     ->  the UNet's engine evaluates every attention block at fp32 accuracy on the fp16 matrix pipe (three-term
+                                     fp16 splits, CddpmEngine(attention_family=...)) instead of the exact fp32 kernel (unset or f32:
+                                     today's behaviour). Read where eval_precision is 32; eval_precision 16 wins. 'x6' is a ValueError.
+    cfg.train_attention_family: h3 -> training_step runs every attention core, forward and backward, on those split kernels
+                                     (UNetTrainer's attention_family). Read where train_attention_precision is 32; 16 wins.
     cfg.train_encoder_precision: 16 -> training_step runs the context encoder's convolutions (all but the 7x7 stem), forward, input gradient
                                      and weight gradient, on the fp16-MFMA kernels (EncoderTrainer's precision: the arithmetic of the
                                      reference's `precision: 16` autocast over self.encoder; unset or 32: fp32 FMA kernels, today's
@@ -48,6 +53,7 @@ import torch.nn as nn
 
 from .OpenAI_Unet import UNetModel as OpenAI_UNet
 from .cond_DDPM import GaussianDiffusion
+from .engine import attention_family_code
 from .generate_noise import gen_noise
 from .mirror_common import AttrDict, HipMirror, _Base, _cfg_get, _to_cpu  # noqa: F401  (re-exported: the names lived here)
 
@@ -113,7 +119,9 @@ class DDPM_2D(HipMirror, _Base):
             use_new_attention_order=True, use_spatial_transformer=_cfg_get(cfg, "spatial_transformer", False),
             transformer_depth=1)
         model.convert_to_fp16()
-        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None), _cfg_get(cfg, "eval_precision", None))
+        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None), _cfg_get(cfg, "eval_precision", None),
+                             _cfg_get(cfg, "attention_family", None))
+        attention_family_code(_cfg_get(cfg, "train_attention_family", "f32"))      # a bad value: ValueError here, before any device
         timesteps = _cfg_get(cfg, "timesteps", 1000)
         self.test_timesteps = _cfg_get(cfg, "test_timesteps", 150)
         self.diffusion = GaussianDiffusion(

@@ -12,8 +12,8 @@ On the HIP path: training_step runs `training.training_step(..., box=, inpaint=)
 cddpm_box_q_sample, the loss is cddpm_op_loss_box); test_step does the reference's K-box loop (:185-215) as ONE
 `GaussianDiffusion.p_losses_grid` call: batched UNet forwards over all K D (box, slice) pairs and one stitching launch. What the two
 mirrors share (trainer aliasing, checkpoint hooks, precision, loss-scale logging, evaluation bookkeeping) is mirror_common.HipMirror.
-The cfg keys `conv_family`, `conv_fallback`, `eval_precision` and `train_attention_precision` (absent in the reference; unset = nothing
-changes) mean what they mean in DDPM_2D.py: `eval_precision: 16` evaluates (test_step, validation_step) with plain fp16 operands in the
+The cfg keys `conv_family`, `conv_fallback`, `eval_precision`, `train_attention_precision`, `attention_family` and
+`train_attention_family` (absent in the reference; unset = nothing changes) mean what they mean in DDPM_2D.py: `eval_precision: 16` evaluates (test_step, validation_step) with plain fp16 operands in the
 UNet's engine; `train_attention_precision: 16` trains the attention cores on the fp16-MFMA kernels. `evalHausdorff: true` reaches the
 standalone metric pass with the rest of the cfg, like `evalSeg`: HausPerVol gets the device Hausdorff distance instead of NaN.
 """
@@ -25,6 +25,7 @@ import torch.nn as nn
 from .DDPM_2D import DDPM_2D as _CondMirror
 from .OpenAI_Unet import UNetModel as OpenAI_UNet
 from .cond_DDPM import GaussianDiffusion
+from .engine import attention_family_code
 from .mirror_common import AttrDict, HipMirror, _Base, _cfg_get
 from .patch_sampling import BoxSampler
 
@@ -48,7 +49,9 @@ class DDPM_2D(HipMirror, _Base):
             num_head_channels=64, num_heads_upsample=-1, use_scale_shift_norm=True, resblock_updown=True,
             use_new_attention_order=True, use_spatial_transformer=False, transformer_depth=1)
         model.convert_to_fp16()
-        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None), _cfg_get(cfg, "eval_precision", None))
+        model._hip.configure(_cfg_get(cfg, "conv_family", None), _cfg_get(cfg, "conv_fallback", None), _cfg_get(cfg, "eval_precision", None),
+                             _cfg_get(cfg, "attention_family", None))
+        attention_family_code(_cfg_get(cfg, "train_attention_family", "f32"))      # a bad value: ValueError here, before any device
         timesteps = _cfg_get(cfg, "timesteps", 1000)
         self.test_timesteps = _cfg_get(cfg, "test_timesteps", 150)
         self.diffusion = GaussianDiffusion(

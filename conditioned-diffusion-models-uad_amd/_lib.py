@@ -65,6 +65,8 @@ SYMBOLS = {
     "cddpm_set_accumulation_switch": (_i, [_vp, _i]),
     "cddpm_set_conv_family": (_i, [_vp, _i]),
     "cddpm_get_conv_family": (_i, [_vp]),
+    "cddpm_set_attention_family": (_i, [_vp, _i]),
+    "cddpm_get_attention_family": (_i, [_vp]),
     "cddpm_set_precision": (_i, [_vp, _i]),
     "cddpm_get_precision": (_i, [_vp]),
     "cddpm_slice_status": (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
@@ -81,6 +83,7 @@ SYMBOLS = {
     "cddpm_op_gn_coef": (_i, [_vp, _fp, _i, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _vp]),
     "cddpm_op_attention": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_attention_p16": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
+    "cddpm_op_attention_h3": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_encoder_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "cddpm_encoder_destroy": (None, [_vp]),
     "cddpm_encoder_last_error": (C.c_char_p, [_vp]),
@@ -92,6 +95,7 @@ SYMBOLS = {
     "cddpm_op_bias_grad": (_i, [_vp, _fp, _i64, _i, _fp, _vp]),
     "cddpm_op_attention_backward": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_attention_backward_p16": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
+    "cddpm_op_attention_backward_h3": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_linear_backward": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
     "cddpm_op_linear": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
     "cddpm_op_conv_in1": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
@@ -135,6 +139,7 @@ SYMBOLS = {
     "cddpm_op_gn_coef_scratch": (_sz, [_i] * 5),
     "cddpm_op_gn_silu_backward_scratch": (_sz, [_i] * 4),
     "cddpm_op_attention_backward_scratch": (_sz, [_i] * 3),
+    "cddpm_op_attention_backward_h3_scratch": (_sz, [_i] * 3),
     "cddpm_op_linear_backward_scratch": (_sz, [_i] * 4),
     "cddpm_op_head_scratch": (_sz, [_i] * 4),
     "cddpm_op_bias_grad_scratch": (_sz, [_i64, _i]),

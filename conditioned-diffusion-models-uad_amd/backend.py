@@ -11,7 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from . import schedule as _schedule
-from .engine import EXACT_FAMILIES, CddpmEngine, conv_family_code, precision_bits
+from .engine import EXACT_FAMILIES, CddpmEngine, attention_family_code, conv_family_code, precision_bits
 
 
 class HipBackend:
@@ -31,12 +31,20 @@ class HipBackend:
         self.conv_fallback: Optional[str] = None     # None: off; 'x6' / 'f32': re-run slices that left the fp16 range there
         self._fallback_engine: Optional[CddpmEngine] = None
         self.eval_precision: int = 32                # 16: the engine evaluates in the reference's `precision: 16` arithmetic
+        self.attention_family: Optional[str] = None  # None: exact fp32 attention; 'h3': fp32-grade fp16 splits (at eval_precision 32)
 
-    def configure(self, conv_family: Optional[str] = None, conv_fallback: Optional[str] = None, eval_precision=None):
-        """the engine's convolution family, the exact family non-finite slices are re-run in and the engine's precision (DDPM_2D:
-        cfg.conv_family, cfg.conv_fallback, cfg.eval_precision); all default to unset = the behaviour without them. eval_precision
-        16 with an exact conv_family is a ValueError: only the h3 family has it."""
+    def configure(self, conv_family: Optional[str] = None, conv_fallback: Optional[str] = None, eval_precision=None,
+                  attention_family: Optional[str] = None):
+        """the engine's convolution family, the exact family non-finite slices are re-run in, the engine's precision and its
+        attention family (DDPM_2D: cfg.conv_family, cfg.conv_fallback, cfg.eval_precision, cfg.attention_family); all default to unset
+        = the behaviour without them. eval_precision 16 with an exact conv_family is a ValueError: only the h3 family has it. A
+        fallback engine keeps exact fp32 attention."""
         bits = 32 if eval_precision is None else precision_bits(eval_precision)
+        if attention_family is not None:
+            attention_family_code(attention_family)
+        if attention_family != self.attention_family:
+            self.attention_family = attention_family
+            self.close()
         if bits == 16 and conv_family is not None and conv_family_code(conv_family) != conv_family_code("h3"):
             raise ValueError(f"eval_precision 16 needs the h3 convolution family, got conv_family={conv_family!r}")
         if bits != self.eval_precision:
@@ -79,7 +87,8 @@ class HipBackend:
             max_h = max(H, e.max_h if e is not None else 0)
             max_w = max(W, e.max_w if e is not None else 0)
             e = CddpmEngine(timesteps=self.timesteps, max_batch=max_b, max_h=max_h, max_w=max_w, device=device,
-                            conv_family=self.conv_family, precision=self.eval_precision, **self._unet_desc)
+                            conv_family=self.conv_family, precision=self.eval_precision, attention_family=self.attention_family,
+                            **self._unet_desc)
             e.load_weights(unet.state_dict())
             self.engine, self._key, self._sched_key = e, wkey, None
         skey = (id(self.buffers), self.objective)

@@ -1,11 +1,13 @@
 // Self-attention core for gfx950: softmax(q k^T / sqrt(d)) v, d = 64, flash-style (the N x N score matrix never leaves registers),
-// forward and backward, in two arithmetics: exact fp32 on v_mfma_f32_32x32x2_f32 and plain fp16 operands on v_mfma_f32_32x32x16_f16.
+// forward and backward, in three arithmetics: exact fp32 on v_mfma_f32_32x32x2_f32, plain fp16 operands on v_mfma_f32_32x32x16_f16, and
+// h3 on the same 16-bit instruction: fp32-grade products from two-term fp16 splits (hi . hi + hi . lo + lo . hi), opt-in per handle / call.
 //
 // Replaces QKVAttention.forward (src/models/modules/OpenAI_Unet.py:457-476): q,k,v = chunk(qkv, 3);
 // heads are contiguous groups of 64 channels; w = softmax_fp32((q s)^T (k s)), s = 64^-1/4; a = w v^T.
 // The two s factors are applied as one exact 2^-3 scale of q.
 //
-// Six kernels behind four launchers; what they share exists once, as __device__ functions: the workgroup decode, the row store,
+// Ten kernels behind six launchers (per arithmetic a forward, a bwd_q and a bwd_kv kernel; h3 also the pass that takes each sample's
+// largest |dA|); what they share exists once, as __device__ functions: the workgroup decode, the row store,
 // the online-softmax tile step, per arithmetic the stage / first-product / second-product pieces, and per arithmetic the forward
 // sweep over the key tiles, which is the forward kernel's body and sweep 1 of the bwd_q kernel. MFMA accumulators go through these
 // helpers by value and come back in small structs, and the two sub-tiles of a tile are a two-element array walked by an unrolled
@@ -301,6 +303,154 @@ __device__ __forceinline__ Sweep p16_forward_sweep(const Wg& w, const f16x8 (&qf
     }
     return f;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// h3: fp32-grade products from two-term fp16 splits on v_mfma_f32_32x32x16_f16, the attention member of the convolutions' h3 family.
+//   An operand x of unknown scale (q / 8, k, v, and dA after its per-sample normalisation) is carried as hi = fp16(x) and
+//   lo = fp16((x - hi) 2^11): the lift keeps lo out of fp16's subnormal range wherever hi is normal. Out of range (|x| >= 65520) hi is
+//   +-inf and lo is -+inf or NaN: non-finite results, never a finite wrong number.
+//   first product  (both operands of unknown scale; images and fragments as p16, once per term): the accumulator takes
+//                  hi . lo + lo . hi first, is multiplied by 2^-11 (16 VALU multiplies), then takes hi . hi: 12 MFMAs per 32 x 32 tile,
+//                  no second accumulator.
+//   second product (the B operand y is P or dS, formed in registers at a known lift): three B operands fp16(y), fp16(y - fp16(y)) and
+//                  fp16(y 2^-11) against the two images, acc += hi . fp16(y) + hi . (y - fp16(y)) + lo . fp16(y 2^-11): 3 MFMAs per
+//                  k-step and channel tile, one accumulator. y's own lo is NOT lifted, so y must not be small: P is taken against the
+//                  running maximum (forward) or normalised (backward) and lifted by 2^15 -- at N = 16384 a flat row's P 2^15 is 2, its lo
+//                  has 13 bits -- and dS = P (dP - D) by 2^10 (dA normalised to [1, 2) per sample: a flat row at N = 16384 is near 2^-3 ...
+//                  2^0, a two-key row near 2^10 ... 2^13). The lifts are exact powers of two and leave with the row store.
+// One 64-key tile of the forward costs a wave 24 + 24 MFMAs of 32 cycles instead of 128 of 64.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr float H3_LO = 2048.f, H3_LO_INV = 1.0f / 2048.f;
+constexpr int H3_P_LIFT = 15, H3_DS_LIFT = 10;
+
+struct H3x4 { f16x4 hi, lo; };
+__device__ __forceinline__ H3x4 h3_split4(float x, float y, float z, float w) {
+    H3x4 r;
+    r.hi = p16_round4(x, y, z, w);
+    r.lo = p16_round4((x - (float)r.hi[0]) * H3_LO, (y - (float)r.hi[1]) * H3_LO, (z - (float)r.hi[2]) * H3_LO, (w - (float)r.hi[3]) * H3_LO);
+    return r;
+}
+// 8 channels of a global row, times the exact 2^e, as the hi and lo fragments of one k-step
+__device__ __forceinline__ void h3_fragment(f16x8& hi, f16x8& lo, const float* p, int e) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    const float4 c = *reinterpret_cast<const float4*>(p + 4);
+    const H3x4 s0 = h3_split4(ldexpf(a.x, e), ldexpf(a.y, e), ldexpf(a.z, e), ldexpf(a.w, e));
+    const H3x4 s1 = h3_split4(ldexpf(c.x, e), ldexpf(c.y, e), ldexpf(c.z, e), ldexpf(c.w, e));
+    hi = __builtin_shufflevector(s0.hi, s1.hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    lo = __builtin_shufflevector(s0.lo, s1.lo, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// what p16_gather read, split into a pair of row images / of transposed images
+__device__ __forceinline__ void h3_stage_rows(_Float16* hi, _Float16* lo, int kq, int cq, const float4 (&v)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const H3x4 s = h3_split4(v[i].x, v[i].y, v[i].z, v[i].w);
+        *reinterpret_cast<f16x4*>(&hi[(4 * kq + i) * P16_RS + 4 * cq]) = s.hi;
+        *reinterpret_cast<f16x4*>(&lo[(4 * kq + i) * P16_RS + 4 * cq]) = s.lo;
+    }
+}
+__device__ __forceinline__ void h3_stage_cols(_Float16* hi, _Float16* lo, int kq, int cq, const float4 (&v)[4]) {
+    const H3x4 s[4] = {h3_split4(v[0].x, v[1].x, v[2].x, v[3].x), h3_split4(v[0].y, v[1].y, v[2].y, v[3].y),
+                       h3_split4(v[0].z, v[1].z, v[2].z, v[3].z), h3_split4(v[0].w, v[1].w, v[2].w, v[3].w)};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        *reinterpret_cast<f16x4*>(&hi[(4 * cq + c) * P16_TS + 4 * kq]) = s[c].hi;
+        *reinterpret_cast<f16x4*>(&lo[(4 * cq + c) * P16_TS + 4 * kq]) = s[c].lo;
+    }
+}
+// (row images)[row][64 channels] . (fragments): one 32 x 32 tile, image row `row` (32 sub + li) in this lane's A operand
+__device__ __forceinline__ f32x16 h3_first_product(const _Float16* rhi, const _Float16* rlo, int row, int lh, const f16x8 (&fh)[4],
+                                                   const f16x8 (&fl)[4]) {
+    f32x16 acc = {};
+    const int o = row * P16_RS + 8 * lh;
+    f16x8 ah[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        ah[s] = *reinterpret_cast<const f16x8*>(rhi + o + 16 * s);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], fl[s], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(rlo + o + 16 * s), fh[s], acc, 0, 0, 0);
+    }
+    acc *= H3_LO_INV;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], fh[s], acc, 0, 0, 0);
+    return acc;
+}
+// registers 8s .. 8s+7 of a first product's accumulator, times the exact 2^lift, as the three B operands of k-step s of the second
+struct H3Operand { f16x8 hi, lo, sc; };
+__device__ __forceinline__ H3Operand h3_operand(f32x16 acc, int s, int lift) {
+    H3Operand b;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float y = ldexpf(acc[8 * s + j], lift);
+        b.hi[j] = (_Float16)y;
+        b.lo[j] = (_Float16)(y - (float)b.hi[j]);
+        b.sc[j] = (_Float16)(y * H3_LO_INV);
+    }
+    return b;
+}
+// acc[ct] += (T^T images)[channel 32 ct + li][rows row0 + {0..3}, row0 + 8 + {0..3}] . b for both channel tiles; row0 as p16_second_product
+__device__ __forceinline__ Acc2 h3_second_product(Acc2 acc, const _Float16* thi, const _Float16* tlo, int li, int row0, const H3Operand& b) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+        const int o = (32 * ct + li) * P16_TS + row0;
+        const f16x8 ah = __builtin_shufflevector(*reinterpret_cast<const f16x4*>(thi + o), *reinterpret_cast<const f16x4*>(thi + o + 8),
+                                                 0, 1, 2, 3, 4, 5, 6, 7);
+        const f16x8 al = __builtin_shufflevector(*reinterpret_cast<const f16x4*>(tlo + o), *reinterpret_cast<const f16x4*>(tlo + o + 8),
+                                                 0, 1, 2, 3, 4, 5, 6, 7);
+        acc.t[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, b.sc, acc.t[ct], 0, 0, 0);
+        acc.t[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b.lo, acc.t[ct], 0, 0, 0);
+        acc.t[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b.hi, acc.t[ct], 0, 0, 0);
+    }
+    return acc;
+}
+
+// The forward over all key tiles for this lane's query (fragments of q / 8). ldsK: K row images, ldsVt: V^T images, hi then lo.
+// O comes back lifted by 2^H3_P_LIFT (P is taken against the running maximum, so the lift holds whatever N is); l is not lifted.
+__device__ __forceinline__ Sweep h3_forward_sweep(const Wg& w, const f16x8 (&qh)[4], const f16x8 (&ql)[4], _Float16* ldsK, _Float16* ldsVt,
+                                                  int N, int C) {
+    const int cq = w.tid & 15, kq = w.tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
+    const float* kp = w.base + C + w.hd * 64;
+    Sweep f = {{}, -INFINITY, 0.f};
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        float4 kv[4], vv[4];
+        p16_gather<false>(kv, vv, kp, w.C3, kp + C, w.C3, k0, N, kq, cq);
+        __syncthreads();   // previous tile fully consumed
+        h3_stage_rows(ldsK, ldsK + 64 * P16_RS, kq, cq, kv);
+        h3_stage_cols(ldsVt, ldsVt + 64 * P16_TS, kq, cq, vv);
+        __syncthreads();
+        f32x16 S[2];
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) S[kt] = h3_first_product(ldsK, ldsK + 64 * P16_RS, 32 * kt + w.li, w.lh, qh, ql);
+        const SoftmaxTile t = softmax_tile(S[0], S[1], f.m, k0, N, w.lh);
+        f.l = f.l * t.alpha + t.psum;
+        f.m = t.m_new;
+        f.O.t[0] *= t.alpha;
+        f.O.t[1] *= t.alpha;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                f.O = h3_second_product(f.O, ldsVt, ldsVt + 64 * P16_TS, w.li, 32 * kt + 16 * s + 4 * w.lh, h3_operand(t.P[kt], s, H3_P_LIFT));
+    }
+    return f;
+}
+
+// acc 2^e, elementwise and exact (ldexp, so that no intermediate power of two has to be a float); poison: 1, or NaN
+__device__ __forceinline__ Acc2 h3_unlift(Acc2 acc, int e, float poison) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc.t[ct][r] = ldexpf(acc.t[ct][r] * poison, e);
+    return acc;
+}
+
+// The backward's normalisation of dA, per sample: amax[b] holds the largest magnitude bits of sample b's dA (attention_h3_amax_kernel).
+// dA 2^-e has its largest magnitude in [1, 2); a non-finite dA poisons its sample (and only it) with NaN; an all-zero dA keeps e = 0.
+struct H3Norm { int e; float poison; };
+__device__ __forceinline__ H3Norm h3_norm(const unsigned* amax, int b) {
+    const unsigned m = amax[b];
+    const int ex = (int)(m >> 23);
+    return H3Norm{m == 0u ? 0 : max(ex, 1) - 127, ex == 255 ? NAN : 1.0f};
+}
 }  // namespace
 
 __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
@@ -337,6 +487,25 @@ void launch_attention_p16(const float* qkv, float* out, int B, int N, int C, hip
     const int heads = C / 64;
     const int nqb = (N + 127) / 128;
     hipLaunchKernelGGL(attention_p16_kernel, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, stream, qkv, out, N, C);
+}
+
+__global__ __launch_bounds__(256, 2) void attention_h3_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                              int N, int C) {
+    __shared__ __attribute__((aligned(16))) _Float16 ldsK[2 * 64 * P16_RS];    // hi, lo x [key][channel]
+    __shared__ __attribute__((aligned(16))) _Float16 ldsVt[2 * 64 * P16_TS];   // hi, lo x [channel][key]
+    const Wg w = wg_decode(qkv, N, C);
+    // Q fragments of this lane's query: k-step s = channels 16 s + 8 lh + {0..7}, times 1/8, split
+    f16x8 qh[4], ql[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) h3_fragment(qh[s], ql[s], w.base + (size_t)min(w.row, N - 1) * w.C3 + w.hd * 64 + 16 * s + 8 * w.lh, -3);
+    const Sweep f = h3_forward_sweep(w, qh, ql, ldsK, ldsVt, N, C);
+    if (w.row < N) store_row(out + ((size_t)w.b * N + w.row) * C + w.hd * 64, f.O, ldexpf(1.0f / f.l, -H3_P_LIFT), w.lh);
+}
+
+void launch_attention_h3(const float* qkv, float* out, int B, int N, int C, hipStream_t stream) {
+    const int heads = C / 64;
+    const int nqb = (N + 127) / 128;
+    hipLaunchKernelGGL(attention_h3_kernel, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, stream, qkv, out, N, C);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -603,6 +772,184 @@ void launch_attention_backward_p16(const float* qkv, const float* da, float* dqk
     const int nb = (N + 127) / 128;
     hipLaunchKernelGGL(attention_bwd_q_p16_kernel, dim3((unsigned)(B * heads * nb)), dim3(256), 0, stream, qkv, da, dqkv, stats, N, C);
     hipLaunchKernelGGL(attention_bwd_kv_p16_kernel, dim3((unsigned)(B * heads * nb)), dim3(256), 0, stream, qkv, da, dqkv, stats, N, C);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same backward in the h3 arithmetic (launch_attention_backward_h3): two kernels, work split, masking and row statistics as the
+// pairs above, all seven N x N x 64 products and sweep 1's two as three-term split products. dA has no natural scale (a loss
+// gradient, times a loss scale, over a batch mean), so a pass in front takes the largest magnitude of each SAMPLE's dA as an integer
+// maximum of the magnitude bits (atomicMax on uint32: exact, order-free, two calls give the same bits) and both kernels work on
+// dA 2^-e, e the exponent of that maximum: the statistics' D, dP and dS are those of the normalised gradient, and 2^e returns with the
+// lifts in the row stores. D_i = sum_c dA_ic a_ic takes the normalised dA in fp32 and the fp32 sweep-1 output.
+//   attention_bwd_q_h3_kernel  : sweep 1 = attention_h3_kernel (K rows, V^T); sweep 2: K rows, V rows, K^T, hi and lo each (53 KB)
+//   attention_bwd_kv_h3_kernel : k, v fragments in registers; per 64-query tile Q/8 and dA rows, (Q/8)^T and dA^T, hi and lo each (70.5 KB)
+// Per 64-row tile a wave issues 48 + 72 (q kernel, sweeps 1 + 2) and 96 (kv kernel) MFMAs of 32 cycles instead of 128 + 192 and 256 of 64.
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void attention_h3_amax_kernel(const float* __restrict__ da, unsigned* __restrict__ amax, long long per_sample) {
+    const float4* p = reinterpret_cast<const float4*>(da + (size_t)blockIdx.y * per_sample);
+    const long long n4 = per_sample >> 2;      // per_sample = N C, C a multiple of 64
+    unsigned m = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const float4 v = p[i];
+        m = max(max(m, __float_as_uint(v.x) & 0x7fffffffu), max(__float_as_uint(v.y) & 0x7fffffffu, __float_as_uint(v.z) & 0x7fffffffu));
+        m = max(m, __float_as_uint(v.w) & 0x7fffffffu);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d, 64));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(&amax[blockIdx.y], m);
+}
+
+__global__ __launch_bounds__(256, 2) void attention_bwd_q_h3_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
+                                                                    float* __restrict__ dqkv, float* __restrict__ stats /*[B][heads][N][2]*/,
+                                                                    const unsigned* __restrict__ amax /*[B]*/, int N, int C) {
+    __shared__ __attribute__((aligned(16))) _Float16 ldsK[2 * 64 * P16_RS];   // K rows, hi and lo
+    __shared__ __attribute__((aligned(16))) _Float16 ldsV[2 * 64 * P16_RS];   // V rows (sweep 2: A operand of dP^T = V . dA^T)
+    __shared__ __attribute__((aligned(16))) _Float16 ldsT[2 * 64 * P16_TS];   // [channel][key]: V^T in sweep 1, K^T in sweep 2
+    const Wg w = wg_decode(qkv, N, C);
+    const H3Norm nm = h3_norm(amax, w.b);
+    const int qrow = min(w.row, N - 1);
+    const float* darow = da + ((size_t)w.b * N + qrow) * C + w.hd * 64;
+    f16x8 qh[4], ql[4], dah[4], dal[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        h3_fragment(qh[s], ql[s], w.base + (size_t)qrow * w.C3 + w.hd * 64 + 16 * s + 8 * w.lh, -3);
+        h3_fragment(dah[s], dal[s], darow + 16 * s + 8 * w.lh, -nm.e);
+    }
+    // ---------------- sweep 1: the h3 forward (running max / sum, O^T 2^15) -> D of the normalised dA
+    const Sweep f = h3_forward_sweep(w, qh, ql, ldsK, ldsT, N, C);
+    float dsum = 0.f;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+            const float4 d4 = *reinterpret_cast<const float4*>(darow + 32 * ct + 8 * rq + 4 * w.lh);
+            dsum += ldexpf(d4.x, -nm.e) * f.O.t[ct][4 * rq + 0] + ldexpf(d4.y, -nm.e) * f.O.t[ct][4 * rq + 1] +
+                    ldexpf(d4.z, -nm.e) * f.O.t[ct][4 * rq + 2] + ldexpf(d4.w, -nm.e) * f.O.t[ct][4 * rq + 3];
+        }
+    dsum += __shfl_xor(dsum, 32, 64);
+    const float Dq = dsum * ldexpf(1.0f / f.l, -H3_P_LIFT);
+    const float lse = f.m + __logf(f.l);
+    if (w.row < N && w.lh == 0) {
+        float* st = stats + (((size_t)w.b * w.heads + w.hd) * N + w.row) * 2;
+        st[0] = lse; st[1] = Dq;
+    }
+    // ---------------- sweep 2: S^T = K . Q^T, dP^T = V . dA^T, dQ^T 2^10 += K^T . (dS^T 2^10)
+    const int cq = w.tid & 15, kq = w.tid >> 4;     // staging: this thread's 4 channels x 4 keys of the tile
+    const float* kp = w.base + C + w.hd * 64;
+    Acc2 dQ = {};
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        float4 kv[4], vv[4];
+        p16_gather<false>(kv, vv, kp, w.C3, kp + C, w.C3, k0, N, kq, cq);
+        __syncthreads();   // previous tile (or sweep 1's last) fully consumed
+        h3_stage_rows(ldsK, ldsK + 64 * P16_RS, kq, cq, kv);
+        h3_stage_rows(ldsV, ldsV + 64 * P16_RS, kq, cq, vv);
+        h3_stage_cols(ldsT, ldsT + 64 * P16_TS, kq, cq, kv);
+        __syncthreads();
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+            f32x16 S = h3_first_product(ldsK, ldsK + 64 * P16_RS, 32 * kt + w.li, w.lh, qh, ql);
+            const f32x16 dP = h3_first_product(ldsV, ldsV + 64 * P16_RS, 32 * kt + w.li, w.lh, dah, dal);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = k0 + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * w.lh;
+                const float pv = (key < N) ? __expf(S[r] - lse) : 0.f;
+                S[r] = pv * (dP[r] - Dq);            // dS^T
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                dQ = h3_second_product(dQ, ldsT, ldsT + 64 * P16_TS, w.li, 32 * kt + 16 * s + 4 * w.lh, h3_operand(S, s, H3_DS_LIFT));
+        }
+    }
+    if (w.row < N) store_row(dqkv + ((size_t)w.b * N + w.row) * w.C3 + w.hd * 64, h3_unlift(dQ, nm.e - H3_DS_LIFT - 3, nm.poison), w.lh);
+}
+
+__global__ __launch_bounds__(256, 2) void attention_bwd_kv_h3_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
+                                                                     float* __restrict__ dqkv, const float* __restrict__ stats,
+                                                                     const unsigned* __restrict__ amax /*[B]*/, int N, int C) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 h3_lds[];
+    _Float16* ldsQ = h3_lds;                          // (Q / 8) rows [query][channel], hi and lo: A operand of S = Q . K^T
+    _Float16* ldsA = ldsQ + 2 * 64 * P16_RS;          // dA rows: A operand of dP = dA . V^T
+    _Float16* ldsQt = ldsA + 2 * 64 * P16_RS;         // [channel][query] images: A operands of dK^T += (Q/8)^T dS
+    _Float16* ldsAt = ldsQt + 2 * 64 * P16_TS;        //                          and dV^T += dA^T P
+    float* ldsL = reinterpret_cast<float*>(ldsAt + 2 * 64 * P16_TS);      // per query: m + log l, D
+    float* ldsD = ldsL + 64;
+    const Wg w = wg_decode(qkv, N, C);
+    const H3Norm nm = h3_norm(amax, w.b);
+    const float* krowp = w.base + (size_t)min(w.row, N - 1) * w.C3 + C + w.hd * 64;
+    // fragments of this lane's key: k-step s = channels 16 s + 8 lh + {0..7}
+    f16x8 kh[4], kl[4], vh[4], vl[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        h3_fragment(kh[s], kl[s], krowp + 16 * s + 8 * w.lh, 0);
+        h3_fragment(vh[s], vl[s], krowp + C + 16 * s + 8 * w.lh, 0);
+    }
+    Acc2 dK = {}, dV = {};
+    const float* st = stats + ((size_t)w.b * w.heads + w.hd) * N * 2;
+    const int cq = w.tid & 15, kq = w.tid >> 4;     // staging: this thread's 4 channels x 4 queries of the tile
+    for (int q0 = 0; q0 < N; q0 += 64) {
+        float4 qv[4], av[4];
+        p16_gather<true>(qv, av, w.base + w.hd * 64, w.C3, da + (size_t)w.b * N * C + w.hd * 64, C, q0, N, kq, cq);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            av[i] = make_float4(ldexpf(av[i].x, -nm.e), ldexpf(av[i].y, -nm.e), ldexpf(av[i].z, -nm.e), ldexpf(av[i].w, -nm.e));
+        float lq = INFINITY, dq_ = 0.f;      // exp(S - inf) = 0: queries past the end contribute nothing
+        if (w.tid < 64 && q0 + w.tid < N) {
+            lq = st[(size_t)(q0 + w.tid) * 2];
+            dq_ = st[(size_t)(q0 + w.tid) * 2 + 1];
+        }
+        __syncthreads();   // previous tile fully consumed
+        h3_stage_rows(ldsQ, ldsQ + 64 * P16_RS, kq, cq, qv);
+        h3_stage_rows(ldsA, ldsA + 64 * P16_RS, kq, cq, av);
+        h3_stage_cols(ldsQt, ldsQt + 64 * P16_TS, kq, cq, qv);
+        h3_stage_cols(ldsAt, ldsAt + 64 * P16_TS, kq, cq, av);
+        if (w.tid < 64) { ldsL[w.tid] = lq; ldsD[w.tid] = dq_; }
+        __syncthreads();
+        // S[query][key] = (Q/8) . K^T and dP[query][key] = dA . V^T: queries in the accumulator registers, the key on the lane
+#pragma unroll 1
+        for (int qt = 0; qt < 2; ++qt) {
+            f32x16 S = h3_first_product(ldsQ, ldsQ + 64 * P16_RS, 32 * qt + w.li, w.lh, kh, kl);
+            f32x16 dP = h3_first_product(ldsA, ldsA + 64 * P16_RS, 32 * qt + w.li, w.lh, vh, vl);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qq = 32 * qt + (r & 3) + 8 * (r >> 2) + 4 * w.lh;
+                const float pv = __expf(S[r] - ldsL[qq]);
+                S[r] = pv;
+                dP[r] = pv * (dP[r] - ldsD[qq]);     // dS
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int row0 = 32 * qt + 16 * s + 4 * w.lh;
+                dV = h3_second_product(dV, ldsAt, ldsAt + 64 * P16_TS, w.li, row0, h3_operand(S, s, H3_P_LIFT));
+                dK = h3_second_product(dK, ldsQt, ldsQt + 64 * P16_TS, w.li, row0, h3_operand(dP, s, H3_DS_LIFT));
+            }
+        }
+    }
+    if (w.row < N) {
+        float* krow_o = dqkv + ((size_t)w.b * N + w.row) * w.C3 + C + w.hd * 64;
+        store_row(krow_o, h3_unlift(dK, nm.e - H3_DS_LIFT, nm.poison), w.lh);
+        store_row(krow_o + C, h3_unlift(dV, nm.e - H3_P_LIFT, nm.poison), w.lh);
+    }
+}
+constexpr size_t H3_KV_LDS = (size_t)(4 * 64 * P16_RS + 4 * 64 * P16_TS) * sizeof(_Float16) + 128 * sizeof(float);
+
+// stats: [B][heads][N][2] floats and amax: B uint32 of scratch
+void launch_attention_backward_h3(const float* qkv, const float* da, float* dqkv, float* stats, unsigned* amax, int B, int N, int C,
+                                  hipStream_t stream) {
+    static bool attr = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_kv_h3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)H3_KV_LDS);
+        return true;
+    }();
+    (void)attr;
+    const int heads = C / 64;
+    const int nb = (N + 127) / 128;
+    const long long per_sample = (long long)N * C;
+    const unsigned chunks = (unsigned)std::min<long long>(64, (per_sample / 4 + 255) / 256);
+    (void)hipMemsetAsync(amax, 0, (size_t)B * sizeof(unsigned), stream);
+    hipLaunchKernelGGL(attention_h3_amax_kernel, dim3(chunks, (unsigned)B), dim3(256), 0, stream, da, amax, per_sample);
+    hipLaunchKernelGGL(attention_bwd_q_h3_kernel, dim3((unsigned)(B * heads * nb)), dim3(256), 0, stream, qkv, da, dqkv, stats, amax, N, C);
+    hipLaunchKernelGGL(attention_bwd_kv_h3_kernel, dim3((unsigned)(B * heads * nb)), dim3(256), H3_KV_LDS, stream, qkv, da, dqkv, stats, amax,
+                       N, C);
 }
 
 }  // namespace cddpm

@@ -494,6 +494,7 @@ int run_attn(cddpm_ctx* h, const AttnW& w, const float* x, float* dst, int B, in
     {
         Prof pa(h, PC_ATTN, 4.0 * B * (double)N * N * w.C, 4.0 * B * (double)N * 4 * w.C, s);
         if (h->precision == 16) launch_attention_p16(h->qkvbuf, h->attbuf, B, N, w.C, s);
+        else if (h->attn_family == 2) launch_attention_h3(h->qkvbuf, h->attbuf, B, N, w.C, s);
         else launch_attention(h->qkvbuf, h->attbuf, B, N, w.C, s);
     }
     ConvArgs p;
@@ -1175,6 +1176,19 @@ int cddpm_set_conv_family(cddpm_handle h, int family) {
     }
     h->gen++;                            // a captured step graph has the family's kernels baked in
     h->family = family;
+    return 0;
+}
+
+int cddpm_get_attention_family(cddpm_handle h) { return h ? h->attn_family : -1; }
+
+int cddpm_set_attention_family(cddpm_handle h, int family) {
+    if (!h) return -1;
+    if (family == 1)
+        return fail(h, "cddpm_set_attention_family: there is no x6 attention (2 = h3: fp32-grade fp16 splits, 0 = f32: exact fp32 MFMA)");
+    if (family != 0 && family != 2) return fail(h, "cddpm_set_attention_family: unknown family %d (2 = h3, 0 = f32)", family);
+    if (family == h->attn_family) return 0;
+    h->gen++;                            // a captured step graph has the family's kernel baked in
+    h->attn_family = family;             // nothing to repack: the attention core has no weights
     return 0;
 }
 

@@ -74,6 +74,10 @@ struct cddpm_ctx {
     // fp16 operands -- hi_only on every convolution conv_launch plans, the fp16-MFMA attention kernel, and the 256-cout workgroups
     // wherever the maximum geometry allows them. Not read by the cddpm_op_* operators.
     int precision = 32;
+    // arithmetic of the attention blocks of a precision-32 reconstruction path (cddpm_set_attention_family; numbering of the
+    // convolution families): 0 = exact fp32 MFMA, 2 = h3, fp32-grade three-term fp16 splits. A precision-16 handle runs the p16 kernel
+    // whatever this says. Not read by the cddpm_op_* operators.
+    int attn_family = 0;
     size_t weight_allocs_begin = 0;      // allocs[weight_allocs_begin ..) are what cddpm_load_weights uploaded
 
     std::vector<cddpm::ResW> res;

@@ -315,6 +315,27 @@ int cddpm_op_attention_backward_p16(cddpm_handle h, const float* qkv_dev, const 
     OP_EPILOGUE()
 }
 
+// the h3 backward: the row statistics, then one uint32 per sample for the largest magnitude of its dA
+static float* attention_backward_h3_scratch(OpScratch& sc, int B, int N, int C, unsigned*& amax) {
+    float* stats = attention_backward_scratch(sc, B, N, C);
+    amax = sc.n<unsigned>((size_t)B);
+    return stats;
+}
+size_t cddpm_op_attention_backward_h3_scratch(int B, int N, int C) {
+    return counted([&](OpScratch& sc) { unsigned* amax; attention_backward_h3_scratch(sc, B, N, C, amax); });
+}
+int cddpm_op_attention_backward_h3(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
+                                   void* stream) {
+    OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_backward_h3: C must be a multiple of 64")
+    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && da_dev && dqkv_dev, "cddpm_op_attention_backward_h3: NULL argument")
+    OpScratch sc(h, s);
+    unsigned* amax;
+    float* stats = attention_backward_h3_scratch(sc, B, N, C, amax);
+    SCRATCH_CHECK(sc)
+    launch_attention_backward_h3(qkv_dev, da_dev, dqkv_dev, stats, amax, B, N, C, s);
+    OP_EPILOGUE()
+}
+
 static float* linear_backward_scratch(OpScratch& sc, int M, int N, int K, int silu_in) {
     const size_t nscr = linear_backward_scratch_floats(M, N, K, silu_in);
     return nscr ? sc.n<float>(nscr) : nullptr;
@@ -768,6 +789,13 @@ int cddpm_op_attention_p16(cddpm_handle h, const float* qkv_dev, float* out_dev,
     OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_p16: C must be a multiple of 64")
     OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && out_dev, "cddpm_op_attention_p16: NULL argument")
     launch_attention_p16(qkv_dev, out_dev, B, N, C, s);
+    OP_EPILOGUE()
+}
+
+int cddpm_op_attention_h3(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream) {
+    OP_CHECK(!(C <= 0 || C % 64 || N < 1 || B < 1), "cddpm_op_attention_h3: C must be a multiple of 64")
+    OP_PROLOGUE(PC_ATTN, 0.0, 0.0, qkv_dev && out_dev, "cddpm_op_attention_h3: NULL argument")
+    launch_attention_h3(qkv_dev, out_dev, B, N, C, s);
     OP_EPILOGUE()
 }
 

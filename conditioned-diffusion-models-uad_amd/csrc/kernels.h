@@ -226,6 +226,10 @@ void launch_attention_backward_flash(const float* qkv, const float* da, float* d
 // the same contract and scratch with plain fp16 operands (q / 8, k, v, dA, and P / dS as MFMA operands) and fp32 accumulators on
 // v_mfma_f32_32x32x16_f16: cddpm_op_attention_backward_p16, the backward of launch_attention_p16
 void launch_attention_backward_p16(const float* qkv, const float* da, float* dqkv, float* stats, int B, int N, int C, hipStream_t stream);
+// the same contract at fp32 accuracy on v_mfma_f32_32x32x16_f16 (two-term fp16 splits, three products; dA normalised per sample by an
+// exact power of two): cddpm_op_attention_backward_h3, the backward of launch_attention_h3. amax = B uint32 of scratch more
+void launch_attention_backward_h3(const float* qkv, const float* da, float* dqkv, float* stats, unsigned* amax, int B, int N, int C,
+                                  hipStream_t stream);
 // backward of y = [SiLU](x) W^T + b: x [M][K], W [N][K], dy [M][N] -> dW [N][K], db [N] (or nullptr), dx [M][K] (or nullptr);
 // a_scratch [M][K] when silu_in
 size_t linear_backward_scratch_floats(int M, int N, int K, int silu_in);      // floats of a_scratch
@@ -271,6 +275,9 @@ void launch_attention(const float* qkv, float* out, int B, int N, int C, hipStre
 // the same contract with plain fp16 operands (q / 8, k, v and P rounded to fp16; fp32 accumulators, softmax and output) on
 // v_mfma_f32_32x32x16_f16: what a precision-16 handle runs (cddpm_set_precision) and cddpm_op_attention_p16
 void launch_attention_p16(const float* qkv, float* out, int B, int N, int C, hipStream_t stream);
+// the same contract at fp32 accuracy on the same instruction: q / 8, k, v and P as two-term fp16 splits, hi . hi + hi . lo + lo . hi,
+// fp32 accumulators, softmax and output. What a handle of attention family h3 runs (cddpm_set_attention_family) and cddpm_op_attention_h3
+void launch_attention_h3(const float* qkv, float* out, int B, int N, int C, hipStream_t stream);
 
 // residual-map post-processing (eval_post.hip; src/utils/utils_eval.py:29-33, :447-464)
 void launch_residual_mask(const float* orig, const float* recon, const float* mask, float* out, int S, int H, int W,

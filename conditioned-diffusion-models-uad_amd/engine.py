@@ -27,6 +27,24 @@ def conv_family_code(name: str) -> int:
     return CONV_FAMILIES[name]
 
 
+# attention families of a handle (cddpm_set_attention_family), in the same numbering: exact fp32 MFMA (what a handle starts with) or the
+# fp32-grade three-term fp16 split. There is no x6 attention: 'x6' is refused, not mapped.
+ATTENTION_FAMILIES = {"f32": 0, "h3": 2}
+
+
+def attention_family_code(name) -> int:
+    """'f32' / 'h3' -> the library's family number; anything else ('x6', None, 2) is a ValueError (no GPU needed)"""
+    if not isinstance(name, str) or name not in ATTENTION_FAMILIES:
+        raise ValueError(f"unknown attention family {name!r}: expected one of {', '.join(ATTENTION_FAMILIES)} (there is no x6 attention)")
+    return ATTENTION_FAMILIES[name]
+
+
+def _attention_symbol(stem: str, precision, family) -> str:
+    """the C ABI symbol of an attention operator: precision 16 selects the p16 kernels whatever the family, as on a handle"""
+    code = attention_family_code(family)
+    return stem + ("_p16" if precision_bits(precision) == 16 else "_h3" if code == 2 else "")
+
+
 # precision of a handle's reconstruction path (cddpm_set_precision): the spellings of Lightning's Trainer(precision=...) that mean
 # fp16 autocast or full precision. There is no bf16 reconstruction: 'bf16' is refused, not mapped.
 PRECISIONS = {16: 16, 32: 32, "16": 16, "16-mixed": 16, "32": 32}
@@ -99,10 +117,12 @@ class CddpmEngine:
     def __init__(self, *, model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3,
                  attention_resolutions=(3, 6, 12), head_channels=64, cond_dim=128, timesteps=1000,
                  max_batch=1, max_h=128, max_w=128, device=None, in_channels=1, out_channels=1, conv_family=None,
-                 precision=None):
+                 precision=None, attention_family=None):
         """conv_family: None (the process default: CDDPM_CONV, else h3), 'h3', 'x6' or 'f32' -- set on the handle before any
-        weights are loaded. precision: None (32), 32, 16, '32', '16' or '16-mixed' -- see set_precision; 16 needs the h3 family."""
+        weights are loaded. precision: None (32), 32, 16, '32', '16' or '16-mixed' -- see set_precision; 16 needs the h3 family.
+        attention_family: None ('f32'), 'f32' or 'h3' -- see set_attention_family."""
         family = None if conv_family is None else conv_family_code(conv_family)
+        attn_family = None if attention_family is None else attention_family_code(attention_family)
         bits = None if precision is None else precision_bits(precision)
         if bits == 16 and conv_family is not None and conv_family != "h3":
             raise ValueError(f"precision 16 needs the h3 convolution family, got conv_family={conv_family!r}")
@@ -138,6 +158,8 @@ class CddpmEngine:
             self._ck(self.lib.cddpm_set_conv_family(self._h, family), "cddpm_set_conv_family")
         if bits is not None:
             self._ck(self.lib.cddpm_set_precision(self._h, bits), "cddpm_set_precision")
+        if attn_family is not None:
+            self._ck(self.lib.cddpm_set_attention_family(self._h, attn_family), "cddpm_set_attention_family")
 
     # ------------------------------------------------------------------ lifetime / errors
     def close(self):
@@ -166,6 +188,18 @@ class CddpmEngine:
         """Change the handle's convolution family. Packed weights belong to a family: after a change to a DIFFERENT family the
         caller must call load_weights (and set_schedule) again -- until then every forward / reverse call raises."""
         self._ck(self.lib.cddpm_set_conv_family(self._h, conv_family_code(name)), "cddpm_set_conv_family")
+
+    @property
+    def attention_family(self) -> str:
+        code = self.lib.cddpm_get_attention_family(self._h)
+        return {v: k for k, v in ATTENTION_FAMILIES.items()}[code]
+
+    def set_attention_family(self, name: str):
+        """Arithmetic of the attention blocks of this engine's forward / reverse calls at precision 32 (cddpm_set_attention_family).
+        'f32': exact fp32 MFMA (the default). 'h3': fp32-grade products from two-term fp16 splits on the fp16 matrix pipe, with the
+        h3 range contract (|q / 8|, |k|, |v| < 65504, else a non-finite slice). At precision 16 the engine runs the fp16 kernel
+        whatever the family is. No weights are reloaded. Any other value raises ValueError before the library is called."""
+        self._ck(self.lib.cddpm_set_attention_family(self._h, attention_family_code(name)), "cddpm_set_attention_family")
 
     @property
     def precision(self) -> int:
@@ -847,10 +881,11 @@ class CddpmEngine:
                                               _stream_ptr(self.device)), "cddpm_op_conv_wgrad")
         return dw, db
 
-    def op_attention_backward(self, qkv, da, precision=32):
+    def op_attention_backward(self, qkv, da, precision=32, family="f32"):
         """dL/dqkv [B,N,3C] of the attention core for da = dL/d(output) [B,N,C]; precision 16: the fp16-MFMA kernels
-        (cddpm_op_attention_backward_p16, the backward of op_attention(..., precision=16)), whatever the engine's own"""
-        what = "cddpm_op_attention_backward_p16" if precision_bits(precision) == 16 else "cddpm_op_attention_backward"
+        (cddpm_op_attention_backward_p16, the backward of op_attention(..., precision=16)), whatever the engine's own and whatever
+        `family`; family 'h3' at precision 32: the fp32-grade split kernels (cddpm_op_attention_backward_h3)"""
+        what = _attention_symbol("cddpm_op_attention_backward", precision, family)
         fn = getattr(self.lib, what)
         B, N, C3 = qkv.shape
         dqkv = torch.empty_like(qkv)
@@ -895,9 +930,10 @@ class CddpmEngine:
                                            coef.data_ptr(), B, HW, _stream_ptr(self.device)), "cddpm_op_gn_coef")
         return coef
 
-    def op_attention(self, qkv, precision=32):
-        """the attention core on qkv [B,N,3C]; precision 16: the fp16-MFMA kernel (cddpm_op_attention_p16), whatever the engine's own"""
-        what = "cddpm_op_attention_p16" if precision_bits(precision) == 16 else "cddpm_op_attention"
+    def op_attention(self, qkv, precision=32, family="f32"):
+        """the attention core on qkv [B,N,3C]; precision 16: the fp16-MFMA kernel (cddpm_op_attention_p16), whatever the engine's own
+        and whatever `family`; family 'h3' at precision 32: the fp32-grade split kernel (cddpm_op_attention_h3)"""
+        what = _attention_symbol("cddpm_op_attention", precision, family)
         fn = getattr(self.lib, what)
         B, N, C3 = qkv.shape
         out = torch.empty((B, N, C3 // 3), dtype=torch.float32, device=self.device)

@@ -99,7 +99,8 @@ class HipMirror:
                                         channel_mult=tuple(unet.channel_mult), num_res_blocks=unet.num_res_blocks,
                                         cond_dim=unet.num_classes, device=device, dropout=float(unet.dropout or 0),       # cfg.dropout_unet
                                         attention_resolutions=tuple(unet.attention_resolutions),                         # cfg.att_res
-                                        attention_precision=_cfg_get(self.cfg, "train_attention_precision", 32))
+                                        attention_precision=_cfg_get(self.cfg, "train_attention_precision", 32),
+                                        attention_family=_cfg_get(self.cfg, "train_attention_family", "f32"))
             self._alias_unet()
             self._load_pending_optimizer_state()
         return self._hip_unet_trainer

@@ -20,8 +20,9 @@ skipped step, grown after `growth_interval` clean ones), with the scale kept on 
 and never stored (csrc/train_kernels.hip, synth.dropout_mask). `attention_resolutions` (the experiment's `att_res`) puts attention
 blocks inside the resolution levels as the reference's constructor does; they run on the middle block's operators. The attention cores
 are exact fp32 at either convolution precision unless the trainer is built with `attention_precision=16` (the mirrors'
-`cfg.train_attention_precision`): then forward and backward run the fp16-MFMA kernels, the arithmetic of autocast. Measured: DESIGN.md
-section 4b.
+`cfg.train_attention_precision`): then forward and backward run the fp16-MFMA kernels, the arithmetic of autocast. Where it is 32,
+`attention_family="h3"` (`cfg.train_attention_family`) runs forward and backward at fp32 accuracy on the fp16 matrix pipe instead
+(three-term fp16 splits, csrc/attention.hip). Measured: DESIGN.md section 4b.
 """
 from __future__ import annotations
 
@@ -35,7 +36,7 @@ from . import schedule as _schedule
 from . import synth as _synth
 from . import encoder_training as _encoder_training
 from ._lib import largest_calls, scratch_query
-from .engine import CddpmEngine, _stream_ptr, check_boxes, precision_bits
+from .engine import ATTENTION_FAMILIES, CddpmEngine, _stream_ptr, attention_family_code, check_boxes, precision_bits
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -158,12 +159,14 @@ def attention_scratch_bytes(program, B, H, W):
     return worst
 
 
-def operator_calls(program, B, H, W, emb_dim=2048, cond_dim=128):
+def operator_calls(program, B, H, W, emb_dim=2048, cond_dim=128, attention_family="f32"):
     """the operator calls of one training step (UNetTrainer.forward / backward over `program`) on a B x H x W batch that take
     temporaries from an arena, as (operator, arguments of its size query). Each call at the most it can take: a GroupNorm without
     kept statistics (swept), a weight gradient at training precision 32 (two fp16 planes per k-image; precision 16 writes one), the
-    embedding Linears batched and one by one."""
+    embedding Linears batched and one by one. attention_family 'h3': the attention backward is cddpm_op_attention_backward_h3, which
+    has a size query of its own (one uint32 per sample on top of the row statistics)."""
     C_ = program[1][2]["cin"]
+    attention_backward = "attention_backward_h3" if attention_family_code(attention_family) == 2 else "attention_backward"
 
     def gn(c, c1, h, w):                 # GroupNorm over cat[c - c1, c1] channels: the coefficient sweep, and the backward
         yield "gn_coef", (c - c1, int(c1 > 0), c1, B, h * w)
@@ -188,7 +191,7 @@ def operator_calls(program, B, H, W, emb_dim=2048, cond_dim=128):
             yield "chan_image_corr", (B, H, W, a["c"])
         elif kind == "attn":
             yield from gn(a["c"], 0, h, w)
-            yield "attention_backward", (B, h * w, a["c"])
+            yield attention_backward, (B, h * w, a["c"])
             yield from wg(3 * a["c"], a["c"], 0, 1, h, w)
             yield from wg(a["c"], a["c"], 0, 1, h, w)
         else:
@@ -204,16 +207,16 @@ def operator_calls(program, B, H, W, emb_dim=2048, cond_dim=128):
                 yield from wg(a["cout"], a["cin"] - c1, c1, 1, ho, wo)
 
 
-def operator_scratch_bytes(program, B, H, W, emb_dim=2048, cond_dim=128):
+def operator_scratch_bytes(program, B, H, W, emb_dim=2048, cond_dim=128, attention_family="f32"):
     """-> (main, side) of `program`'s training step on a B x H x W batch: largest_calls over operator_calls"""
-    return largest_calls(operator_calls(program, B, H, W, emb_dim, cond_dim))
+    return largest_calls(operator_calls(program, B, H, W, emb_dim, cond_dim, attention_family))
 
 
-def arena_bytes(program, B, H, W, emb_dim=2048, cond_dim=128):
+def arena_bytes(program, B, H, W, emb_dim=2048, cond_dim=128, attention_family="f32"):
     """-> (main, side): what UNetTrainer._fit gives cddpm_op_set_scratch on its two handles for a B x H x W batch -- the largest call of
     the UNet's step (`program` None: a trainer without a UNet's parameters) and of the context encoder's, which runs on the same handles
     whenever one is trained jointly (encoder_training.operator_scratch_bytes: a function of the geometry), and never below ARENA_FLOOR"""
-    unet = operator_scratch_bytes(program, B, H, W, emb_dim, cond_dim) if program else (0, 0)
+    unet = operator_scratch_bytes(program, B, H, W, emb_dim, cond_dim, attention_family) if program else (0, 0)
     enc = _encoder_training.operator_scratch_bytes(B, H, W, cond_dim)
     return max(ARENA_FLOOR, unet[0], enc[0]), max(ARENA_FLOOR, unet[1], enc[1])
 
@@ -228,12 +231,18 @@ class UNetTrainer:
 
     def __init__(self, params: Dict[str, torch.Tensor], *, model_channels=128, channel_mult=(1, 2, 2), num_res_blocks=3,
                  cond_dim=128, device=None, exp_refresh=50, overlap_wgrad=None, dropout=0.0, dropout_seed=None,
-                 attention_resolutions=(3, 6, 12), attention_precision=32):
+                 attention_resolutions=(3, 6, 12), attention_precision=32, attention_family="f32"):
         self.dev = torch.device(device) if device is not None else next(iter(params.values())).device
         # arithmetic of every attention core of the program, middle and in-level, forward and backward: 32 = the exact-fp32 kernels;
         # 16 (the spellings of engine.precision_bits) = cddpm_op_attention_p16 / cddpm_op_attention_backward_p16, what fp16 autocast
         # over QKVAttention computes. Per trainer, independent of the process-wide convolution precision (set_precision).
         self.attention_precision = precision_bits(attention_precision)
+        # ... and where that is 32, which of the two fp32-grade arithmetics: 'f32' = the exact-fp32 kernels, 'h3' = cddpm_op_attention_h3 /
+        # cddpm_op_attention_backward_h3 (three-term fp16 splits on the fp16 matrix pipe). attention_precision=16 wins over it.
+        self.attention_family = {v: k for k, v in ATTENTION_FAMILIES.items()}[attention_family_code(attention_family)]
+        self._attn_ops = ("cddpm_op_attention_p16", "cddpm_op_attention_backward_p16") if self.attention_precision == 16 else \
+                         ("cddpm_op_attention_h3", "cddpm_op_attention_backward_h3") if self.attention_family == "h3" else \
+                         ("cddpm_op_attention", "cddpm_op_attention_backward")
         self._cfg = dict(model_channels=model_channels, channel_mult=tuple(channel_mult), num_res_blocks=num_res_blocks, cond_dim=cond_dim)
         self.C, self.mult, self.nres, self.cond_dim = model_channels, tuple(channel_mult), num_res_blocks, cond_dim
         self.att_res = tuple(int(a) for a in attention_resolutions)      # the model's: attention behind the ResBlocks of the levels it names
@@ -320,7 +329,8 @@ class UNetTrainer:
                 torch.cuda.synchronize(self.dev)
                 e.close()
             self.eng = CddpmEngine(timesteps=2, max_batch=B, max_h=H, max_w=W, device=self.dev, **self._cfg)
-            main, side = arena_bytes(self.program if self._convs else None, B, H, W, 8 * self.C, self.cond_dim or 0)
+            main, side = arena_bytes(self.program if self._convs else None, B, H, W, 8 * self.C, self.cond_dim or 0,
+                                     "f32" if self.attention_precision == 16 else self.attention_family)
             rc = self.eng.lib.cddpm_op_set_scratch(self.eng._h, main)
             if rc != 0:
                 raise RuntimeError("cddpm_op_set_scratch failed: " + self.eng.lib.cddpm_last_error(self.eng._h).decode())
@@ -644,7 +654,7 @@ class UNetTrainer:
                 coefn = self.gn_coef(cur, None, name + ".norm")
                 qkv = self.conv(name + ".qkv", cur, None, coefn, False, stats=False)
                 att = self._new(Bc, h_, w_, Cc)
-                attn = self.lib.cddpm_op_attention_p16 if self.attention_precision == 16 else self.lib.cddpm_op_attention
+                attn = getattr(self.lib, self._attn_ops[0])
                 self._ck(attn(self.h, _p(qkv), _p(att), Bc, h_ * w_, Cc, self._s()), "op_attention")
                 out = self.conv(name + ".proj_out", att, res=cur)
                 sv[name] = dict(x=cur, coefn=coefn, qkv=qkv, att=att, rec=self.rec_of(cur))
@@ -700,7 +710,7 @@ class UNetTrainer:
                 da = self.dgrad(name + ".proj_out", d)
                 Bc, h_, w_, Cc = r["x"].shape
                 dqkv = torch.empty_like(r["qkv"])
-                attn_bwd = self.lib.cddpm_op_attention_backward_p16 if self.attention_precision == 16 else self.lib.cddpm_op_attention_backward
+                attn_bwd = getattr(self.lib, self._attn_ops[1])
                 self._ck(attn_bwd(self.h, _p(r["qkv"]), _p(da), _p(dqkv), Bc, h_ * w_, Cc, self._s()), "op_attention_backward")
                 self.wgrad(name + ".qkv", r["x"], None, r["coefn"], False, dqkv)
                 dn = self.dgrad(name + ".qkv", dqkv)

@@ -165,6 +165,18 @@ int cddpm_get_conv_family(cddpm_handle h);      /* the family, or -1 for a NULL 
 int cddpm_set_precision(cddpm_handle h, int bits);
 int cddpm_get_precision(cddpm_handle h);        /* 32 or 16, or -1 for a NULL handle */
 
+/* Attention family of a handle: the arithmetic of every attention block, middle and in-level, of cddpm_unet_forward / cddpm_p_sample /
+ * cddpm_reverse / cddpm_reverse_range / cddpm_ddim_step at precision 32, in the convolution families' numbering.
+ *   CDDPM_CONV_F32 (what a handle starts with, whatever CDDPM_CONV says): exact fp32 products, the kernel of cddpm_op_attention;
+ *   CDDPM_CONV_H3: fp32-grade products from two-term fp16 splits on the 16-bit matrix pipe, the kernel of cddpm_op_attention_h3, with
+ *                  its range contract (|q / 8|, |k|, |v| < 65504; outside it that slice is non-finite, which cddpm_slice_status finds);
+ *   CDDPM_CONV_X6: refused with "cddpm_set_attention_family: there is no x6 attention (...)"; any other value is an error too.
+ * Rule: a precision-16 handle runs the kernel of cddpm_op_attention_p16 WHATEVER its attention family is; the family is kept and takes
+ * effect when the handle returns to precision 32. Independent of the convolution family; nothing is repacked (the attention core has
+ * no weights); a change invalidates a captured step graph. The cddpm_op_* operators neither read nor change it. */
+int cddpm_set_attention_family(cddpm_handle h, int family);
+int cddpm_get_attention_family(cddpm_handle h);      /* the family, or -1 for a NULL handle */
+
 /* Per-slice status of x_dev [B,1,H,W] (16-byte aligned, H * W a multiple of 4): status_dev[b] (int32 [B]) = 1 if slice b holds an
  * inf or a NaN, else 0. One kernel launch for the whole batch on `stream`, no host synchronisation: the caller copies the B flags.
  * What a caller uses to find the slices of a reconstruction that left the fp16 range of an h3 handle and re-run only those on a
@@ -489,6 +501,21 @@ int cddpm_op_attention_backward(cddpm_handle h, const float* qkv_dev, const floa
  * offset is formed in 64 bits; N = 16384 (B 4, C 128) has been run and timed only. */
 int cddpm_op_attention_backward_p16(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
                                     void* stream);
+/* the same contract (arguments, errors, profiling class 2) at fp32 accuracy on v_mfma_f32_32x32x16_f16, the backward of
+ * cddpm_op_attention_h3 and in its arithmetic: all seven N x N x 64 products and the recomputed forward's two are three-term split
+ * products (hi . hi + hi . lo + lo . hi), fp32 accumulators; the running max / sum, P, D and dS = P (dP - D) are fp32 VALU work; P
+ * (lifted by 2^15) and dS (by 2^10) are split only as MFMA operands; dqkv is fp32.
+ * da is normalised per SAMPLE: a pass in front takes the largest |da| of each sample as an integer maximum of the magnitude bits (no
+ * float atomics: two calls give the same bits, and a sample's bits do not depend on its batch), the kernels work on da 2^-e with that
+ * maximum in [1, 2), and 2^e returns in the stores -- the result is the same function of da 2^k for every k, loss scales included.
+ * Scratch: cddpm_op_attention_backward_h3_scratch (the row statistics of cddpm_op_attention_backward_scratch and one uint32 per sample).
+ * Range: as cddpm_op_attention_h3 for q, k, v; a non-finite da makes ALL of that sample's dqkv NaN; the lifted dS must stay below
+ * 65504, i.e. |P (dP - D)| < 63 for the normalised da (|v| of order 1 gives at most ~10) -- beyond it that sample's dq and dk are
+ * non-finite. Never a finite wrong number, never another sample.
+ * Tested against float64 autograd under the rule of the exact operator (tests/test_gpu_attention_h3.py): its shapes and regimes,
+ * da scaled by 2^-30 ... 2^10, and N = 16384 (C 64) on a subset of rows. */
+int cddpm_op_attention_backward_h3(cddpm_handle h, const float* qkv_dev, const float* da_dev, float* dqkv_dev, int B, int N, int C,
+                                   void* stream);
 /* backward of torch.nn.Linear behind an optional SiLU, y = [SiLU](x) W^T + b (emb_layers / time_embed / label_emb,
  * OpenAI_Unet.py:201-207, :583-602): x_dev [M,K], w_dev [N,K], dy_dev [M,N] -> dw_dev [N,K], db_dev [N] (may be NULL), dx_dev [M,K]
  * (may be NULL). */
@@ -624,11 +651,13 @@ int cddpm_op_set_scratch(cddpm_handle h, size_t bytes);
  * staged through the arena: 256-byte-rounded C floats more for each). A shape the operator refuses gives 0.
  * cddpm_op_conv_wgrad_scratch: precision 16 | 32 = the process-wide training precision to plan for, 0 = the current one
  * (cddpm_get_train_precision); 32 takes the most, so an arena sized for it serves either. db_dev does not change the request.
- * cddpm_op_attention_backward_scratch serves cddpm_op_attention_backward and cddpm_op_attention_backward_p16. */
+ * cddpm_op_attention_backward_scratch serves cddpm_op_attention_backward and cddpm_op_attention_backward_p16;
+ * cddpm_op_attention_backward_h3 has a query of its own, cddpm_op_attention_backward_h3_scratch. */
 size_t cddpm_op_conv_wgrad_scratch(int C0, int C1, int upsample, int Cout, int ksize, int B, int H, int W, int precision);
 size_t cddpm_op_gn_coef_scratch(int C0, int has_src1, int C1, int B, int HW);
 size_t cddpm_op_gn_silu_backward_scratch(int has_rec, int B, int HW, int C);
 size_t cddpm_op_attention_backward_scratch(int B, int N, int C);
+size_t cddpm_op_attention_backward_h3_scratch(int B, int N, int C);
 size_t cddpm_op_linear_backward_scratch(int M, int N, int K, int silu_in);
 size_t cddpm_op_head_scratch(int B, int H, int W, int C);
 size_t cddpm_op_bias_grad_scratch(int64_t npix, int C);
@@ -805,6 +834,15 @@ int cddpm_op_attention(cddpm_handle h, const float* qkv_dev, float* out_dev, int
  * fp16 (RNE) once, products on v_mfma_f32_32x32x16_f16 with fp32 accumulators, the running max / sum softmax in fp32, P rounded to
  * fp16 only as an MFMA operand, fp32 output. The attention kernel of a precision-16 handle (cddpm_set_precision); any handle may call it. */
 int cddpm_op_attention_p16(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream);
+/* the same contract at fp32 accuracy on the fp16 matrix pipe (v_mfma_f32_32x32x16_f16), the attention member of the h3 family: q / 8,
+ * k and v are carried as hi = fp16(x), lo = fp16((x - hi) 2^11), P (against the running maximum, lifted by 2^15) as fp16(P),
+ * fp16(P - fp16(P)) and fp16(P 2^-11); each product is hi . hi + hi . lo + lo . hi with fp32 accumulation, lo . lo (2^-22) is dropped;
+ * the softmax is fp32 VALU work as in the other two kernels; input and output are fp32. 48 MFMAs of 32 cycles per wave and 64-key tile
+ * where cddpm_op_attention issues 128 of 64.
+ * Range contract, as for the h3 convolutions: it holds for |q / 8|, |k|, |v| < 65504. An element outside it (or non-finite) gives
+ * non-finite outputs for that sample only -- never a finite wrong number, never another sample.
+ * What a handle of attention family h3 runs (cddpm_set_attention_family); any handle may call it. */
+int cddpm_op_attention_h3(cddpm_handle h, const float* qkv_dev, float* out_dev, int B, int N, int C, void* stream);
 
 /* ---- context encoder ---------------------------------------------------------------
  * Replaces the module get_encoder builds (src/models/modules/DDPM_encoder.py:6-29): timm resnet50(in_chans=1,

@@ -1,8 +1,9 @@
 """Worst / median relative error of the training step's gradients against float64 autograd through the oracle, as JSON (one process per
 arithmetic: the families are chosen once per process from the environment, e.g. CDDPM_TRAIN_PRECISION=16).
-usage: python tools/train_grad_check.py [--attention-precision 16|32] [--gradient NAME] [--encoder-precision 16|32 --joint-steps N]
+usage: python tools/train_grad_check.py [--attention-precision 16|32] [--attention-family f32|h3] [--gradient NAME] [--encoder-precision 16|32 --joint-steps N]
                                         [B H W [DESCRIPTOR]]
 --attention-precision: UNetTrainer's attention_precision (16: the fp16-MFMA attention forward and backward; default 32).
+--attention-family: UNetTrainer's attention_family, read where the attention precision is 32 (h3: fp32-grade fp16 splits; default f32).
 --joint-steps N: instead of the gradient check, N joint optimisation steps (training_step(..., encoder=enc)) on one fixed batch with the
 context encoder built at --encoder-precision (EncoderTrainer's precision) and dynamic loss scaling on; reports each step's loss, which
 steps the guard skipped, skipped_steps and the final loss_scale.
@@ -28,6 +29,7 @@ import cddpm_oracle as oracle  # noqa: E402  (test infrastructure: this tool is 
 
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--attention-precision", default="32")
+_ap.add_argument("--attention-family", default="f32")
 _ap.add_argument("--gradient", default=None)
 _ap.add_argument("--encoder-precision", default="32")
 _ap.add_argument("--joint-steps", type=int, default=0)
@@ -46,7 +48,7 @@ if _a.joint_steps > 0:
     et = importlib.import_module(PKG + ".encoder_training")
     dev = torch.device("cuda", 0)
     trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in synth.synth_state_dict(0, **arch).items()}, device=dev,
-                             attention_precision=_a.attention_precision, **arch)
+                             attention_precision=_a.attention_precision, attention_family=_a.attention_family, **arch)
     trainer.enable_loss_scaling()
     enc = et.EncoderTrainer({k: torch.from_numpy(v) for k, v in synth.synth_encoder_state_dict(0).items()}, trainer, precision=encoder_precision)
     x01 = torch.from_numpy(synth.synth_slices(3, 0, B, H, W)).reshape(B, 1, H, W).to(dev)
@@ -72,7 +74,7 @@ x0 = x01 * 2 - 1
 ref_out = oracle.unet_forward(oracle.q_sample(x0.double(), t, noise.double(), buf64), t, cond.double() if cond_dim else None, sd, **arch)
 dev = torch.device("cuda", 0)
 trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd_np.items()}, device=dev, cond_dim=cond_dim or None,
-                         attention_precision=_a.attention_precision, **arch)
+                         attention_precision=_a.attention_precision, attention_family=_a.attention_family, **arch)
 buf = sched.schedule_buffers(T)
 xt = buf["sqrt_alphas_cumprod"][t].reshape(-1, 1, 1, 1) * x0 + buf["sqrt_one_minus_alphas_cumprod"][t].reshape(-1, 1, 1, 1) * noise
 out = trainer.forward(xt.to(dev), t.to(dev), cond.to(dev) if cond_dim else None)
@@ -87,6 +89,7 @@ for k, v in sd.items():
     errs.append(float((g - v.grad).abs().max() / (v.grad.abs().max() + 1e-30)))
 res = {"forward_max_abs_err": float((out.double().cpu() - ref_out.detach()).abs().max()), "worst": max(errs), "median": float(np.median(errs)),
        "finite": bool(np.isfinite(errs).all()), "n": len(errs), "attention_precision": trainer.attention_precision,
+       "attention_family": trainer.attention_family,
        "encoder_precision": encoder_precision}
 if _a.gradient:
     res["gradient_sha256"] = hashlib.sha256(grads[_a.gradient].detach().cpu().contiguous().numpy().tobytes()).hexdigest()

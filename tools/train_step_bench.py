@@ -1,12 +1,15 @@
 """Times the training step (training.py: forward + loss + backward + Adam, all on the HIP operators) on one GPU.
     python tools/train_step_bench.py [--batch 16] [--size 128] [--steps 5] [--warmup 2]
     python tools/train_step_bench.py --gpus N            (starts the N ranks itself: the line below as a child process)
+    python tools/train_step_bench.py --attention-resolutions 1,2,4 --attention-family f32 h3 [--out profiles/attention_h3_bench.json]
+                                                         (one trainer per family in ONE process, their steps interleaved; one GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/train_step_bench.py   (data-parallel, RCCL)
 BASELINE config 5 is 128x1x128x128 over 8 GPUs data-parallel = 16 slices per GPU and step (weak scaling: --batch is per rank)."""
 import argparse
 import importlib
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -28,6 +31,10 @@ def main():
                          "experiment's 3,6,12 = attention in the middle block only")
     ap.add_argument("--attention-precision", default="32",
                     help="UNetTrainer's attention_precision: 16 = the fp16-MFMA attention forward and backward, 32 (default) = exact fp32")
+    ap.add_argument("--attention-family", nargs="+", default=["f32"], metavar="FAMILY",
+                    help="UNetTrainer's attention_family where the attention precision is 32: f32 (default) = exact fp32, h3 = fp32-grade fp16 "
+                         "splits. Several families: one trainer each, timed step by step in alternation (median, min, max per family)")
+    ap.add_argument("--out", default=None, help="with several families: merge the result into this JSON file under the key 'train_step'")
     ap.add_argument("--encoder-precision", default="32",
                     help="EncoderTrainer's precision (with --encoder): 16 = its convolutions on fp16 operands (fp16-MFMA kernels), 32 (default) = "
                          "fp32 FMA kernels")
@@ -50,8 +57,11 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
     arch = {} if a.attention_resolutions is None else {"attention_resolutions": tuple(int(v) for v in a.attention_resolutions.split(","))}
     sd = synth.synth_state_dict(0, **arch)
+    if len(a.attention_family) > 1:
+        assert not ddp and not a.encoder and not a.phases, "several attention families: one GPU, the UNet's step only"
+        return compare_families(a, tr, synth, torch, dev, sd, arch)
     trainer = tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd.items()}, device=dev, dropout=a.dropout, dropout_seed=1,
-                             attention_precision=a.attention_precision, **arch)
+                             attention_precision=a.attention_precision, attention_family=a.attention_family[0], **arch)
     enc = None
     if a.encoder:
         et = importlib.import_module(PKG + ".encoder_training")
@@ -82,7 +92,7 @@ def main():
     arith = "fp32-emulated convolutions" if bits == 32 else "fp16-operand convolutions (precision 16)"
     res = {"workload": f"training step {B}x1x{S}x{S} (noise-pred MSE, {arith}, Adam" + (", context encoder trained jointly)" if enc else ")"), "ms_per_step": dt * 1e3,
            "precision": bits, "dropout": a.dropout, "attention_resolutions": list(trainer.att_res), "attention_precision": trainer.attention_precision,
-           "encoder_precision": enc.precision if enc else None,
+           "attention_family": trainer.attention_family, "encoder_precision": enc.precision if enc else None,
            "slices_per_s": world * B / dt, "n_gpus": world, "losses": losses, "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
     if a.phases:
         buf = importlib.import_module(PKG + ".schedule").schedule_buffers(T)
@@ -105,6 +115,46 @@ def main():
     if ddp:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def compare_families(a, tr, synth, torch, dev, sd, arch):
+    """one trainer per attention family on the same weights and batch; after the warm-up, a.steps rounds of one step per family in
+    alternation, each step timed on its own between two device synchronisations"""
+    B, S, T = a.batch, a.size, 1000
+    x01 = torch.from_numpy(synth.synth_slices(1, 0, B, S, S)).reshape(B, 1, S, S).to(dev)
+    cond = torch.from_numpy(synth.synth_cond(1, 0, B)).to(dev)
+    noise = torch.from_numpy(synth.noise_xT(1, 0, B, S, S)).reshape(B, 1, S, S).to(dev)
+    t = torch.tensor([(137 * (i + 1)) % T for i in range(B)], dtype=torch.long, device=dev)
+    trainers = {f: tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd.items()}, device=dev, dropout=a.dropout, dropout_seed=1,
+                                  attention_precision=a.attention_precision, attention_family=f, **arch) for f in a.attention_family}
+    step = lambda trainer: float(tr.training_step(trainer, x01, cond, t=t, noise=noise, objective="pred_noise", loss_type="l2"))
+    ms, losses = {f: [] for f in trainers}, {f: [] for f in trainers}
+    for i in range(a.warmup + a.steps):
+        for f, trainer in trainers.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss = step(trainer)
+            torch.cuda.synchronize()
+            if i >= a.warmup:
+                ms[f].append((time.perf_counter() - t0) * 1e3)
+            losses[f].append(loss)
+    res = {"workload": f"training step {B}x1x{S}x{S} (noise-pred MSE, Adam), one trainer per attention family, steps interleaved",
+           "precision": tr.get_precision(), "attention_resolutions": list(next(iter(trainers.values())).att_res),
+           "attention_precision": next(iter(trainers.values())).attention_precision, "timer": "host clock between device synchronisations",
+           "ms_per_step": {f: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v), samples=len(v)) for f, v in ms.items()},
+           "losses": losses, "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
+    print(json.dumps(res))
+    if a.out:
+        doc = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                doc = json.load(f)
+        doc["train_step"] = res
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+    for trainer in trainers.values():
+        trainer.close()
 
 
 if __name__ == "__main__":
