@@ -32,8 +32,6 @@ import math
 import torch
 import torch.nn as nn
 
-import warnings
-
 from .mirror_common import AttrDict, HipMirror, _Base, _cfg_get, _to_cpu
 from .synth import SPARK_ENC_PREFIX, spark_param_shapes
 
@@ -118,6 +116,7 @@ class _Tree(nn.Module):
 
 
 class Spark_2D(_Base):
+    SCALER_CHECK_EVERY, SCALER_STALL_SKIPS = HipMirror.SCALER_CHECK_EVERY, HipMirror.SCALER_STALL_SKIPS      # of HipMirror._watch_loss_scale
 
     def __init__(self, cfg, prefix=None):
         super().__init__()
@@ -258,30 +257,8 @@ class Spark_2D(_Base):
         self._param_versions = tuple(p._version for p in self.model.parameters())
         self._log(f"{self.prefix}train/Loss_comb", loss, input.shape[0])
         if tr_.loss_scaling:
-            self._watch_loss_scale(tr_)
+            HipMirror._watch_loss_scale(self, tr_, record=self.logged)
         return {"loss": loss}
-
-    def _watch_loss_scale(self, tr_):
-        """HipMirror._watch_loss_scale for this trainer: the loss scale and the skipped steps are logged from device tensors (no read-back);
-        every SCALER_CHECK_EVERY steps the consecutive skips are read once, and SCALER_STALL_SKIPS of them in a row -- gradients that are
-        non-finite at any scale -- give one RuntimeWarning"""
-        for name, value in (("train/loss_scale", tr_.scaler[:1].view(torch.float32)[0].clone()), ("train/skipped_steps", tr_.ctrl[3].float())):
-            self.logged[name] = value
-            if hasattr(self, "log") and _Base is not nn.Module:
-                try:
-                    self.log(f"{self.prefix}{name}", value, on_step=True, on_epoch=False)
-                except Exception:
-                    pass
-        self._scaler_steps = getattr(self, "_scaler_steps", 0) + 1
-        if self._scaler_steps % HipMirror.SCALER_CHECK_EVERY:
-            return
-        skips = tr_.consecutive_skips
-        if skips < HipMirror.SCALER_STALL_SKIPS:
-            self._scaler_warned = False
-        elif not getattr(self, "_scaler_warned", False):
-            self._scaler_warned = True
-            warnings.warn(f"{skips} training steps in a row were skipped for non-finite gradients (loss scale now {tr_.loss_scale:g}): "
-                          "the gradients are not finite at any scale -- a NaN / inf input or a diverged run?", RuntimeWarning, stacklevel=2)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx: int):

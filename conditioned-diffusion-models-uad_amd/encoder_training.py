@@ -21,6 +21,7 @@ from typing import Dict, Optional
 
 import torch
 
+from . import optimizer as _optimizer
 from ._lib import largest_calls
 from .engine import _stream_ptr, precision_bits
 
@@ -90,28 +91,21 @@ def operator_scratch_bytes(B, H, W, cond_dim=128):
     return largest_calls(operator_calls(B, H, W, cond_dim))
 
 
-class EncoderTrainer:
+class EncoderTrainer(_optimizer.FlatOptimizer):
     """params: timm state_dict of the ResNet-50 (names conv1.weight, bn1.*, layerS.I.convJ.weight, layerS.I.bnJ.*, layerS.0.downsample.*,
     fc.*; running_mean / running_var included). `ops`: an object with `.lib`, `.h`, `.dev` (a training.UNetTrainer: the operators run on
     its handles and scratch arenas, which it sizes for the encoder's calls as well as its own: operator_scratch_bytes).
     precision: 32 (default) = fp32 FMA convolutions; 16 (the spellings of engine.precision_bits) = fp16 operands, fp32 accumulation."""
 
+    LAYOUT_ERROR = "encoder optimizer state was saved for another parameter layout"
+
     def __init__(self, params: Dict[str, torch.Tensor], ops, drop_path_rate: float = 0.0, *, precision=32):
         self.precision = precision_bits(precision)            # parsed before a device is touched: a bad value is a ValueError here
-        self.ops, self.dev = ops, ops.dev
+        self.ops = ops
+        # whose control block and loss scaler a guarded adam_step runs under: the trainer the encoder is trained jointly with
+        self.optimizer = ops
         train_names = [k for k in params if not (k.endswith("running_mean") or k.endswith("running_var") or k.endswith("num_batches_tracked"))]
-        sizes = [(int(params[k].numel()) + 63) // 64 * 64 for k in train_names]
-        self.flat = torch.zeros(sum(sizes), dtype=torch.float32, device=self.dev)
-        self.gflat = torch.zeros_like(self.flat)
-        self.p: Dict[str, torch.Tensor] = {}
-        self.g: Dict[str, torch.Tensor] = {}
-        off = 0
-        for k, n in zip(train_names, sizes):
-            v = params[k]
-            self.p[k] = self.flat[off:off + v.numel()].view(v.shape)
-            self.g[k] = self.gflat[off:off + v.numel()].view(v.shape)
-            self.p[k].copy_(v.detach().to(self.dev, torch.float32))
-            off += n
+        super().__init__(params, train_names, ops.dev)      # flat, gflat, p, g, state, and a control block for a step of its own
         self.buf = {k: params[k].detach().to(self.dev, torch.float32).clone() for k in params
                     if k.endswith("running_mean") or k.endswith("running_var")}
         self.blocks = []
@@ -134,7 +128,6 @@ class EncoderTrainer:
         img = torch.float16 if self.precision == 16 else torch.float32
         self.wf = {k: torch.empty(co * ci * kk * kk, dtype=img, device=self.dev) for k, (co, ci, kk, _s) in self.convs.items()}
         self.wd = {k: torch.empty(co * ci * kk * kk, dtype=img, device=self.dev) for k, (co, ci, kk, _s) in self.convs.items()}
-        self.state: Dict[str, object] = {}
         self.repack()
 
     # ------------------------------------------------------------------ plumbing
@@ -463,47 +456,29 @@ class EncoderTrainer:
         return g
 
     def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=None, guarded=False, extra_unscale=None):
-        """Adam over the flat buffer under the guard of the handle's trainer (`ops`: training.UNetTrainer): the encoder and the UNet are ONE
-        optimizer in the reference (`optim.Adam(self.parameters())`, DDPM_2D.py:305-306), so the step count and the skip decision are the
-        UNet trainer's control block. guarded: `ops.guard(others=(self,))` was called for this step; else the encoder is stepped alone.
-        grad_scale None: 1, or -- guarded, with the trainer's dynamic loss scaling on -- its device scale, the loss scale too is shared
-        (gradient = gflat * extra_unscale (default 1) / scale; the trainer updates the scale after this)."""
-        st = self.state
-        if "m" not in st:
-            st["m"], st["v"] = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        """Adam over the flat buffer under the guard of the trainer it is trained with (`optimizer`: training.UNetTrainer): the encoder and
+        the UNet are ONE optimizer in the reference (`optim.Adam(self.parameters())`, DDPM_2D.py:305-306), so the step count and the skip
+        decision are that trainer's control block. guarded: its `guard(others=(self,))` was called for this step; else the encoder is
+        stepped alone, under its own control block. grad_scale None: 1, or -- guarded, with the trainer's dynamic loss scaling on -- its
+        device scale, the loss scale too is shared (gradient = gflat * extra_unscale (default 1) / scale; the trainer updates the scale
+        after this)."""
         if not guarded:
-            if getattr(self, "ctrl", None) is None:
-                self.ctrl = torch.zeros(8, dtype=torch.int32, device=self.dev)
-            self._ck(self.lib.cddpm_op_grad_check(self.h, _p(self.gflat), self.gflat.numel(), _p(self.ctrl), self._s()), "op_grad_check")
-            self._ck(self.lib.cddpm_op_guard_commit(self.h, _p(self.ctrl), C.c_float(betas[0]), C.c_float(betas[1]), self._s()), "op_guard_commit")
-            ctrl = self.ctrl
+            _optimizer.guard(self, (self,), betas)
+        opt = self.optimizer if guarded else self
+        scaler = opt.step_scaler(grad_scale)
+        if scaler is not None:
+            _optimizer.update(opt, self, lr, betas, eps, unscale=1.0 if extra_unscale is None else extra_unscale, scaler=scaler)
         else:
-            ctrl = self.ops._ctrl()
-        if guarded and grad_scale is None and getattr(self.ops, "loss_scaling", False):
-            if self.ops.scaler is None:
-                raise RuntimeError("adam_step with dynamic loss scaling: no loss was formed yet (loss_and_grad)")
-            self._ck(self.lib.cddpm_op_adam_scaled(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
-                                                   C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps),
-                                                   C.c_float(1.0 if extra_unscale is None else extra_unscale), _p(ctrl), _p(self.ops.scaler),
-                                                   self._s()), "op_adam_scaled")
-        else:
-            unscale = 1.0 / (grad_scale if grad_scale is not None else 1.0)
-            self._ck(self.lib.cddpm_op_adam_guarded(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
-                                                    C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(unscale),
-                                                    _p(ctrl), self._s()), "op_adam_guarded")
+            _optimizer.update(opt, self, lr, betas, eps, unscale=1.0 / (grad_scale if grad_scale is not None else 1.0))
         self.repack()
 
     def optimizer_state(self) -> Dict[str, torch.Tensor]:
-        st = self.state
-        if "m" not in st:
-            st["m"], st["v"] = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        return {"m": st["m"].detach().clone(), "v": st["v"].detach().clone(), "layout": [(k, int(v.numel())) for k, v in self.p.items()]}
+        m, v = _optimizer.moments(self)
+        return {"m": m.detach().clone(), "v": v.detach().clone(), "layout": self.layout()}
 
     def load_optimizer_state(self, state) -> None:
-        if [tuple(x) for x in state["layout"]] != [(k, int(v.numel())) for k, v in self.p.items()]:
-            raise ValueError("encoder optimizer state was saved for another parameter layout")
-        self.state["m"] = state["m"].to(self.dev, torch.float32).clone()
-        self.state["v"] = state["v"].to(self.dev, torch.float32).clone()
+        self.check_layout(state["layout"])
+        self.load_moments(state["m"], state["v"])
 
     def parameters_changed(self) -> None:
         """parameters were written from outside (load_state_dict into the aliased module): rebuild the operators' weight images"""

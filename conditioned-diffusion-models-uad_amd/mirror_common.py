@@ -175,16 +175,25 @@ class HipMirror:
         if seed is not None or not trainer.loss_scaling:
             trainer.enable_loss_scaling(**(seed or {}))
 
-    def _watch_loss_scale(self, trainer):
-        """logs the loss scale and the skipped steps (device tensors: no read-back here) and, every SCALER_CHECK_EVERY steps, reads the
-        consecutive skips once: SCALER_STALL_SKIPS of them in a row mean the gradients are non-finite whatever the scale (a NaN input, a
-        diverged run) -- one RuntimeWarning instead of a run that silently stops learning"""
-        if hasattr(self, "log") and _Base is not nn.Module:
+    def _watch_loss_scale(self, trainer, record=None):
+        """logs the loss scale and the skipped steps (device tensors: no read-back here; `record`: a dict that takes the two values as
+        well, whether or not there is a logger) and, every SCALER_CHECK_EVERY steps, reads the consecutive skips once:
+        SCALER_STALL_SKIPS of them in a row mean the gradients are non-finite whatever the scale (a NaN input, a diverged run) -- one
+        RuntimeWarning instead of a run that silently stops learning. Spark_2D, no HipMirror itself, calls it too (with `record`)."""
+        log = self.log if hasattr(self, "log") and _Base is not nn.Module else None
+        if log is not None or record is not None:
             try:
-                self.log(f"{self.prefix}train/loss_scale", trainer.scaler[:1].view(torch.float32)[0].clone(), on_step=True, on_epoch=False)
-                self.log(f"{self.prefix}train/skipped_steps", trainer._ctrl()[3].float(), on_step=True, on_epoch=False)
-            except Exception:
-                pass
+                values = {"train/loss_scale": trainer.loss_scale_tensor().clone(), "train/skipped_steps": trainer.ctrl[3].float()}
+            except (AttributeError, TypeError):         # a trainer without the device blocks: nothing to log
+                values = {}
+            for name, value in values.items():
+                if record is not None:
+                    record[name] = value
+                if log is not None:
+                    try:
+                        log(f"{self.prefix}{name}", value, on_step=True, on_epoch=False)
+                    except Exception:
+                        pass
         self._scaler_steps = getattr(self, "_scaler_steps", 0) + 1
         if self._scaler_steps % self.SCALER_CHECK_EVERY:
             return

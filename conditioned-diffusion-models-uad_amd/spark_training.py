@@ -28,13 +28,13 @@ from typing import Dict, Optional
 
 import torch
 
+from . import optimizer as _optimizer
 from ._lib import largest_calls
 from .encoder_training import BN_EPS, BN_MOMENTUM, EncoderTrainer, pyramid_operator_calls, _p
 from .engine import _stream_ptr, precision_bits
 
 ENC_PREFIX = "sparse_encoder.sp_cnn."
 ENC_DIMS = (2048, 1024, 512, 256)            # channels of the maps densify reads, smallest map first
-DEFAULT_INIT_SCALE = 65536.0                 # torch.cuda.amp.GradScaler()'s init_scale: where the reference's Trainer starts
 
 
 def decoder_layers(dec_dim=128):
@@ -80,7 +80,7 @@ def arena_bytes(B, H, W, dec_dim=128, precision=32):
     return largest_calls(operator_calls(B, H, W, dec_dim, precision))[0]
 
 
-class SparKTrainer:
+class SparKTrainer(_optimizer.FlatOptimizer):
     """params: the reference's state dict of SparK_2D without the `model.` prefix (sparse_encoder.sp_cnn.*, en_de_norms.*, en_de_lins.*,
     mask_tokens.*, dense_decoder.*; running statistics included, num_batches_tracked and the image-norm buffers ignored).
     loss_weights (w_mask, w_l1): loss = w_mask * masked L2 + w_l1 * mean |reco - x| -- (1, 0) is `loss_on_mask: True`, (delta_mask, 1) the
@@ -88,6 +88,12 @@ class SparKTrainer:
     precision: 32 (default) | 16, the spellings of engine.precision_bits ("bf16" and anything else: ValueError) -- the arithmetic of the
     sparse ResNet-50's convolutions (module docstring). 16 turns dynamic loss scaling on (enable_loss_scaling's defaults) and needs a
     GPU device: with any other it is a ValueError, raised like a bad precision before a device is touched."""
+
+    # torch.cuda.amp.GradScaler()'s own init_scale and so the reference Trainer's start (DESIGN.md section 4b-g, measured inside the
+    # stages: at most 0.001 % of the dz operands stay below fp16's smallest normal, the largest is 1.3e4 at 3x96x96 and falls with the
+    # batch; a batch that overflows there backs off in its first steps). A default start: enable_loss_scaling makes the block at once.
+    DEFAULT_INIT_SCALE = 65536.0
+    LAYOUT_ERROR = "SparK optimizer state was saved for another parameter layout"
 
     def __init__(self, params: Dict[str, torch.Tensor], device=None, *, dec_dim=128, drop_path_rate=0.05, loss_weights=(1.0, 0.0), precision=32):
         self.precision = precision_bits(precision)            # parsed before a device is touched: a bad value is a ValueError here
@@ -105,75 +111,20 @@ class SparKTrainer:
         self.ops = UNetTrainer({"w": torch.zeros(64)}, device=self.dev, overlap_wgrad=False)
         self.enc = EncoderTrainer({k[len(ENC_PREFIX):]: v for k, v in params.items() if k.startswith(ENC_PREFIX)}, self.ops, drop_path_rate,
                                   precision=self.precision)
+        self.enc.optimizer = self           # one AdamW over both buffers: this trainer's control block and scaler
         skip = ("num_batches_tracked", "running_mean", "running_var")
         own = {k: v for k, v in params.items() if not k.startswith(ENC_PREFIX) and k.split(".")[0] in ("en_de_norms", "en_de_lins", "mask_tokens", "dense_decoder")}
-        names = [k for k in own if not k.endswith(skip)]
-        sizes = [(int(own[k].numel()) + 63) // 64 * 64 for k in names]
-        self.flat = torch.zeros(sum(sizes), dtype=torch.float32, device=self.dev)
-        self.gflat = torch.zeros_like(self.flat)
-        self.p: Dict[str, torch.Tensor] = {}
-        self.g: Dict[str, torch.Tensor] = {}
-        off = 0
-        for k, n in zip(names, sizes):
-            v = own[k]
-            self.p[k] = self.flat[off:off + v.numel()].view(v.shape)
-            self.g[k] = self.gflat[off:off + v.numel()].view(v.shape)
-            self.p[k].copy_(v.detach().to(self.dev, torch.float32))
-            off += n
+        super().__init__(own, [k for k in own if not k.endswith(skip)], self.dev)      # flat, gflat, p, g, state, ctrl, the loss scaler (off)
         self.buf = {k: own[k].detach().to(self.dev, torch.float32).clone() for k in own if k.endswith(("running_mean", "running_var"))}
         want = {n + ".weight" for n, *_ in decoder_layers(self.dec_dim)} | {f"mask_tokens.{i}" for i in range(4)}
         missing = sorted(want - set(self.p))
         if missing:
             raise ValueError(f"SparKTrainer: the state dict lacks {', '.join(missing[:4])}{' ...' if len(missing) > 4 else ''}")
         self.layers = {n: (kind, ci, co, k) for n, kind, ci, co, k in decoder_layers(self.dec_dim)}
-        self.state: Dict[str, object] = {}
-        self.ctrl = torch.zeros(8, dtype=torch.int32, device=self.dev)
         self._arena = (0, 0, 0)
         self.saved = None
-        self.loss_scaling = False           # dynamic loss scaling (enable_loss_scaling): on by default at precision 16, available at 32
-        self.scaler: Optional[torch.Tensor] = None
-        if self.precision == 16:
+        if self.precision == 16:            # dynamic loss scaling: on by default at precision 16, available at 32
             self.enable_loss_scaling()
-
-    # ------------------------------------------------------------------ dynamic loss scaling (torch's GradScaler, the scale on the device)
-    def enable_loss_scaling(self, init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, growth_tracker=0):
-        """UNetTrainer.enable_loss_scaling for this step: torch.cuda.amp.GradScaler's rule on the device block of include/cddpm.h ("Dynamic
-        loss scaling") -- a skipped step multiplies the scale by backoff_factor, growth_interval clean steps in a row by growth_factor.
-        init_scale None: 65536, GradScaler's own start and so the reference Trainer's (measured inside the
-        stages: at most 0.001 % of the dz operands stay below fp16's smallest normal, the largest is 1.3e4 at 3x96x96 and falls with the
-        batch; a batch that overflows there backs off in its first steps). Scale and factors must be powers of two (ValueError
-        otherwise): the unscale is then exact. Starts a fresh scaler state at once; no step reads the scale back."""
-        from .training import _scaler_block, loss_scaling_settings
-        cfg = loss_scaling_settings(DEFAULT_INIT_SCALE if init_scale is None else init_scale, growth_factor, backoff_factor, growth_interval,
-                                    growth_tracker)
-        self.scaler_init = cfg["init_scale"]
-        self.scaler_cfg = (cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"])
-        self.scaler_tracker0 = cfg["growth_tracker"]
-        self.scaler = _scaler_block(self.scaler_init, self.scaler_tracker0, 0, self.dev)
-        self.loss_scaling = True
-
-    def disable_loss_scaling(self):
-        """back to unscaled gradients and the plain guarded update (what precision 32 runs by default). At precision 16 this trains the
-        encoder on flushed gradients unless the loss weights carry a scale themselves."""
-        self.loss_scaling, self.scaler = False, None
-
-    def _scaler_read(self, i):
-        return self.scaler[:1].view(torch.float32).item() if i == 0 else int(self.scaler[i].item())
-
-    @property
-    def loss_scale(self) -> Optional[float]:
-        """the scale the next loss gradient is formed with (reads the device block: synchronises); None with loss scaling off"""
-        return self._scaler_read(0) if self.loss_scaling else None
-
-    @property
-    def growth_tracker(self) -> int:
-        """clean steps since the scale last changed (reads the device counter)"""
-        return self._scaler_read(1) if self.loss_scaling else 0
-
-    @property
-    def consecutive_skips(self) -> int:
-        """skipped steps in a row up to now (reads the device counter)"""
-        return self._scaler_read(2) if self.loss_scaling else 0
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -338,68 +289,37 @@ class SparKTrainer:
         decays nothing and does not count. With dynamic loss scaling on, the order of include/cddpm.h: the checks, one commit,
         cddpm_op_adamw_scaled on both buffers (the gradient buffers hold scale x the gradient; the scale of this step's loss is divided
         out on the device), one cddpm_op_scaler_update."""
-        lib, ctrl = self.lib, self.ctrl
-        bufs = (self, self.enc)
-        for t in bufs:
-            if "m" not in t.state:
-                t.state["m"], t.state["v"] = torch.zeros_like(t.flat), torch.zeros_like(t.flat)
-            self._ck(lib.cddpm_op_grad_check(self.h, _p(t.gflat), t.gflat.numel(), _p(ctrl), self._s()), "op_grad_check")
-        self._ck(lib.cddpm_op_guard_commit(self.h, _p(ctrl), C.c_float(betas[0]), C.c_float(betas[1]), self._s()), "op_guard_commit")
-        for t in bufs:
-            if self.loss_scaling:
-                self._ck(lib.cddpm_op_adamw_scaled(self.h, _p(t.flat), _p(t.gflat), _p(t.state["m"]), _p(t.state["v"]), t.flat.numel(), C.c_float(lr),
-                                                   C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(weight_decay), C.c_float(1.0),
-                                                   _p(ctrl), _p(self.scaler), self._s()), "op_adamw_scaled")
-            else:
-                self._ck(lib.cddpm_op_adamw_guarded(self.h, _p(t.flat), _p(t.gflat), _p(t.state["m"]), _p(t.state["v"]), t.flat.numel(), C.c_float(lr),
-                                                    C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(weight_decay), C.c_float(1.0),
-                                                    _p(ctrl), self._s()), "op_adamw_guarded")
-        if self.loss_scaling:
-            g, b, n = self.scaler_cfg
-            self._ck(lib.cddpm_op_scaler_update(self.h, _p(ctrl), _p(self.scaler), C.c_float(g), C.c_float(b), n, self._s()), "op_scaler_update")
+        owners = (self, self.enc)
+        _optimizer.guard(self, owners, betas)
+        scaler = self.step_scaler()
+        for t in owners:
+            _optimizer.update(self, t, lr, betas, eps, weight_decay=weight_decay, scaler=scaler)
+        if scaler is not None:
+            self.update_loss_scale()
         self.enc.repack()
 
-    @property
-    def step_count(self) -> int:
-        return int(self.ctrl[1].item())
-
-    @property
-    def skipped_steps(self) -> int:
-        return int(self.ctrl[3].item())
-
-    def _layout(self):
-        return [("enc:" + k, int(v.numel())) for k, v in self.enc.p.items()] + [(k, int(v.numel())) for k, v in self.p.items()]
+    def layout(self):
+        """of both buffers, the encoder's first under an "enc:" prefix: the order of optimizer_state's m and v"""
+        return [("enc:" + k, n) for k, n in self.enc.layout()] + super().layout()
 
     def optimizer_state(self) -> Dict[str, object]:
         """Adam's moments of both buffers (encoder first) with the layout they belong to and the step count: what mirror_common checkpoints"""
-        for t in (self, self.enc):
-            if "m" not in t.state:
-                t.state["m"], t.state["v"] = torch.zeros_like(t.flat), torch.zeros_like(t.flat)
-        out = {"m": torch.cat([self.enc.state["m"], self.state["m"]]).detach().clone(),
-               "v": torch.cat([self.enc.state["v"], self.state["v"]]).detach().clone(), "layout": self._layout(),
+        (em, ev), (m, v) = _optimizer.moments(self.enc), _optimizer.moments(self)
+        out = {"m": torch.cat([em, m]).detach().clone(), "v": torch.cat([ev, v]).detach().clone(), "layout": self.layout(),
                "step": self.step_count, "skipped": self.skipped_steps}
-        if self.loss_scaling:               # UNetTrainer.optimizer_state's layout: the settings and the device block
-            g, b, n = self.scaler_cfg
-            out["scaler"] = {"init_scale": self.scaler_init, "growth_factor": g, "backoff_factor": b, "growth_interval": n,
-                             "growth_tracker": self.scaler_tracker0, "state": self.scaler.detach().clone()}
+        if self.loss_scaling:               # UNetTrainer.optimizer_state's entry: the settings and the device block
+            out["scaler"] = self.scaler_state()
         return out
 
     def load_optimizer_state(self, state) -> None:
-        if [tuple(x) for x in state["layout"]] != self._layout():
-            raise ValueError("SparK optimizer state was saved for another parameter layout")
+        self.check_layout(state["layout"])
         n = self.enc.flat.numel()
-        for key in ("m", "v"):
-            t = state[key].to(self.dev, torch.float32)
-            self.enc.state[key], self.state[key] = t[:n].clone(), t[n:].clone()
+        self.enc.load_moments(state["m"][:n], state["v"][:n])
+        self.load_moments(state["m"][n:], state["v"][n:])
         self.ctrl.zero_()
         self.ctrl[1], self.ctrl[3] = int(state.get("step", 0)), int(state.get("skipped", 0))
         # the bias corrections of the control block are rewritten by the next cddpm_op_guard_commit before any update reads them
-        sc = state.get("scaler")            # absent: saved without dynamic loss scaling -- the scaler is left as it is
-        if sc is not None:
-            self.enable_loss_scaling(init_scale=sc["init_scale"], growth_factor=sc["growth_factor"], backoff_factor=sc["backoff_factor"],
-                                     growth_interval=sc["growth_interval"], growth_tracker=sc["growth_tracker"])
-            if sc.get("state") is not None:
-                self.scaler = sc["state"].to(self.dev, torch.int32).clone()
+        self.load_scaler_state(state.get("scaler"))      # absent: saved without dynamic loss scaling -- the scaler is left as it is
 
     def parameters_changed(self) -> None:
         self.enc.repack()

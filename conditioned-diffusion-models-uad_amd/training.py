@@ -35,8 +35,11 @@ import torch
 from . import schedule as _schedule
 from . import synth as _synth
 from . import encoder_training as _encoder_training
+from . import optimizer as _optimizer
 from ._lib import largest_calls, scratch_query
 from .engine import ATTENTION_FAMILIES, CddpmEngine, _stream_ptr, attention_family_code, check_boxes, precision_bits
+from .optimizer import FlatOptimizer, _integer
+from .optimizer import _power_of_two, _scaler_block, loss_scaling_from_grad_scaler, loss_scaling_settings  # noqa: F401  (importable from here)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -221,7 +224,7 @@ def arena_bytes(program, B, H, W, emb_dim=2048, cond_dim=128, attention_family="
     return max(ARENA_FLOOR, unet[0], enc[0]), max(ARENA_FLOOR, unet[1], enc[1])
 
 
-class UNetTrainer:
+class UNetTrainer(FlatOptimizer):
     """Forward + backward + Adam of the conditioned UNet on NHWC device tensors, device-resident: the parameters live in ONE flat fp32
     buffer (`flat`; `p[name]` are views with the reference's state_dict names and shapes), their gradients in a second one (`gflat`,
     `g[name]`): every backward operator writes its parameter gradients straight into those views, the data-parallel all-reduce is one
@@ -270,18 +273,7 @@ class UNetTrainer:
         lead = [n + ".weight" for n in emb_names] + [n + ".bias" for n in emb_names]
         names = lead + [k for k in params if k not in set(lead)]
         self._lead = set(lead)          # written by ONE linear backward at the end of the backward pass (when batched: emb_rows > 0)
-        sizes = [(int(params[k].numel()) + 63) // 64 * 64 for k in names]       # 256-byte aligned views
-        self.flat = torch.zeros(sum(sizes), dtype=torch.float32, device=self.dev)
-        self.gflat = torch.zeros_like(self.flat)
-        self.p: Dict[str, torch.Tensor] = {}
-        self.g: Dict[str, torch.Tensor] = {}
-        off = 0
-        for k, n in zip(names, sizes):
-            v = params[k]
-            self.p[k] = self.flat[off:off + v.numel()].view(v.shape)
-            self.g[k] = self.gflat[off:off + v.numel()].view(v.shape)
-            self.p[k].copy_(v.detach().to(self.dev, torch.float32))
-            off += n
+        super().__init__(params, names, self.dev)       # flat, gflat, p, g, state, ctrl, the loss scaler (off)
         self.emb_off, self.emb_rows = {}, 0
         if emb_names and all(params[n + ".weight"].numel() % 64 == 0 and params[n + ".bias"].numel() % 64 == 0 for n in emb_names):
             E = params[emb_names[0] + ".weight"].shape[1]
@@ -291,7 +283,6 @@ class UNetTrainer:
             nw = self.emb_rows * E
             self.emb_w, self.emb_gw = self.flat[:nw].view(self.emb_rows, E), self.gflat[:nw].view(self.emb_rows, E)
             self.emb_b, self.emb_gb = self.flat[nw:nw + self.emb_rows], self.gflat[nw:nw + self.emb_rows]
-        self.state: Dict[str, object] = {}
         self.eng: Optional[CddpmEngine] = None
         # weight gradients on a SIDE stream (and a second handle: an operator's temporaries come from its handle's arena, one call at a
         # time): nothing in the backward pass waits for a weight gradient, so the k-image passes (memory bound) and the wgrad GEMMs run
@@ -300,9 +291,7 @@ class UNetTrainer:
         self.overlap_wgrad = (_os.environ.get("CDDPM_TRAIN_OVERLAP", "1") != "0") if overlap_wgrad is None else bool(overlap_wgrad)
         self.eng_w: Optional[CddpmEngine] = None
         self.side = None
-        self.grad_scale = 1.0
-        self.loss_scaling = False           # dynamic loss scaling (enable_loss_scaling); off: the fixed scale of loss_and_grad
-        self.scaler: Optional[torch.Tensor] = None
+        self.grad_scale = 1.0               # the fixed scale of loss_and_grad (dynamic loss scaling: enable_loss_scaling)
         self.exp_refresh = exp_refresh
         self._convs = self._conv_table()
         self._fit(1, 16, 16)
@@ -791,22 +780,30 @@ class UNetTrainer:
         return g
 
     # ------------------------------------------------------------------ loss of p_losses + one optimizer step
+    def _loss_scale(self, B, H, W, grad_scale):
+        """the scale of one loss -> the device scaler block (dynamic loss scaling on and no grad_scale given; made here at the first
+        loss, where no start was configured at the fixed path's scale; self.grad_scale is then None), or None with self.grad_scale =
+        grad_scale, by default B*H*W rounded up to a power of two (see cddpm_op_loss)"""
+        default = float(2 ** math.ceil(math.log2(B * H * W)))
+        if self.loss_scaling and grad_scale is None:
+            self.join_side()
+            self._start_scaler(default)
+            self.grad_scale = None
+            return self.scaler
+        self.grad_scale = float(grad_scale) if grad_scale is not None else default
+        return None
+
     def loss_and_grad(self, model_out, target, p2w=None, loss_type="l1", grad_scale=None):
         """-> (loss, grad_scale * dL/d(model_out)); grad_scale defaults to B*H*W rounded up to a power of two (see cddpm_op_loss). With
         dynamic loss scaling on and no grad_scale given, the scale is the device one (`loss_scale`; self.grad_scale is then None)."""
         B, _c, H, W = model_out.shape
         dout = torch.empty_like(model_out)
         loss_b = self._new(B)
-        if self.loss_scaling and grad_scale is None:
-            self.join_side()
-            if self.scaler is None:        # the first step: the default start is the fixed path's scale
-                init = self.scaler_init if self.scaler_init is not None else float(2 ** math.ceil(math.log2(B * H * W)))
-                self.scaler = _scaler_block(init, self.scaler_tracker0, 0, self.dev)
-            self.grad_scale = None
+        scaler = self._loss_scale(B, H, W, grad_scale)
+        if scaler is not None:
             self._ck(self.lib.cddpm_op_loss_scaled(self.h, _p(model_out), _p(target.contiguous().float()), _p(p2w), int(loss_type == "l2"), B,
-                                                   H * W, _p(self.scaler), _p(dout), _p(loss_b), self._s()), "op_loss_scaled")
+                                                   H * W, _p(scaler), _p(dout), _p(loss_b), self._s()), "op_loss_scaled")
             return loss_b.mean(), dout
-        self.grad_scale = float(grad_scale) if grad_scale is not None else float(2 ** math.ceil(math.log2(B * H * W)))
         self._ck(self.lib.cddpm_op_loss(self.h, _p(model_out), _p(target.contiguous().float()), _p(p2w), int(loss_type == "l2"), B, H * W,
                                         C.c_float(self.grad_scale), _p(dout), _p(loss_b), self._s()), "op_loss")
         return loss_b.mean(), dout
@@ -816,89 +813,20 @@ class UNetTrainer:
         (x0, y1, x2, y3) on the device, one per slice. The target (x0, or the noise inside the box and 0 outside) and `inpaint`'s paste
         are formed inside the kernel. The loss scale follows loss_and_grad: fixed, or the device one under dynamic loss scaling."""
         B, _c, H, W = model_out.shape
-        scaler = None
-        if self.loss_scaling and grad_scale is None:
-            self.join_side()
-            if self.scaler is None:
-                init = self.scaler_init if self.scaler_init is not None else float(2 ** math.ceil(math.log2(B * H * W)))
-                self.scaler = _scaler_block(init, self.scaler_tracker0, 0, self.dev)
-            self.grad_scale, scaler, scale = None, self.scaler, 0.0
-        else:
-            scale = self.grad_scale = float(grad_scale) if grad_scale is not None else float(2 ** math.ceil(math.log2(B * H * W)))
+        scaler = self._loss_scale(B, H, W, grad_scale)
         loss_b, dout = self.eng.loss_box(model_out, x0.contiguous().float(), noise.contiguous().float() if noise is not None else None, box,
-                                         objective=objective, loss_type=loss_type, inpaint=inpaint, w_b=p2w, grad_scale=scale, scaler=scaler)
+                                         objective=objective, loss_type=loss_type, inpaint=inpaint, w_b=p2w,
+                                         grad_scale=0.0 if scaler is not None else self.grad_scale, scaler=scaler)
         return loss_b.mean(), dout
 
-    # ------------------------------------------------------------------ dynamic loss scaling (torch's GradScaler, the scale on the device)
-    def enable_loss_scaling(self, init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, growth_tracker=0):
-        """turns on dynamic loss scaling with torch.cuda.amp.GradScaler's rule (torch._amp_update_scale_): a skipped step halves the scale
-        (x backoff_factor), `growth_interval` clean steps in a row double it (x growth_factor). init_scale None: the fixed path's
-        2^ceil(log2(B*H*W)) of the first batch, so the first steps do not change. Scale and factors must be powers of two (the unscale is
-        then exact: a step at scale S is bit-identical to the fixed path with grad_scale=S). Starts a fresh scaler state (growth tracker
-        `growth_tracker`, no skips); the device state is created at the next loss. Invalid values raise ValueError."""
-        cfg = loss_scaling_settings(init_scale, growth_factor, backoff_factor, growth_interval, growth_tracker)
-        self.scaler_init = cfg["init_scale"]
-        self.scaler_cfg = (cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"])
-        self.scaler_tracker0 = cfg["growth_tracker"]
-        self.scaler = None
-        self.loss_scaling = True
-
-    def update_loss_scale(self):
-        """step (d) of include/cddpm.h's dynamic loss scaling: after every Adam update of the step, the scale follows the step's skip
-        decision (one single-thread launch on the main stream)"""
-        self.join_side()
-        g, b, n = self.scaler_cfg
-        self._ck(self.lib.cddpm_op_scaler_update(self.h, _p(self._ctrl()), _p(self.scaler), C.c_float(g), C.c_float(b), n, self._s()),
-                 "op_scaler_update")
-
-    def _scaler_read(self, i):
-        self.join_side()
-        if self.scaler is None:
-            return None
-        return self.scaler[:1].view(torch.float32).item() if i == 0 else int(self.scaler[i].item())
-
-    @property
-    def loss_scale(self) -> Optional[float]:
-        """the loss scale the next step is formed with: the device scale when dynamic scaling is on (reads it: synchronises; before the
-        first step the configured start, None for the batch-size default), else the fixed scale of the last loss_and_grad"""
-        if not self.loss_scaling:
-            return self.grad_scale
-        return self._scaler_read(0) if self.scaler is not None else self.scaler_init
-
-    @property
-    def growth_tracker(self) -> int:
-        """clean steps since the scale last changed (dynamic scaling; reads the device counter)"""
-        return self._scaler_read(1) if self.scaler is not None else getattr(self, "scaler_tracker0", 0)
-
-    @property
-    def consecutive_skips(self) -> int:
-        """skipped steps in a row up to now (dynamic scaling; reads the device counter)"""
-        return self._scaler_read(2) if self.scaler is not None else 0
-
     # ------------------------------------------------------------------ the guarded update (GradScaler's skip of a non-finite step)
-    def _ctrl(self):
-        """int32[8] on the device: {non-finite flag, optimizer step, skip, skipped so far, bias corrections} (include/cddpm.h,
-        cddpm_op_guard_commit); shared with an EncoderTrainer running on this handle: one optimizer, one decision"""
-        if getattr(self, "ctrl", None) is None:
-            self.ctrl = torch.zeros(8, dtype=torch.int32, device=self.dev)
-        return self.ctrl
-
+    # Control block, loss scaler (enable_loss_scaling: no default start, so the first loss makes the block at the fixed path's
+    # 2^ceil(log2(B*H*W)) and the first steps do not change) and the update itself: optimizer.FlatOptimizer. `ctrl` and `scaler` are
+    # shared with an EncoderTrainer running on this handle: one optimizer, one decision, one scale.
     def guard(self, others=(), betas=(0.9, 0.999)):
         """checks this trainer's gradients (and those of `others`) for inf / NaN and commits the decision for this step on the device:
         a step with a non-finite gradient neither updates parameters / moments nor advances the step count"""
-        ctrl = self._ctrl()
-        for tr_ in (self, *others):
-            self._ck(self.lib.cddpm_op_grad_check(self.h, _p(tr_.gflat), tr_.gflat.numel(), _p(ctrl), self._s()), "op_grad_check")
-        self._ck(self.lib.cddpm_op_guard_commit(self.h, _p(ctrl), C.c_float(betas[0]), C.c_float(betas[1]), self._s()), "op_guard_commit")
-
-    @property
-    def step_count(self) -> int:
-        """optimizer steps taken (skipped ones do not count); reads the device counter (synchronises)"""
-        return int(self._ctrl()[1].item())
-
-    @property
-    def skipped_steps(self) -> int:
-        return int(self._ctrl()[3].item())
+        _optimizer.guard(self, (self, *others), betas)
 
     def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=None, guarded=False, extra_unscale=None):
         """torch.optim.Adam(lr=1e-4) of DDPM_2D.configure_optimizers (DDPM_2D.py:305-306) on every parameter: one launch over the flat buffers
@@ -907,26 +835,17 @@ class UNetTrainer:
         grad_scale given, the gradient is gflat * extra_unscale (default 1) / the device scale of this step's loss; unguarded, the scale is
         then updated here (guarded: the caller runs update_loss_scale after the last Adam update of the step)."""
         st = self.state
-        if "m" not in st:
-            st["m"], st["v"] = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         if not guarded:
             self.guard(betas=betas)
         st["calls"] = st.get("calls", 0) + 1
-        if self.loss_scaling and grad_scale is None:
-            if self.scaler is None:
-                raise RuntimeError("adam_step with dynamic loss scaling: no loss was formed yet (loss_and_grad)")
+        scaler = self.step_scaler(grad_scale)
+        if scaler is not None:
             self.join_side()
-            self._ck(self.lib.cddpm_op_adam_scaled(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
-                                                   C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps),
-                                                   C.c_float(1.0 if extra_unscale is None else extra_unscale), _p(self._ctrl()), _p(self.scaler),
-                                                   self._s()), "op_adam_scaled")
+            _optimizer.update(self, self, lr, betas, eps, unscale=1.0 if extra_unscale is None else extra_unscale, scaler=scaler)
             if not guarded:
                 self.update_loss_scale()
         else:
-            unscale = 1.0 / (grad_scale if grad_scale is not None else self.grad_scale)
-            self._ck(self.lib.cddpm_op_adam_guarded(self.h, _p(self.flat), _p(self.gflat), _p(st["m"]), _p(st["v"]), self.flat.numel(),
-                                                    C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps), C.c_float(unscale),
-                                                    _p(self._ctrl()), self._s()), "op_adam_guarded")
+            _optimizer.update(self, self, lr, betas, eps, unscale=1.0 / (grad_scale if grad_scale is not None else self.grad_scale))
         if self._convs:
             if self.exp_refresh and st["calls"] % self.exp_refresh == 0:
                 self.refresh_exponents()
@@ -936,38 +855,23 @@ class UNetTrainer:
     def optimizer_state(self) -> Dict[str, torch.Tensor]:
         """what a checkpoint must carry besides the parameters to resume this optimizer: Adam's m, v (flat, this trainer's layout), the
         device control block with the step count and, with dynamic loss scaling on, the scaler ("scaler": its settings and device block)"""
-        st = self.state
-        if "m" not in st:
-            st["m"], st["v"] = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        m, v = _optimizer.moments(self)
         # wexp / calls: the convolutions' pre-scale exponents are refreshed every `exp_refresh` updates, not every update -- a resumed run
         # must multiply with the exponents (and refresh on the schedule) the uninterrupted run would
-        out = {"m": st["m"].detach().clone(), "v": st["v"].detach().clone(), "ctrl": self._ctrl().detach().clone(),
-               "layout": [(k, int(v.numel())) for k, v in self.p.items()], "wexp": dict(getattr(self, "wexp", {})),
-               "calls": int(st.get("calls", 0))}
+        out = {"m": m.detach().clone(), "v": v.detach().clone(), "ctrl": self.ctrl.detach().clone(), "layout": self.layout(),
+               "wexp": dict(getattr(self, "wexp", {})), "calls": int(self.state.get("calls", 0))}
         if self.dropout > 0:               # a resumed run continues the mask sequence
             out["dropout"] = dropout_state(self.dropout_seed, self.dropout_step)
         if self.loss_scaling:
-            self.join_side()
-            g, b, n = self.scaler_cfg
-            out["scaler"] = {"init_scale": self.scaler_init, "growth_factor": g, "backoff_factor": b, "growth_interval": n,
-                             "growth_tracker": self.scaler_tracker0, "state": None if self.scaler is None else self.scaler.detach().clone()}
+            out["scaler"] = self.scaler_state()
         return out
 
     def load_optimizer_state(self, state) -> None:
-        layout = [(k, int(v.numel())) for k, v in self.p.items()]
-        if [tuple(x) for x in state["layout"]] != layout:
-            raise ValueError("optimizer state was saved for another parameter layout")
-        self.state["m"] = state["m"].to(self.dev, torch.float32).clone()
-        self.state["v"] = state["v"].to(self.dev, torch.float32).clone()
-        self._ctrl().copy_(state["ctrl"].to(self.dev, torch.int32))
+        self.check_layout(state["layout"])
+        self.load_moments(state["m"], state["v"])
+        self.ctrl.copy_(state["ctrl"].to(self.dev, torch.int32))
         self.state["calls"] = int(state.get("calls", 0))
-        sc = state.get("scaler")           # absent: saved without dynamic loss scaling -- the scaler is left as it is
-        if sc is not None:
-            self.enable_loss_scaling(init_scale=sc["init_scale"], growth_factor=sc["growth_factor"], backoff_factor=sc["backoff_factor"],
-                                     growth_interval=sc["growth_interval"], growth_tracker=sc["growth_tracker"])
-            if sc.get("state") is not None:
-                self.join_side()
-                self.scaler = sc["state"].to(self.dev, torch.int32).clone()
+        self.load_scaler_state(state.get("scaler"))      # absent: saved without dynamic loss scaling -- the scaler is left as it is
         if state.get("wexp") and self._convs:
             self.wexp = {k: int(state["wexp"][k]) for k in self._convs}
             self.repack()
@@ -1013,50 +917,6 @@ def dropout_from_state(state) -> "tuple[int, int]":
     seed, step = (int(v) if isinstance(v, torch.Tensor) and v.numel() == 1 else v for v in (seed, step))
     d = dropout_state(seed, step)
     return d["seed"], d["step"]
-
-
-def _power_of_two(x) -> bool:
-    try:
-        x = float(x)
-    except (TypeError, ValueError):
-        return False
-    return math.isfinite(x) and x > 0 and math.frexp(x)[0] == 0.5
-
-
-def _scaler_block(scale: float, tracker: int, skips: int, dev) -> torch.Tensor:
-    """the device scaler state of include/cddpm.h: int32[4] = {bits of the fp32 loss scale, growth tracker, consecutive skips, 0}"""
-    blk = torch.tensor([0, int(tracker), int(skips), 0], dtype=torch.int32)
-    blk[:1].view(torch.float32).fill_(float(scale))
-    return blk.to(dev)
-
-
-def _integer(x) -> bool:
-    return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x) and int(x) == x
-
-
-def loss_scaling_settings(init_scale=None, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, growth_tracker=0) -> Dict[str, object]:
-    """the checked arguments of UNetTrainer.enable_loss_scaling (torch GradScaler's defaults; init_scale None: the batch-size default).
-    The scale and both factors must be powers of two (growth > 1, backoff < 1) so that unscaling stays exact; ValueError otherwise."""
-    if init_scale is not None and not (_power_of_two(init_scale) and float(init_scale) < 2.0 ** 127):
-        raise ValueError(f"init_scale must be a finite power of two, got {init_scale!r}")
-    if not (_power_of_two(growth_factor) and float(growth_factor) > 1.0):
-        raise ValueError(f"growth_factor must be a power of two > 1, got {growth_factor!r}")
-    if not (_power_of_two(backoff_factor) and float(backoff_factor) < 1.0):
-        raise ValueError(f"backoff_factor must be a power of two < 1, got {backoff_factor!r}")
-    if not (_integer(growth_interval) and 1 <= growth_interval < 2 ** 31):
-        raise ValueError(f"growth_interval must be an integer >= 1, got {growth_interval!r}")
-    if not (_integer(growth_tracker) and 0 <= growth_tracker < 2 ** 31):
-        raise ValueError(f"growth_tracker must be an integer >= 0, got {growth_tracker!r}")
-    return {"init_scale": None if init_scale is None else float(init_scale), "growth_factor": float(growth_factor),
-            "backoff_factor": float(backoff_factor), "growth_interval": int(growth_interval), "growth_tracker": int(growth_tracker)}
-
-
-def loss_scaling_from_grad_scaler(state) -> Dict[str, object]:
-    """UNetTrainer.enable_loss_scaling's arguments from a torch GradScaler.state_dict() -- what Lightning 1.5's native AMP plugin stores in
-    a checkpoint under `native_amp_scaling_state`: {"scale", "growth_factor", "backoff_factor", "growth_interval", "_growth_tracker"}.
-    Values outside what enable_loss_scaling accepts raise ValueError."""
-    return loss_scaling_settings(float(state["scale"]), state.get("growth_factor", 2.0), state.get("backoff_factor", 0.5),
-                                 state.get("growth_interval", 2000), state.get("_growth_tracker", 0))
 
 
 def lightning_precision_bits(precision) -> int:

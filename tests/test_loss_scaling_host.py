@@ -72,6 +72,41 @@ def test_seed_from_a_grad_scaler_state_dict():
         tr.loss_scaling_from_grad_scaler(dict(sd, scale=1000.0))
 
 
+@pytest.mark.parametrize("start", [None, 65536.0])
+def test_scaler_state_round_trips_with_and_without_the_device_block(start):
+    """optimizer.FlatOptimizer on the CPU, for both kinds of trainer (no default start: the block waits for the first loss; a default
+    start: made at once): scaler_state() -> load_scaler_state() restores settings and block; no "scaler" entry leaves the scaler alone"""
+    opt = load_pkg("optimizer")
+    cls = type("T", (opt.FlatOptimizer,), {"DEFAULT_INIT_SCALE": start})
+    make = lambda: cls({"w": torch.arange(3.0)}, ["w"], "cpu")
+    src = make()
+    assert not src.loss_scaling and src.scaler is None and src.loss_scale is None and src.growth_tracker == src.consecutive_skips == 0
+    src.enable_loss_scaling(growth_interval=7, growth_tracker=3)
+    assert (src.scaler is None) == (start is None) and src.loss_scale == start and src.growth_tracker == 3
+    for with_block in (start is not None, True):
+        if with_block:
+            src._start_scaler(256.0)                # the first loss of a trainer without a default start
+            src.scaler[2] = 2
+        st = {"scaler": src.scaler_state()}
+        assert set(st["scaler"]) == {"init_scale", "growth_factor", "backoff_factor", "growth_interval", "growth_tracker", "state"}
+        assert (st["scaler"]["state"] is not None) == with_block and st["scaler"]["init_scale"] == start
+        dst = make()
+        dst.load_scaler_state(st.get("scaler"))
+        assert dst.loss_scaling and dst.scaler_cfg == (2.0, 0.5, 7) and dst.growth_tracker == 3
+        assert dst.loss_scale == src.loss_scale and dst.consecutive_skips == src.consecutive_skips == (2 if with_block else 0)
+        if with_block:
+            assert torch.equal(dst.scaler, src.scaler) and dst.scaler is not st["scaler"]["state"] and dst.scaler.dtype == torch.int32
+            assert dst.loss_scale == (start or 256.0)
+        block = dst.scaler
+        dst.load_scaler_state({}.get("scaler"))     # a state saved without dynamic loss scaling
+        assert dst.loss_scaling and dst.scaler is block and dst.scaler_cfg == (2.0, 0.5, 7)
+    off = make()
+    off.load_scaler_state({}.get("scaler"))
+    assert not off.loss_scaling and off.scaler is None
+    src.disable_loss_scaling()
+    assert not src.loss_scaling and src.scaler is None and src.loss_scale is None
+
+
 def test_mirror_keeps_a_native_amp_seed_pending_until_precision_16():
     mod = _mirror()
     sd = {"scale": 2.0 ** 12, "growth_factor": 2.0, "backoff_factor": 0.5, "growth_interval": 2000, "_growth_tracker": 5}

@@ -7,11 +7,16 @@ library for sizes (cddpm_op_*_scratch) that an older library does not export. Bu
     python tools/scratch_plan_ab.py --run BASE_ROOT [--out profiles/scratch_plan_ab.json]
 Variants: "base" = BASE_ROOT, "prod" = this tree. Each runs in its own process on its own Python package and library.
     bits   sha256 of dw and db of cddpm_op_conv_wgrad at WGRAD_SHAPES and of the flat gradient buffer after one training step of two small
-           descriptors, each at training precision 32 and 16; every digest must equal the base's (exit 1 otherwise)
+           descriptors, each at training precision 32 and 16; then of the optimizer's state (parameters, Adam's m and v, the control
+           block, the loss scaler) after a few steps of every step path -- the UNet at the fixed scale with exponent refreshes, by hand
+           under a dynamic loss scale through a skip, a back-off and a growth, with the context encoder trained jointly, SparK
+           pre-training at precision 16 and 32 -- and after a resume from optimizer_state(), whose format is digested too
+           (optimizer_bits); every digest must equal the base's (exit 1 otherwise)
     arena  the `bytes` of every cddpm_op_set_scratch call while a trainer is fitted to ARENA_GEOMETRIES (recorded, not compared)
-    time   one 16 x 128 x 128 training step with the context encoder trained jointly (what tools/train_step_bench.py --encoder times): HIP
-           events around a window of WINDOW steps after a warm-up; AB_SAMPLES (4) samples per process, AB_ROUNDS (3) rounds with the
-           variants interleaved. Verdict: prod's median inside or below base's [min, max] of this run"""
+    time   one 16 x 128 x 128 training step with the context encoder trained jointly (what tools/train_step_bench.py --encoder times) and
+           one 32 x 96 x 96 SparK pre-training step at precision 16 (what tools/spark_step_bench.py times: the step most exposed to host
+           overhead): HIP events around a window of WINDOW steps after a warm-up; AB_SAMPLES (4) samples per process, AB_ROUNDS (3)
+           rounds with the variants interleaved. Verdict: prod's median inside or below base's [min, max] of this run"""
 import hashlib
 import importlib
 import json
@@ -33,11 +38,12 @@ ARENA_GEOMETRIES = [(16, 128, 128), (32, 96, 96), (64, 128, 128)]
 WINDOW = 2
 
 
-def _trainer(tr, synth, torch, case=None):
+def _trainer(tr, synth, torch, case=None, params=None, **more):
     kw = {} if case is None else dict(model_channels=case["model_channels"], channel_mult=case["channel_mult"], num_res_blocks=case["num_res_blocks"],
                                       attention_resolutions=case["attention_resolutions"])
-    sd = synth.synth_state_dict(0, num_classes=(case["cond_dim"] if case else 128), **kw)
-    return tr.UNetTrainer({k: torch.from_numpy(v) for k, v in sd.items()}, device=torch.device("cuda", 0), cond_dim=(case["cond_dim"] if case else 128), **kw)
+    if params is None:
+        params = {k: torch.from_numpy(v) for k, v in synth.synth_state_dict(0, num_classes=(case["cond_dim"] if case else 128), **kw).items()}
+    return tr.UNetTrainer(params, device=torch.device("cuda", 0), cond_dim=(case["cond_dim"] if case else 128), **kw, **more)
 
 
 def _batch(synth, torch, B, H, W, cond_dim=128):
@@ -46,6 +52,121 @@ def _batch(synth, torch, B, H, W, cond_dim=128):
     noise = torch.from_numpy(synth.noise_xT(1, 0, B, H, W)).reshape(B, 1, H, W).cuda()
     t = torch.tensor([(137 * (i + 1)) % 1000 for i in range(B)], dtype=torch.long, device="cuda")
     return x01, cond, noise, t
+
+
+def _spark(torch, B, side, precision, params=None):
+    """a SparKTrainer on synth's state dict (or `params`), one batch and its cell mask drawn under a fixed seed at ratio 0.65 -- the
+    batch tests/test_gpu_spark_training_p16.py steps"""
+    synth, st, mirror = (importlib.import_module(f"{PKG}.{m}") for m in ("synth", "spark_training", "Spark_2D"))
+    if params is None:
+        params = {k[len("model."):]: torch.from_numpy(v) for k, v in synth.synth_spark_state_dict(0, input_size=side).items()}
+    torch.manual_seed(B + side)
+    x = torch.rand(B, 1, side, side)
+    f = side // 32
+    active = mirror.draw_mask(B, f, round(f * f * (1 - 0.65)))
+    return st.SparKTrainer(params, torch.device("cuda", 0), precision=precision), x.cuda(), active.cuda()
+
+
+def optimizer_bits(out, sha):
+    """digests of the optimizer's state after a few steps of every step path, and after a resume (module docstring)"""
+    import torch
+    tr, synth, et = (importlib.import_module(f"{PKG}.{m}") for m in ("training", "synth", "encoder_training"))
+
+    def canon(x):
+        if torch.is_tensor(x):
+            return [str(x.dtype), list(x.shape), sha(x)]
+        if isinstance(x, dict):
+            return [[k, canon(x[k])] for k in sorted(x)]
+        return [canon(v) for v in x] if isinstance(x, (list, tuple)) else repr(x)
+
+    def digest(tag, opt, **owners):
+        for name, o in owners.items():
+            out[f"{tag} {name} flat"], out[f"{tag} {name} m"], out[f"{tag} {name} v"] = sha(o.flat), sha(o.state["m"]), sha(o.state["v"])
+        out[f"{tag} ctrl"] = sha(opt.ctrl)
+        if opt.scaler is not None:
+            out[f"{tag} scaler"] = sha(opt.scaler)
+
+    def resume(tag, old, fresh, step, **owners):
+        state = old.optimizer_state()
+        out[f"{tag} optimizer_state format"] = hashlib.sha256(json.dumps(canon(state)).encode()).hexdigest()
+        fresh.load_optimizer_state(state)
+        step(fresh)
+        torch.cuda.synchronize()
+        digest(tag + " resumed", fresh, **{k: getattr(fresh, a) if a else fresh for k, a in owners.items()})
+
+    case = STEP_CASES["cond4"]
+    x01, cond, noise, t = _batch(synth, torch, *case["geometry"], case["cond_dim"])
+    for bits in (32, 16):                # the fixed scale; exp_refresh 2: the second update refreshes the exponents before it re-packs
+        tr.set_precision(bits)
+        trainer = _trainer(tr, synth, torch, case, exp_refresh=2)
+        for _ in range(3):
+            tr.training_step(trainer, x01, cond, t=t, noise=noise)
+        torch.cuda.synchronize()
+        digest(f"cond4 p{bits} 3 steps", trainer, unet=trainer)
+        trainer.close()
+
+    def by_hand(trainer, inf=False):     # as tests/test_gpu_loss_scaling.py drives it: the unguarded adam_step guards, updates, rescales
+        out_ = trainer.forward(x01 * 2 - 1, t, cond)
+        _loss, dout = trainer.loss_and_grad(out_, noise, None, "l2")
+        if inf:
+            dout[0, 0, 3, 3] = float("inf")
+        trainer.backward(dout)
+        trainer.adam_step(lr=1e-4)
+    trainer = _trainer(tr, synth, torch, case, exp_refresh=2)
+    trainer.enable_loss_scaling(growth_interval=2)
+    for i in range(4):                   # clean, skipped (back-off), clean, clean (growth)
+        by_hand(trainer, inf=(i == 1))
+    torch.cuda.synchronize()
+    digest("cond4 p16 scaler by hand", trainer, unet=trainer)
+    out["cond4 p16 scaler by hand counters"] = repr((trainer.step_count, trainer.skipped_steps, trainer.loss_scale, trainer.growth_tracker))
+    resume("cond4 p16 scaler", trainer, _trainer(tr, synth, torch, case, params={k: v.clone() for k, v in trainer.p.items()}, exp_refresh=2),
+           by_hand, unet=None)
+    trainer.close()
+
+    case = STEP_CASES["attn_levels"]     # at 2 x 64 x 64, the geometry tests/test_gpu_loss_scaling.py trains the encoder jointly at
+    x01, cond, noise, t = _batch(synth, torch, 2, 64, 64, case["cond_dim"])
+    trainer = _trainer(tr, synth, torch, case)
+    trainer.enable_loss_scaling()
+    enc = et.EncoderTrainer({k: torch.from_numpy(v) for k, v in synth.synth_encoder_state_dict(0).items()}, trainer, drop_path_rate=0.0)
+    for _ in range(2):
+        tr.training_step(trainer, x01, None, t=t, noise=noise, encoder=enc)
+    torch.cuda.synchronize()
+    digest("attn_levels p16 scaler + encoder 2 steps", trainer, unet=trainer, encoder=enc)
+    trainer.close()
+    tr.set_precision(32)
+
+    def spark_step(spark):
+        spark.forward(x, active, drop_scales={})
+        spark.backward()
+        spark.adamw_step(lr=1e-3)
+    for precision, steps in ((16, 5), (32, 2)):      # 16: the default scaler, which backs off from 65536 on this batch in its first steps
+        spark, x, active = _spark(torch, 4, 64, precision)
+        for _ in range(steps):
+            spark_step(spark)
+        torch.cuda.synchronize()
+        digest(f"spark p{precision} {steps} steps", spark, own=spark, encoder=spark.enc)
+        out[f"spark p{precision} counters"] = repr((spark.step_count, spark.skipped_steps, spark.loss_scale))
+        if precision == 16:
+            fresh = _spark(torch, 4, 64, 16, params={k: v.clone() for k, v in spark.state_dict().items()})[0]
+            resume("spark p16", spark, fresh, spark_step, own=None, encoder="enc")
+            fresh.close()
+        spark.close()
+
+
+def _windows(torch, step, samples):
+    """ms per step of `samples` windows of WINDOW steps between two HIP events, after a warm-up"""
+    for _ in range(2):
+        step()          # warm-up
+    ms = []
+    for _ in range(samples):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(WINDOW):
+            step()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1) / WINDOW)
+    return ms
 
 
 def child(root, mode, samples):
@@ -72,6 +193,7 @@ def child(root, mode, samples):
                 trainer.close()
         tr.set_precision(32)
         e.close()
+        optimizer_bits(out, sha)
     elif mode == "arena":
         lib = importlib.import_module(PKG + "._lib").load_library()
         set_scratch, seen = lib.cddpm_op_set_scratch, []
@@ -88,19 +210,16 @@ def child(root, mode, samples):
         enc = et.EncoderTrainer({k: torch.from_numpy(v) for k, v in synth.synth_encoder_state_dict(0).items()}, trainer, drop_path_rate=0.05)
         x01, cond, noise, t = _batch(synth, torch, 16, 128, 128)
         step = lambda: tr.training_step(trainer, x01, cond, t=t, noise=noise, objective="pred_noise", loss_type="l2", encoder=enc)
-        for _ in range(2):
-            step()          # warm-up
-        ms = []
-        for _ in range(samples):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(WINDOW):
-                step()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1) / WINDOW)
-        out["training step 16x128x128 + encoder"] = ms
+        out["training step 16x128x128 + encoder"] = _windows(torch, step, samples)
         trainer.close()
+        spark, x, active = _spark(torch, 32, 96, 16)
+
+        def step():
+            spark.forward(x, active)
+            spark.backward()
+            spark.adamw_step(lr=1e-4)
+        out["SparK step 32x96x96 p16"] = _windows(torch, step, samples)
+        spark.close()
     print(json.dumps(out))
 
 
