@@ -1116,6 +1116,34 @@ int cddpm_eval_hausdorff(cddpm_handle h, const uint8_t* pred_dev, const float* s
     return 0;
 }
 
+static bool aug_in_range(int B, int H, int W, int D) {
+    return B >= 1 && B <= CDDPM_AUG_MAX_BATCH && H >= 1 && W >= 1 && D >= 1 && H <= CDDPM_AUG_MAX_AXIS && W <= CDDPM_AUG_MAX_AXIS && D <= CDDPM_AUG_MAX_AXIS;
+}
+
+size_t cddpm_aug_workspace_bytes(int B, int H, int W, int D) {
+    if (!aug_in_range(B, H, W, D)) {
+        fail(nullptr, "cddpm_aug_workspace_bytes: B = %d outside 1 ... %d or volume %dx%dx%d outside 1 ... %d per axis", B, CDDPM_AUG_MAX_BATCH, H, W, D,
+             CDDPM_AUG_MAX_AXIS);
+        return 0;
+    }
+    return aug_workspace_bytes(B, H, W, D);
+}
+
+int cddpm_aug_slices(cddpm_handle h, const float* bank_dev, int N, int H, int W, int D, const int32_t* meta_dev, const float* par_dev,
+                     int B, void* ws_dev, size_t ws_bytes, float* out_dev, void* stream) {
+    if (!h) return -1;
+    if (!bank_dev || !meta_dev || !par_dev || !ws_dev || !out_dev) return fail(h, "cddpm_aug_slices: NULL argument");
+    if (N < 1) return fail(h, "cddpm_aug_slices: a bank of %d volumes", N);
+    if (!aug_in_range(B, H, W, D))
+        return fail(h, "cddpm_aug_slices: B = %d outside 1 ... %d or volume %dx%dx%d outside 1 ... %d per axis", B, CDDPM_AUG_MAX_BATCH, H, W, D,
+                    CDDPM_AUG_MAX_AXIS);
+    const size_t need = aug_workspace_bytes(B, H, W, D);
+    if (ws_bytes < need) return fail(h, "cddpm_aug_slices: workspace of %zu bytes, need %zu", ws_bytes, need);
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, launch_aug_slices(bank_dev, N, H, W, D, meta_dev, par_dev, B, ws_dev, ws_bytes, out_dev, (hipStream_t)stream));
+    return 0;
+}
+
 int cddpm_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev, const int32_t* t_dev, int t_uniform,
                    const float* sqrt_ac_host, const float* sqrt_1mac_host, int T, float* out_dev, int B, int H, int W,
                    void* stream) {

@@ -297,6 +297,11 @@ size_t hausdorff_workspace_bytes(int R, int D1, int D2);
 hipError_t launch_eval_hausdorff(const uint8_t* pred, const float* seg, int R, int D1, int D2, int squeeze, void* ws, size_t ws_bytes,
                                  double* out, uint8_t* edges_out, int32_t* dist2_out, hipStream_t s);
 
+// augmented training slices from a resident bank (augment.hip; src/datamodules/create_dataset.py:220-250, :143-193)
+size_t aug_workspace_bytes(int B, int H, int W, int D);
+hipError_t launch_aug_slices(const float* bank, int N, int H, int W, int D, const int32_t* meta, const float* par, int B, void* ws,
+                             size_t ws_bytes, float* out, hipStream_t s);
+
 // ---- training-mode kernels of the context encoder (encoder_train.hip)
 int enc_conv_split(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);     // planes of `part` (1: not used)
 void launch_enc_conv(const float* src, const float* w_img, float* dst, int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed,

@@ -650,6 +650,81 @@ class CddpmEngine:
                  "cddpm_eval_hausdorff")
         return out
 
+    # ------------------------------------------------------------------ augmented training slices (augment.hip)
+    AUG_META, AUG_PAR, AUG_ALL, AUG_MAX_SIGMA = 4, 28, 15, 8.0                # include/cddpm.h
+
+    @classmethod
+    def check_augment_tables(cls, meta: np.ndarray, par: np.ndarray, N: int, D: int) -> None:
+        """what cddpm_aug_slices' first kernel refuses per sample, checked on the host tables before they are copied: a RuntimeError names
+        the first bad row. meta [B, 4] int32 {volume, z, flags, g | axis << 8}, par [B, 28] fp32 {gamma, sigma0..2, I, c[20], unused}."""
+        if meta.ndim != 2 or meta.shape[1] != cls.AUG_META or meta.dtype != np.int32:
+            raise RuntimeError(f"meta must be [B, {cls.AUG_META}] int32, got {meta.shape} {meta.dtype}")
+        if par.shape != (meta.shape[0], cls.AUG_PAR) or par.dtype != np.float32:
+            raise RuntimeError(f"par must be [{meta.shape[0]}, {cls.AUG_PAR}] float32, got {par.shape} {par.dtype}")
+        if meta.shape[0] < 1:
+            raise RuntimeError("an empty batch")
+        axis, sig = meta[:, 3] >> 8, par[:, 1:4]
+        for what, bad in ((f"volume outside [0, {N})", (meta[:, 0] < 0) | (meta[:, 0] >= N)),
+                          (f"z outside [0, {D})", (meta[:, 1] < 0) | (meta[:, 1] >= D)),
+                          ("ghosting axis outside 0 ... 2", (axis < 0) | (axis > 2)),
+                          ("unknown flag bits", (meta[:, 2] & ~cls.AUG_ALL) != 0),
+                          (f"sigma_voxel outside [0, {cls.AUG_MAX_SIGMA:g}]", ~((sig >= 0) & (sig <= cls.AUG_MAX_SIGMA)).all(axis=1)),
+                          ("a non-finite parameter", ~np.isfinite(par[:, [0] + list(range(4, 25))]).all(axis=1))):
+            if bad.any():
+                b = int(np.argmax(bad))
+                raise RuntimeError(f"cddpm_aug_slices: sample {b}: {what} (meta {meta[b].tolist()}, sigma {sig[b].tolist()})")
+
+    def _augment_buffers(self, B: int, H: int, W: int, D: int):
+        """cddpm_aug_slices' workspace, asked for once per geometry and largest batch through the library's own size query
+        (cddpm_aug_workspace_bytes, the operator-scratch convention), and two pinned staging rows for the tables, so that one copy can be
+        in flight while the next is filled. A smaller batch of the same geometry runs in the same buffers."""
+        key = (H, W, D)
+        st = getattr(self, "_aug", None)
+        if st is None or st["key"] != key or B > st["cap"]:
+            need = int(self.lib.cddpm_aug_workspace_bytes(B, H, W, D))
+            if need == 0:
+                raise RuntimeError(f"cddpm_aug_workspace_bytes: {self.lib.cddpm_last_error(None).decode()}")
+            row = 4 * (self.AUG_META + self.AUG_PAR)
+            st = self._aug = dict(key=key, cap=B, ws=torch.empty(need, dtype=torch.uint8, device=self.device),
+                                  host=[torch.empty(B * row, dtype=torch.uint8).pin_memory() for _ in range(2)],
+                                  dev=[torch.empty(B * row, dtype=torch.uint8, device=self.device) for _ in range(2)],
+                                  done=[None, None], turn=0)
+        return st
+
+    def augment_slices(self, bank, meta, par, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One batch of augmented training slices from a resident bank (cddpm_aug_slices; get_augment + vol2slice of the reference's
+        create_dataset.py:220-250, :143-193). bank: an augment.VolumeBank on this engine's device; meta [B, 4] int32 and par [B, 28] fp32:
+        HOST tables (numpy or CPU tensors), one row per output slice, as IntensityAugment.draw returns them. They are checked here
+        (check_augment_tables: a bad row raises before anything is copied or enqueued and `out` stays untouched), staged through pinned
+        memory with ONE asynchronous host-to-device copy, and applied by one library call on the current stream. Returns out [B, H, W]
+        fp32 on the device (`out=`: written in place)."""
+        meta = np.ascontiguousarray(meta.numpy() if isinstance(meta, torch.Tensor) else meta)
+        par = np.ascontiguousarray(par.numpy() if isinstance(par, torch.Tensor) else par)
+        data = _check_dev(bank.data, "bank.data", self.device)
+        N, D, H, W = data.shape
+        self.check_augment_tables(meta, par, N, D)
+        B = meta.shape[0]
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (B, H, W)
+              or not out.is_contiguous()):
+            raise RuntimeError(f"out must be a contiguous [{B}, {H}, {W}] float32 tensor on {self.device}")
+        st = self._augment_buffers(B, H, W, D)
+        i = st["turn"]
+        st["turn"] = 1 - i
+        if st["done"][i] is not None:
+            st["done"][i].synchronize()                # the copy that last read this staging row (two calls ago) has long finished
+        host, dev, nm, tot = st["host"][i], st["dev"][i], B * 4 * self.AUG_META, B * 4 * (self.AUG_META + self.AUG_PAR)
+        host[:nm].view(torch.int32).view(B, self.AUG_META).copy_(torch.from_numpy(meta))
+        host[nm:tot].view(torch.float32).view(B, self.AUG_PAR).copy_(torch.from_numpy(par))
+        dev[:tot].copy_(host[:tot], non_blocking=True)
+        st["done"][i] = torch.cuda.Event()
+        st["done"][i].record(torch.cuda.current_stream(self.device))
+        self._ck(self.lib.cddpm_aug_slices(self._h, data.data_ptr(), N, H, W, D, dev.data_ptr(), dev.data_ptr() + nm, B,
+                                           st["ws"].data_ptr(), st["ws"].numel(), out.data_ptr(), _stream_ptr(self.device)),
+                 "cddpm_aug_slices")
+        return out
+
     def simplex_noise(self, B: int, H: int, W: int, *, seed: int, octaves: int = 6, persistence: float = 0.8,
                       frequency: float = 64.0) -> torch.Tensor:
         """gen_noise for noisetype 'simplex': float16 [B,1,H,W], the same field for every batch item, bit-exact

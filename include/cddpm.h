@@ -353,6 +353,75 @@ size_t cddpm_hausdorff_workspace_bytes(int R, int D1, int D2);
 int cddpm_eval_hausdorff(cddpm_handle h, const uint8_t* pred_dev, const float* seg_dev, int R, int D1, int D2, int flags,
                          void* ws_dev, size_t ws_bytes, double* out_dev, uint8_t* edges_dev, int32_t* dist2_dev, void* stream);
 
+/* ---- Augmented training slices (csrc/augment.hip) -------------------------------------------------------
+ * Replaces, for `aug_intensity: True`, the per-item work of the reference's training datamodule: get_augment
+ * (src/datamodules/create_dataset.py:220-250) = Compose(RandomGamma(p=.5), RandomBiasField(p=.25), RandomBlur(p=.25),
+ * RandomGhosting(p=.5)) of torchio on the whole preloaded volume, then vol2slice (:143-193), which keeps one slice. Status:
+ * PINNED TO NUMPY / SCIPY, UNPINNED TO TORCHIO. The rules below restate torchio 0.18.9x's transforms; torchio itself was not
+ * available to compare with, numpy and scipy were (tests/augment_reference.py). The random draws are the caller's
+ * (augment.IntensityAugment.draw); this entry applies one table row per output slice.
+ * The bank is [N][D][H][W] fp32, slice-major: torchio's [1, H, W, D] volume permuted once, so a slice is a contiguous [H][W]
+ * image. Axis numbers keep torchio's meaning: 0 = H, 1 = W, 2 = D. Every extent is 1 ... CDDPM_AUG_MAX_AXIS.
+ *   meta_dev [B][CDDPM_AUG_META] int32: {volume, z, flags, g | axis << 8} -- bank volume, output slice, the stage bits below,
+ *            the ghosting's num_ghosts g (0 ... 255) and axis.
+ *   par_dev  [B][CDDPM_AUG_PAR] fp32: {gamma, sigma0, sigma1, sigma2, I, c[20], 3 unused} -- the exponent, the blur's sigma per
+ *            axis in VOXELS (std / spacing), the ghosting's intensity, the bias field's coefficients.
+ * Stages, in Compose's order; a sample with flags = 0 is a bit-exact copy of its slice:
+ *   CDDPM_AUG_GAMMA  y = sign(x) |x|^gamma (torchio's rule for data with negatives; x^gamma otherwise).
+ *   CDDPM_AUG_BIAS   y = x exp(sum_i c_i X^a Y^b Z^c), i counting a in 0..3, then b in 0..3-a, then c in 0..3-a-b; X, Y, Z the
+ *                    coordinates along axes 0, 1, 2: u(i) = (2 i - L + 1) / (L - 1), 0 where L = 1, and 0^0 = 1.
+ *                    Gamma and bias are evaluated together in double and rounded to fp32 once.
+ *   CDDPM_AUG_BLUR   scipy.ndimage.gaussian_filter(vol, sigma) with its defaults: separable, axis 0, 1, 2; radius
+ *                    int(4 sigma + 0.5); weights exp(-k^2 / (2 sigma^2)) normalised; boundary `reflect` (d c b a | a b c d |
+ *                    d c b a) by repeated reflection, so a radius may exceed the axis; an axis with sigma <= 1e-15 is skipped;
+ *                    line sums in double, fp32 between the passes.
+ *   CDDPM_AUG_GHOST  torchio scales the planes s = 0, g, 2 g, ... of the fft-shifted spectrum along the axis by 1 - I, restores
+ *                    the plane s = L / 2, inverts and keeps the real part. The mask depends on the axis frequency alone, so this
+ *                    is y = x - I (c (*) x), a circular convolution along the axis with
+ *                    c[d] = (1 / L) sum over s = 0, g, 2 g, ... < L, s != L / 2 of cos(2 pi (s - L / 2) d / L),
+ *                    built in double with the argument reduced in integers, accumulated in double and evaluated at the output
+ *                    slice only. g = 0 or I = 0: the identity (torchio's early return).
+ * Errors: -1 with the reason in cddpm_last_error(h) for what the host can see -- a NULL pointer, N < 1, an extent outside
+ * 1 ... CDDPM_AUG_MAX_AXIS, B outside 1 ... CDDPM_AUG_MAX_BATCH, a short workspace -- before anything is enqueued. The two tables
+ * live on the device: the first kernel reads them alone, and a row with volume outside [0, N), z outside [0, D), axis > 2,
+ * unknown flag bits, a sigma outside [0, CDDPM_AUG_MAX_SIGMA] or a non-finite parameter is flagged: no kernel reads the bank
+ * or writes the output for that sample, and its CDDPM_AUG_BAD_* bits stand in the status word. After the call the first B int32
+ * of ws_dev are the status words of the B samples (0: done). Callers with host tables check them before the copy
+ * (CddpmEngine.augment_slices). */
+#define CDDPM_AUG_GAMMA 1
+#define CDDPM_AUG_BIAS 2
+#define CDDPM_AUG_BLUR 4
+#define CDDPM_AUG_GHOST 8
+#define CDDPM_AUG_ALL 15
+#define CDDPM_AUG_META 4
+#define CDDPM_AUG_PAR 28
+#define CDDPM_AUG_PAR_GAMMA 0
+#define CDDPM_AUG_PAR_SIGMA 1            /* 1, 2, 3: axes 0, 1, 2 */
+#define CDDPM_AUG_PAR_INTENSITY 4
+#define CDDPM_AUG_PAR_COEF 5
+#define CDDPM_AUG_BIAS_COEFS 20
+#define CDDPM_AUG_MAX_AXIS 1024
+#define CDDPM_AUG_MAX_BATCH 65535
+#define CDDPM_AUG_MAX_SIGMA 8            /* in voxels: radius 32 */
+#define CDDPM_AUG_MAX_RADIUS 32
+#define CDDPM_AUG_BAD_VOLUME 1           /* status bits of a sample */
+#define CDDPM_AUG_BAD_Z 2
+#define CDDPM_AUG_BAD_AXIS 4
+#define CDDPM_AUG_BAD_SIGMA 8
+#define CDDPM_AUG_BAD_FLAGS 16
+#define CDDPM_AUG_BAD_VALUE 32
+
+/* workspace bytes of cddpm_aug_slices for B samples of an H x W x D bank: the status words, the per-sample weight tables and two
+ * work volumes per sample. Host arithmetic, callable without a GPU. Outside the supported range: 0, with the reason in
+ * cddpm_last_error(NULL). */
+size_t cddpm_aug_workspace_bytes(int B, int H, int W, int D);
+
+/* out_dev [B][H][W] fp32: sample b is slice z_b of volume_b after the stages its flags select. Runs on `stream`; nothing
+ * allocates or synchronises inside. A sample's result depends on its own table row alone and its arithmetic runs in a fixed
+ * order: bitwise reproducible, and independent of the batch it is computed in. */
+int cddpm_aug_slices(cddpm_handle h, const float* bank_dev, int N, int H, int W, int D, const int32_t* meta_dev, const float* par_dev,
+                     int B, void* ws_dev, size_t ws_bytes, float* out_dev /* [B][H][W] */, void* stream);
+
 /* Replaces q_sample (src/models/modules/cond_DDPM.py:548-554) fused with normalize_to_neg_one_to_one (:75):
  * out = sqrt_ac[t_b] * (2 x01 - 1) + sqrt_1mac[t_b] * noise; coefficient tables are host arrays [T]
  * uploaded on first use. Used by the single-step reconstruction (GaussianDiffusion.forward, :647-655). t_b = t_dev[b] kept inside
