@@ -62,6 +62,9 @@ SYMBOLS = {
     "cddpm_eval_hausdorff": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _fp, _fp, _fp, _vp]),
     "cddpm_aug_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cddpm_aug_slices": (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _fp, _i, _vp, _sz, _fp, _vp]),
+    "cddpm_prep_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, C.c_double]),
+    "cddpm_prep_volume": (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _fp, _vp, _vp, _vp]),
+    "cddpm_prep_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp]),
     "cddpm_q_sample": (_i, [_vp, _fp, _fp, _fp, _i, _fp, _fp, _i, _fp, _i, _i, _i, _vp]),
     "cddpm_set_clip_denoised": (_i, [_vp, _i]),
     "cddpm_set_accumulation_switch": (_i, [_vp, _i]),

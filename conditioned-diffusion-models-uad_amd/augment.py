@@ -13,8 +13,11 @@ sequence of random draws is this module's own: the reference draws inside 4 Data
 reproduce against itself. Here every value is a function of (seed, epoch, position in the epoch's global order) alone -- not of the batch
 size, the rank or the call history -- from synth's counter RNG on stream ids of its own.
 
-Out of scope: reading NIfTI and get_transform's crop, rescale and resample (the bank takes preprocessed volumes); every other get_augment
-key and the vol2slice variants the training datamodule does not use (refused with NotImplementedError, the convention of DDPM_encoder.py).
+A bank is built from preprocessed volumes (`VolumeBank(...)`) or from raw ones (`VolumeBank.from_raw`, through preprocess.py: sitk_reader's
+smoothing and get_transform's crop, rescale and resample on the device, every volume written straight into its slot).
+
+Out of scope: reading NIfTI; every other get_augment key and the vol2slice variants the training datamodule does not use (refused with
+NotImplementedError, the convention of DDPM_encoder.py).
 """
 from __future__ import annotations
 
@@ -156,6 +159,35 @@ class VolumeBank:
         if len(self.spacing) != 3 or min(self.spacing) <= 0:
             raise ValueError(f"spacing must be three positive numbers, got {spacing!r}")
         self.data = torch.stack([v.to(torch.float32).permute(2, 0, 1) for v in vols]).contiguous().to(self.device)
+
+    @classmethod
+    def from_raw(cls, volumes, masks, device, preprocess, spacing: Optional[Sequence[float]] = None) -> "VolumeBank":
+        """A bank of RAW volumes of one shape ([H, W, D] arrays or tensors, on the host or the device), each preprocessed on the device
+        by `preprocess` (a preprocess.VolumePreprocess) straight into its slot: no staging copy. masks: one per volume, or None (each
+        mask is then vol > 0, as `Train` builds it without a mask path, create_dataset.py:31). spacing: the voxel size after Resample,
+        by default `rescaleFactor` per axis (raw volumes at 1 mm). The calls' records ([N, 16] float64, on the device) are kept in
+        `records`, the preprocessed masks ([N, D', H', W'] uint8) in `masks`."""
+        volumes = list(volumes)
+        if not volumes:
+            raise ValueError("an empty bank")
+        masks = [None] * len(volumes) if masks is None else list(masks)
+        if len(masks) != len(volumes):
+            raise ValueError(f"{len(volumes)} volumes and {len(masks)} masks")
+        shapes = {tuple(torch.as_tensor(v).shape[-3:]) for v in volumes}
+        if len(shapes) != 1:
+            raise ValueError(f"every volume of a bank has one shape, got {sorted(shapes)}")
+        h, w, d = preprocess.output_shape(next(iter(shapes)))
+        self = cls.__new__(cls)
+        self.device = torch.device(device)
+        self.spacing = tuple(float(s) for s in (spacing if spacing is not None else (preprocess.factor,) * 3))
+        if len(self.spacing) != 3 or min(self.spacing) <= 0:
+            raise ValueError(f"spacing must be three positive numbers, got {spacing!r}")
+        self.data = torch.empty(len(volumes), d, h, w, dtype=torch.float32, device=self.device)
+        self.masks = torch.empty(len(volumes), d, h, w, dtype=torch.uint8, device=self.device)
+        records = [preprocess.run(v, m, device=self.device, out=self.data[n], mask_out=self.masks[n])["record"]
+                   for n, (v, m) in enumerate(zip(volumes, masks))]
+        self.records = torch.stack(records)
+        return self
 
     def __len__(self) -> int:
         return self.data.shape[0]

@@ -1144,6 +1144,67 @@ int cddpm_aug_slices(cddpm_handle h, const float* bank_dev, int N, int H, int W,
     return 0;
 }
 
+// what the host can see of a preprocessing geometry; the reason, or NULL
+static const char* prep_refusal(int H, int W, int D, int stages, int allowed, int th, int tw, int td, double f) {
+    const int M = CDDPM_PREP_MAX_AXIS;
+    if (H < 1 || W < 1 || D < 1 || H > M || W > M || D > M) return "volume outside 1 ... 1024 per axis";
+    if (stages & ~allowed) return "unknown or unsupported stage bits";
+    if ((stages & CDDPM_PREP_CROPPAD) && (th < 1 || tw < 1 || td < 1 || th > M || tw > M || td > M)) return "target outside 1 ... 1024 per axis";
+    if (stages & CDDPM_PREP_RESAMPLE) {
+        if (!(f >= 1.0) || !std::isfinite(f)) return "resample factor f < 1 or not finite";
+        const bool cp = (stages & CDDPM_PREP_CROPPAD) != 0;
+        if (f != 1.0 && ((cp ? th : H) == 1 || (cp ? tw : W) == 1 || (cp ? td : D) == 1)) return "an axis of length 1 is not resampled with f != 1";
+    }
+    return nullptr;
+}
+
+size_t cddpm_prep_workspace_bytes(int H, int W, int D, int stages, int th, int tw, int td, double f) {
+    if (const char* why = prep_refusal(H, W, D, stages, CDDPM_PREP_ALL, th, tw, td, f)) {
+        fail(nullptr, "cddpm_prep_workspace_bytes: %s (volume %dx%dx%d, stages 0x%x, target %dx%dx%d, f %g)", why, H, W, D, stages, th, tw, td, f);
+        return 0;
+    }
+    return prep_workspace_bytes(H, W, D, stages, th, tw, td, f);
+}
+
+int cddpm_prep_volume(cddpm_handle h, const float* vol_dev, const uint8_t* mask_dev, int H, int W, int D, int stages, int iterations, int th,
+                      int tw, int td, const double* par_host, void* ws_dev, size_t ws_bytes, float* out_dev, uint8_t* mask_out_dev,
+                      double* record_dev, void* stream) {
+    if (!h) return -1;
+    if (!vol_dev || !par_host || !ws_dev || !out_dev || !record_dev) return fail(h, "cddpm_prep_volume: NULL argument");
+    const double f = par_host[CDDPM_PREP_PAR_FACTOR], lo = par_host[CDDPM_PREP_PAR_PERC_LO], hi = par_host[CDDPM_PREP_PAR_PERC_HI];
+    if (const char* why = prep_refusal(H, W, D, stages, CDDPM_PREP_ALL, th, tw, td, f))
+        return fail(h, "cddpm_prep_volume: %s (volume %dx%dx%d, stages 0x%x, target %dx%dx%d, f %g)", why, H, W, D, stages, th, tw, td, f);
+    if ((stages & CDDPM_PREP_RESCALE) && !(0.0 <= lo && lo <= hi && hi <= 100.0))
+        return fail(h, "cddpm_prep_volume: percentiles (%g, %g) outside 0 <= lo <= hi <= 100", lo, hi);
+    if (stages & CDDPM_PREP_SMOOTH) {
+        if (iterations < 0 || iterations > CDDPM_PREP_MAX_ITERATIONS)
+            return fail(h, "cddpm_prep_volume: %d iterations outside 0 ... %d", iterations, CDDPM_PREP_MAX_ITERATIONS);
+        bool ok = std::isfinite(par_host[CDDPM_PREP_PAR_DT]);
+        for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(par_host[CDDPM_PREP_PAR_SPACING + a]) && par_host[CDDPM_PREP_PAR_SPACING + a] > 0.0;
+        if (!ok) return fail(h, "cddpm_prep_volume: dt not finite or a spacing not positive and finite");
+    }
+    if ((const void*)out_dev == (const void*)vol_dev) return fail(h, "cddpm_prep_volume: output equal to input");
+    if (mask_out_dev && (const void*)mask_out_dev == (const void*)mask_dev) return fail(h, "cddpm_prep_volume: mask output equal to mask input");
+    const size_t need = prep_workspace_bytes(H, W, D, stages, th, tw, td, f);
+    if (ws_bytes < need) return fail(h, "cddpm_prep_volume: workspace of %zu bytes, need %zu", ws_bytes, need);
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, launch_prep_volume(vol_dev, mask_dev, H, W, D, stages, iterations, th, tw, td, par_host, ws_dev, ws_bytes, out_dev, mask_out_dev,
+                                   record_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int cddpm_prep_labels(cddpm_handle h, const uint8_t* lab_dev, int H, int W, int D, int stages, int th, int tw, int td, double f, uint8_t* out_dev,
+                      void* stream) {
+    if (!h) return -1;
+    if (!lab_dev || !out_dev) return fail(h, "cddpm_prep_labels: NULL argument");
+    if (const char* why = prep_refusal(H, W, D, stages, CDDPM_PREP_CROPPAD | CDDPM_PREP_RESAMPLE, th, tw, td, f))
+        return fail(h, "cddpm_prep_labels: %s (volume %dx%dx%d, stages 0x%x, target %dx%dx%d, f %g)", why, H, W, D, stages, th, tw, td, f);
+    if (out_dev == lab_dev) return fail(h, "cddpm_prep_labels: output equal to input");
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, launch_prep_labels(lab_dev, H, W, D, stages, th, tw, td, f, out_dev, (hipStream_t)stream));
+    return 0;
+}
+
 int cddpm_q_sample(cddpm_handle h, const float* x01_dev, const float* noise_dev, const int32_t* t_dev, int t_uniform,
                    const float* sqrt_ac_host, const float* sqrt_1mac_host, int T, float* out_dev, int B, int H, int W,
                    void* stream) {

@@ -302,6 +302,13 @@ size_t aug_workspace_bytes(int B, int H, int W, int D);
 hipError_t launch_aug_slices(const float* bank, int N, int H, int W, int D, const int32_t* meta, const float* par, int B, void* ws,
                              size_t ws_bytes, float* out, hipStream_t s);
 
+// raw volumes preprocessed on the device (preprocess.hip; src/datamodules/create_dataset.py:196-218, :252-258)
+size_t prep_workspace_bytes(int H, int W, int D, int stages, int th, int tw, int td, double f);
+hipError_t launch_prep_volume(const float* vol, const uint8_t* mask, int H, int W, int D, int stages, int iterations, int th, int tw, int td,
+                              const double* par, void* ws, size_t ws_bytes, float* out, uint8_t* mask_out, double* record, hipStream_t s);
+hipError_t launch_prep_labels(const uint8_t* lab, int H, int W, int D, int stages, int th, int tw, int td, double f, uint8_t* out,
+                              hipStream_t s);
+
 // ---- training-mode kernels of the context encoder (encoder_train.hip)
 int enc_conv_split(int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed);     // planes of `part` (1: not used)
 void launch_enc_conv(const float* src, const float* w_img, float* dst, int B, int H, int W, int Cin, int Cout, int K, int stride, int transposed,

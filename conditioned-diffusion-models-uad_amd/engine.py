@@ -725,6 +725,88 @@ class CddpmEngine:
                  "cddpm_aug_slices")
         return out
 
+    # ------------------------------------------------------------------ preprocessed volumes (preprocess.hip)
+    PREP_SMOOTH, PREP_CROPPAD, PREP_RESCALE, PREP_RESAMPLE, PREP_ALL, PREP_RECORD = 1, 2, 4, 8, 15, 16      # include/cddpm.h
+
+    @classmethod
+    def prep_output_shape(cls, shape: Sequence[int], stages: int, target: Optional[Sequence[int]], f: float) -> Tuple[int, int, int]:
+        """(H', W', D') of a preprocessed (H, W, D) volume: the target under CROPPAD, then ceil(N / f) per axis under RESAMPLE"""
+        out = tuple(int(t) for t in target) if stages & cls.PREP_CROPPAD else tuple(int(n) for n in shape)
+        if stages & cls.PREP_RESAMPLE and float(f) != 1.0:
+            out = tuple(int(np.ceil(n / float(f))) for n in out)
+        return out
+
+    def _prep_workspace(self, key) -> torch.Tensor:
+        """cddpm_prep_volume's workspace, asked for once per geometry (H, W, D, stages, th, tw, td, f) through the library's own size
+        query (the operator-scratch convention); a call of another geometry replaces it"""
+        st = getattr(self, "_prep", None)
+        if st is None or st[0] != key:
+            need = int(self.lib.cddpm_prep_workspace_bytes(*key))
+            if need == 0:
+                raise RuntimeError(f"cddpm_prep_workspace_bytes: {self.lib.cddpm_last_error(None).decode()}")
+            st = self._prep = (key, torch.empty(need, dtype=torch.uint8, device=self.device))
+        return st[1]
+
+    def _check_labels(self, t, name: str, shape) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.device or t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+            raise RuntimeError(f"{name} must be a uint8 tensor of shape {tuple(shape)} on {self.device}")
+        return t.contiguous()
+
+    def preprocess_volume(self, vol: torch.Tensor, mask: Optional[torch.Tensor] = None, *, stages: int, target: Optional[Sequence[int]] = None,
+                          perc: Sequence[float] = (1.0, 99.0), f: float = 1.0, dt: float = 0.125, iterations: int = 3,
+                          spacing: Sequence[float] = (1.0, 1.0, 1.0), out: Optional[torch.Tensor] = None,
+                          mask_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """One raw volume through the stages of cddpm_prep_volume (sitk_reader's CurvatureFlow and get_transform's CropOrPad,
+        RescaleIntensity, Resample; create_dataset.py:252-258, :196-218). vol [H, W, D] fp32 and mask [H, W, D] uint8 (None: vol > 0) on
+        this engine's device, torchio's layout. Returns device tensors: vol [D', H', W'] fp32 and mask [D', H', W'] uint8, slice-major
+        (`out=`, `mask_out=`: written in place, e.g. a slot of a VolumeBank), and record [PREP_RECORD] float64."""
+        vol = _check_dev(vol, "vol", self.device)
+        if vol.dim() != 3:
+            raise RuntimeError(f"vol must be [H, W, D], got {tuple(vol.shape)}")
+        H, W, D = vol.shape
+        if mask is not None:
+            mask = self._check_labels(mask, "mask", vol.shape)
+        stages, f = int(stages), float(f)
+        th, tw, td = (int(t) for t in target) if stages & self.PREP_CROPPAD else (0, 0, 0)
+        ws = self._prep_workspace((H, W, D, stages, th, tw, td, f))
+        h2, w2, d2 = self.prep_output_shape(vol.shape, stages, target, f)
+        if out is None:
+            out = torch.empty(d2, h2, w2, dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (d2, h2, w2)
+              or not out.is_contiguous()):
+            raise RuntimeError(f"out must be a contiguous [{d2}, {h2}, {w2}] float32 tensor on {self.device}")
+        if mask_out is None:
+            mask_out = torch.empty(d2, h2, w2, dtype=torch.uint8, device=self.device)
+        elif (not isinstance(mask_out, torch.Tensor) or mask_out.device != self.device or mask_out.dtype != torch.uint8
+              or tuple(mask_out.shape) != (d2, h2, w2) or not mask_out.is_contiguous()):
+            raise RuntimeError(f"mask_out must be a contiguous [{d2}, {h2}, {w2}] uint8 tensor on {self.device}")
+        record = torch.empty(self.PREP_RECORD, dtype=torch.float64, device=self.device)
+        par = (C.c_double * 8)(float(dt), *(float(s) for s in spacing), float(perc[0]), float(perc[1]), f, 0.0)
+        self._ck(self.lib.cddpm_prep_volume(self._h, vol.data_ptr(), mask.data_ptr() if mask is not None else None, H, W, D, stages,
+                                            int(iterations), th, tw, td, C.addressof(par), ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                            mask_out.data_ptr(), record.data_ptr(), _stream_ptr(self.device)), "cddpm_prep_volume")
+        return dict(vol=out, mask=mask_out, record=record)
+
+    def preprocess_labels(self, lab: torch.Tensor, *, stages: int, target: Optional[Sequence[int]] = None, f: float = 1.0,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A label volume [H, W, D] uint8 through CROPPAD and RESAMPLE alone (cddpm_prep_labels; the other stage bits of `stages` are
+        dropped: images only). Returns [D', H', W'] uint8 on the device."""
+        if not isinstance(lab, torch.Tensor) or lab.dim() != 3:
+            raise RuntimeError("lab must be a [H, W, D] uint8 tensor")
+        lab = self._check_labels(lab, "lab", lab.shape)
+        H, W, D = lab.shape
+        stages, f = int(stages) & (self.PREP_CROPPAD | self.PREP_RESAMPLE), float(f)
+        th, tw, td = (int(t) for t in target) if stages & self.PREP_CROPPAD else (0, 0, 0)
+        h2, w2, d2 = self.prep_output_shape(lab.shape, stages, target, f)
+        if out is None:
+            out = torch.empty(d2, h2, w2, dtype=torch.uint8, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.uint8 or tuple(out.shape) != (d2, h2, w2)
+              or not out.is_contiguous()):
+            raise RuntimeError(f"out must be a contiguous [{d2}, {h2}, {w2}] uint8 tensor on {self.device}")
+        self._ck(self.lib.cddpm_prep_labels(self._h, lab.data_ptr(), H, W, D, stages, th, tw, td, f, out.data_ptr(),
+                                            _stream_ptr(self.device)), "cddpm_prep_labels")
+        return out
+
     def simplex_noise(self, B: int, H: int, W: int, *, seed: int, octaves: int = 6, persistence: float = 0.8,
                       frequency: float = 64.0) -> torch.Tensor:
         """gen_noise for noisetype 'simplex': float16 [B,1,H,W], the same field for every batch item, bit-exact

@@ -422,6 +422,87 @@ size_t cddpm_aug_workspace_bytes(int B, int H, int W, int D);
 int cddpm_aug_slices(cddpm_handle h, const float* bank_dev, int N, int H, int W, int D, const int32_t* meta_dev, const float* par_dev,
                      int B, void* ws_dev, size_t ws_bytes, float* out_dev /* [B][H][W] */, void* stream);
 
+/* ---- Preprocessed volumes (csrc/preprocess.hip) ------------------------------------------------------------
+ * Replaces what the reference's datamodule does to a volume on the CPU before it is cached (Train) or handed to test_step (Eval,
+ * which has no cache, src/datamodules/create_dataset.py:52-92): sitk_reader's CurvatureFlow (:252-258) and get_transform's
+ * CropOrPad, RescaleIntensity and Resample (:196-218). Status: PINNED TO NUMPY / SCIPY, UNPINNED TO TORCHIO AND SIMPLEITK. The
+ * rules below restate torchio >=0.18.90,<0.19 and ITK from recollection; neither was available to compare with, numpy and scipy
+ * were (tests/preprocess_reference.py). Reading NIfTI files is not built.
+ * The input is a C-contiguous [H][W][D] fp32 volume (torchio's layout), label volumes are uint8 of the same shape. Axis numbers
+ * keep torchio's meaning: 0 = H, 1 = W, 2 = D. The output is slice-major [D'][H'][W'] (the layout of augment.VolumeBank), labels
+ * uint8 in the same layout, written directly at the destination the caller names. Every extent is 1 ... CDDPM_PREP_MAX_AXIS.
+ * Stages, in the reference's order; a call with no stage set is a bit-exact copy into the output layout:
+ *   CDDPM_PREP_SMOOTH    sitk.CurvatureFlow(timeStep = dt, numberOfIterations): per iteration v <- v + dt u, stored as fp32. With
+ *                        s_i = 1 / spacing_i, central differences and neighbours clamped to the edge:
+ *                        dx_i = (v+i - v-i) s_i / 2, dxx_i = (v+i - 2 v + v-i) s_i^2, dxy_ij = (v++ - v+- - v-+ + v--) s_i s_j / 4,
+ *                        m = sum dx_i^2, u = 0 where m < 1e-9, else
+ *                        u = (sum_i dxx_i sum_{j != i} dx_j^2 - 2 sum_{i<j} dx_i dx_j dxy_ij) / m, evaluated in double.
+ *                        Images only, never label volumes.
+ *   CDDPM_PREP_CROPPAD   tio.CropOrPad((th, tw, td), padding_mode = 0): per axis delta = target - size; padding |delta| puts
+ *                        ceil(|delta| / 2) zeros in front and floor(|delta| / 2) behind, cropping removes voxels in the same split.
+ *                        The same bounds for image and labels.
+ *   CDDPM_PREP_RESCALE   tio.RescaleIntensity((0, 1), percentiles = (lo, hi), masking_method = mask): values = vol[mask > 0] (n of
+ *                        them, after the stages above; a NULL mask is vol > 0); per percentile p, v = p (n - 1) / 100, k = floor(v):
+ *                        cutoff = numpy's linear interpolation between the order statistics k and min(k + 1, n - 1) at v - k, an
+ *                        exact selection on the device; the whole volume is clipped to the cutoffs and [min, max] of the clipped
+ *                        volume mapped to [0, 1], y = (clip(x) - min) / (max - min), in double. An empty mask or max == min leaves
+ *                        the volume unchanged (torchio warns and returns) and sets CDDPM_PREP_UNCHANGED with its reason.
+ *   CDDPM_PREP_RESAMPLE  tio.Resample(f, image_interpolation = 'bspline') at input spacing 1: output size ceil(N / f) per axis,
+ *                        output voxel i samples x = (i + 1/2) f - 1/2. Images: scipy.ndimage.map_coordinates(order = 3,
+ *                        mode = 'mirror') with its prefilter (pole sqrt(3) - 2, axes 0, 1, 2), coefficients and the 64 taps in
+ *                        double, rounded once. Labels: the nearest voxel floor(x + 1/2). A sample point outside [-1/2, N - 1/2)
+ *                        gives 0 (ITK's default pixel). f = 1 skips the stage.
+ * par_host [CDDPM_PREP_PAR] float64, a HOST array: {dt, spacing0, spacing1, spacing2, perc_lo, perc_hi, f, unused}.
+ * record_dev [CDDPM_PREP_RECORD] float64 is written by every call that is enqueued: the status bits, the mask count, the four
+ * order statistics (low k, low k + 1, high k, high k + 1; -0.0 is reported as +0.0), both cutoffs, min and max of the clipped volume;
+ * slots the call's stages do not compute are 0. A non-finite input value sets CDDPM_PREP_BAD_VALUE: no output is then written.
+ * Errors: -1 with the reason in cddpm_last_error(h), before anything is enqueued, for what the host can see -- a NULL pointer,
+ * an extent or target outside 1 ... CDDPM_PREP_MAX_AXIS, unknown stage bits, percentiles outside 0 <= lo <= hi <= 100, f < 1,
+ * RESAMPLE with f != 1 on an axis of length 1 (its rule is not recalled with confidence), dt, spacing or f not finite, spacing
+ * <= 0, iterations outside 0 ... CDDPM_PREP_MAX_ITERATIONS, a short workspace, output equal to input. */
+#define CDDPM_PREP_SMOOTH 1
+#define CDDPM_PREP_CROPPAD 2
+#define CDDPM_PREP_RESCALE 4
+#define CDDPM_PREP_RESAMPLE 8
+#define CDDPM_PREP_ALL 15
+#define CDDPM_PREP_MAX_AXIS 1024
+#define CDDPM_PREP_MAX_ITERATIONS 64
+#define CDDPM_PREP_PAR 8
+#define CDDPM_PREP_PAR_DT 0
+#define CDDPM_PREP_PAR_SPACING 1         /* 1, 2, 3: axes 0, 1, 2 */
+#define CDDPM_PREP_PAR_PERC_LO 4
+#define CDDPM_PREP_PAR_PERC_HI 5
+#define CDDPM_PREP_PAR_FACTOR 6
+#define CDDPM_PREP_BAD_VALUE 1           /* status bits: a non-finite input value (the output is not written) */
+#define CDDPM_PREP_BAD_MASK 2            /* rescale: the mask is empty */
+#define CDDPM_PREP_BAD_RANGE 4           /* rescale: max == min after clipping */
+#define CDDPM_PREP_UNCHANGED 8           /* rescale: the volume went on unchanged (set with BAD_MASK or BAD_RANGE) */
+#define CDDPM_PREP_RECORD 16             /* slots of the record (float64) */
+#define CDDPM_PREP_REC_STATUS 0
+#define CDDPM_PREP_REC_COUNT 1
+#define CDDPM_PREP_REC_STAT 2            /* 2 ... 5 */
+#define CDDPM_PREP_REC_CUT_LO 6
+#define CDDPM_PREP_REC_CUT_HI 7
+#define CDDPM_PREP_REC_MIN 8
+#define CDDPM_PREP_REC_MAX 9
+
+/* workspace bytes of cddpm_prep_volume for an H x W x D input, these stages, target (th, tw, td) (read under CROPPAD) and factor f
+ * (read under RESAMPLE): state words, tap tables, two fp32 work volumes under SMOOTH, one float64 coefficient volume under
+ * RESAMPLE with f != 1. Host arithmetic, callable without a GPU. Outside the supported range: 0, with the reason in
+ * cddpm_last_error(NULL). */
+size_t cddpm_prep_workspace_bytes(int H, int W, int D, int stages, int th, int tw, int td, double f);
+
+/* out_dev [D'][H'][W'] fp32; mask_dev [H][W][D] uint8 or NULL (vol > 0 after SMOOTH); mask_out_dev [D'][H'][W'] uint8 or NULL: the
+ * mask through CROPPAD and RESAMPLE. Runs on `stream`; nothing allocates or synchronises inside; reductions across workgroups
+ * are integer atomics: bitwise reproducible. */
+int cddpm_prep_volume(cddpm_handle h, const float* vol_dev, const uint8_t* mask_dev, int H, int W, int D, int stages, int iterations,
+                      int th, int tw, int td, const double* par_host, void* ws_dev, size_t ws_bytes, float* out_dev,
+                      uint8_t* mask_out_dev, double* record_dev, void* stream);
+
+/* a label volume (mask, segmentation) through CROPPAD and RESAMPLE alone (other stage bits are refused): out_dev [D'][H'][W'] uint8 */
+int cddpm_prep_labels(cddpm_handle h, const uint8_t* lab_dev, int H, int W, int D, int stages, int th, int tw, int td, double f,
+                      uint8_t* out_dev, void* stream);
+
 /* Replaces q_sample (src/models/modules/cond_DDPM.py:548-554) fused with normalize_to_neg_one_to_one (:75):
  * out = sqrt_ac[t_b] * (2 x01 - 1) + sqrt_1mac[t_b] * noise; coefficient tables are host arrays [T]
  * uploaded on first use. Used by the single-step reconstruction (GaussianDiffusion.forward, :647-655). t_b = t_dev[b] kept inside
