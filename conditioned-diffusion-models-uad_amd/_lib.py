@@ -62,6 +62,8 @@ SYMBOLS = {
     "cddpm_eval_hausdorff": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _fp, _fp, _fp, _vp]),
     "cddpm_aug_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cddpm_aug_slices": (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _fp, _i, _vp, _sz, _fp, _vp]),
+    "cddpm_aug_pipeline_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "cddpm_aug_pipeline": (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _fp, _i, _vp, _sz, _fp, _vp]),
     "cddpm_prep_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, C.c_double]),
     "cddpm_prep_volume": (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _fp, _vp, _vp, _vp]),
     "cddpm_prep_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp]),

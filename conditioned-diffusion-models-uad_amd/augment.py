@@ -16,8 +16,16 @@ size, the rank or the call history -- from synth's counter RNG on stream ids of 
 A bank is built from preprocessed volumes (`VolumeBank(...)`) or from raw ones (`VolumeBank.from_raw`, through preprocess.py: sitk_reader's
 smoothing and get_transform's crop, rescale and resample on the device, every volume written straight into its slot).
 
-Out of scope: reading NIfTI; every other get_augment key and the vol2slice variants the training datamodule does not use (refused with
-NotImplementedError, the convention of DDPM_encoder.py).
+The other get_augment keys -- what someone training on a smaller data set switches on first -- go through `SliceAugment` and a second
+library call (cddpm_aug_pipeline, `CddpmEngine.augment_pipeline`): get_augment's whole order as eleven gated slots, random_bias (p .25),
+random_noise, random_ghosting, random_blur, random_gamma, random_affine and random_flip (.5 each), then the policy group above. The
+rules of the new stages (noise from a counter RNG, the affine as a trilinear gather padded with the volume's minimum, the flip) are in
+include/cddpm.h, "The augmentation pipeline", restated in tests/augment_pipeline_reference.py. `IntensityAugment` stays what it was,
+refusals included. Mask and label volumes are not transformed: the mirrors' training_step reads `vol` only.
+
+Out of scope: reading NIfTI; random_elastic and random_motion (their rules live in SimpleITK's B-spline transform and in a k-space
+composite) and the vol2slice variants the training datamodule does not use (refused with NotImplementedError, the convention of
+DDPM_encoder.py).
 """
 from __future__ import annotations
 
@@ -31,6 +39,7 @@ from .mirror_common import _cfg_get
 
 STREAM_AUGMENT = 0x6000        # counter word 3 of a sample's draws (clear of synth's 0x1001-4 and its 0x2000 ... 0x5000 + ordinal ranges)
 STREAM_AUG_ORDER = 0x6001      # ... of the epoch's permutation
+STREAM_AUG_NOISE = 0x6002      # ... of the noise stage's voxels, on the device (keyed by a sample's own two key words)
 
 GAMMA, BIAS, BLUR, GHOST = 1, 2, 4, 8          # flag bits (include/cddpm.h: CDDPM_AUG_*), in Compose's order
 META, PAR = 4, 28
@@ -39,6 +48,21 @@ REFUSED_KEYS = ("random_bias", "random_motion", "random_noise", "random_ghosting
                 "random_affine", "random_flip")
 # slots of a sample's 32 draws (8 Philox quads)
 _U_GATE, _U_GAMMA, _U_COEF, _U_STD, _U_INTENSITY, _W_GHOSTS, _W_AXIS, _W_Z = 0, 4, 5, 25, 28, 29, 30, 31
+
+# the eleven slots of cddpm_aug_pipeline (include/cddpm.h: CDDPM_PIPE_*), in get_augment's order
+SLOT_BIAS, SLOT_NOISE, SLOT_GHOST, SLOT_BLUR, SLOT_GAMMA, SLOT_AFFINE, SLOT_FLIP = 1, 2, 4, 8, 16, 32, 64
+POLICY_GAMMA, POLICY_BIAS, POLICY_BLUR, POLICY_GHOST = 128, 256, 512, 1024
+SLOTS = (SLOT_BIAS, SLOT_NOISE, SLOT_GHOST, SLOT_BLUR, SLOT_GAMMA, SLOT_AFFINE, SLOT_FLIP, POLICY_GAMMA, POLICY_BIAS, POLICY_BLUR, POLICY_GHOST)
+PIPE_META, PIPE_PAR = 8, 64
+_SET = 25                      # a parameter set {gamma, sigma0..2, I, c[20]}: the slot set at column 0, the policy set at 25
+_COL_NOISE_STD, _COL_MATRIX = 50, 51
+PIPELINE_KEYS = {"random_bias": SLOT_BIAS, "random_noise": SLOT_NOISE, "random_ghosting": SLOT_GHOST, "random_blur": SLOT_BLUR,
+                 "random_gamma": SLOT_GAMMA, "random_affine": SLOT_AFFINE, "random_flip": SLOT_FLIP}
+PIPELINE_REFUSED_KEYS = ("random_motion", "random_elastic")
+# words 32 .. 75 of a sample's draws (quads 8 .. 18): the seven gates and the flip's inner draw, the slot set, the noise, the affine
+_V_GATE, _V_FLIP_INNER, _V_GAMMA, _V_COEF, _V_STD, _V_INTENSITY, _X_GHOSTS, _X_AXIS, _V_NOISE_STD, _X_KEY, _V_SCALES, _V_DEGREES = (
+    32, 39, 40, 41, 61, 64, 65, 66, 67, 68, 70, 73)
+_PIPE_QUADS = 19
 
 
 def _words(seed: int, c1: int, c2, stream: int, nquads: int) -> np.ndarray:
@@ -132,6 +156,110 @@ class IntensityAugment:
         return meta, par
 
 
+def euler_matrix(degrees) -> np.ndarray:
+    """R = Rz Rx Ry in float64 (the order of ITK's Euler3DTransform by default) for the angles about axes 0, 1, 2 in degrees"""
+    ax, ay, az = (float(np.deg2rad(d)) for d in degrees)
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], dtype=np.float64)
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], dtype=np.float64)
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]], dtype=np.float64)
+    return Rz @ Rx @ Ry
+
+
+def affine_matrix(degrees, scales, spacing) -> np.ndarray:
+    """the affine's output-to-source voxel matrix M = diag(1 / s) diag(1 / scales) R^T diag(s) in float64, s the voxel spacing: an
+    offset from the centre in output voxels goes to mm, through the inverse of the rotation and of the scaling, and back to voxels"""
+    s = np.asarray(spacing, dtype=np.float64)
+    return np.diag(1.0 / s) @ np.diag(1.0 / np.asarray(scales, dtype=np.float64)) @ euler_matrix(degrees).T @ np.diag(s)
+
+
+class SliceAugment:
+    """The general recipe: get_augment's order as the eleven slots of cddpm_aug_pipeline -- RandomBiasField(p=.25), RandomNoise(p=.5),
+    RandomGhosting(p=.5), RandomBlur(p=.5), RandomGamma(p=.5), RandomAffine(p=.5), RandomFlip(axes=0, p=.5), then the `aug_intensity`
+    policy group of IntensityAugment -- with torchio's default ranges. `p`: slot bit -> probability; a slot that is not built has none.
+    The flip's bit is set when its gate AND RandomFlip's own flip_probability draw fall below their probabilities."""
+
+    KEY_P = {SLOT_BIAS: 0.25, SLOT_NOISE: 0.5, SLOT_GHOST: 0.5, SLOT_BLUR: 0.5, SLOT_GAMMA: 0.5, SLOT_AFFINE: 0.5, SLOT_FLIP: 0.5}
+    POLICY_P = {POLICY_GAMMA: 0.5, POLICY_BIAS: 0.25, POLICY_BLUR: 0.25, POLICY_GHOST: 0.5}      # IntensityAugment.DEFAULT_P
+    NOISE_STD = (0.0, 0.25)        # RandomNoise: mean = 0, std ~ U(0, 0.25)
+    SCALES = (0.9, 1.1)            # RandomAffine: scales = 0.1, degrees = 10, per axis; no translation
+    DEGREES = (-10.0, 10.0)
+    FLIP_PROBABILITY = 0.5         # RandomFlip's own draw, inside the p = .5 gate
+
+    def __init__(self, p=None):
+        self.p = dict({**self.KEY_P, **self.POLICY_P} if p is None else p)
+        for bit, v in self.p.items():
+            if bit not in SLOTS or not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"slot {bit!r} with probability {v!r}")
+
+    @property
+    def stages(self) -> Tuple[int, ...]:
+        """the slots that are built, in the order they are applied"""
+        return tuple(b for b in SLOTS if b in self.p)
+
+    @classmethod
+    def from_cfg(cls, cfg, onlyBrain=False, slice=None, seq_slices=None) -> "SliceAugment":
+        """get_augment(cfg) (create_dataset.py:220-250): every key of PIPELINE_KEYS that is set builds its slot with the reference's
+        probability, `aug_intensity` the four policy slots, in any combination. random_elastic, random_motion, `unique_slice` and
+        vol2slice's onlyBrain / slice / seq_slices are refused."""
+        def refuse(what):
+            raise NotImplementedError(f"augment: {what} is not built natively")
+        for key in PIPELINE_REFUSED_KEYS:
+            if _cfg_get(cfg, key, False):
+                refuse(f"get_augment's {key}")
+        if _cfg_get(cfg, "unique_slice", False):
+            refuse("vol2slice's unique_slice")
+        for name, v in (("onlyBrain", onlyBrain), ("slice", slice is not None), ("seq_slices", seq_slices is not None)):
+            if v:
+                refuse(f"vol2slice({name}=...)")
+        p = {bit: cls.KEY_P[bit] for key, bit in PIPELINE_KEYS.items() if _cfg_get(cfg, key, False)}
+        if _cfg_get(cfg, "aug_intensity", False):
+            p.update(cls.POLICY_P)
+        return cls(p=p)
+
+    def draw(self, seed: int, epoch: int, positions, D: int, spacing: Sequence[float] = (2.0, 2.0, 2.0), volumes=None):
+        """-> (meta [P, 8] int32, par [P, 64] fp32), the host tables of cddpm_aug_pipeline for the samples at `positions` of epoch
+        `epoch`'s global order; row p is a function of (seed, epoch, positions[p]) alone. Quads 0 .. 7 of the sample's draws mean what
+        they mean to IntensityAugment.draw: z, the policy gates and the policy set are its values bit for bit. Quads 8 .. 18 hold the
+        seven gates, the slot set (same ranges as the policy's), std ~ U(0, 0.25) and the two key words of the noise, and the affine's
+        scales ~ U(0.9, 1.1) and degrees ~ U(-10, 10) per axis, from which affine_matrix builds M in float64."""
+        positions = np.asarray(positions, dtype=np.int64).reshape(-1)
+        w = _words(int(seed), int(epoch), positions, STREAM_AUGMENT, _PIPE_QUADS)
+        u = synth._u01(w).astype(np.float64)
+        P = positions.shape[0]
+        policy = IntensityAugment(p={1 << k: self.p[bit] for k, bit in enumerate(SLOTS[7:]) if bit in self.p})
+        m4, p28 = policy.draw(seed, epoch, positions, D, spacing, volumes)
+        flags = m4[:, 2].astype(np.int32) << 7
+        for k, bit in enumerate(SLOTS[:7]):
+            if bit in self.p:
+                on = u[:, _V_GATE + k] < self.p[bit]
+                if bit == SLOT_FLIP:
+                    on &= u[:, _V_FLIP_INNER] < self.FLIP_PROBABILITY
+                flags |= np.where(on, bit, 0).astype(np.int32)
+
+        def span(lo_hi, x):
+            return lo_hi[0] + (lo_hi[1] - lo_hi[0]) * x
+        I = IntensityAugment
+        meta = np.zeros((P, PIPE_META), dtype=np.int32)
+        par = np.zeros((P, PIPE_PAR), dtype=np.float32)
+        meta[:, 0:2] = m4[:, 0:2]
+        meta[:, 2] = flags
+        lo, hi = I.NUM_GHOSTS
+        meta[:, 3] = (lo + _below(w[:, _X_GHOSTS], hi - lo + 1)) | (_below(w[:, _X_AXIS], 3) << 8)
+        meta[:, 4] = m4[:, 3]
+        meta[:, 5:7] = w[:, _X_KEY:_X_KEY + 2].view(np.int32)
+        par[:, 0] = np.exp(span(I.LOG_GAMMA, u[:, _V_GAMMA]))
+        par[:, 1:4] = span(I.STD, u[:, _V_STD:_V_STD + 3]) / np.asarray(spacing, dtype=np.float64).reshape(1, 3)
+        par[:, 4] = span(I.INTENSITY, u[:, _V_INTENSITY])
+        par[:, 5:25] = span(I.COEF, u[:, _V_COEF:_V_COEF + 20])
+        par[:, _SET:2 * _SET] = p28[:, :_SET]
+        par[:, _COL_NOISE_STD] = span(self.NOISE_STD, u[:, _V_NOISE_STD])
+        scales, degrees = span(self.SCALES, u[:, _V_SCALES:_V_SCALES + 3]), span(self.DEGREES, u[:, _V_DEGREES:_V_DEGREES + 3])
+        for r in range(P):
+            par[r, _COL_MATRIX:_COL_MATRIX + 9] = affine_matrix(degrees[r], scales[r], spacing).reshape(9)
+        return meta, par
+
+
 class VolumeBank:
     """Preprocessed volumes of one shape, resident on the device as [N, D, H, W] fp32 (slice-major: a slice is a contiguous [H, W] image).
     volumes: a list or tensor of [H, W, D] or [1, H, W, D] volumes -- torchio's layout, what the reference's cached subjects hold in
@@ -205,9 +333,10 @@ class DeviceSliceLoader:
     [k world B, (k + 1) world B) and rank r takes its rows [r B, (r + 1) B): the union over the ranks is the one-rank run of batch
     world * B, bit for bit. drop_last=False keeps a last, shorter global batch; a rank whose rows fall outside it yields nothing for it.
     Each step is one asynchronous host-to-device copy of the two tables and one cddpm_aug_slices call (CddpmEngine.augment_slices); the
-    workspace is asked for once. engine: the handle the call runs on (None: a handle of the smallest geometry, made here)."""
+    workspace is asked for once. augment: an IntensityAugment or None (that call), or a SliceAugment, whose tables go to
+    cddpm_aug_pipeline (CddpmEngine.augment_pipeline) instead. engine: the handle the call runs on (None: a handle of the smallest geometry, made here)."""
 
-    def __init__(self, bank: VolumeBank, batch_size: int, seed: int, augment: Optional[IntensityAugment] = None, shuffle: bool = True,
+    def __init__(self, bank: VolumeBank, batch_size: int, seed: int, augment=None, shuffle: bool = True,
                  drop_last: bool = True, rank: int = 0, world: int = 1, engine=None):
         if batch_size < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError(f"batch_size {batch_size}, rank {rank} of world {world}")
@@ -247,7 +376,8 @@ class DeviceSliceLoader:
         H, W, _D = self.bank.shape
         for first, count in self._rows():
             meta, par = self.tables(first, count)
-            x = self.engine.augment_slices(self.bank, meta, par)
+            call = self.engine.augment_pipeline if isinstance(self.augment, SliceAugment) else self.engine.augment_slices
+            x = call(self.bank, meta, par)
             yield {"vol": {"data": x.view(count, 1, H, W, 1)}}
 
     def close(self) -> None:

@@ -1144,6 +1144,30 @@ int cddpm_aug_slices(cddpm_handle h, const float* bank_dev, int N, int H, int W,
     return 0;
 }
 
+size_t cddpm_aug_pipeline_workspace_bytes(int B, int H, int W, int D) {
+    if (!aug_in_range(B, H, W, D)) {
+        fail(nullptr, "cddpm_aug_pipeline_workspace_bytes: B = %d outside 1 ... %d or volume %dx%dx%d outside 1 ... %d per axis", B, CDDPM_AUG_MAX_BATCH, H, W, D,
+             CDDPM_AUG_MAX_AXIS);
+        return 0;
+    }
+    return aug_pipeline_workspace_bytes(B, H, W, D);
+}
+
+int cddpm_aug_pipeline(cddpm_handle h, const float* bank_dev, int N, int H, int W, int D, const int32_t* meta_dev, const float* par_dev,
+                       int B, void* ws_dev, size_t ws_bytes, float* out_dev, void* stream) {
+    if (!h) return -1;
+    if (!bank_dev || !meta_dev || !par_dev || !ws_dev || !out_dev) return fail(h, "cddpm_aug_pipeline: NULL argument");
+    if (N < 1) return fail(h, "cddpm_aug_pipeline: a bank of %d volumes", N);
+    if (!aug_in_range(B, H, W, D))
+        return fail(h, "cddpm_aug_pipeline: B = %d outside 1 ... %d or volume %dx%dx%d outside 1 ... %d per axis", B, CDDPM_AUG_MAX_BATCH, H, W, D,
+                    CDDPM_AUG_MAX_AXIS);
+    const size_t need = aug_pipeline_workspace_bytes(B, H, W, D);
+    if (ws_bytes < need) return fail(h, "cddpm_aug_pipeline: workspace of %zu bytes, need %zu", ws_bytes, need);
+    HIPCHECK(h, hipSetDevice(h->device));
+    HIPCHECK(h, launch_aug_pipeline(bank_dev, N, H, W, D, meta_dev, par_dev, B, ws_dev, ws_bytes, out_dev, (hipStream_t)stream));
+    return 0;
+}
+
 // what the host can see of a preprocessing geometry; the reason, or NULL
 static const char* prep_refusal(int H, int W, int D, int stages, int allowed, int th, int tw, int td, double f) {
     const int M = CDDPM_PREP_MAX_AXIS;

@@ -301,6 +301,9 @@ hipError_t launch_eval_hausdorff(const uint8_t* pred, const float* seg, int R, i
 size_t aug_workspace_bytes(int B, int H, int W, int D);
 hipError_t launch_aug_slices(const float* bank, int N, int H, int W, int D, const int32_t* meta, const float* par, int B, void* ws,
                              size_t ws_bytes, float* out, hipStream_t s);
+size_t aug_pipeline_workspace_bytes(int B, int H, int W, int D);
+hipError_t launch_aug_pipeline(const float* bank, int N, int H, int W, int D, const int32_t* meta, const float* par, int B, void* ws,
+                               size_t ws_bytes, float* out, hipStream_t s);
 
 // raw volumes preprocessed on the device (preprocess.hip; src/datamodules/create_dataset.py:196-218, :252-258)
 size_t prep_workspace_bytes(int H, int W, int D, int stages, int th, int tw, int td, double f);

@@ -674,22 +674,55 @@ class CddpmEngine:
                 b = int(np.argmax(bad))
                 raise RuntimeError(f"cddpm_aug_slices: sample {b}: {what} (meta {meta[b].tolist()}, sigma {sig[b].tolist()})")
 
-    def _augment_buffers(self, B: int, H: int, W: int, D: int):
-        """cddpm_aug_slices' workspace, asked for once per geometry and largest batch through the library's own size query
-        (cddpm_aug_workspace_bytes, the operator-scratch convention), and two pinned staging rows for the tables, so that one copy can be
-        in flight while the next is filled. A smaller batch of the same geometry runs in the same buffers."""
+    def _augment_buffers(self, entry: str, B: int, H: int, W: int, D: int):
+        """the workspace of `entry` (cddpm_aug_slices or cddpm_aug_pipeline), asked for once per geometry and largest batch through the
+        library's own size query (cddpm_aug_workspace_bytes / cddpm_aug_pipeline_workspace_bytes, the operator-scratch convention), and two
+        pinned staging rows for the tables, so that one copy can be in flight while the next is filled. A smaller batch of the same
+        geometry runs in the same buffers."""
+        query, meta_n, par_n = self._AUG_ENTRIES[entry]
         key = (H, W, D)
-        st = getattr(self, "_aug", None)
+        cache = self.__dict__.setdefault("_aug", {})
+        st = cache.get(entry)
         if st is None or st["key"] != key or B > st["cap"]:
-            need = int(self.lib.cddpm_aug_workspace_bytes(B, H, W, D))
+            need = int(getattr(self.lib, query)(B, H, W, D))
             if need == 0:
-                raise RuntimeError(f"cddpm_aug_workspace_bytes: {self.lib.cddpm_last_error(None).decode()}")
-            row = 4 * (self.AUG_META + self.AUG_PAR)
-            st = self._aug = dict(key=key, cap=B, ws=torch.empty(need, dtype=torch.uint8, device=self.device),
-                                  host=[torch.empty(B * row, dtype=torch.uint8).pin_memory() for _ in range(2)],
-                                  dev=[torch.empty(B * row, dtype=torch.uint8, device=self.device) for _ in range(2)],
-                                  done=[None, None], turn=0)
+                raise RuntimeError(f"{query}: {self.lib.cddpm_last_error(None).decode()}")
+            row = 4 * (meta_n + par_n)
+            st = cache[entry] = dict(key=key, cap=B, ws=torch.empty(need, dtype=torch.uint8, device=self.device),
+                                     host=[torch.empty(B * row, dtype=torch.uint8).pin_memory() for _ in range(2)],
+                                     dev=[torch.empty(B * row, dtype=torch.uint8, device=self.device) for _ in range(2)],
+                                     done=[None, None], turn=0)
         return st
+
+    def _augment_call(self, entry: str, check, bank, meta, par, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """what augment_slices and augment_pipeline share: the host check of the two tables, their staging through pinned memory with ONE
+        asynchronous host-to-device copy, and the library call on the current stream"""
+        _query, meta_n, par_n = self._AUG_ENTRIES[entry]
+        meta = np.ascontiguousarray(meta.numpy() if isinstance(meta, torch.Tensor) else meta)
+        par = np.ascontiguousarray(par.numpy() if isinstance(par, torch.Tensor) else par)
+        data = _check_dev(bank.data, "bank.data", self.device)
+        N, D, H, W = data.shape
+        check(meta, par, N, D)
+        B = meta.shape[0]
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (B, H, W)
+              or not out.is_contiguous()):
+            raise RuntimeError(f"out must be a contiguous [{B}, {H}, {W}] float32 tensor on {self.device}")
+        st = self._augment_buffers(entry, B, H, W, D)
+        i = st["turn"]
+        st["turn"] = 1 - i
+        if st["done"][i] is not None:
+            st["done"][i].synchronize()                # the copy that last read this staging row (two calls ago) has long finished
+        host, dev, nm, tot = st["host"][i], st["dev"][i], B * 4 * meta_n, B * 4 * (meta_n + par_n)
+        host[:nm].view(torch.int32).view(B, meta_n).copy_(torch.from_numpy(meta))
+        host[nm:tot].view(torch.float32).view(B, par_n).copy_(torch.from_numpy(par))
+        dev[:tot].copy_(host[:tot], non_blocking=True)
+        st["done"][i] = torch.cuda.Event()
+        st["done"][i].record(torch.cuda.current_stream(self.device))
+        self._ck(getattr(self.lib, entry)(self._h, data.data_ptr(), N, H, W, D, dev.data_ptr(), dev.data_ptr() + nm, B,
+                                          st["ws"].data_ptr(), st["ws"].numel(), out.data_ptr(), _stream_ptr(self.device)), entry)
+        return out
 
     def augment_slices(self, bank, meta, par, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One batch of augmented training slices from a resident bank (cddpm_aug_slices; get_augment + vol2slice of the reference's
@@ -698,32 +731,46 @@ class CddpmEngine:
         (check_augment_tables: a bad row raises before anything is copied or enqueued and `out` stays untouched), staged through pinned
         memory with ONE asynchronous host-to-device copy, and applied by one library call on the current stream. Returns out [B, H, W]
         fp32 on the device (`out=`: written in place)."""
-        meta = np.ascontiguousarray(meta.numpy() if isinstance(meta, torch.Tensor) else meta)
-        par = np.ascontiguousarray(par.numpy() if isinstance(par, torch.Tensor) else par)
-        data = _check_dev(bank.data, "bank.data", self.device)
-        N, D, H, W = data.shape
-        self.check_augment_tables(meta, par, N, D)
-        B = meta.shape[0]
-        if out is None:
-            out = torch.empty(B, H, W, dtype=torch.float32, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (B, H, W)
-              or not out.is_contiguous()):
-            raise RuntimeError(f"out must be a contiguous [{B}, {H}, {W}] float32 tensor on {self.device}")
-        st = self._augment_buffers(B, H, W, D)
-        i = st["turn"]
-        st["turn"] = 1 - i
-        if st["done"][i] is not None:
-            st["done"][i].synchronize()                # the copy that last read this staging row (two calls ago) has long finished
-        host, dev, nm, tot = st["host"][i], st["dev"][i], B * 4 * self.AUG_META, B * 4 * (self.AUG_META + self.AUG_PAR)
-        host[:nm].view(torch.int32).view(B, self.AUG_META).copy_(torch.from_numpy(meta))
-        host[nm:tot].view(torch.float32).view(B, self.AUG_PAR).copy_(torch.from_numpy(par))
-        dev[:tot].copy_(host[:tot], non_blocking=True)
-        st["done"][i] = torch.cuda.Event()
-        st["done"][i].record(torch.cuda.current_stream(self.device))
-        self._ck(self.lib.cddpm_aug_slices(self._h, data.data_ptr(), N, H, W, D, dev.data_ptr(), dev.data_ptr() + nm, B,
-                                           st["ws"].data_ptr(), st["ws"].numel(), out.data_ptr(), _stream_ptr(self.device)),
-                 "cddpm_aug_slices")
-        return out
+        return self._augment_call("cddpm_aug_slices", self.check_augment_tables, bank, meta, par, out)
+
+    # the eleven-slot pipeline (include/cddpm.h, "The augmentation pipeline")
+    PIPE_META, PIPE_PAR, PIPE_ALL = 8, 64, 2047
+    PIPE_META_GHOST, PIPE_META_POLICY_GHOST, PIPE_PAR_SLOT, PIPE_PAR_POLICY, PIPE_PAR_NOISE_STD, PIPE_PAR_MATRIX = 3, 4, 0, 25, 50, 51
+    _AUG_ENTRIES = {"cddpm_aug_slices": ("cddpm_aug_workspace_bytes", AUG_META, AUG_PAR),
+                    "cddpm_aug_pipeline": ("cddpm_aug_pipeline_workspace_bytes", PIPE_META, PIPE_PAR)}
+
+    @classmethod
+    def check_pipeline_tables(cls, meta: np.ndarray, par: np.ndarray, N: int, D: int) -> None:
+        """check_augment_tables for cddpm_aug_pipeline's tables: meta [B, 8] int32 {volume, z, flags, g | axis << 8 of the ghosting slot
+        and of the policy ghosting, key0, key1, unused}, par [B, 64] fp32 {slot set [25], policy set [25], noise std, M[9], unused}.
+        g is the word's low byte, so every g a word can hold is in range; a negative word or an axis above 2 is refused per slot."""
+        if meta.ndim != 2 or meta.shape[1] != cls.PIPE_META or meta.dtype != np.int32:
+            raise RuntimeError(f"meta must be [B, {cls.PIPE_META}] int32, got {meta.shape} {meta.dtype}")
+        if par.shape != (meta.shape[0], cls.PIPE_PAR) or par.dtype != np.float32:
+            raise RuntimeError(f"par must be [{meta.shape[0]}, {cls.PIPE_PAR}] float32, got {par.shape} {par.dtype}")
+        if meta.shape[0] < 1:
+            raise RuntimeError("an empty batch")
+        checks = [(f"volume outside [0, {N})", (meta[:, 0] < 0) | (meta[:, 0] >= N)),
+                  (f"z outside [0, {D})", (meta[:, 1] < 0) | (meta[:, 1] >= D)),
+                  ("unknown flag bits", (meta[:, 2] & ~cls.PIPE_ALL) != 0)]
+        for name, col, par0 in (("slot", cls.PIPE_META_GHOST, cls.PIPE_PAR_SLOT), ("policy", cls.PIPE_META_POLICY_GHOST, cls.PIPE_PAR_POLICY)):
+            word, sig = meta[:, col], par[:, par0 + 1:par0 + 4]
+            checks += [(f"{name} ghosting word: g | axis << 8 with axis outside 0 ... 2", (word < 0) | ((word >> 8) > 2)),
+                       (f"{name} sigma_voxel outside [0, {cls.AUG_MAX_SIGMA:g}]", ~((sig >= 0) & (sig <= cls.AUG_MAX_SIGMA)).all(axis=1)),
+                       (f"a non-finite {name} parameter", ~np.isfinite(par[:, [par0] + list(range(par0 + 4, par0 + 25))]).all(axis=1))]
+        checks += [("a non-finite noise std", ~np.isfinite(par[:, cls.PIPE_PAR_NOISE_STD])),
+                   ("a non-finite affine matrix entry", ~np.isfinite(par[:, cls.PIPE_PAR_MATRIX:cls.PIPE_PAR_MATRIX + 9]).all(axis=1))]
+        for what, bad in checks:
+            if bad.any():
+                b = int(np.argmax(bad))
+                raise RuntimeError(f"cddpm_aug_pipeline: sample {b}: {what} (meta {meta[b].tolist()})")
+
+    def augment_pipeline(self, bank, meta, par, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One batch of training slices through get_augment's whole order (cddpm_aug_pipeline: the individual bias, noise, ghosting, blur
+        and gamma, the affine and the flip, then the policy group, then vol2slice). meta [B, 8] int32 and par [B, 64] fp32: HOST tables
+        as augment.SliceAugment.draw returns them. Checked (check_pipeline_tables), staged and applied exactly as augment_slices does.
+        Returns out [B, H, W] fp32 on the device (`out=`: written in place)."""
+        return self._augment_call("cddpm_aug_pipeline", self.check_pipeline_tables, bank, meta, par, out)
 
     # ------------------------------------------------------------------ preprocessed volumes (preprocess.hip)
     PREP_SMOOTH, PREP_CROPPAD, PREP_RESCALE, PREP_RESAMPLE, PREP_ALL, PREP_RECORD = 1, 2, 4, 8, 15, 16      # include/cddpm.h

@@ -422,6 +422,81 @@ size_t cddpm_aug_workspace_bytes(int B, int H, int W, int D);
 int cddpm_aug_slices(cddpm_handle h, const float* bank_dev, int N, int H, int W, int D, const int32_t* meta_dev, const float* par_dev,
                      int B, void* ws_dev, size_t ws_bytes, float* out_dev /* [B][H][W] */, void* stream);
 
+/* ---- The augmentation pipeline (csrc/augment.hip) -------------------------------------------------------
+ * get_augment (src/datamodules/create_dataset.py:220-250) composes its transforms in one fixed order, the individual keys first,
+ * then the `aug_intensity` policy group. This entry is that order as ELEVEN STAGE SLOTS, each gated per sample by one flag bit and
+ * with parameters of its own (the reference's probabilities in brackets; the draws are the caller's, augment.SliceAugment.draw):
+ *   random_bias (.25) . random_noise (.5) . random_ghosting (.5) . random_blur (.5) . random_gamma (.5) . random_affine (.5) .
+ *   random_flip (.5) . policy gamma (.5) . policy bias (.25) . policy blur (.25) . policy ghosting (.5)
+ * then vol2slice's one slice. random_motion (before the noise) and random_elastic (before the affine) are NOT built: their rules
+ * live in a k-space composite and in SimpleITK's B-spline transform. Mask and label volumes are not transformed: the training step
+ * reads `vol` only. Status: PINNED TO NUMPY / SCIPY, UNPINNED TO TORCHIO AND SIMPLEITK (tests/augment_pipeline_reference.py).
+ * Bank, axis numbers, extents, the stream and the allocation rule, the status words at the head of the workspace and the -1
+ * errors are those of cddpm_aug_slices above; a flagged sample's output is never written.
+ *   meta_dev [B][CDDPM_PIPE_META] int32: {volume, z, flags, g | axis << 8 of the ghosting slot, g | axis << 8 of the policy
+ *            ghosting, key0, key1, unused} -- key0 and key1 are the two Philox key words of the noise stage.
+ *   par_dev  [B][CDDPM_PIPE_PAR] fp32: {slot set [25], policy set [25], noise std, M[9], 4 unused}. A set is the 25 columns
+ *            {gamma, sigma0, sigma1, sigma2, I, c[20]} of cddpm_aug_slices' par (CDDPM_AUG_PAR_* from the set's first column):
+ *            the slot set at CDDPM_PIPE_PAR_SLOT serves the individual bias, ghosting, blur and gamma, the policy set at
+ *            CDDPM_PIPE_PAR_POLICY the policy group. M is the affine's row-major 3 x 3 matrix over the axes (H, W, D).
+ * Stages. Every one computes in double and rounds to fp32 once; flags = 0 is a bit-exact copy of the slice.
+ *   CDDPM_PIPE_BIAS, _BLUR, _GAMMA   the rules of CDDPM_AUG_BIAS, _BLUR, _GAMMA with the slot set; bias and gamma are passes of
+ *                    their own here (the noise, ghosting and blur slots lie between them).
+ *   CDDPM_PIPE_GHOST the rule of CDDPM_AUG_GHOST with the slot set, evaluated at EVERY voxel, since later stages read them all:
+ *                    about n L double multiply-adds per sample for n voxels and an axis of L.
+ *   CDDPM_PIPE_NOISE y = x + std n(v), mean 0 (torchio's RandomNoise draws std from U(0, 0.25)). v is the voxel's index in the
+ *                    bank's memory order, (d H + h) W + w. Philox4x32-10 keyed by (key0, key1) at the counter
+ *                    (v / 4, 0, 0, 0x6002) gives four words; u = ((word >> 9) + 0.5) 2^-23; the quad's four normals are
+ *                    r_a cos(2 pi u_1), r_a sin(2 pi u_1), r_b cos(2 pi u_3), r_b sin(2 pi u_3) with r_a = sqrt(-2 ln u_0),
+ *                    r_b = sqrt(-2 ln u_2) (the order of synth.normal_quads), and voxel v takes number v % 4. The rule is the
+ *                    real-number function of the two uniforms, evaluated in double. std = 0 leaves the volume bit for bit.
+ *   CDDPM_PIPE_AFFINE torchio's RandomAffine with its defaults: scales U(0.9, 1.1) and degrees U(-10, 10) per axis, no
+ *                    translation, centre of the image, linear interpolation, default_pad_value = 'minimum'. The caller builds
+ *                    R = Rz Rx Ry (ITK's Euler3DTransform order) in float64 and the output-to-source voxel matrix
+ *                    M = diag(1 / s) diag(1 / scales) R^T diag(s), s the voxel spacing, and rounds M to fp32 into the table. For
+ *                    the output voxel p the source point is q = c + M (p - c) in double, c = (L - 1) / 2 per axis. q is inside
+ *                    iff -0.5 <= q_a <= L_a - 0.5 on all three axes. Inside: trilinear interpolation in double over floor(q)
+ *                    and floor(q) + 1, both clamped to [0, L - 1]. Outside: the minimum of the volume being transformed (the
+ *                    sample's volume after the earlier slots), an exact reduction computed only when the bit is set; volumes are
+ *                    taken to be finite. Whether a positive angle turns as torchio's does (RAS against LPS) cannot be pinned
+ *                    here; the draw is symmetric about 0, so either sign has the same distribution.
+ *   CDDPM_PIPE_FLIP  RandomFlip(axes = 0): y[h] = x[H - 1 - h], exact. One gather serves affine and flip: with both bits set the
+ *                    output voxel p takes the affine's sample at flip(p), which is the flip applied to the affine's output.
+ *   CDDPM_PIPE_POLICY_GAMMA, _BIAS, _BLUR, _GHOST   cddpm_aug_slices' four stages with the policy set: a row with only these bits
+ *                    gives that entry's output for the corresponding four-bit row, bit for bit.
+ * A row is flagged as there (CDDPM_AUG_BAD_* bits; the axis and sigma checks cover both sets, the value check also the std and M). */
+#define CDDPM_PIPE_BIAS 1
+#define CDDPM_PIPE_NOISE 2
+#define CDDPM_PIPE_GHOST 4
+#define CDDPM_PIPE_BLUR 8
+#define CDDPM_PIPE_GAMMA 16
+#define CDDPM_PIPE_AFFINE 32
+#define CDDPM_PIPE_FLIP 64
+#define CDDPM_PIPE_POLICY_GAMMA 128
+#define CDDPM_PIPE_POLICY_BIAS 256
+#define CDDPM_PIPE_POLICY_BLUR 512
+#define CDDPM_PIPE_POLICY_GHOST 1024
+#define CDDPM_PIPE_ALL 2047
+#define CDDPM_PIPE_META 8
+#define CDDPM_PIPE_META_GHOST 3
+#define CDDPM_PIPE_META_POLICY_GHOST 4
+#define CDDPM_PIPE_META_KEY 5            /* 5, 6 */
+#define CDDPM_PIPE_PAR 64
+#define CDDPM_PIPE_PAR_SLOT 0
+#define CDDPM_PIPE_PAR_POLICY 25
+#define CDDPM_PIPE_PAR_NOISE_STD 50
+#define CDDPM_PIPE_PAR_MATRIX 51         /* 51 ... 59 */
+
+/* workspace bytes of cddpm_aug_pipeline: as cddpm_aug_workspace_bytes, with the tables of two parameter sets. Host arithmetic,
+ * callable without a GPU; outside the supported range: 0, with the reason in cddpm_last_error(NULL). */
+size_t cddpm_aug_pipeline_workspace_bytes(int B, int H, int W, int D);
+
+/* out_dev [B][H][W] fp32: sample b is slice z_b of volume_b after the slots its flags select. Runs on `stream`; nothing allocates
+ * or synchronises inside. A sample's result depends on its own table row alone and its arithmetic runs in a fixed order: bitwise
+ * reproducible, and independent of the batch it is computed in. */
+int cddpm_aug_pipeline(cddpm_handle h, const float* bank_dev, int N, int H, int W, int D, const int32_t* meta_dev, const float* par_dev,
+                       int B, void* ws_dev, size_t ws_bytes, float* out_dev /* [B][H][W] */, void* stream);
+
 /* ---- Preprocessed volumes (csrc/preprocess.hip) ------------------------------------------------------------
  * Replaces what the reference's datamodule does to a volume on the CPU before it is cached (Train) or handed to test_step (Eval,
  * which has no cache, src/datamodules/create_dataset.py:52-92): sitk_reader's CurvatureFlow (:252-258) and get_transform's

@@ -6,7 +6,11 @@ those; the workspace is sized by the warm-up. Needs an MI355X: no device, no num
 The wall time of the float32 numpy / scipy restatement of the same 32 samples (tests/augment_reference.py) on this host's CPU with
 `--threads` threads is printed beside it for scale only: another algorithm on another processor, no comparison of kernels.
 
-    python tools/augment_bench.py [--reps 50] [--out profiles/augment_bench.json]
+`--recipe pipeline` times the eleven-slot pipeline the same way (CddpmEngine.augment_pipeline, cddpm_aug_pipeline): SliceAugment's own draw
+(bias p=.25, noise, ghosting, blur, gamma, affine p=.5, flip p=.25, then the policy group) and every slot on in every sample, beside
+the restatement of tests/augment_pipeline_reference.py, and writes profiles/augment_pipeline_bench.json.
+
+    python tools/augment_bench.py [--reps 50] [--recipe intensity|pipeline] [--out profiles/augment_bench.json]
 """
 import argparse
 import importlib
@@ -32,11 +36,15 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "augment_bench.json"))
+    ap.add_argument("--recipe", choices=("intensity", "pipeline"), default="intensity")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    pipe = a.recipe == "pipeline"
+    a.out = a.out or os.path.join(ROOT, "profiles", "augment_pipeline_bench.json" if pipe else "augment_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("no HIP device: the augmentation is timed on an MI355X or not at all")
     import augment_reference as AR
+    import augment_pipeline_reference as PR
     A = importlib.import_module(f"{PKG}.augment")
     eng = importlib.import_module(f"{PKG}.engine").CddpmEngine(timesteps=2, max_batch=1, max_h=16, max_w=16)
     stream = torch.cuda.current_stream(eng.device)
@@ -45,30 +53,34 @@ def main():
     bank = A.VolumeBank(vols, eng.device)
     order = A.epoch_order(0, 0, VOLUMES)
     pos = np.arange(BATCH)
-    drawn = A.IntensityAugment().draw(0, 0, pos, SHAPE[2], bank.spacing, volumes=order[pos % VOLUMES])
+    recipe = A.SliceAugment() if pipe else A.IntensityAugment()
+    call, restate = (eng.augment_pipeline, PR.pipeline_slice) if pipe else (eng.augment_slices, AR.augment_slice)
+    names = ("bias", "noise", "ghost", "blur", "gamma", "affine", "flip", "policy_gamma", "policy_bias", "policy_blur", "policy_ghost") if pipe else (
+        "gamma", "bias", "blur", "ghost")
+    drawn = recipe.draw(0, 0, pos, SHAPE[2], bank.spacing, volumes=order[pos % VOLUMES])
     every = (drawn[0].copy(), drawn[1].copy())
-    every[0][:, 2] = 15
+    every[0][:, 2] = (1 << len(names)) - 1
     rows = []
     for name, (meta, par) in (("recipe draw", drawn), ("every stage on", every)):
         for _ in range(a.warmup):
-            out = eng.augment_slices(bank, meta, par)
+            out = call(bank, meta, par)
         torch.cuda.synchronize()
         ts = []
         for _ in range(a.reps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-            eng.augment_slices(bank, meta, par)
+            call(bank, meta, par)
             e1.record(stream)
             e1.synchronize()
             ts.append(e0.elapsed_time(e1))
         got = out.cpu().numpy()
         t0 = time.perf_counter()
         with ThreadPoolExecutor(a.threads) as ex:
-            ref = list(ex.map(lambda b: AR.augment_slice(vols[meta[b, 0]], meta[b], par[b], np.float32), range(BATCH)))
+            ref = list(ex.map(lambda b: restate(vols[meta[b, 0]], meta[b], par[b], np.float32), range(BATCH)))
         host_ms = (time.perf_counter() - t0) * 1e3
         err = max(float(np.abs(got[b] - ref[b]).max()) for b in range(BATCH))
         row = dict(batch=name, samples=BATCH, shape=list(SHAPE), bank_volumes=VOLUMES,
-                   stage_counts={k: int(((meta[:, 2] & bit) != 0).sum()) for k, bit in (("gamma", 1), ("bias", 2), ("blur", 4), ("ghost", 8))},
+                   stage_counts={k: int(((meta[:, 2] & (1 << i)) != 0).sum()) for i, k in enumerate(names)},
                    device_ms_median=statistics.median(ts), device_ms_min=min(ts), max_abs_delta_vs_float32_restatement=err,
                    scipy_host_ms=host_ms, scipy_host_threads=a.threads,
                    scipy_host_note="another algorithm on another processor: for scale only")
@@ -78,7 +90,8 @@ def main():
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(dict(device=torch.cuda.get_device_name(0), reps=a.reps, warmup=a.warmup,
-                       method="device events around one CddpmEngine.augment_slices call (table check, one H2D copy, cddpm_aug_slices), median",
+                       method=f"device events around one CddpmEngine.{call.__name__} call (table check, one H2D copy, "
+                              f"{'cddpm_aug_pipeline' if pipe else 'cddpm_aug_slices'}), median",
                        rows=rows), f, indent=1)
 
 
