@@ -674,6 +674,19 @@ int cddpm_op_enc_stem_wgrad(cddpm_handle h, const float* x_dev, const float* dz_
     launch_enc_stem_wgrad(x_dev, dz_dev, part, dw_dev, B, H, W, s);
     OP_EPILOGUE()
 }
+// BatchNorm of the dense ResNet-50: batchnorm_train.hip without a mask, on this entry's own plan -- N / 256 pixel chunks (it fixes the order
+// of the fp64 sums and the grid), 2 planes per chunk in the backward (no inactive pixels, no dfill), C a multiple of 64, and N = 1 accepted
+// (the biased variance folds into run_var: no status word)
+static int enc_bn_chunks(int64_t N) {
+    int64_t n = N / 256;            // >= 16 pixels per pixel lane of a chunk; the folds read the chunks serially
+    if (n > 32) n = 32;
+    return n < 1 ? 1 : (int)n;
+}
+static BnShape enc_bn_shape(int64_t N, int HW, int C) {
+    BnShape g;
+    g.N = N; g.HW = HW; g.C = C; g.active = nullptr; g.f = 1; g.H = g.W = 0;
+    return g;
+}
 static double* enc_bn_scratch(OpScratch& sc, int64_t N, int C, bool backward, float*& k) {
     double* part = sc.n<double>((size_t)enc_bn_chunks(N) * 2 * C);
     k = backward ? sc.n<float>((size_t)2 * C) : nullptr;
@@ -690,8 +703,9 @@ int cddpm_op_enc_bn_forward(cddpm_handle h, const float* z_dev, const float* gam
     float* k;
     double* part = enc_bn_scratch(sc, N, C, false, k);
     SCRATCH_CHECK(sc)
-    launch_enc_bn_forward(z_dev, gamma_dev, beta_dev, sample_scale_dev, res_dev, relu, eps, momentum, run_mean_dev, run_var_dev, mean_rstd_dev, y_dev,
-                          part, N, HW, C, s);
+    const BnShape g = enc_bn_shape(N, HW, C);
+    launch_bn_train_stats(g, z_dev, enc_bn_chunks(N), eps, momentum, run_mean_dev, run_var_dev, mean_rstd_dev, part, nullptr, s);
+    launch_bn_train_act(g, z_dev, mean_rstd_dev, gamma_dev, beta_dev, sample_scale_dev, res_dev, nullptr, relu != 0, y_dev, s);
     OP_EPILOGUE()
 }
 int cddpm_op_enc_bn_backward(cddpm_handle h, const float* z_dev, const float* y_dev, const float* dy_dev, const float* mean_rstd_dev,
@@ -703,8 +717,8 @@ int cddpm_op_enc_bn_backward(cddpm_handle h, const float* z_dev, const float* y_
     float* k;
     double* part = enc_bn_scratch(sc, N, C, true, k);
     SCRATCH_CHECK(sc)
-    launch_enc_bn_backward(z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, sample_scale_dev, relu, dz_dev, dres_dev, dgamma_dev, dbeta_dev, k, part, N,
-                           HW, C, s);
+    launch_bn_train_backward(enc_bn_shape(N, HW, C), z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, sample_scale_dev, relu != 0, 1, enc_bn_chunks(N), 2,
+                             dz_dev, dres_dev, dgamma_dev, dbeta_dev, nullptr, k, part, s);
     OP_EPILOGUE()
 }
 int cddpm_op_enc_maxpool(cddpm_handle h, const float* x_dev, float* y_dev, int B, int H, int W, int C, int backward, const float* dy_dev, float* dx_dev,
@@ -816,6 +830,19 @@ static bool spark_bn_shape_ok(int64_t N, int HW, int C, bool masked, int f, int 
     return N > 0 && N <= 0x7FFFFFFF && H > 0 && W > 0 && HW > 0 && (int64_t)H * W == HW && N % HW == 0 && C >= 4 && C % 4 == 0 && C <= 65536 &&
            (!masked || (f >= 1 && H % f == 0 && W % f == 0 && (N / HW) * f * f <= 0x7FFFFFFF));
 }
+// sparse / dense BatchNorm of SparK pre-training: batchnorm_train.hip on this entry's own plan -- N C / 16384 pixel chunks, 3 planes per chunk
+// in the backward (the third: the sums over inactive pixels, dfill), C a multiple of 4, and fewer than two values per channel reported
+// through the status words with nothing written
+static int spark_bn_chunks(int64_t N, int C) {
+    int64_t n = N * C / 16384;            // >= 16 K elements per chunk; the folds read the chunks serially
+    if (n > 128) n = 128;
+    return n < 1 ? 1 : (int)n;
+}
+static BnShape spark_bn_shape(int64_t N, int HW, int C, const uint8_t* active, int f, int H, int W) {
+    BnShape g;
+    g.N = N; g.HW = HW; g.C = C; g.active = active; g.f = f; g.H = H; g.W = W;
+    return g;
+}
 static double* spark_bn_scratch(OpScratch& sc, int64_t N, int C, bool backward, float*& k, int*& status) {
     double* part = sc.n<double>((size_t)spark_bn_chunks(N, C) * (backward ? 3 : 2) * C);
     k = backward ? sc.n<float>((size_t)2 * C) : nullptr;
@@ -845,13 +872,13 @@ int cddpm_op_spark_bn_forward(cddpm_handle h, const float* z_dev, const float* g
     OP_PROLOGUE(PC_ENC, 0.0, 0.0,
                 z_dev && gamma_dev && beta_dev && mean_rstd_dev && y_dev && spark_aligned({z_dev, gamma_dev, beta_dev, res_dev, mean_rstd_dev, y_dev, fill_dev}),
                 "cddpm_op_spark_bn_forward: NULL argument or a tensor that is not 16-byte aligned")
-    const int B = (int)(N / HW);
+    const BnShape g = spark_bn_shape(N, HW, C, active_dev, f, H, W);
     OpScratch sc(h, s);
     float* k; int* status;
     double* part = spark_bn_scratch(sc, N, C, false, k, status);
     SCRATCH_CHECK(sc)
     if (training) {
-        launch_spark_bn_stats(z_dev, active_dev, f, B, H, W, C, eps, momentum, run_mean_dev, run_var_dev, mean_rstd_dev, part, status, s);
+        launch_bn_train_stats(g, z_dev, spark_bn_chunks(N, C), eps, momentum, run_mean_dev, run_var_dev, mean_rstd_dev, part, status, s);
         if (active_dev) {        // n_act is the device's count: read its verdict back before anything is written from statistics of one row
             int st[2] = {0, 0};
             HIPCHECK(h, hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, s));
@@ -861,9 +888,9 @@ int cddpm_op_spark_bn_forward(cddpm_handle h, const float* z_dev, const float* g
                                "(torch's BatchNorm1d raises here)", st[1]);
         }
     } else {
-        launch_spark_bn_eval_stats(run_mean_dev, run_var_dev, eps, C, mean_rstd_dev, s);
+        launch_bn_eval_stats(run_mean_dev, run_var_dev, eps, C, mean_rstd_dev, s);
     }
-    launch_spark_bn_act(z_dev, mean_rstd_dev, gamma_dev, beta_dev, sample_scale_dev, res_dev, active_dev, f, fill_dev, act, y_dev, B, H, W, C, s);
+    launch_bn_train_act(g, z_dev, mean_rstd_dev, gamma_dev, beta_dev, sample_scale_dev, res_dev, fill_dev, act, y_dev, s);
     OP_EPILOGUE()
 }
 int cddpm_op_spark_bn_backward(cddpm_handle h, const float* z_dev, const float* y_dev, const float* dy_dev, const float* mean_rstd_dev,
@@ -881,8 +908,8 @@ int cddpm_op_spark_bn_backward(cddpm_handle h, const float* z_dev, const float* 
     float* k; int* status;
     double* part = spark_bn_scratch(sc, N, C, true, k, status);
     SCRATCH_CHECK(sc)
-    launch_spark_bn_backward(z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, sample_scale_dev, act, active_dev, f, training, dz_dev, dres_dev, dgamma_dev,
-                             dbeta_dev, dfill_dev, k, part, (int)(N / HW), H, W, C, s);
+    launch_bn_train_backward(spark_bn_shape(N, HW, C, active_dev, f, H, W), z_dev, y_dev, dy_dev, mean_rstd_dev, gamma_dev, sample_scale_dev, act, training,
+                             spark_bn_chunks(N, C), 3, dz_dev, dres_dev, dgamma_dev, dbeta_dev, dfill_dev, k, part, s);
     OP_EPILOGUE()
 }
 int cddpm_op_spark_mask_mul(cddpm_handle h, const float* x_dev, const uint8_t* active_dev, float* y_dev, int B, int H, int W, int C, int f, void* stream) {

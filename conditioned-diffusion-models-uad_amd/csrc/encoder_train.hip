@@ -10,11 +10,8 @@
 //                          where that division is exact): K in {1, 3}, stride in {1, 2}, weights as [taps][K-dim][N-dim] images
 //   enc_wgrad_kernel       dW: contraction over output pixels, 64 ci x 64 co per workgroup and tap, P pixel ranges, fixed-order fold
 //   enc_stem_*             the 7 x 7 / 2 single-channel stem: forward and dW (its input gradient is never needed)
-//   enc_chan_partial / fold   per-channel reductions in fp64: BatchNorm batch statistics (+ running-statistics update, momentum 0.1,
-//                          unbiased running variance as torch) and the two sums of its backward
-//   enc_bn_act / enc_bn_bwd_apply   y = relu(((z - mean) rstd gamma + beta) s[b] + res) and its backward (s[b]: stochastic-depth scale
-//                          of the residual branch per sample, 1 when unused)
 //   max-pool 3x3/2 backward (gather form: deterministic), global average pool forward / backward, weight image packing
+// The training-mode BatchNorm (+ ReLU, shortcut, stochastic-depth scale) behind cddpm_op_enc_bn_* is batchnorm_train.hip.
 #include "kernels.h"
 #include <hip/hip_runtime.h>
 
@@ -292,155 +289,6 @@ void launch_enc_stem_wgrad(const float* x, const float* dz, double* part /* 32 *
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, P = 32;
     hipLaunchKernelGGL(enc_stem_wgrad_kernel, dim3(49, P), dim3(256), 0, s, x, dz, part, B, H, W, Ho, Wo, P);
     hipLaunchKernelGGL(enc_stem_wgrad_fold_kernel, dim3((49 * 64 + 255) / 256), dim3(256), 0, s, part, P, dw);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- BatchNorm (+ ReLU, shortcut)
-// per-channel pair of sums over the N = B * HW pixels, in fp64: workgroup = (pixel chunk, 64 channels), thread = (channel quad, pixel lane)
-//   MODE 0: (sum z, sum z^2)      MODE 1: g = dy [y > 0 if relu] s[b]; (sum g, sum g zhat), zhat = (z - mean) rstd
-template <int MODE>
-__global__ __launch_bounds__(256) void enc_chan_partial_kernel(const float* __restrict__ z, const float* __restrict__ y, const float* __restrict__ dy,
-                                                               const float* __restrict__ mr, const float* __restrict__ sscale, int relu,
-                                                               long long N, int HW, int C, int nchunk, double* __restrict__ part) {
-    __shared__ double red[2][16][64 + 1];
-    const int tid = threadIdx.x, q = tid & 15, r = tid >> 4, c = blockIdx.y * 64 + 4 * q;
-    const long long per = (N + nchunk - 1) / nchunk, p0 = per * blockIdx.x, p1 = p0 + per < N ? p0 + per : N;
-    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
-    float mean[4] = {0, 0, 0, 0}, rstd[4] = {1, 1, 1, 1};
-    if (MODE == 1)
-        for (int i = 0; i < 4; ++i) { mean[i] = mr[c + i]; rstd[i] = mr[C + c + i]; }
-    for (long long p = p0 + r; p < p1; p += 16) {
-        const float4 zv = *reinterpret_cast<const float4*>(z + (size_t)p * C + c);
-        const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
-        if (MODE == 0) {
-            for (int i = 0; i < 4; ++i) { s0[i] += zz[i]; s1[i] += (double)zz[i] * zz[i]; }
-        } else {
-            const float4 dv = *reinterpret_cast<const float4*>(dy + (size_t)p * C + c);
-            float gg[4] = {dv.x, dv.y, dv.z, dv.w};
-            if (relu) {
-                const float4 yv = *reinterpret_cast<const float4*>(y + (size_t)p * C + c);
-                const float yy[4] = {yv.x, yv.y, yv.z, yv.w};
-                for (int i = 0; i < 4; ++i) gg[i] = yy[i] > 0.f ? gg[i] : 0.f;
-            }
-            const float sc = sscale ? sscale[p / HW] : 1.f;
-            for (int i = 0; i < 4; ++i) {
-                const float g = gg[i] * sc;
-                s0[i] += g;
-                s1[i] += (double)g * ((zz[i] - mean[i]) * rstd[i]);
-            }
-        }
-    }
-    for (int i = 0; i < 4; ++i) { red[0][r][4 * q + i] = s0[i]; red[1][r][4 * q + i] = s1[i]; }
-    __syncthreads();
-    if (tid < 128) {
-        const int w = tid >> 6, cc = tid & 63;
-        double t = 0;
-        for (int k = 0; k < 16; ++k) t += red[w][k][cc];
-        part[((size_t)blockIdx.x * 2 + w) * C + blockIdx.y * 64 + cc] = t;
-    }
-}
-// batch statistics: mr = (mean | rstd); running statistics as torch.nn.BatchNorm2d in training mode (momentum, unbiased variance)
-__global__ __launch_bounds__(256) void enc_bn_stats_fold_kernel(const double* __restrict__ part, int nchunk, int C, long long N, float eps, float momentum,
-                                                                float* __restrict__ mr, float* __restrict__ run_mean, float* __restrict__ run_var) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s0 = 0, s1 = 0;
-    for (int k = 0; k < nchunk; ++k) { s0 += part[((size_t)k * 2) * C + c]; s1 += part[((size_t)k * 2 + 1) * C + c]; }
-    const double mean = s0 / (double)N;
-    double var = s1 / (double)N - mean * mean;
-    if (var < 0) var = 0;
-    mr[c] = (float)mean;
-    mr[C + c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (run_mean) {
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)mean;
-        const double unb = N > 1 ? var * (double)N / (double)(N - 1) : var;
-        run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)unb;
-    }
-}
-// backward sums -> dgamma, dbeta and the two per-channel means the elementwise pass needs (k = (sum g / N | sum g zhat / N))
-__global__ __launch_bounds__(256) void enc_bn_bwd_fold_kernel(const double* __restrict__ part, int nchunk, int C, long long N, float* __restrict__ dgamma,
-                                                              float* __restrict__ dbeta, float* __restrict__ k) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s0 = 0, s1 = 0;
-    for (int j = 0; j < nchunk; ++j) { s0 += part[((size_t)j * 2) * C + c]; s1 += part[((size_t)j * 2 + 1) * C + c]; }
-    dbeta[c] = (float)s0;
-    dgamma[c] = (float)s1;
-    k[c] = (float)(s0 / (double)N);
-    k[C + c] = (float)(s1 / (double)N);
-}
-__global__ __launch_bounds__(256) void enc_bn_act_kernel(const float* __restrict__ z, const float* __restrict__ mr, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, const float* __restrict__ sscale, const float* __restrict__ res,
-                                                         int relu, float* __restrict__ y, long long N, int HW, int C) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int nq = C >> 2;
-    if (e >= N * nq) return;
-    const int c = 4 * (int)(e % nq);
-    const long long p = e / nq;
-    const float4 zv = *reinterpret_cast<const float4*>(z + (size_t)p * C + c);
-    const float4 m = *reinterpret_cast<const float4*>(mr + c), rs = *reinterpret_cast<const float4*>(mr + C + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c);
-    const float sc = sscale ? sscale[p / HW] : 1.f;
-    float4 o;
-    o.x = ((zv.x - m.x) * rs.x * g.x + b.x) * sc; o.y = ((zv.y - m.y) * rs.y * g.y + b.y) * sc;
-    o.z = ((zv.z - m.z) * rs.z * g.z + b.z) * sc; o.w = ((zv.w - m.w) * rs.w * g.w + b.w) * sc;
-    if (res) {
-        const float4 rv = *reinterpret_cast<const float4*>(res + (size_t)p * C + c);
-        o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
-    }
-    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-    *reinterpret_cast<float4*>(y + (size_t)p * C + c) = o;
-}
-// dz = gamma rstd (g - k0 - zhat k1), g = dy [y > 0] s[b]; dres (optional) = dy [y > 0]: the gradient of the shortcut operand
-__global__ __launch_bounds__(256) void enc_bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ y, const float* __restrict__ dy,
-                                                               const float* __restrict__ mr, const float* __restrict__ gamma, const float* __restrict__ k,
-                                                               const float* __restrict__ sscale, int relu, float* __restrict__ dz,
-                                                               float* __restrict__ dres, long long N, int HW, int C) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int nq = C >> 2;
-    if (e >= N * nq) return;
-    const int c = 4 * (int)(e % nq);
-    const long long p = e / nq;
-    const float4 zv = *reinterpret_cast<const float4*>(z + (size_t)p * C + c);
-    float4 dv = *reinterpret_cast<const float4*>(dy + (size_t)p * C + c);
-    if (relu) {
-        const float4 yv = *reinterpret_cast<const float4*>(y + (size_t)p * C + c);
-        dv.x = yv.x > 0.f ? dv.x : 0.f; dv.y = yv.y > 0.f ? dv.y : 0.f; dv.z = yv.z > 0.f ? dv.z : 0.f; dv.w = yv.w > 0.f ? dv.w : 0.f;
-    }
-    if (dres) *reinterpret_cast<float4*>(dres + (size_t)p * C + c) = dv;
-    const float sc = sscale ? sscale[p / HW] : 1.f;
-    const float4 m = *reinterpret_cast<const float4*>(mr + c), rs = *reinterpret_cast<const float4*>(mr + C + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 k0 = *reinterpret_cast<const float4*>(k + c), k1 = *reinterpret_cast<const float4*>(k + C + c);
-    float4 o;
-    o.x = g.x * rs.x * (dv.x * sc - k0.x - (zv.x - m.x) * rs.x * k1.x);
-    o.y = g.y * rs.y * (dv.y * sc - k0.y - (zv.y - m.y) * rs.y * k1.y);
-    o.z = g.z * rs.z * (dv.z * sc - k0.z - (zv.z - m.z) * rs.z * k1.z);
-    o.w = g.w * rs.w * (dv.w * sc - k0.w - (zv.w - m.w) * rs.w * k1.w);
-    *reinterpret_cast<float4*>(dz + (size_t)p * C + c) = o;
-}
-int enc_bn_chunks(long long N) {
-    long long n = N / 256;            // >= 16 pixels per pixel lane of a chunk; the folds read the chunks serially
-    if (n > 32) n = 32;
-    return n < 1 ? 1 : (int)n;
-}
-void launch_enc_bn_forward(const float* z, const float* gamma, const float* beta, const float* sscale, const float* res, int relu, float eps,
-                           float momentum, float* run_mean, float* run_var, float* mr, float* y, double* part, long long N, int HW, int C,
-                           hipStream_t s) {
-    const int nchunk = enc_bn_chunks(N);
-    hipLaunchKernelGGL(enc_chan_partial_kernel<0>, dim3(nchunk, C / 64), dim3(256), 0, s, z, nullptr, nullptr, nullptr, nullptr, 0, N, HW, C, nchunk, part);
-    hipLaunchKernelGGL(enc_bn_stats_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, nchunk, C, N, eps, momentum, mr, run_mean, run_var);
-    const long long total = N * (C / 4);
-    hipLaunchKernelGGL(enc_bn_act_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, z, mr, gamma, beta, sscale, res, relu, y, N, HW, C);
-}
-void launch_enc_bn_backward(const float* z, const float* y, const float* dy, const float* mr, const float* gamma, const float* sscale, int relu,
-                            float* dz, float* dres, float* dgamma, float* dbeta, float* k /* 2 C */, double* part, long long N, int HW, int C,
-                            hipStream_t s) {
-    const int nchunk = enc_bn_chunks(N);
-    hipLaunchKernelGGL(enc_chan_partial_kernel<1>, dim3(nchunk, C / 64), dim3(256), 0, s, z, y, dy, mr, sscale, relu, N, HW, C, nchunk, part);
-    hipLaunchKernelGGL(enc_bn_bwd_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, nchunk, C, N, dgamma, dbeta, k);
-    const long long total = N * (C / 4);
-    hipLaunchKernelGGL(enc_bn_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, z, y, dy, mr, gamma, k, sscale, relu, dz, dres,
-                       N, HW, C);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- pooling

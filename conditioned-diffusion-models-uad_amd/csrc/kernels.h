@@ -333,20 +333,46 @@ void launch_enc_wgrad_p16(const float* x, const float* dz, float* part, int P, f
                           hipStream_t s);
 void launch_enc_stem_fwd(const float* x, const float* w, float* z, int B, int H, int W, hipStream_t s);
 void launch_enc_stem_wgrad(const float* x, const float* dz, double* part /* 32 * 49 * 64 */, float* dw, int B, int H, int W, hipStream_t s);
-int enc_bn_chunks(long long N);
-void launch_enc_bn_forward(const float* z, const float* gamma, const float* beta, const float* sscale, const float* res, int relu, float eps,
-                           float momentum, float* run_mean, float* run_var, float* mr, float* y, double* part, long long N, int HW, int C,
-                           hipStream_t s);
-void launch_enc_bn_backward(const float* z, const float* y, const float* dy, const float* mr, const float* gamma, const float* sscale, int relu,
-                            float* dz, float* dres, float* dgamma, float* dbeta, float* k, double* part, long long N, int HW, int C,
-                            hipStream_t s);
 void launch_enc_maxpool(const float* x, float* y, int B, int H, int W, int C, hipStream_t s);
 void launch_enc_maxpool_backward(const float* x, const float* dy, float* dx, int B, int H, int W, int C, hipStream_t s);
 void launch_enc_avgpool(const float* x, float* g, int B, int HW, int C, hipStream_t s);
 void launch_enc_avgpool_backward(const float* dg, float* dx, int B, int HW, int C, hipStream_t s);
 
-// ---- SparK masked pre-training (spark_train.hip): sparse / dense BatchNorm with a fill value and ReLU6, the mask multiply, the
-// small-channel convolution family (gather kernel in two index forms + weight gradient), the masked loss
+// ---- training BatchNorm (batchnorm_train.hip): the one implementation behind cddpm_op_enc_bn_* and cddpm_op_spark_bn_*, dense or over the
+// active pixels of a cell mask, with a fill value, ReLU / ReLU6, evaluation mode. The caller decides what its results depend on: `nchunk`
+// (pixel chunks: the order of the fp64 sums and the grid), `planes` (per chunk of the backward's `part`: 2 without a mask, 3 with one -- the
+// third holds the sums over inactive pixels, dfill) and `status` (given: fewer than two values per channel write nothing but status = {1, n};
+// nullptr: a single value folds its biased variance into run_var)
+struct BnShape {
+    long long N; int HW, C;             // N = B HW pixels of C channels (a multiple of 4)
+    const unsigned char* active;        // [B][f][f] cell mask or nullptr; f, H, W are read with a mask only (f divides H and W, HW = H W)
+    int f, H, W;
+};
+void launch_bn_train_stats(const BnShape& g, const float* z, int nchunk, float eps, float momentum, float* run_mean, float* run_var, float* mr,
+                           double* part /* nchunk x 2 x C */, int* status, hipStream_t s);
+void launch_bn_eval_stats(const float* run_mean, const float* run_var, float eps, int C, float* mr, hipStream_t s);
+void launch_bn_train_act(const BnShape& g, const float* z, const float* mr, const float* gamma, const float* beta, const float* sscale,
+                         const float* res, const float* fill, int act, float* y, hipStream_t s);
+void launch_bn_train_backward(const BnShape& g, const float* z, const float* y, const float* dy, const float* mr, const float* gamma, const float* sscale,
+                              int act, int training, int nchunk, int planes, float* dz, float* dres, float* dgamma, float* dbeta, float* dfill,
+                              float* k /* 2 C */, double* part /* nchunk x planes x C */, hipStream_t s);
+// number of set cells of active [ncell]; every thread of the 256-thread workgroup calls it (red: 256 ints of LDS) and gets the count
+__device__ __forceinline__ int count_active_cells(const unsigned char* __restrict__ active, int ncell, int* red) {
+    int c = 0;
+    for (int i = threadIdx.x; i < ncell; i += 256) c += active[i] != 0;
+    red[threadIdx.x] = c;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const int r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// ---- SparK masked pre-training (spark_train.hip): the mask multiply, the small-channel convolution family (gather kernel in two index
+// forms + weight gradient), the masked loss
 struct SparkConv {
     const float* src; const float* w; const float* bias; float* dst;
     float* part;               // [Z][pixels][Cd] contraction-split planes, or nullptr (no split)
@@ -357,15 +383,6 @@ struct SparkConv {
     int Z;                     // set by the launcher
 };
 struct SparkWgrad { const float* d; const float* g; float* part; int B, Hq, Wq, Hg, Wg, Cd, Cg, K, stride, pad, P; };
-int spark_bn_chunks(long long N, int C);
-void launch_spark_bn_stats(const float* z, const unsigned char* active, int f, int B, int H, int W, int C, float eps, float momentum, float* run_mean,
-                           float* run_var, float* mr, double* part, int* status, hipStream_t s);
-void launch_spark_bn_eval_stats(const float* run_mean, const float* run_var, float eps, int C, float* mr, hipStream_t s);
-void launch_spark_bn_act(const float* z, const float* mr, const float* gamma, const float* beta, const float* sscale, const float* res,
-                         const unsigned char* active, int f, const float* fill, int act, float* y, int B, int H, int W, int C, hipStream_t s);
-void launch_spark_bn_backward(const float* z, const float* y, const float* dy, const float* mr, const float* gamma, const float* sscale, int act,
-                              const unsigned char* active, int f, int training, float* dz, float* dres, float* dgamma, float* dbeta, float* dfill,
-                              float* k, double* part, int B, int H, int W, int C, hipStream_t s);
 void launch_spark_mask_mul(const float* x, const unsigned char* active, float* y, int B, int H, int W, int C, int f, hipStream_t s);
 int spark_conv_split(long long M, int Cd, int Cs, int K);
 void launch_spark_conv(SparkConv a, hipStream_t s);

@@ -1,9 +1,7 @@
 // Kernels of SparK masked pre-training (reference src/models/Spark_2D.py; src/models/modules/spark/{Spark_2D,encoder,decoder}.py): what
-// the pre-training step needs beside the ResNet-50's training operators (encoder_train.hip). Everything NHWC fp32, memory- and
-// launch-bound work: small channel counts (2048 -> 128 at f x f down to 4 -> 1 at the image's resolution), no matrix pipe. Pieces:
-//   spark_chan_partial / folds   BatchNorm over the ACTIVE pixels only (encoder.py:25-35: BatchNorm1d over the gathered rows) or over
-//                          all of them (active == nullptr: the decoder's BatchNorm2d, decoder.py:26-27), fp64 sums, n_act counted on
-//                          the device from the cell mask; y = act((active ? bn(z) : fill) s[b] + res), act = none | ReLU | ReLU6
+// the pre-training step needs beside the ResNet-50's training operators (encoder_train.hip) and the sparse / dense BatchNorm behind
+// cddpm_op_spark_bn_* (batchnorm_train.hip). Everything NHWC fp32, memory- and launch-bound work: small channel counts (2048 -> 128 at
+// f x f down to 4 -> 1 at the image's resolution), no matrix pipe. Pieces:
 //   spark_mask_mul         y = x * active_ex (Spark_2D.py:150-151, encoder.py:19-22)
 //   spark_conv_kernel      one 64 x 64-tile gather convolution in two index forms, any channel counts, weights read in place through
 //                          strides: form 0 gathers ys = y stride + ky - pad (Conv2d forward, ConvTranspose2d input gradient), form 1
@@ -15,253 +13,6 @@
 #include <hip/hip_runtime.h>
 
 namespace cddpm {
-
-// number of set cells of active [ncell]; every thread of the 256-thread workgroup calls it and gets the count
-__device__ __forceinline__ int spark_count_active(const unsigned char* __restrict__ active, int ncell, int* red) {
-    int c = 0;
-    for (int i = threadIdx.x; i < ncell; i += 256) c += active[i] != 0;
-    red[threadIdx.x] = c;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const int r = red[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ float spark_act_grad(float g, float y, int act) {
-    if (act == 1) return y > 0.f ? g : 0.f;
-    if (act == 2) return (y > 0.f && y < 6.f) ? g : 0.f;
-    return g;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- BatchNorm
-struct SparkBn {
-    const float *z, *y, *dy, *mr, *sscale;
-    const unsigned char* active;      // [B][f][f] or nullptr (every pixel active)
-    int f, ch, cw;                    // cells per side; pixels per cell: ch = H / f, cw = W / f
-    int W, HW, C, act;
-    long long N;
-    int nchunk, qpb, rows;            // pixel chunks; channel quads per workgroup; pixel lanes per workgroup (qpb rows <= 256)
-    double* part;                     // [nchunk][2 | 3][C]
-};
-__device__ __forceinline__ bool spark_pixel_active(const SparkBn& a, long long p) {
-    if (!a.active) return true;
-    const int b = (int)(p / a.HW), rem = (int)(p - (long long)b * a.HW);
-    const int y = rem / a.W, x = rem - y * a.W;
-    return a.active[((size_t)b * a.f + y / a.ch) * a.f + x / a.cw] != 0;
-}
-// per-channel sums over the pixels of one chunk, fp64. MODE 0: (sum z, sum z^2) over active pixels. MODE 1: g = dy act'(y) s[b];
-// (sum g, sum g zhat) over active pixels, (sum g) over inactive ones
-template <int MODE>
-__global__ __launch_bounds__(256) void spark_chan_partial_kernel(const SparkBn a) {
-    constexpr int NS = MODE == 0 ? 2 : 3;
-    __shared__ double red[NS][1024];
-    const int tid = threadIdx.x, q = tid % a.qpb, r = tid / a.qpb, cw4 = a.qpb * 4;
-    const int c = (blockIdx.y * a.qpb + q) * 4;
-    const bool valid = r < a.rows && c < a.C;
-    const long long per = (a.N + a.nchunk - 1) / a.nchunk, p0 = per * blockIdx.x, p1 = p0 + per < a.N ? p0 + per : a.N;
-    double s[NS][4];
-    for (int j = 0; j < NS; ++j)
-        for (int i = 0; i < 4; ++i) s[j][i] = 0.0;
-    if (valid) {
-        float mean[4] = {0, 0, 0, 0}, rstd[4] = {1, 1, 1, 1};
-        if (MODE == 1)
-            for (int i = 0; i < 4; ++i) { mean[i] = a.mr[c + i]; rstd[i] = a.mr[a.C + c + i]; }
-        for (long long p = p0 + r; p < p1; p += a.rows) {
-            const bool on = spark_pixel_active(a, p);
-            if (MODE == 0) {
-                if (!on) continue;
-                const float4 zv = *reinterpret_cast<const float4*>(a.z + (size_t)p * a.C + c);
-                const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
-                for (int i = 0; i < 4; ++i) { s[0][i] += zz[i]; s[1][i] += (double)zz[i] * zz[i]; }
-            } else {
-                const float4 dv = *reinterpret_cast<const float4*>(a.dy + (size_t)p * a.C + c);
-                float gg[4] = {dv.x, dv.y, dv.z, dv.w};
-                if (a.act) {
-                    const float4 yv = *reinterpret_cast<const float4*>(a.y + (size_t)p * a.C + c);
-                    const float yy[4] = {yv.x, yv.y, yv.z, yv.w};
-                    for (int i = 0; i < 4; ++i) gg[i] = spark_act_grad(gg[i], yy[i], a.act);
-                }
-                const float sc = a.sscale ? a.sscale[p / a.HW] : 1.f;
-                if (on) {
-                    const float4 zv = *reinterpret_cast<const float4*>(a.z + (size_t)p * a.C + c);
-                    const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
-                    for (int i = 0; i < 4; ++i) {
-                        const float g = gg[i] * sc;
-                        s[0][i] += g;
-                        s[1][i] += (double)g * ((zz[i] - mean[i]) * rstd[i]);
-                    }
-                } else {
-                    for (int i = 0; i < 4; ++i) s[NS - 1][i] += gg[i] * sc;
-                }
-            }
-        }
-    }
-    if (r < a.rows)
-        for (int j = 0; j < NS; ++j)
-            for (int i = 0; i < 4; ++i) red[j][r * cw4 + 4 * q + i] = s[j][i];
-    __syncthreads();
-    if (tid < NS * cw4) {
-        const int w = tid / cw4, cc = tid - w * cw4, ch = blockIdx.y * cw4 + cc;
-        if (ch < a.C) {
-            double t = 0;
-            for (int k = 0; k < a.rows; ++k) t += red[w][k * cw4 + cc];
-            a.part[((size_t)blockIdx.x * NS + w) * a.C + ch] = t;
-        }
-    }
-}
-// batch statistics over the n_act active pixels: mr = (mean | rstd); running statistics as torch's BatchNorm in training mode (momentum,
-// unbiased variance). n_act < 2: nothing is written but status = {1, n_act} (torch's BatchNorm1d raises there)
-__global__ __launch_bounds__(256) void spark_bn_stats_fold_kernel(const double* __restrict__ part, int nchunk, int C, long long N,
-                                                                  const unsigned char* __restrict__ active, int ncell, int cellpx, float eps,
-                                                                  float momentum, float* __restrict__ mr, float* __restrict__ run_mean,
-                                                                  float* __restrict__ run_var, int* __restrict__ status) {
-    __shared__ int red[256];
-    const long long n = active ? (long long)spark_count_active(active, ncell, red) * cellpx : N;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && status) { status[0] = n < 2; status[1] = (int)n; }
-    if (n < 2) return;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s0 = 0, s1 = 0;
-    for (int k = 0; k < nchunk; ++k) { s0 += part[((size_t)k * 2) * C + c]; s1 += part[((size_t)k * 2 + 1) * C + c]; }
-    const double mean = s0 / (double)n;
-    double var = s1 / (double)n - mean * mean;
-    if (var < 0) var = 0;
-    mr[c] = (float)mean;
-    mr[C + c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (run_mean) {
-        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)mean;
-        run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)(var * (double)n / (double)(n - 1));
-    }
-}
-// evaluation mode: the running statistics stand in for the batch's
-__global__ __launch_bounds__(256) void spark_bn_eval_stats_kernel(const float* __restrict__ run_mean, const float* __restrict__ run_var, float eps, int C,
-                                                                  float* __restrict__ mr) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    mr[c] = run_mean[c];
-    mr[C + c] = (float)(1.0 / sqrt((double)run_var[c] + (double)eps));
-}
-__global__ __launch_bounds__(256) void spark_bn_act_kernel(const SparkBn a, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           const float* __restrict__ fill, const float* __restrict__ res, float* __restrict__ out) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int nq = a.C >> 2;
-    if (e >= a.N * nq) return;
-    const int c = 4 * (int)(e % nq);
-    const long long p = e / nq;
-    float4 o;
-    if (spark_pixel_active(a, p)) {
-        const float4 zv = *reinterpret_cast<const float4*>(a.z + (size_t)p * a.C + c);
-        const float4 m = *reinterpret_cast<const float4*>(a.mr + c), rs = *reinterpret_cast<const float4*>(a.mr + a.C + c);
-        const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c);
-        o.x = (zv.x - m.x) * rs.x * g.x + b.x; o.y = (zv.y - m.y) * rs.y * g.y + b.y;
-        o.z = (zv.z - m.z) * rs.z * g.z + b.z; o.w = (zv.w - m.w) * rs.w * g.w + b.w;
-    } else {
-        o = fill ? *reinterpret_cast<const float4*>(fill + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float sc = a.sscale ? a.sscale[p / a.HW] : 1.f;
-    o.x *= sc; o.y *= sc; o.z *= sc; o.w *= sc;
-    if (res) {
-        const float4 rv = *reinterpret_cast<const float4*>(res + (size_t)p * a.C + c);
-        o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
-    }
-    if (a.act) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-    if (a.act == 2) { o.x = fminf(o.x, 6.f); o.y = fminf(o.y, 6.f); o.z = fminf(o.z, 6.f); o.w = fminf(o.w, 6.f); }
-    *reinterpret_cast<float4*>(out + (size_t)p * a.C + c) = o;
-}
-// backward sums -> dgamma, dbeta, dfill and the two per-channel means of the elementwise pass (k = (sum g / n_act | sum g zhat / n_act);
-// both 0 in evaluation mode, where the statistics do not depend on z)
-__global__ __launch_bounds__(256) void spark_bn_bwd_fold_kernel(const double* __restrict__ part, int nchunk, int C, long long N,
-                                                                const unsigned char* __restrict__ active, int ncell, int cellpx, int training,
-                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dfill,
-                                                                float* __restrict__ k) {
-    __shared__ int red[256];
-    const long long n = active ? (long long)spark_count_active(active, ncell, red) * cellpx : N;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double s0 = 0, s1 = 0, s2 = 0;
-    for (int j = 0; j < nchunk; ++j) {
-        s0 += part[((size_t)j * 3) * C + c]; s1 += part[((size_t)j * 3 + 1) * C + c]; s2 += part[((size_t)j * 3 + 2) * C + c];
-    }
-    dbeta[c] = (float)s0;
-    dgamma[c] = (float)s1;
-    if (dfill) dfill[c] = (float)s2;
-    const bool stats = training && n > 0;
-    k[c] = stats ? (float)(s0 / (double)n) : 0.f;
-    k[C + c] = stats ? (float)(s1 / (double)n) : 0.f;
-}
-// dz = active ? gamma rstd (g - k0 - zhat k1) : 0, g = dy act'(y) s[b]; dres (optional) = dy act'(y)
-__global__ __launch_bounds__(256) void spark_bn_bwd_apply_kernel(const SparkBn a, const float* __restrict__ gamma, const float* __restrict__ k,
-                                                                 float* __restrict__ dz, float* __restrict__ dres) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int nq = a.C >> 2;
-    if (e >= a.N * nq) return;
-    const int c = 4 * (int)(e % nq);
-    const long long p = e / nq;
-    float4 dv = *reinterpret_cast<const float4*>(a.dy + (size_t)p * a.C + c);
-    if (a.act) {
-        const float4 yv = *reinterpret_cast<const float4*>(a.y + (size_t)p * a.C + c);
-        dv.x = spark_act_grad(dv.x, yv.x, a.act); dv.y = spark_act_grad(dv.y, yv.y, a.act);
-        dv.z = spark_act_grad(dv.z, yv.z, a.act); dv.w = spark_act_grad(dv.w, yv.w, a.act);
-    }
-    if (dres) *reinterpret_cast<float4*>(dres + (size_t)p * a.C + c) = dv;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (spark_pixel_active(a, p)) {
-        const float sc = a.sscale ? a.sscale[p / a.HW] : 1.f;
-        const float4 zv = *reinterpret_cast<const float4*>(a.z + (size_t)p * a.C + c);
-        const float4 m = *reinterpret_cast<const float4*>(a.mr + c), rs = *reinterpret_cast<const float4*>(a.mr + a.C + c);
-        const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-        const float4 k0 = *reinterpret_cast<const float4*>(k + c), k1 = *reinterpret_cast<const float4*>(k + a.C + c);
-        o.x = g.x * rs.x * (dv.x * sc - k0.x - (zv.x - m.x) * rs.x * k1.x);
-        o.y = g.y * rs.y * (dv.y * sc - k0.y - (zv.y - m.y) * rs.y * k1.y);
-        o.z = g.z * rs.z * (dv.z * sc - k0.z - (zv.z - m.z) * rs.z * k1.z);
-        o.w = g.w * rs.w * (dv.w * sc - k0.w - (zv.w - m.w) * rs.w * k1.w);
-    }
-    *reinterpret_cast<float4*>(dz + (size_t)p * a.C + c) = o;
-}
-int spark_bn_chunks(long long N, int C) {
-    long long n = N * C / 16384;            // >= 16 K elements per chunk; the folds read the chunks serially
-    if (n > 128) n = 128;
-    return n < 1 ? 1 : (int)n;
-}
-static SparkBn spark_bn_args(const float* z, const float* y, const float* dy, const float* mr, const float* sscale, const unsigned char* active,
-                             int f, int H, int W, int C, int act, long long N, double* part) {
-    SparkBn a;
-    a.z = z; a.y = y; a.dy = dy; a.mr = mr; a.sscale = sscale; a.active = active; a.f = f; a.ch = H / f; a.cw = W / f;
-    a.W = W; a.HW = H * W; a.C = C; a.act = act; a.N = N; a.nchunk = spark_bn_chunks(N, C);
-    a.qpb = C / 4 < 16 ? C / 4 : 16; a.rows = 256 / a.qpb; a.part = part;
-    return a;
-}
-static dim3 spark_bn_partial_grid(const SparkBn& a) { return dim3(a.nchunk, (a.C / 4 + a.qpb - 1) / a.qpb); }
-void launch_spark_bn_stats(const float* z, const unsigned char* active, int f, int B, int H, int W, int C, float eps, float momentum, float* run_mean,
-                           float* run_var, float* mr, double* part, int* status, hipStream_t s) {
-    const long long N = (long long)B * H * W;
-    const SparkBn a = spark_bn_args(z, nullptr, nullptr, nullptr, nullptr, active, f, H, W, C, 0, N, part);
-    hipLaunchKernelGGL(spark_chan_partial_kernel<0>, spark_bn_partial_grid(a), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(spark_bn_stats_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, a.nchunk, C, N, active, B * f * f, a.ch * a.cw, eps,
-                       momentum, mr, run_mean, run_var, status);
-}
-void launch_spark_bn_eval_stats(const float* run_mean, const float* run_var, float eps, int C, float* mr, hipStream_t s) {
-    hipLaunchKernelGGL(spark_bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, s, run_mean, run_var, eps, C, mr);
-}
-void launch_spark_bn_act(const float* z, const float* mr, const float* gamma, const float* beta, const float* sscale, const float* res,
-                         const unsigned char* active, int f, const float* fill, int act, float* y, int B, int H, int W, int C, hipStream_t s) {
-    const long long N = (long long)B * H * W, total = N * (C / 4);
-    const SparkBn a = spark_bn_args(z, nullptr, nullptr, mr, sscale, active, f, H, W, C, act, N, nullptr);
-    hipLaunchKernelGGL(spark_bn_act_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, gamma, beta, fill, res, y);
-}
-void launch_spark_bn_backward(const float* z, const float* y, const float* dy, const float* mr, const float* gamma, const float* sscale, int act,
-                              const unsigned char* active, int f, int training, float* dz, float* dres, float* dgamma, float* dbeta, float* dfill,
-                              float* k, double* part, int B, int H, int W, int C, hipStream_t s) {
-    const long long N = (long long)B * H * W, total = N * (C / 4);
-    const SparkBn a = spark_bn_args(z, y, dy, mr, sscale, active, f, H, W, C, act, N, part);
-    hipLaunchKernelGGL(spark_chan_partial_kernel<1>, spark_bn_partial_grid(a), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(spark_bn_bwd_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, a.nchunk, C, N, active, B * f * f, a.ch * a.cw, training,
-                       dgamma, dbeta, dfill, k);
-    hipLaunchKernelGGL(spark_bn_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, gamma, k, dz, dres);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- mask multiply
 __global__ __launch_bounds__(256) void spark_mask_mul_kernel(const float* x /* may be y */, const unsigned char* __restrict__ active, float* y,
@@ -514,7 +265,7 @@ __global__ __launch_bounds__(256) void spark_loss_partial_kernel(const float* __
                                                                  float* __restrict__ drec, double* __restrict__ part) {
     __shared__ int cnt[256];
     __shared__ double red[2][256];
-    const int n_masked = ncell - spark_count_active(active, ncell, cnt);
+    const int n_masked = ncell - count_active_cells(active, ncell, cnt);
     if (scaler) {
         const float scale = reinterpret_cast<const float*>(scaler)[0];
         w_mask *= scale; w_l1 *= scale;
@@ -544,7 +295,7 @@ __global__ __launch_bounds__(256) void spark_loss_partial_kernel(const float* __
 __global__ __launch_bounds__(256) void spark_loss_fold_kernel(const double* __restrict__ part, int nchunk, const unsigned char* __restrict__ active, int ncell,
                                                               int cellpx, long long total, float* __restrict__ loss) {
     __shared__ int cnt[256];
-    const int n_masked = ncell - spark_count_active(active, ncell, cnt);
+    const int n_masked = ncell - count_active_cells(active, ncell, cnt);
     if (threadIdx.x >= 2) return;
     double t = 0;
     for (int k = 0; k < nchunk; ++k) t += part[(size_t)k * 2 + threadIdx.x];

@@ -5,7 +5,7 @@ forward with saved activations and the backward of every operator, what `loss.ba
 training_step (src/models/DDPM_2D.py:114-135; Adam over self.parameters(), :305-306).
 
 Same construction as training.UNetTrainer: Python sequencing C-ABI operators (include/cddpm.h, "training-mode operators of the context
-encoder"; csrc/encoder_train.hip, csrc/encoder_train_p16.hip), one flat fp32 parameter buffer / gradient buffer / Adam state, weight images re-packed on the device
+encoder"; csrc/encoder_train.hip, csrc/encoder_train_p16.hip, csrc/batchnorm_train.hip), one flat fp32 parameter buffer / gradient buffer / Adam state, weight images re-packed on the device
 after every update. The operators run on the UNet trainer's handles; what they take from its arenas is a function of the geometry
 (operator_scratch_bytes), which that trainer sizes its arenas for.
 
@@ -31,6 +31,35 @@ BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
+
+
+def spark_bn_forward(t, name, z, act, active=None, f=1, *, res=None, sscale=None, fill=None, training=True):
+    """cddpm_op_spark_bn_forward on parameter group `name` of trainer t (the owner of p, buf and the handle): sparse (active uint8
+    [B,f,f]) or dense BatchNorm of z [B,H,W,C], act 0 | 1 (ReLU) | 2 (ReLU6) -> y, (mean | rstd)"""
+    B, H, W, Cc = z.shape
+    mr, y = t._new(2, Cc), torch.empty_like(z)
+    t._ck(t.lib.cddpm_op_spark_bn_forward(t.h, _p(z), _p(t.p[name + ".weight"]), _p(t.p[name + ".bias"]), _p(sscale), _p(res), int(act),
+                                          C.c_float(BN_EPS), C.c_float(BN_MOMENTUM), _p(t.buf[name + ".running_mean"]),
+                                          _p(t.buf[name + ".running_var"]), _p(mr), _p(y), B * H * W, H * W, Cc, _p(active), f, H, W, _p(fill),
+                                          int(training), t._s()), "op_spark_bn_forward")
+    return y, mr
+
+
+def spark_bn_backward(t, name, z, y, dy, mr, act, active=None, f=1, *, sscale=None, want_dres=False, dfill=None, training=True):
+    """cddpm_op_spark_bn_backward of spark_bn_forward (training as there) -> dz, dres (None unless wanted); dgamma, dbeta land in t.g"""
+    B, H, W, Cc = z.shape
+    dz = torch.empty_like(z)
+    dres = torch.empty_like(z) if want_dres else None
+    t._ck(t.lib.cddpm_op_spark_bn_backward(t.h, _p(z), _p(y), _p(dy), _p(mr), _p(t.p[name + ".weight"]), _p(sscale), int(act), _p(dz), _p(dres),
+                                           _p(t.g[name + ".weight"]), _p(t.g[name + ".bias"]), B * H * W, H * W, Cc, _p(active), f, H, W,
+                                           _p(dfill), int(training), t._s()), "op_spark_bn_backward")
+    return dz, dres
+
+
+def plain_bn(relu, active, fill, training):
+    """the one rule of EncoderTrainer.bn and bn_bwd: a BatchNorm without a mask, a fill value (forward) or its gradient (backward), ReLU6
+    or evaluation mode is the dense ResNet-50's and goes through cddpm_op_enc_bn_*; every other goes through cddpm_op_spark_bn_*"""
+    return active is None and fill is None and training and int(relu) != 2
 
 
 def operator_calls(B, H, W, cond_dim=128):
@@ -195,7 +224,12 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
             return
         self._ck(op(self.h, _p(x), _p(dz), _p(self.g[name + ".weight"]), B, H, W, ci, co, kk, st, self._s()), "op_enc_conv_wgrad")
 
-    def bn(self, name, z, relu, res=None, sscale=None):
+    def bn(self, name, z, relu, res=None, sscale=None, *, active=None, f=1, fill=None, training=True):
+        """training-mode BatchNorm on parameter group `name` -> y, (mean | rstd). relu: 0 | 1 (ReLU) | 2 (ReLU6). Plain (no mask, fill,
+        ReLU6 or evaluation mode: the dense ResNet-50) it is cddpm_op_enc_bn_forward; anything else is cddpm_op_spark_bn_forward, sparse
+        (active uint8 [B,f,f]) or dense. Both run the one BatchNorm of the library, each on its own chunk plan (include/cddpm.h)."""
+        if not plain_bn(relu, active, fill, training):
+            return spark_bn_forward(self, name, z, relu, active, f, res=res, sscale=sscale, fill=fill, training=training)
         B, H, W, Cc = z.shape
         mr, y = self._new(2, Cc), torch.empty_like(z)
         self._ck(self.lib.cddpm_op_enc_bn_forward(self.h, _p(z), _p(self.p[name + ".weight"]), _p(self.p[name + ".bias"]), _p(sscale), _p(res),
@@ -204,7 +238,11 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
                  "op_enc_bn_forward")
         return y, mr
 
-    def bn_bwd(self, name, z, y, dy, mr, relu, sscale=None, want_dres=False):
+    def bn_bwd(self, name, z, y, dy, mr, relu, sscale=None, want_dres=False, *, active=None, f=1, dfill=None, training=True):
+        """the backward of bn() with the same relu, active, f and training (dfill: the gradient of its fill) -> dz, dres (None
+        unless wanted); the gradients of the group's weight and bias land in g"""
+        if not plain_bn(relu, active, dfill, training):
+            return spark_bn_backward(self, name, z, y, dy, mr, relu, active, f, sscale=sscale, want_dres=want_dres, dfill=dfill, training=training)
         B, H, W, Cc = z.shape
         dz = torch.empty_like(z)
         dres = torch.empty_like(z) if want_dres else None
@@ -213,45 +251,99 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
                                                    self._s()), "op_enc_bn_backward")
         return dz, dres
 
-    # ------------------------------------------------------------------ forward (training mode), activations saved
-    def forward(self, x: torch.Tensor, drop_scales: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
-        """x [B,1,H,W] on the device -> context [B, cond_dim]. drop_scales (tests): per-block [B] scales instead of fresh random draws."""
-        x = x.float().contiguous()
+    def mask_mul_(self, x, active, f):
+        """x [B,H,W,C] *= the mask dilated to H x W, in place"""
+        B, H, W, Cc = x.shape
+        self._ck(self.lib.cddpm_op_spark_mask_mul(self.h, _p(x), _p(active), _p(x), B, H, W, Cc, f, self._s()), "op_spark_mask_mul")
+        return x
+
+    # ------------------------------------------------------------------ the ResNet-50, forward with saved activations and backward
+    # One walk for the dense network (forward / backward) and for the sparse one of SparK pre-training (forward_pyramid / backward_pyramid:
+    # the ResNet-50 after SparseEncoder.dense_model_to_sparse, reference spark/encoder.py:163-204). There every BatchNorm is a BatchNorm1d
+    # over the ACTIVE pixels that writes zeros elsewhere (`mask` = dict(active=, f=), handed to bn / bn_bwd), and every convolution and
+    # pooling output is multiplied by the mask at its resolution. A convolution is always followed by such a BatchNorm, which neither reads
+    # the inactive pixels nor lets a gradient through to them, so the convolutions run unmasked (cddpm_op_enc_conv as it is); the input
+    # and the max-pool output are masked by cddpm_op_spark_mask_mul.
+    def _walk(self, x, drop_scales, mask=None, training=True):
+        """x [B,1,H,W] fp32 contiguous: stem -> BatchNorm -> max pool -> the 16 bottleneck blocks -> (activations by name, last map).
+        drop_scales: per-block [B] scales instead of fresh random draws; training False (with a mask): running statistics, no
+        stochastic depth"""
         B, _c, H, W = x.shape
-        sv: Dict[str, object] = dict(x=x)
+        kw = {} if mask is None else dict(mask, training=training)
         H1, W1 = (H + 1) // 2, (W + 1) // 2
         z0 = self._new(B, H1, W1, 64)
         self._ck(self.lib.cddpm_op_enc_stem(self.h, _p(x), _p(self.p["conv1.weight"]), _p(z0), B, H, W, self._s()), "op_enc_stem")
-        a0, mr0 = self.bn("bn1", z0, True)
-        H2, W2 = (H1 + 1) // 2, (W1 + 1) // 2
-        cur = self._new(B, H2, W2, 64)
+        a0, mr0 = self.bn("bn1", z0, True, **kw)
+        cur = self._new(B, (H1 + 1) // 2, (W1 + 1) // 2, 64)
         self._ck(self.lib.cddpm_op_enc_maxpool(self.h, _p(a0), _p(cur), B, H1, W1, 64, 0, None, None, self._s()), "op_enc_maxpool")
-        sv.update(z0=z0, a0=a0, mr0=mr0)
+        if mask is not None:
+            self.mask_mul_(cur, **mask)
+        sv: Dict[str, object] = dict(x=x, z0=z0, a0=a0, mr0=mr0)
         for bk in self.blocks:
             n = bk["name"]
             ss = None
-            if drop_scales is not None:
+            if training and drop_scales is not None:
                 ss = drop_scales.get(n)
                 ss = None if ss is None else ss.to(self.dev, torch.float32).contiguous()
-            elif bk["drop"] > 0:
+            elif training and bk["drop"] > 0:
                 keep = 1.0 - bk["drop"]
                 ss = (torch.floor(keep + torch.rand(B, device=self.dev)) / keep).contiguous()     # timm.layers.drop_path
             z1 = self.conv(n + ".conv1", cur)
-            a1, mr1 = self.bn(n + ".bn1", z1, True)
+            a1, mr1 = self.bn(n + ".bn1", z1, True, **kw)
             z2 = self.conv(n + ".conv2", a1)
-            a2, mr2 = self.bn(n + ".bn2", z2, True)
+            a2, mr2 = self.bn(n + ".bn2", z2, True, **kw)
             z3 = self.conv(n + ".conv3", a2)
             r = dict(inp=cur, z1=z1, a1=a1, mr1=mr1, z2=z2, a2=a2, mr2=mr2, z3=z3, ss=ss)
             sc = cur
             if bk["down"]:
                 zd = self.conv(n + ".downsample.0", cur)
-                sc, mrd = self.bn(n + ".downsample.1", zd, False)
+                sc, mrd = self.bn(n + ".downsample.1", zd, False, **kw)
                 r.update(zd=zd, mrd=mrd)
-            out, mr3 = self.bn(n + ".bn3", z3, True, res=sc, sscale=ss)
+            out, mr3 = self.bn(n + ".bn3", z3, True, res=sc, sscale=ss, **kw)
             r.update(mr3=mr3, out=out)
             sv[n] = r
             cur = out
-        Bc, Hc, Wc, Cc = cur.shape
+        return sv, cur
+
+    def _block_backward(self, bk, r, d, mask=None):
+        """d = dL/d(the block's output) -> dL/d(its input); the gradients of its parameters land in g"""
+        n, inp = bk["name"], r["inp"]
+        kw = mask or {}
+        hw = (inp.shape[1], inp.shape[2])
+        dz3, dsc = self.bn_bwd(n + ".bn3", r["z3"], r["out"], d, r["mr3"], True, r["ss"], want_dres=True, **kw)
+        da2 = self.conv(n + ".conv3", dz3, transposed=True, in_hw=(r["a2"].shape[1], r["a2"].shape[2]))
+        self.wgrad(n + ".conv3", r["a2"], dz3)
+        dz2, _ = self.bn_bwd(n + ".bn2", r["z2"], r["a2"], da2, r["mr2"], True, **kw)
+        da1 = self.conv(n + ".conv2", dz2, transposed=True, in_hw=hw)
+        self.wgrad(n + ".conv2", r["a1"], dz2)
+        dz1, _ = self.bn_bwd(n + ".bn1", r["z1"], r["a1"], da1, r["mr1"], True, **kw)
+        dinp = self.conv(n + ".conv1", dz1, transposed=True, in_hw=hw)
+        self.wgrad(n + ".conv1", inp, dz1)
+        if bk["down"]:
+            dzd, _ = self.bn_bwd(n + ".downsample.1", r["zd"], None, dsc, r["mrd"], False, **kw)
+            self.ops.add_(dinp, self.conv(n + ".downsample.0", dzd, transposed=True, in_hw=hw))
+            self.wgrad(n + ".downsample.0", inp, dzd)
+        else:
+            self.ops.add_(dinp, dsc)
+        return dinp
+
+    def _stem_backward(self, sv, d, mask=None):
+        """d = dL/d(the max pool's output): max pool, bn1 and the stem's weight gradient (the input's gradient is never needed)"""
+        a0, z0, x = sv["a0"], sv["z0"], sv["x"]
+        B, H1, W1, _c = a0.shape
+        da0 = torch.empty_like(a0)
+        self._ck(self.lib.cddpm_op_enc_maxpool(self.h, _p(a0), None, B, H1, W1, 64, 1, _p(d), _p(da0), self._s()), "op_enc_maxpool (backward)")
+        dz0, _ = self.bn_bwd("bn1", z0, a0, da0, sv["mr0"], True, **(mask or {}))
+        self._ck(self.lib.cddpm_op_enc_stem_wgrad(self.h, _p(x), _p(dz0), _p(self.g["conv1.weight"]), B, x.shape[2], x.shape[3], self._s()),
+                 "op_enc_stem_wgrad")
+        if hasattr(self.ops, "join_side"):
+            self.ops.join_side()
+
+    # ------------------------------------------------------------------ forward (training mode), activations saved
+    def forward(self, x: torch.Tensor, drop_scales: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+        """x [B,1,H,W] on the device -> context [B, cond_dim]. drop_scales (tests): per-block [B] scales instead of fresh random draws."""
+        sv, cur = self._walk(x.float().contiguous(), drop_scales)
+        B, Hc, Wc, Cc = cur.shape
         gap = self._new(B, Cc)
         self._ck(self.lib.cddpm_op_enc_avgpool(self.h, _p(cur), _p(gap), B, Hc * Wc, Cc, 0, self._s()), "op_enc_avgpool")
         wfc, bfc = self.p["fc.weight"], self.p["fc.bias"]
@@ -280,72 +372,16 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
         d = torch.empty_like(last)
         self._ck(self.lib.cddpm_op_enc_avgpool(self.h, _p(dgap), _p(d), B, Hc * Wc, Cc, 1, self._s()), "op_enc_avgpool (backward)")
         for bk in reversed(self.blocks):
-            n, r = bk["name"], sv[bk["name"]]
-            inp = r["inp"]
-            hw = (inp.shape[1], inp.shape[2])
-            dz3, dsc = self.bn_bwd(n + ".bn3", r["z3"], r["out"], d, r["mr3"], True, r["ss"], want_dres=True)
-            da2 = self.conv(n + ".conv3", dz3, transposed=True, in_hw=(r["a2"].shape[1], r["a2"].shape[2]))
-            self.wgrad(n + ".conv3", r["a2"], dz3)
-            dz2, _ = self.bn_bwd(n + ".bn2", r["z2"], r["a2"], da2, r["mr2"], True)
-            da1 = self.conv(n + ".conv2", dz2, transposed=True, in_hw=hw)
-            self.wgrad(n + ".conv2", r["a1"], dz2)
-            dz1, _ = self.bn_bwd(n + ".bn1", r["z1"], r["a1"], da1, r["mr1"], True)
-            dinp = self.conv(n + ".conv1", dz1, transposed=True, in_hw=hw)
-            self.wgrad(n + ".conv1", inp, dz1)
-            if bk["down"]:
-                dzd, _ = self.bn_bwd(n + ".downsample.1", r["zd"], None, dsc, r["mrd"], False)
-                self.ops.add_(dinp, self.conv(n + ".downsample.0", dzd, transposed=True, in_hw=hw))
-                self.wgrad(n + ".downsample.0", inp, dzd)
-            else:
-                self.ops.add_(dinp, dsc)
-            d = dinp
+            d = self._block_backward(bk, sv[bk["name"]], d)
             if buckets is not None:
                 if getattr(buckets, "on", True) and hasattr(self.ops, "join_side"):
                     self.ops.join_side()          # the side stream's weight gradients have landed before a collective reads the buffer
-                buckets.mark_final(self.grad_offset(n + "."))
-        a0, z0 = sv["a0"], sv["z0"]
-        B, H1, W1, _c = a0.shape
-        da0 = torch.empty_like(a0)
-        self._ck(self.lib.cddpm_op_enc_maxpool(self.h, _p(a0), None, B, H1, W1, 64, 1, _p(d), _p(da0), self._s()), "op_enc_maxpool (backward)")
-        dz0, _ = self.bn_bwd("bn1", z0, a0, da0, sv["mr0"], True)
-        x = sv["x"]
-        self._ck(self.lib.cddpm_op_enc_stem_wgrad(self.h, _p(x), _p(dz0), _p(g["conv1.weight"]), B, x.shape[2], x.shape[3], self._s()),
-                 "op_enc_stem_wgrad")
-        if hasattr(self.ops, "join_side"):
-            self.ops.join_side()
+                buckets.mark_final(self.grad_offset(bk["name"] + "."))
+        self._stem_backward(sv, d)
         self.saved = None
         return g
 
     # ------------------------------------------------------------------ SparK pre-training: the sparse encoder's pyramid
-    # The ResNet-50 after SparseEncoder.dense_model_to_sparse (reference spark/encoder.py:163-204): every BatchNorm is a BatchNorm1d over the
-    # ACTIVE pixels that writes zeros elsewhere, every convolution and pooling output is multiplied by the mask at its resolution. A
-    # convolution is always followed by such a BatchNorm, which neither reads the inactive pixels nor lets a gradient through to them, so
-    # the convolutions run unmasked (cddpm_op_enc_conv as it is); the input and the max-pool output are masked by cddpm_op_spark_mask_mul.
-    def sbn(self, name, z, act, active=None, f=1, res=None, sscale=None, fill=None, training=True):
-        """cddpm_op_spark_bn_forward on parameter group `name`: sparse (active uint8 [B,f,f]) or dense BatchNorm; -> y, (mean | rstd)"""
-        B, H, W, Cc = z.shape
-        mr, y = self._new(2, Cc), torch.empty_like(z)
-        self._ck(self.lib.cddpm_op_spark_bn_forward(self.h, _p(z), _p(self.p[name + ".weight"]), _p(self.p[name + ".bias"]), _p(sscale), _p(res), int(act),
-                                                    C.c_float(BN_EPS), C.c_float(BN_MOMENTUM), _p(self.buf[name + ".running_mean"]),
-                                                    _p(self.buf[name + ".running_var"]), _p(mr), _p(y), B * H * W, H * W, Cc, _p(active), f, H, W,
-                                                    _p(fill), int(training), self._s()), "op_spark_bn_forward")
-        return y, mr
-
-    def sbn_bwd(self, name, z, y, dy, mr, act, active=None, f=1, sscale=None, want_dres=False, dfill=None):
-        B, H, W, Cc = z.shape
-        dz = torch.empty_like(z)
-        dres = torch.empty_like(z) if want_dres else None
-        self._ck(self.lib.cddpm_op_spark_bn_backward(self.h, _p(z), _p(y), _p(dy), _p(mr), _p(self.p[name + ".weight"]), _p(sscale), int(act), _p(dz),
-                                                     _p(dres), _p(self.g[name + ".weight"]), _p(self.g[name + ".bias"]), B * H * W, H * W, Cc,
-                                                     _p(active), f, H, W, _p(dfill), 1, self._s()), "op_spark_bn_backward")
-        return dz, dres
-
-    def mask_mul_(self, x, active, f):
-        """x [B,H,W,C] *= the mask dilated to H x W, in place"""
-        B, H, W, Cc = x.shape
-        self._ck(self.lib.cddpm_op_spark_mask_mul(self.h, _p(x), _p(active), _p(x), B, H, W, Cc, f, self._s()), "op_spark_mask_mul")
-        return x
-
     def _stage_end(self):
         """name of each stage's last block -> index of its map among the four of forward_pyramid"""
         ends = [bk["name"] for i, bk in enumerate(self.blocks) if i + 1 == len(self.blocks) or self.blocks[i + 1]["down"]]
@@ -355,105 +391,46 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
         """x [B,1,H,W] (H, W multiples of 32), active bool / uint8 [B,f,f] or [B,1,f,f] with f = H / 32, both on the device -> the masked
         outputs of layer1..4 as NHWC tensors [B,8f,8f,256], [B,4f,4f,512], [B,2f,2f,1024], [B,f,f,2048] (forward_features with pyramid = 4,
         reference spark/resnet.py:13-34) and latent [B,2048] = the layer4 map's mean over its pixels (src/models/Spark_2D.py:32).
-        training False: running statistics, no stochastic depth, nothing kept for a backward. drop_scales: as forward()."""
+        training False: running statistics, no stochastic depth, nothing kept for a backward. drop_scales: as forward().
+        saved_pyramid keeps the keys of saved (without gap / last) plus active and f; its "x" is the masked input as [B,1,H,W], the shape
+        forward() keeps (the same memory as the NHWC [B,H,W,1] the stem reads)."""
         B, _c, H, W = x.shape
         active = active.reshape(B, -1)
         f = int(round(active.shape[1] ** 0.5))
         if f * f != active.shape[1] or H != 32 * f or W != 32 * f:
             raise ValueError(f"forward_pyramid: a {H} x {W} input needs a [{B}, {H // 32}, {H // 32}] mask (side / 32), got {active.shape[1]} cells")
-        active = active.to(self.dev, torch.uint8).contiguous()
-        xm = x.float().reshape(B, H, W, 1).clone()
-        self.mask_mul_(xm, active, f)
-        kw = dict(active=active, f=f, training=training)
-        H1, W1 = H // 2, W // 2
-        z0 = self._new(B, H1, W1, 64)
-        self._ck(self.lib.cddpm_op_enc_stem(self.h, _p(xm), _p(self.p["conv1.weight"]), _p(z0), B, H, W, self._s()), "op_enc_stem")
-        a0, mr0 = self.sbn("bn1", z0, 1, **kw)
-        cur = self._new(B, H1 // 2, W1 // 2, 64)
-        self._ck(self.lib.cddpm_op_enc_maxpool(self.h, _p(a0), _p(cur), B, H1, W1, 64, 0, None, None, self._s()), "op_enc_maxpool")
-        self.mask_mul_(cur, active, f)
-        sv: Dict[str, object] = dict(x=xm, z0=z0, a0=a0, mr0=mr0, active=active, f=f)
-        feats = []
-        for bk in self.blocks:
-            n = bk["name"]
-            ss = None
-            if training and drop_scales is not None:
-                ss = drop_scales.get(n)
-                ss = None if ss is None else ss.to(self.dev, torch.float32).contiguous()
-            elif training and bk["drop"] > 0:
-                keep = 1.0 - bk["drop"]
-                ss = (torch.floor(keep + torch.rand(B, device=self.dev)) / keep).contiguous()     # timm.layers.drop_path
-            z1 = self.conv(n + ".conv1", cur)
-            a1, mr1 = self.sbn(n + ".bn1", z1, 1, **kw)
-            z2 = self.conv(n + ".conv2", a1)
-            a2, mr2 = self.sbn(n + ".bn2", z2, 1, **kw)
-            z3 = self.conv(n + ".conv3", a2)
-            r = dict(inp=cur, z1=z1, a1=a1, mr1=mr1, z2=z2, a2=a2, mr2=mr2, z3=z3, ss=ss)
-            sc = cur
-            if bk["down"]:
-                zd = self.conv(n + ".downsample.0", cur)
-                sc, mrd = self.sbn(n + ".downsample.1", zd, 0, **kw)
-                r.update(zd=zd, mrd=mrd)
-            out, mr3 = self.sbn(n + ".bn3", z3, 1, res=sc, sscale=ss, **kw)
-            r.update(mr3=mr3, out=out)
-            sv[n] = r
-            cur = out
-            if n in self._stage_end():
-                feats.append(out)
+        mask = dict(active=active.to(self.dev, torch.uint8).contiguous(), f=f)
+        xm = x.float().reshape(B, 1, H, W).clone(memory_format=torch.contiguous_format)
+        self.mask_mul_(xm.view(B, H, W, 1), **mask)
+        sv, cur = self._walk(xm, drop_scales, mask, training)
+        sv.update(mask)
         Bc, Hc, Wc, Cc = cur.shape
         latent = self._new(B, Cc)
         self._ck(self.lib.cddpm_op_enc_avgpool(self.h, _p(cur), _p(latent), B, Hc * Wc, Cc, 0, self._s()), "op_enc_avgpool")
         self.saved_pyramid = sv if training else None
-        return feats, latent
+        return [sv[n]["out"] for n in self._stage_end()], latent
 
     def backward_pyramid(self, dfeats) -> Dict[str, torch.Tensor]:
         """dfeats: dL/d(the four maps of forward_pyramid), NHWC, layer1..4 (None: no gradient into that map) -> the gradient of every
         parameter (no gradient flows through latent: the pre-training loss does not read it)"""
-        sv, g = self.saved_pyramid, self.g
+        sv = self.saved_pyramid
         if sv is None:
             raise RuntimeError("backward_pyramid: no training-mode forward_pyramid to differentiate")
-        active, f = sv["active"], sv["f"]
-        kw = dict(active=active, f=f)
+        mask = dict(active=sv["active"], f=sv["f"])
         stage_end = self._stage_end()
         d = None
         for bk in reversed(self.blocks):
-            n, r = bk["name"], sv[bk["name"]]
+            n = bk["name"]
             if n in stage_end and dfeats[stage_end[n]] is not None:
                 df = dfeats[stage_end[n]].float().contiguous()
                 d = df.clone() if d is None else self.ops.add_(d, df)
             if d is None:
                 raise ValueError("backward_pyramid: the gradient of the layer4 map is needed")
-            inp = r["inp"]
-            hw = (inp.shape[1], inp.shape[2])
-            dz3, dsc = self.sbn_bwd(n + ".bn3", r["z3"], r["out"], d, r["mr3"], 1, sscale=r["ss"], want_dres=True, **kw)
-            da2 = self.conv(n + ".conv3", dz3, transposed=True, in_hw=(r["a2"].shape[1], r["a2"].shape[2]))
-            self.wgrad(n + ".conv3", r["a2"], dz3)
-            dz2, _ = self.sbn_bwd(n + ".bn2", r["z2"], r["a2"], da2, r["mr2"], 1, **kw)
-            da1 = self.conv(n + ".conv2", dz2, transposed=True, in_hw=hw)
-            self.wgrad(n + ".conv2", r["a1"], dz2)
-            dz1, _ = self.sbn_bwd(n + ".bn1", r["z1"], r["a1"], da1, r["mr1"], 1, **kw)
-            dinp = self.conv(n + ".conv1", dz1, transposed=True, in_hw=hw)
-            self.wgrad(n + ".conv1", inp, dz1)
-            if bk["down"]:
-                dzd, _ = self.sbn_bwd(n + ".downsample.1", r["zd"], None, dsc, r["mrd"], 0, **kw)
-                self.ops.add_(dinp, self.conv(n + ".downsample.0", dzd, transposed=True, in_hw=hw))
-                self.wgrad(n + ".downsample.0", inp, dzd)
-            else:
-                self.ops.add_(dinp, dsc)
-            d = dinp
-        self.mask_mul_(d, active, f)                                   # the masked max-pool output (SparseMaxPooling, encoder.py:42-43)
-        a0, z0 = sv["a0"], sv["z0"]
-        B, H1, W1, _c = a0.shape
-        da0 = torch.empty_like(a0)
-        self._ck(self.lib.cddpm_op_enc_maxpool(self.h, _p(a0), None, B, H1, W1, 64, 1, _p(d), _p(da0), self._s()), "op_enc_maxpool (backward)")
-        dz0, _ = self.sbn_bwd("bn1", z0, a0, da0, sv["mr0"], 1, **kw)
-        x = sv["x"]
-        self._ck(self.lib.cddpm_op_enc_stem_wgrad(self.h, _p(x), _p(dz0), _p(g["conv1.weight"]), B, x.shape[1], x.shape[2], self._s()),
-                 "op_enc_stem_wgrad")
-        if hasattr(self.ops, "join_side"):
-            self.ops.join_side()
+            d = self._block_backward(bk, sv[n], d, mask)
+        self.mask_mul_(d, **mask)                                      # the masked max-pool output (SparseMaxPooling, encoder.py:42-43)
+        self._stem_backward(sv, d, mask)
         self.saved_pyramid = None
-        return g
+        return self.g
 
     def adam_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=None, guarded=False, extra_unscale=None):
         """Adam over the flat buffer under the guard of the trainer it is trained with (`optimizer`: training.UNetTrainer): the encoder and

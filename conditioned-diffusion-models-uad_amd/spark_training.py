@@ -4,7 +4,7 @@
 (spark/decoder.py), the masked L2 loss [+ the L1 mean], the backward of all of it and AdamW (src/models/Spark_2D.py:123-124).
 
 Same construction as the other trainers: Python sequencing C-ABI operators (include/cddpm.h, "operators of SparK masked pre-training";
-csrc/spark_train.hip) on NHWC fp32 device tensors. The densify and decoder parameters live in ONE flat fp32 buffer (`flat`, views `p[name]`
+csrc/spark_train.hip, csrc/batchnorm_train.hip) on NHWC fp32 device tensors. The densify and decoder parameters live in ONE flat fp32 buffer (`flat`, views `p[name]`
 under the reference's names without the `model.` prefix), their gradients in a second (`gflat`), Adam's moments in two more; the ResNet-50's
 are the EncoderTrainer's (`enc.flat`, ...). The operators run on a handle of this trainer's own, whose arena it sizes for its calls from
 the library's size queries (operator_calls).
@@ -30,7 +30,7 @@ import torch
 
 from . import optimizer as _optimizer
 from ._lib import largest_calls
-from .encoder_training import BN_EPS, BN_MOMENTUM, EncoderTrainer, pyramid_operator_calls, _p
+from .encoder_training import EncoderTrainer, pyramid_operator_calls, spark_bn_backward, spark_bn_forward, _p
 from .engine import _stream_ptr, precision_bits
 
 ENC_PREFIX = "sparse_encoder.sp_cnn."
@@ -188,21 +188,10 @@ class SparKTrainer(_optimizer.FlatOptimizer):
                                                     int(kind == "convT"), self._s()), "op_spark_conv_wgrad")
 
     def bn(self, name, z, act, active=None, f=1, res=None, fill=None, training=True):
-        B, H, W, Cc = z.shape
-        mr, y = self._new(2, Cc), torch.empty_like(z)
-        self._ck(self.lib.cddpm_op_spark_bn_forward(self.h, _p(z), _p(self.p[name + ".weight"]), _p(self.p[name + ".bias"]), None, _p(res), int(act),
-                                                    C.c_float(BN_EPS), C.c_float(BN_MOMENTUM), _p(self.buf[name + ".running_mean"]),
-                                                    _p(self.buf[name + ".running_var"]), _p(mr), _p(y), B * H * W, H * W, Cc, _p(active), f, H, W,
-                                                    _p(fill), int(training), self._s()), "op_spark_bn_forward")
-        return y, mr
+        return spark_bn_forward(self, name, z, act, active, f, res=res, fill=fill, training=training)
 
     def bn_bwd(self, name, z, y, dy, mr, act, active=None, f=1, dfill=None):
-        B, H, W, Cc = z.shape
-        dz = torch.empty_like(z)
-        self._ck(self.lib.cddpm_op_spark_bn_backward(self.h, _p(z), _p(y), _p(dy), _p(mr), _p(self.p[name + ".weight"]), None, int(act), _p(dz), None,
-                                                     _p(self.g[name + ".weight"]), _p(self.g[name + ".bias"]), B * H * W, H * W, Cc, _p(active), f, H, W,
-                                                     _p(dfill), 1, self._s()), "op_spark_bn_backward")
-        return dz
+        return spark_bn_backward(self, name, z, y, dy, mr, act, active, f, dfill=dfill)[0]
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, active: torch.Tensor, training=True, drop_scales: Optional[Dict[str, torch.Tensor]] = None):

@@ -683,7 +683,7 @@ int cddpm_op_gn_coef(cddpm_handle h, const float* src0_dev, int C0, const float*
 size_t cddpm_packed_conv_bytes(int Cout, int Cin, int taps);
 int cddpm_pack_conv_weights(const float* w_host, int Cout, int Cin, int taps, void* dst_host, int* scale_exp_out);
 
-/* ---- the training step (csrc/train_kernels.hip, csrc/encoder_train.hip): the operators that the host
+/* ---- the training step (csrc/train_kernels.hip, csrc/encoder_train.hip, csrc/batchnorm_train.hip): the operators that the host
  *      sequencing of the package (training.py, encoder_training.py) strings into src/models/DDPM_2D.py:114-135 -> cond_DDPM.py:565-645
  *      with gradients, Adam (:305-306) and the gradient all-reduce. Host-pointer variants (w_host ...) serve the kernel tests; the step
  *      itself runs on the device-resident calls further down (cddpm_op_pack_conv, cddpm_op_conv_packed, scratch arena). */
@@ -928,6 +928,10 @@ int cddpm_op_gn_coef_rec(cddpm_handle h, const float* rec0_dev, int n0, int C0, 
  *   for the backward, running statistics updated as torch does (momentum, unbiased variance) when given; s_b (sample_scale_dev [B] or NULL = 1) is
  *   the stochastic-depth scale of the residual branch (timm drop_path).  cddpm_op_enc_bn_backward: dz, dgamma, dbeta and (dres_dev given) the
  *   shortcut operand's gradient dy [y > 0].
+ *   There is ONE training BatchNorm in the library (csrc/batchnorm_train.hip); this pair and cddpm_op_spark_bn_forward / _backward below are
+ *   two callers of it. What this pair fixes: no mask, no fill value, ReLU or none, training mode; C a multiple of 64; the pixels are summed
+ *   in clamp(N / 256, 1, 32) chunks (the order of the fp64 sums, hence the bits, and the grid); 2 planes of partial sums per chunk in the
+ *   backward's scratch; N = 1 is accepted (the biased variance then goes into the running variance).
  * cddpm_op_enc_maxpool: 3x3 / 2 pad 1 forward (backward = 0) or its backward in gather form (first maximum in row-major order, as torch;
  *   deterministic).  cddpm_op_enc_avgpool: global average pool x [B,HW,C] -> g [B,C], or (backward = 1) dL/dg [B,C] (first pointer) -> dL/dx (second). */
 int cddpm_op_enc_pack_w(cddpm_handle h, const float* w_dev, int Cout, int Cin, int K, float* wf_dev, float* wd_dev, void* stream);
@@ -965,13 +969,17 @@ int cddpm_op_enc_maxpool(cddpm_handle h, const float* x_dev, float* y_dev, int B
                          void* stream);
 int cddpm_op_enc_avgpool(cddpm_handle h, const float* x_dev, float* g_dev, int B, int HW, int C, int backward, void* stream);
 
-/* ---- operators of SparK masked pre-training (csrc/spark_train.hip): what reference src/models/Spark_2D.py trains beside the ResNet-50 --
+/* ---- operators of SparK masked pre-training (csrc/spark_train.hip, csrc/batchnorm_train.hip): what reference src/models/Spark_2D.py trains beside the ResNet-50 --
  * the sparse BatchNorm of the converted encoder (src/models/modules/spark/encoder.py:25-35, :183-190), densify (spark/Spark_2D.py:157-171),
  * the LightDecoder (spark/decoder.py:17-76), spatial_loss (spark/Spark_2D.py:180-199) and AdamW (src/models/Spark_2D.py:123-124). NHWC fp32
  * device tensors; nothing uses float atomics, two calls give the same bits.
  * The cell mask active_dev: uint8 [B][f][f]; pixel (b, y, x) of an H x W tensor is active iff active[b][y f / H][x f / W] (H and W multiples
  * of f: the mask dilated to the tensor's resolution, encoder.py:13-16).
- * cddpm_op_spark_bn_forward / _backward: cddpm_op_enc_bn_forward / _backward, sparse or dense, with a fill value and ReLU6:
+ * cddpm_op_spark_bn_forward / _backward: the BatchNorm of cddpm_op_enc_bn_forward / _backward (one implementation, csrc/batchnorm_train.hip)
+ *   with all of its options -- sparse or dense, a fill value, ReLU6, evaluation mode -- on this pair's own plan: C a multiple of 4, the
+ *   pixels summed in clamp(N C / 16384, 1, 128) chunks, 3 planes of partial sums per chunk in the backward's scratch (the third: dfill),
+ *   fewer than two values per channel refused. Where both chunk rules give the same count (C = 64, N <= 8192) the two pairs return the
+ *   same bits for the same dense call.
  *   y = act((active ? ((z - mean_c) rstd_c gamma_c + beta_c) : fill_c) s_b + res), act 0 none | 1 ReLU | 2 ReLU6 (decoder.py:26).
  *   active_dev NULL = dense (nn.BatchNorm2d); given = BatchNorm1d over the active pixels only (sp_bn_forward): batch statistics in fp64 over the
  *   n_act active pixels, n_act counted on the device, running mean / unbiased variance updated with n_act. fill_dev [C] or NULL = 0: what

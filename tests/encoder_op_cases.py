@@ -3,7 +3,8 @@ test_gpu_encoder_training_calls.py): the case tables, the plans the library itse
 references, each computed once per process and never modified. Nothing here needs a GPU.
 
 The tables are data. Which plan a case reaches -- the contraction split Z of a convolution (enc_conv_split), the pixel ranges P of a weight
-gradient (enc_wgrad_parts, enc_wgrad_p16_parts), the chunks of a BatchNorm reduction (enc_bn_chunks) -- is read back from the library's own
+gradient (enc_wgrad_parts, enc_wgrad_p16_parts), the chunks of a BatchNorm reduction (enc_bn_chunks: the rule of the
+cddpm_op_enc_bn_* entries in csrc/cddpm_ops.hip; the BatchNorm itself is csrc/batchnorm_train.hip) -- is read back from the library's own
 size queries (cddpm_op_enc_*_scratch of include/cddpm.h: host code): a request is a whole number of planes, so the plane count is the
 quotient. No plan formula is restated here; tests/test_encoder_op_cases_host.py asserts that the tables reach the plans they are there for.
 

@@ -1,5 +1,6 @@
 """What the tests of the SparK operators share (tests/test_spark_op_cases_host.py, tests/test_gpu_spark_ops_edges.py): the plan rules of
-csrc/spark_train.hip restated in Python with the source line beside each, one table of cases per operator (a comment states the edge each
+csrc/spark_train.hip, of the BatchNorm behind cddpm_op_spark_bn_* (csrc/batchnorm_train.hip) and of that entry (csrc/cddpm_ops.hip) restated in
+Python with the source line beside each, one table of cases per operator (a comment states the edge each
 case is there for), seeded operands, float64 references written from each operation's definition, and the results a wrong kernel of a
 given kind would produce (`mut`). Nothing here needs a GPU; everything is computed once per process (lru_cache) and never modified.
 
@@ -42,30 +43,30 @@ def r256(nbytes):
 
 
 def count_trips(ncell):
-    """spark_count_active, spark_train.hip:22: for (i = threadIdx.x; i < ncell; i += 256) -> trips of thread 0"""
+    """count_active_cells, kernels.h:362: for (i = threadIdx.x; i < ncell; i += 256) -> trips of thread 0"""
     return len(range(0, ncell, 256))
 
 
 def bn_chunks(N, C):
-    """spark_bn_chunks, spark_train.hip:224-228"""
+    """spark_bn_chunks, cddpm_ops.hip:836-840: the chunk rule of the cddpm_op_spark_bn_* entries"""
     return max(1, min(128, N * C // 16384))
 
 
 def bn_lanes(C):
-    """spark_bn_args / spark_bn_partial_grid, spark_train.hip:234, 237 -> (qpb, rows, blockIdx.y blocks)"""
+    """bn_train_args / launch_bn_chan_partial, batchnorm_train.hip:238, 243 -> (qpb, rows, blockIdx.y blocks)"""
     qpb = min(C // 4, 16)
     return qpb, 256 // qpb, (C // 4 + qpb - 1) // qpb
 
 
 def chunk_ranges(N, nchunk):
-    """per = ceil(N / nchunk), [per k, min(per k + per, N)): spark_train.hip:64 (BatchNorm), :476 (channel sum), :517 (loss).
+    """per = ceil(N / nchunk), [per k, min(per k + per, N)): batchnorm_train.hip:54 (BatchNorm), spark_train.hip:227 (channel sum), :274 (loss).
     A range whose start is at or beyond N is empty"""
     per = (N + nchunk - 1) // nchunk
     return [(per * k, max(per * k, min(per * k + per, N))) for k in range(nchunk)]
 
 
 def conv_split(M, Cd, Cs, K):
-    """spark_conv_split, spark_train.hip:373-379 -> (Z, nstep)"""
+    """spark_conv_split, spark_train.hip:124-130 -> (Z, nstep)"""
     wgs = ((M + 63) // 64) * ((Cd + 63) // 64)
     nstep = K * K * ((Cs + 15) // 16)
     Z = 1
@@ -75,34 +76,34 @@ def conv_split(M, Cd, Cs, K):
 
 
 def step_ranges(nstep, Z):
-    """spark_conv_kernel, spark_train.hip:331: s0 = nstep z / Z, s1 = nstep (z + 1) / Z; step = tap nck + 16-channel chunk (:306)"""
+    """spark_conv_kernel, spark_train.hip:82: s0 = nstep z / Z, s1 = nstep (z + 1) / Z; step = tap nck + 16-channel chunk (:57)"""
     return [(nstep * z // Z, nstep * (z + 1) // Z) for z in range(Z)]
 
 
 def wgrad_parts(M, Cd, Cg, K):
-    """spark_wgrad_parts, spark_train.hip:460-466"""
+    """spark_wgrad_parts, spark_train.hip:211-217"""
     per = ((Cd + 63) // 64) * ((Cg + 63) // 64) * K * K
     return max(1, min((512 + per - 1) // per, M // 64, 64))
 
 
 def pixel_ranges(M, P):
-    """spark_wgrad_kernel, spark_train.hip:402: m0 = M part / P, m1 = M (part + 1) / P, walked in steps of 16 pixels (:410)"""
+    """spark_wgrad_kernel, spark_train.hip:153: m0 = M part / P, m1 = M (part + 1) / P, walked in steps of 16 pixels (:161)"""
     return [(M * k // P, M * (k + 1) // P) for k in range(P)]
 
 
 def chan_sum_chunks(M, C):
-    """spark_chan_sum_chunks, spark_train.hip:495-499"""
+    """spark_chan_sum_chunks, spark_train.hip:246-250"""
     return max(1, min(256, M * C // 8192))
 
 
 def loss_chunks(total):
-    """spark_loss_chunks, spark_train.hip:547-551"""
+    """spark_loss_chunks, spark_train.hip:304-308"""
     return max(1, min(256, total // 4096))
 
 
 def cell_mask(active, H, W, swap=False):
-    """bool [B,f,f] -> bool [B,H,W] by the kernels' own index ((b f + y / ch) f + x / cw), ch = H / f, cw = W / f (spark_train.hip:51-53,
-    :275, :524). swap: ch and cw exchanged; an index that then leaves the mask reads 0"""
+    """bool [B,f,f] -> bool [B,H,W] by the kernels' own index ((b f + y / ch) f + x / cw), ch = H / f, cw = W / f (batchnorm_train.hip:38-40,
+    spark_train.hip:26, :281). swap: ch and cw exchanged; an index that then leaves the mask reads 0"""
     B, f = active.shape[0], active.shape[1]
     ch, cw = (W // f, H // f) if swap else (H // f, W // f)
     b, y, x = torch.arange(B).view(B, 1, 1), torch.arange(H).view(1, H, 1), torch.arange(W).view(1, 1, W)
@@ -134,7 +135,7 @@ def _bn(B, H, W, f, C, sparse, act, **kw):
 
 
 BN_CASES = {
-    # 297 cells, one pixel each: spark_count_active's second trip; active cells at index >= 256. Residual, sample scale, dres, running statistics
+    # 297 cells, one pixel each: count_active_cells' second trip; active cells at index >= 256. Residual, sample scale, dres, running statistics
     "cells297_relu_res_ss": _bn(33, 3, 3, 3, 64, True, 1, res=True, ss=True, dres=True),
     # H != W with ch = 5 != cw = 7; C = 72: 18 quads over two blockIdx.y blocks, the second partial. ReLU6 with fill and residual
     "rect_c72_relu6_fill_res": _bn(2, 10, 14, 2, 72, True, 2, res=True, fill=True, dres=True),
@@ -349,7 +350,7 @@ def conv_plan(case):
     _, _, (Ho, Wo), _ = conv_geom(case)
     Zy, ny = conv_split(B * Ho * Wo, Cout, Cin, K)
     Zd, nd = conv_split(B * H * W, Cin, Cout, K)
-    Cd, Cg = (Cin, Cout) if tc else (Cout, Cin)            # cddpm_ops.hip:913
+    Cd, Cg = (Cin, Cout) if tc else (Cout, Cin)            # cddpm_ops.hip:968
     return dict(Zy=Zy, steps_y=ny, Zdx=Zd, steps_dx=nd, P=wgrad_parts(B * H * W, Cd, Cg, K), db_chunks=chan_sum_chunks(B * Ho * Wo, Cout) if bias else 0)
 
 
@@ -506,7 +507,7 @@ LOSS_CASES = {
     "ragged_all_masked": (3, 51, 63, 3, "all_masked", (0.5, 1.0), True),
     "ragged_nothing_masked": (3, 51, 63, 3, "nothing_masked", (0.5, 1.0), True),
     "ragged_no_gradient": (3, 51, 63, 3, "mixed", (0.5, 1.0), False),            # drec_dev = NULL: the scalars are unchanged
-    # 320 cells: spark_count_active's second trip; total 1280 < 4096: one chunk
+    # 320 cells: count_active_cells' second trip; total 1280 < 4096: one chunk
     "cells320_below_4096": (5, 16, 16, 8, "mixed", (0.5, 1.0), True),
     # the cap: 256 chunks of 4113, the last 3861
     "cap256": (1, 1026, 1026, 2, "mixed", (0.5, 1.0), True),

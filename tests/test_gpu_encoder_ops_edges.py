@@ -1,4 +1,4 @@
-"""GPU: the training operators of the context encoder (csrc/encoder_train.hip and encoder_train_p16.hip behind cddpm_op_enc_*) one call at a
+"""GPU: the training operators of the context encoder (csrc/encoder_train.hip, encoder_train_p16.hip and batchnorm_train.hip behind cddpm_op_enc_*) one call at a
 time at the edges of their plans: many row tiles with a ragged last one, every contraction split, weight-gradient pixel ranges from one to the
 cap, chunked BatchNorm reductions, max-pool inputs full of ties. The cases are tests/encoder_op_cases.py's; that they reach those plans is
 what tests/test_encoder_op_cases_host.py asserts on the CPU. References are float64 on the CPU (for precision 16 on the operands rounded to
@@ -154,8 +154,9 @@ def test_two_calls_return_identical_bits(ops, case, precision):
 
 
 # ---------------------------------------------------------------------------------------------------------------- BatchNorm
-def run_bn(ops, case, o, opt):
-    """forward and backward on the device -> dict of float64 NCHW / per-channel results (keys as EC.bn_reference)"""
+def run_bn(ops, case, o, opt, entry="enc"):
+    """forward and backward on the device -> dict of float64 NCHW / per-channel results (keys as EC.bn_reference). entry "spark": the same
+    call through cddpm_op_spark_bn_forward / _backward without a mask or a fill value, f = 1, in training mode, act = relu"""
     lib, h = ops.lib, ops.h
     B, C_, H, W = case
     N, HW = B * H * W, H * W
@@ -169,13 +170,15 @@ def run_bn(ops, case, o, opt):
         rm.out.copy_(o["run_mean"].float()), rv.out.copy_(o["run_var"].float())
     relu = int(opt["relu"])
     mr, y = Banded((2, C_), band), Banded((B, H, W, C_), band)
-    ok(ops, lib.cddpm_op_enc_bn_forward(h, zg.ptr(), gam.data_ptr(), bet.data_ptr(), p(ssg), rg and rg.ptr(), relu, C.c_float(EC.BN_EPS), C.c_float(EC.BN_MOMENTUM),
-                                        rm and rm.ptr(), rv and rv.ptr(), mr.ptr(), y.ptr(), N, HW, C_, None))
+    forward, backward = (lib.cddpm_op_enc_bn_forward, lib.cddpm_op_enc_bn_backward) if entry == "enc" else (lib.cddpm_op_spark_bn_forward, lib.cddpm_op_spark_bn_backward)
+    tail = (None,) if entry == "enc" else (None, 1, H, W, None, 1, None)          # stream | active, f, H, W, fill / dfill, training, stream
+    ok(ops, forward(h, zg.ptr(), gam.data_ptr(), bet.data_ptr(), p(ssg), rg and rg.ptr(), relu, C.c_float(EC.BN_EPS), C.c_float(EC.BN_MOMENTUM),
+                    rm and rm.ptr(), rv and rv.ptr(), mr.ptr(), y.ptr(), N, HW, C_, *tail))
     dz, dres = Banded((B, H, W, C_), band), (Banded((B, H, W, C_), band) if opt["dres"] else None)
     dg, db = Banded((C_,), 64), Banded((C_,), 64)
     assert not (opt["y_null"] and relu)
-    ok(ops, lib.cddpm_op_enc_bn_backward(h, zg.ptr(), None if opt["y_null"] else y.ptr(), dyg.ptr(), mr.ptr(), gam.data_ptr(), p(ssg), relu, dz.ptr(),
-                                         dres and dres.ptr(), dg.ptr(), db.ptr(), N, HW, C_, None))
+    ok(ops, backward(h, zg.ptr(), None if opt["y_null"] else y.ptr(), dyg.ptr(), mr.ptr(), gam.data_ptr(), p(ssg), relu, dz.ptr(),
+                     dres and dres.ptr(), dg.ptr(), db.ptr(), N, HW, C_, *tail))
     torch.cuda.synchronize()
     what = "x".join(map(str, case)) + " " + EC.bn_option_id(opt)
     mrc = mr.check(what + " mean|rstd").double()
@@ -229,6 +232,29 @@ def test_batchnorm_with_a_large_mean(ops, case, ratio):
     print(case, "ratio", ratio, {k: f"{e:.1e} (torch fp32 {t:.1e})" for k, (e, t) in rows.items()})
     for k, (e, t) in rows.items():
         assert e < max(BN_LIMIT, 4 * t), (k, e, t)
+
+
+@pytest.mark.parametrize("opt", [EC.BN_OPTIONS[1], EC.BN_OPTIONS[2]], ids=EC.bn_option_id)        # everything on; nothing on (no ReLU: y may be NULL)
+@pytest.mark.parametrize("case", [(2, 64, 9, 7),          # N = 126: one chunk, a ragged lane tail
+                                  (2, 64, 23, 29)],       # N = 1334: five chunks, the last ragged, a sample boundary inside a chunk
+                         ids=lambda c: "x".join(map(str, c)))
+def test_batchnorm_entries_are_one_implementation(ops, case, opt):
+    """cddpm_op_enc_bn_* and cddpm_op_spark_bn_* (no mask, f = 1, no fill, training) run the same kernels (csrc/batchnorm_train.hip); what
+    differs is the plan each entry hands them. At C = 64 and N <= 8192 both chunk rules give N / 256 chunks (N 64 / 16384), so every
+    result has the same bits: the fp64 partial sums are taken and folded in the same order, the elementwise passes are the same code."""
+    B, C_, H, W = case
+    N, HW = B * H * W, H * W
+    q = lambda name: getattr(ops.lib, f"cddpm_op_{name}_scratch")(N, HW, C_)
+    r256 = lambda n: (n + 255) // 256 * 256
+    nchunk = max(1, N // 256)
+    assert q("enc_bn_forward") == r256(nchunk * 2 * C_ * 8)                           # the two rules agree here: nchunk chunks of 2 planes ...
+    assert q("spark_bn_forward") == r256(nchunk * 2 * C_ * 8) + 256                   # ... + the status words
+    assert q("spark_bn_backward") == r256(nchunk * 3 * C_ * 8) + r256(2 * C_ * 4)     # 3 planes in the spark entry's backward
+    o = EC.bn_operands(case)
+    enc, spark = run_bn(ops, case, o, opt, "enc"), run_bn(ops, case, o, opt, "spark")
+    assert set(enc) == set(spark) >= {"y", "mean", "rstd", "dz", "dgamma", "dbeta"}
+    for k in enc:
+        assert torch.equal(enc[k].float().view(torch.int32), spark[k].float().view(torch.int32)), k
 
 
 # ---------------------------------------------------------------------------------------------------------------- pooling
