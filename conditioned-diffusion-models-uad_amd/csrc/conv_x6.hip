@@ -24,14 +24,31 @@
 //
 // GEMM view:  D[pixel][cout] = sum_{tap, ci} act(X)[pixel + tap][ci] * Wt[tap][ci][cout]
 //   M = 256 pixels (8 image rows x 32 columns), N = 128 output channels, K step = 32 input channels x 1 tap
-//   = 2 MFMA k-steps of 16. 8 waves (2 per SIMD), each owns 64 pixels x 64 couts = 2 x 2 MFMA tiles.
+//   (bf16 form: 2 MFMA k-steps of 16; fp16 form: one MFMA of 16 x 16 x 32). 8 waves (2 per SIMD), each owns 64 pixels x 64 couts:
+//   2 x 2 MFMA tiles of 32 x 32 (bf16 form) or 4 x 4 tiles of 16 x 16 (fp16 form). Which 64 pixels:
+//     row fragments (bf16 form; fp16 form: 1x1 taps and the 256-cout workgroups): tile rows 2 wm, 2 wm + 1, all 32 columns; an A fragment
+//       is 16 (32) consecutive columns of one row;
+//     column fragments (fp16 form, 3x3 and folded 2x2 taps, 128-cout workgroups -- conv_colfrag): tile columns 4 wm .. 4 wm + 3 and
+//       16 + 4 wm .. 16 + 4 wm + 3, all 8 rows; an A fragment is the 8 rows of one column and of the column 16 further right. A weight stage
+//       is one ROW of taps (ky fixed, kx = 0, 1, 2), and fragment j + 1 of tap kx is fragment j of tap kx + 1: the stage keeps a ring of four
+//       column fragments per term and reads 4 + 1 + 1 columns (12 ds_read_b128 with both terms) where row fragments read 3 x 4 (24); with the
+//       24 weight fragments 36 reads per 144 MFMAs instead of 48 (folded 2x2: 26 instead of 32). Each output is the same products added in the
+//       same order -- which row of an MFMA tile holds a pixel does not enter the sum -- so the two mappings agree bit for bit
+//       (tests/test_gpu_conv_fragment_reuse.py against the digests of the row-fragment build). The epilogue hands the accumulators back to
+//       the row partition through LDS, so stores, residual adds and the statistics records are formed exactly as with row fragments.
 // LDS (one workgroup per CU): per pixel / per cout row SP = 4 NS slots of 16 B (slot = split s, u = channel / 8):
-//   NS = 3: stride 12 slots, slot (s, u) at 4 s + (u ^ ((row >> 2) & 3));  NS = 2: stride 8, (4 s + u) ^ ((row >> 1) & 7)
-//   -> 16 consecutive rows x one slot cover all 16 four-bank groups: ds_read_b128 of a fragment is conflict free.
-//   act patch (8+2) x (32+2) pixels (65 | 43.5 KB) + 2 weight stages (bf16: one slab [128 cout][SP] = 24.6 KB each;
-//   fp16: a row of three taps = 3 x 16 KB each) + coefficient cache;
+//   weights, and the patch of the bf16 form:  NS = 3: stride 12 slots, slot (s, u) at 4 s + (u ^ ((row >> 2) & 3));  NS = 2: stride 8,
+//   (4 s + u) ^ ((row >> 1) & 7) -> 16 consecutive rows x one slot cover all 16 four-bank groups: ds_read_b128 of a fragment is conflict free.
+//   patch of the fp16 form, row fragments: stride 8, slot bits 1, 2 swizzled by the pixel's column (swz16 below);
+//   column fragments: patch row pitch PW * 8 + 2 slots (2 mod 16 times an odd number), pixel (pr, pc) at pr * pitch + 8 pc, slot
+//   (4 s + u) ^ 4 (pc & 1) inside it: the 16 lanes one LDS cycle serves are the 8 rows of a column at u and of the column 16 further at u ^ 1,
+//   8 even slot offsets x 2 -> all 16 four-bank groups, for every tap (a tap's row adds a multiple of the pitch, its column a constant);
+//   exchanging hi and mid in odd columns keeps the two pixels of a ds_write_b64 group on different banks. No address arithmetic per tap.
+//   act patch (8+2) x (32+2) pixels (bf16 65 KB | fp16 43.5 KB, with column fragments 44.0 KB) + 2 weight stages
+//   (bf16: one slab [128 cout][SP] = 24.6 KB each; fp16: a row of three taps = 3 x 16 KB each) + coefficient cache;
 //   the packed global weight image (host-split, pack_conv_weights_split) IS the LDS image: staging is a 16-B copy.
-// A lane's 16-B fragment = 8 consecutive channels = its K elements of one k-step (lane>>5 selects the half).
+// A lane's 16-B fragment = 8 consecutive channels = its K elements of one k-step (bf16 form: lane >> 5 selects the half; fp16 form: lane >> 4
+// selects the quarter of the 32-channel chunk).
 #include "kernels.h"
 #include "conv_split.h"
 #include <algorithm>
@@ -54,6 +71,14 @@ namespace cddpm {
 // one long-lived chain (rounding noise of a K = 4608 dot product 7.6e-7 of rms(C) instead of 1.9e-7; the reference's CPU fmaf chain:
 // 1.2e-6 -- tools/ubench/bf16_split_accuracy.hip, rows "h3" / "h3 fold96" / "cpu fma32").
 static constexpr int ROWS = 8;      // image rows of a workgroup's pixel tile (x 32 columns), two per wave
+// 16 x 16 form: which instantiations hold COLUMN fragments (a fragment = the 8 rows of one patch column and of the column 16 further
+// right, so that the A operand of tap kx + 1 is the A operand of tap kx one fragment on: a row of taps reads each column once).
+// Results are identical either way; the 1x1 form has one tap and nothing to reuse, and the 256-cout workgroups (NB = 2: 128 accumulator
+// registers in one chain, 253 VGPRs as they are) spill with the ring (3x3: 129 VGPRs, 176 B of scratch per lane), so they keep row
+// fragments. Kernel and launcher (LDS size) both ask here.
+static constexpr bool conv_colfrag(int ns, int taps, bool hi1, int nb) { return ns == 2 && taps != 1 && nb == 1; }
+static constexpr int conv_colfrag_pitch(int pw) { return pw * 8 + 2; }      // 16-B slots per patch row: 2 mod 16 x odd -> the 8 rows of a column start in 8 different even slots
+static constexpr int conv_colfrag_slots(int pw, int ph) { return (ph * conv_colfrag_pitch(pw) + 15) & ~15; }
 template <int TAPS, int NS, bool HI1 = false, int NB = 1>
 __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a) {
     static_assert(NB == 1 || (NB == 2 && NS == 2 && TAPS != 1), "two cout blocks per workgroup: 16 x 16 fp16 form, LDS-DMA loop (3x3 and folded 2x2) only");
@@ -77,9 +102,13 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     constexpr int WK = WSLOTS / THREADS;                // 16-B pieces of ONE slab per thread: 3 | 2
     static_assert(WSLOTS % THREADS == 0, "weight slab must divide evenly");
 
+    constexpr bool COLF = conv_colfrag(NS, TAPS, HI1, NB);      // column fragments (16 x 16 form)
+    constexpr int CPITCH = conv_colfrag_pitch(PW);              // ... their patch row pitch in slots
+    constexpr int ASLOTS = COLF ? conv_colfrag_slots(PW, PH) : NPIX * SP;
+
     extern __shared__ v4f lds[];
-    v4f* ldsA = lds;                    // NPIX * SP slots
-    v4f* ldsW = lds + NPIX * SP;        // 2 * WSTAGE
+    v4f* ldsA = lds;                    // ASLOTS slots
+    v4f* ldsW = lds + ASLOTS;           // 2 * WSTAGE
     v4f* ldsC = ldsW + 2 * WSTAGE;      // GroupNorm/FiLM coefficients of this sample (3 x Cin floats)
 
     const int tid = threadIdx.x;
@@ -148,12 +177,13 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     const int c4 = tid & 7;
     int psrc[NK];
     unsigned centre = 0;
-    unsigned colswz = 0;                 // 16x16 form: swz16(column) of entry k in bits 3k .. 3k+2
+    unsigned colswz = 0;                 // 16x16 form: swz16(column) of entry k in bits 3k .. 3k+2 (column fragments: patch row | column parity << 4 in bits 5k .. 5k+4)
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         const int q = (tid >> 3) + (THREADS / 8) * k;
         const int pr = q / PW, pc = q - pr * PW;
-        if constexpr (M16) colswz |= (unsigned)swz16(pc) << (3 * k);
+        if constexpr (COLF) colswz |= (unsigned)(pr | ((pc & 1) << 4)) << (5 * k);
+        else if constexpr (M16) colswz |= (unsigned)swz16(pc) << (3 * k);
         const int y = UP2 ? (y0 + pr + pa - 1) : (y0 + pr - PAD), x = UP2 ? (x0 + pc + pb - 1) : (x0 + pc - PAD);
         const bool valid = (q < NPIX) && (y >= 0) && (y < gridH) && (x >= 0) && (x < gridW);
         const int sy = (!UP2 && a.upsample) ? (y >> 1) : y, sx = (!UP2 && a.upsample) ? (x >> 1) : x;
@@ -237,7 +267,9 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 // 4 channels = half a slot: slot u = c4 >> 1 of each split, half c4 & 1
 #pragma unroll
                 for (int sp = 0; sp < (HI1 ? 1 : NS); ++sp) {        // (hi-only products never read the mid plane: it is neither computed nor stored)
-                    const int sl = M16 ? (q * 8 + ((4 * sp + (c4 >> 1)) ^ (int)((colswz >> (3 * k)) & 7u))) : slot_a(q, sp, c4 >> 1);
+                    // column fragments: pixel (pr, pc) at pr * CPITCH + 8 pc = 8 q + 2 pr, odd columns with hi and mid exchanged
+                    const int sl = COLF ? (q * 8 + 2 * (int)((colswz >> (5 * k)) & 15u) + ((4 * sp + (c4 >> 1)) ^ (4 * (int)((colswz >> (5 * k + 4)) & 1u))))
+                                 : M16 ? (q * 8 + ((4 * sp + (c4 >> 1)) ^ (int)((colswz >> (3 * k)) & 7u))) : slot_a(q, sp, c4 >> 1);
                     dst[sl * 2 + (c4 & 1)] = __builtin_bit_cast(v2f, sreg[k][sp]);
                 }
             }
@@ -293,9 +325,13 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     // pair for the weights; everything else is an instruction offset. A tap's ky adds ky * PW * 8 slots.
     constexpr int NKX = (TAPS == 9) ? 3 : (UP2 ? 2 : 1);
     static_assert(!M16 || TPS == NKX, "16x16 form: a weight stage is one row of taps, so the column shift is the unrolled index");
-    int a_hi[NKX], a_mid[NKX], b_hi = 0, b_mid = 0;
+    int a_hi[NKX], a_mid[NKX], b_hi = 0, b_mid = 0, a_col = 0;
     if constexpr (M16) {
         const int r16 = lane & 15, g = lane >> 4;
+        // column fragments: wave wm owns the patch columns 4 wm + c and 16 + 4 wm + c (c = fragment j + tap kx: 0 .. 3 + NKX - 1), MFMA row
+        // r16 = patch row r16 & 7 of the left (r16 < 8) or right column. ONE base: the column c (8 c slots, hi / mid at 4 (c & 1) and its
+        // complement), the tap row ky and the term are offsets from it.
+        a_col = (r16 & 7) * CPITCH + (4 * wm + 16 * (r16 >> 3)) * 8 + g;
 #pragma unroll
         for (int kx = 0; kx < NKX; ++kx) {
             const int pc = r16 + kx;
@@ -392,6 +428,55 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             }
         }
     };
+
+    // Column fragments: NT taps kx = KX0 .. KX0 + NT - 1 of tap row ky against the weight slabs wb, wb + WSLOTS, ... (a whole stage:
+    // KX0 = 0, NT = TPS; the 1x1 skip segment: its centre tap alone). Tap tt multiplies the columns tt .. tt + 3 of the ring: the first
+    // tap reads four columns, each later one only the column that enters (into the registers of the one that left), requested in front
+    // of its MFMAs on the three retained columns. Per output the products and their order are those of compute(): the accumulators restart
+    // (C = 0) in the first product of the stage's first tap.
+    auto compute_cols = [&](auto hc, auto kx0c, auto ntc, int ky, const v4f* wb) {
+        constexpr int HB = decltype(hc)::value, KX0 = decltype(kx0c)::value, NT = decltype(ntc)::value;
+        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+        const v4f* ap = ldsA + (a_col + ky * CPITCH);
+        const v4f* bh = wb + b_hi;
+        const v4f* bm = wb + b_mid;
+        f16x8 fa[2][NT + 3];
+        auto read_col = [&](int c) {
+            const int pc = KX0 + c;         // column shift against the wave's first column: its parity is the patch column's
+            fa[0][c] = __builtin_bit_cast(f16x8, ap[pc * 8 + 4 * (pc & 1)]);
+            if constexpr (!HI1) fa[1][c] = __builtin_bit_cast(f16x8, ap[pc * 8 + 4 * ((pc & 1) ^ 1)]);
+        };
+#pragma unroll
+        for (int c = 0; c < 4; ++c) read_col(c);
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) {
+            if (tt > 0) {
+                __builtin_amdgcn_sched_barrier(0);      // not earlier: the column that left gives up its registers with the previous tap's last MFMAs
+                read_col(tt + 3);
+            }
+#pragma unroll
+            for (int nh = 0; nh < 2; ++nh) {
+                f16x8 fb[2][2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    fb[0][j] = __builtin_bit_cast(f16x8, bh[tt * WSLOTS + 128 * (2 * nh + j)]);
+                    if constexpr (!HI1) fb[1][j] = __builtin_bit_cast(f16x8, bm[tt * WSLOTS + 128 * (2 * nh + j)]);
+                }
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {       // mid*hi, hi*mid, hi*hi
+                    const int sa = (p == 0) ? 1 : 0, sb = (p == 1) ? 1 : 0;
+                    if constexpr (HI1) { if (p < 2) continue; }
+                    const bool first = (NB == 1) && (tt == 0) && (HI1 ? p == 2 : p == 0);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc16[HB][i][2 * nh + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[sa][tt + i], fb[sb][j], first ? zero4 : acc16[HB][i][2 * nh + j], 0, 0, 0);
+                }
+            }
+        }
+    };
+    constexpr int SKY = (TAPS == 1) ? 0 : 1, SKX = (TAPS == 9) ? 1 : 0;      // the skip segment's (centre) tap
 
     if constexpr (TPS == 1) {
     // ---- main loop: weights double-buffered in LDS and prefetched through registers one stage ahead;
@@ -496,6 +581,10 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 const v4f* pn = last_st ? wstage(chunk + 1, 0, 0, nsl_next) : wstage(chunk, 0, st + 1, nsl_next);
                 dma_stage(pn, nsl_next, buf ^ 1);
             }
+            if constexpr (COLF) {      // (a main stage is tap row ky = st)
+                if (main_seg) compute_cols(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, TPS>{}, st, ldsW + buf * WSTAGE);
+                else compute_cols(std::integral_constant<int, 0>{}, std::integral_constant<int, SKX>{}, std::integral_constant<int, 1>{}, SKY, ldsW + buf * WSTAGE);
+            } else
 #pragma unroll
             for (int tt = 0; tt < TPS; ++tt)
                 if (tt < ntaps) {
@@ -525,6 +614,10 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                                             : (st == nst - 1 ? wstage(chunk, HB + 1, 0, nsl_next) : wstage(chunk, HB, st + 1, nsl_next));
                     dma_stage(pn, nsl_next, buf ^ 1);
                 }
+                if constexpr (COLF) {
+                    if (main_seg) compute_cols(hc, std::integral_constant<int, 0>{}, std::integral_constant<int, TPS>{}, st, ldsW + buf * WSTAGE);
+                    else compute_cols(hc, std::integral_constant<int, SKX>{}, std::integral_constant<int, 1>{}, SKY, ldsW + buf * WSTAGE);
+                } else
 #pragma unroll
                 for (int tt = 0; tt < TPS; ++tt)
                     if (tt < ntaps) {
@@ -581,7 +674,14 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     //      that every lane moves 16 B; bias, residual and the GroupNorm statistics of the output are applied here.
     {
         constexpr int TRS = M16 ? 36 : 32;                            // row stride of the transpose region (36: conflict-free for the 16 x 16 C layout)
-        float* tr = reinterpret_cast<float*>(lds) + wave * (64 * TRS);   // [64 pixels][32 channels]
+        // column fragments: a wave's accumulators are 8 rows x 8 columns of the tile, but outputs, residual adds and the statistics records
+        // are formed over 2 rows x 32 columns per wave as ever (the fp32 record sums depend on that order). Each wave therefore writes into
+        // the regions of the four waves of its cout half, at the pixel index the row partition gives, behind workgroup barriers; the
+        // regions sit 8 floats further apart so that the two row quads a store instruction covers do not share banks.
+        constexpr int TRW = 64 * TRS + (COLF ? 8 : 0);
+        float* tr = reinterpret_cast<float*>(lds) + wave * TRW;          // [64 pixels][32 channels]
+        // lane l, register r of column fragment j: MFMA row 4 (l >> 4) + r = tile row 4 ((l >> 4) & 1) + r, column 4 wm + j + 16 (l >> 5)
+        float* trx = reinterpret_cast<float*>(lds) + (4 * wn + 2 * ((lane >> 4) & 1)) * TRW + (4 * wm + 16 * (lane >> 5)) * TRS + (lane & 15);
         const int cq = lane & 7;
         const int prow = lane >> 3;
         const int tilesY4 = (gridH + 3) >> 2;                         // statistics records are per 4-row band (kernels.h)
@@ -590,7 +690,16 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         for (int q = 0; q < 2 * NB; ++q) {
             const int hb = q >> 1, nt = q & 1;
             const int co = (NB * cb + hb) * 128 + 64 * wn + 32 * nt + 4 * cq;
-            if constexpr (M16) {
+            if constexpr (COLF) {
+#pragma unroll
+                for (int t16 = 0; t16 < 4; ++t16)
+#pragma unroll
+                    for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)      // row r of the quad: wave 2 (..) + (r >> 1) of the row partition, its row r & 1
+                            trx[(r >> 1) * TRW + (32 * (r & 1) + t16) * TRS + 16 * n2] =
+                                (NB == 2) ? acc16[hb][t16][2 * nt + n2][r] : tot16[t16][2 * nt + n2][r];
+            } else if constexpr (M16) {
                 // C tile layout of the 16 x 16 form: register r of lane l = row 4 (l >> 4) + r (pixel), column l & 15 (cout)
 #pragma unroll
                 for (int t16 = 0; t16 < 4; ++t16)
@@ -607,7 +716,8 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     for (int r = 0; r < 16; ++r)
                         tr[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = tot[mt][nt][r];
             }
-            __builtin_amdgcn_wave_barrier();
+            if constexpr (COLF) __syncthreads();
+            else __builtin_amdgcn_wave_barrier();
             const v4f bias = a.bias ? *reinterpret_cast<const v4f*>(a.bias + co) : v4f{0.f, 0.f, 0.f, 0.f};
             const float wsc = (NS == 2) ? a.wscale_inv : 1.0f;      // fp16 weights were pre-scaled by a power of two
             v4f ssum = v4f{0.f, 0.f, 0.f, 0.f}, ssq = ssum;
@@ -651,7 +761,8 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     *reinterpret_cast<v4f*>(o + 4) = v4f{ssum.z, ssq.z, ssum.w, ssq.w};
                 }
             }
-            __builtin_amdgcn_wave_barrier();
+            if constexpr (COLF) { if (q + 1 < 2 * NB) __syncthreads(); }      // every wave has read its region before the next quarter lands in it
+            else __builtin_amdgcn_wave_barrier();
         }
     }
 }
@@ -677,8 +788,9 @@ static void launch_split(const ConvArgs& a, hipStream_t stream) {
     const size_t coef_lds = a.coef ? (size_t)3 * (a.C0 + a.C1) * sizeof(float) : 0;
     const int npix = (a.taps == 9) ? (ROWS + 2) * 34 : (up2 ? (ROWS + 1) * 33 : ROWS * 32);     // patch pixels (kernel: NPIX)
     const int tps = (NS == 2) ? (a.taps == 9 ? 3 : (up2 ? 2 : 1)) : 1;                             // taps per weight stage (kernel: TPS)
-    const size_t main = (size_t)(npix + 2 * tps * 128) * (4 * NS) * 16 + coef_lds;
-    const size_t tr = (size_t)ROWS * 64 * 36 * sizeof(float);   // epilogue transpose regions alias the buffers (stride <= 36)
+    const bool colf = conv_colfrag(NS, a.taps, a.hi_only, nb2 ? 2 : 1);    const int aslots = colf ? (a.taps == 9 ? conv_colfrag_slots(34, ROWS + 2) : conv_colfrag_slots(33, ROWS + 1)) : npix * 4 * NS;      // patch slots (kernel: ASLOTS)
+    const size_t main = (size_t)(aslots + 2 * tps * 128 * 4 * NS) * 16 + coef_lds;
+    const size_t tr = (size_t)ROWS * (64 * 36 + 8) * sizeof(float);   // epilogue transpose regions alias the buffers (stride <= 36, + 8 between regions)
     const size_t lds = main > tr ? main : tr;
     static bool attr = false;
     if (!attr) {

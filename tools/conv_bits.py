@@ -1,26 +1,153 @@
 #!/usr/bin/env python3
-"""md5 of the fused convolution's output bytes on fixed random inputs, per library build (CDDPM_LIB): two builds that claim the same
-arithmetic in the same order must print the same digests.  usage: CDDPM_LIB=<so> python tools/conv_bits.py"""
+"""md5 of the fused convolution's output bytes on fixed inputs, per library build (CDDPM_LIB): two builds that claim the same arithmetic
+in the same order must print the same digests.
+
+    CDDPM_LIB=<so> python tools/conv_bits.py [--mode default|nb2|p16|all] [--json FILE] [--parent COMMIT]
+
+Inputs come from numpy.random.default_rng(SEED) on the host (one generator per case, keyed by the case's position) and are copied to the
+device: no device generator is involved. The cases are the smallest shapes at which the wave -> pixel mapping of the 16 x 16 form can go
+wrong (csrc/conv_x6.hip: column fragments): one full tile, ragged rows and a partial / narrow last column tile, two sources with two cout
+blocks, the identity affine, the folded upsample's patch and parity classes, the 1x1 skip segment, the statistics records (digest of the
+coefficients that op_conv_gn returns), and three larger layers. Modes:
+    default  a precision-32 handle
+    nb2      the same under CDDPM_NB2=force (256-cout workgroups wherever the kernel can; the switch is read once per process, so this
+             mode wants a process of its own: `all` starts one)
+    p16      a precision-16 handle: the operators again, and a small UNet forward (plain-fp16 convolutions: the hi-only kernels)
+`default` and `p16` also digest that UNet forward. --json writes {parent, seed, cases, modes: {mode: {case: md5}}} (tests/golden/
+conv_bits_parent.json is this file, written once with CDDPM_LIB set to a build of the parent commit)."""
+import argparse
 import hashlib
 import importlib
+import json
 import os
+import subprocess
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-eng_mod = importlib.import_module("conditioned-diffusion-models-uad_amd.engine")
-e = eng_mod.CddpmEngine(timesteps=10, max_batch=4, max_h=64, max_w=64)
-torch.manual_seed(0)
-for (C0, C1, Cout, H, W, coef, res) in [(128, 0, 128, 64, 64, True, False), (256, 128, 256, 32, 40, True, True), (256, 0, 128, 24, 24, False, False)]:
-    B = 3
-    x0 = torch.randn(B, H, W, C0, device="cuda")
-    x1 = torch.randn(B, H, W, C1, device="cuda") if C1 else None
-    cf = torch.stack([torch.randn(B, C0 + C1) * 0.2, 1 + 0.2 * torch.randn(B, C0 + C1), torch.randn(B, C0 + C1) * 0.2]).cuda().contiguous() if coef else None
-    w = torch.randn(Cout, C0 + C1, 3, 3) / ((C0 + C1) * 9) ** 0.5
-    bias = torch.randn(Cout) * 0.1
-    r = torch.randn(B, H, W, Cout, device="cuda") if res else None
-    out = e.op_conv(x0, x1, cf, coef, 0, w, bias, r, False, 3)
-    torch.cuda.synchronize()
-    print((C0, C1, Cout, H, W), hashlib.md5(out.cpu().numpy().tobytes()).hexdigest(), float(out.abs().mean()))
+PKG = "conditioned-diffusion-models-uad_amd"
+SEED = 20261021
+MODES = ("default", "nb2", "p16")
+
+# name: (op, B, C0, C1, Cout, H, W of the SOURCE, coef, silu, res, skipC)     op: conv | up2 (folded upsample, output 2H x 2W, res_upsample)
+CASES = {
+    "conv 128>128 8x32": ("conv", 2, 128, 0, 128, 8, 32, 1, 1, 0, 0),
+    "conv 128>128 12x40": ("conv", 2, 128, 0, 128, 12, 40, 1, 1, 0, 0),
+    "conv 128>128 24x24": ("conv", 2, 128, 0, 128, 24, 24, 1, 1, 0, 0),
+    "cat 256+128>256 16x40 +res": ("conv", 2, 256, 128, 256, 16, 40, 1, 1, 1, 0),
+    "conv 256>128 24x24 nocoef": ("conv", 3, 256, 0, 128, 24, 24, 0, 0, 0, 0),
+    "up2 256>256 9x13 +res_up": ("up2", 2, 256, 0, 256, 9, 13, 1, 1, 1, 0),
+    "up2 256>256 8x16 +res_up": ("up2", 2, 256, 0, 256, 8, 16, 1, 1, 1, 0),
+    "skip 128>128 +384 16x32": ("skip", 2, 128, 0, 128, 16, 32, 1, 1, 0, 384),
+    "gn 128>128 12x40": ("gn", 2, 128, 0, 128, 12, 40, 0, 0, 0, 0),
+    "conv 128>128 64x64": ("conv", 3, 128, 0, 128, 64, 64, 1, 1, 0, 0),
+    "cat 256+128>256 32x40 +res": ("conv", 3, 256, 128, 256, 32, 40, 1, 1, 1, 0),
+}
+UNET = dict(model_channels=128, channel_mult=(1, 2), num_res_blocks=1, attention_resolutions=(3, 6, 12))      # + geometry (2, 16, 24), t = (123, 877)
+
+
+def md5(t):
+    return hashlib.md5(t.detach().cpu().numpy().tobytes()).hexdigest()
+
+
+def run_case(e, index, spec):
+    """{suffix: md5} of one case on engine e"""
+    op, B, C0, C1, Cout, H, W, coef, silu, res, sk = spec
+    rng = np.random.default_rng([SEED, index])
+    n = lambda *shape, scale=1.0: torch.from_numpy((rng.standard_normal(shape, dtype=np.float32) * np.float32(scale)))
+    Cin = C0 + C1
+    x0 = n(B, H, W, C0).cuda()
+    x1 = n(B, H, W, C1).cuda() if C1 else None
+    cf = torch.stack([n(B, Cin, scale=0.2), 1 + n(B, Cin, scale=0.2), n(B, Cin, scale=0.2)]).contiguous().cuda() if coef else None
+    w = n(Cout, Cin, 3, 3, scale=1.0 / (Cin * 9) ** 0.5)
+    bias = n(Cout, scale=0.1)
+    if op == "conv":
+        r = n(B, H, W, Cout).cuda() if res else None
+        return {"": md5(e.op_conv(x0, x1, cf, silu, 0, w, bias, r, False, 3))}
+    if op == "up2":
+        r = n(B, H, W, Cout).cuda() if res else None
+        return {"": md5(e.op_conv(x0, None, cf, silu, 2, w, bias, r, bool(res), 3))}
+    if op == "skip":
+        skip, wskip = n(B, H, W, sk).cuda(), n(Cout, sk, 1, 1, scale=1.0 / sk ** 0.5)
+        return {"": md5(e.op_conv_skip(x0, cf, silu, w, bias, skip, wskip))}
+    out, co = e.op_conv_gn(x0, w, bias, 1 + n(Cout, scale=0.1), n(Cout, scale=0.1))
+    return {"": md5(out), " coef": md5(co)}
+
+
+def unet_digest(E, precision):
+    synth = importlib.import_module(PKG + ".synth")
+    B, H, W = 2, 16, 24
+    e = E.CddpmEngine(timesteps=1000, max_batch=B, max_h=H, max_w=W, precision=precision, cond_dim=128, **UNET)
+    try:
+        e.load_weights(synth.synth_state_dict(3, num_classes=128, **UNET))
+        e.set_schedule(importlib.import_module(PKG + ".schedule").schedule_buffers(1000), "pred_x0")
+        rng = np.random.default_rng([SEED, 1000])
+        x = torch.from_numpy(rng.standard_normal((B, 1, H, W), dtype=np.float32)).cuda()
+        cond = torch.from_numpy(rng.standard_normal((B, 128), dtype=np.float32)).cuda()
+        return md5(e.unet_forward(x, torch.tensor([123, 877], dtype=torch.long).cuda(), cond))
+    finally:
+        e.close()
+
+
+def digests(mode):
+    """{case: md5} of one mode, in this process (nb2: the caller has set CDDPM_NB2=force before the library's first convolution)"""
+    assert mode in MODES, mode
+    assert (os.environ.get("CDDPM_NB2") == "force") == (mode == "nb2"), "nb2 <=> CDDPM_NB2=force, per process"
+    E = importlib.import_module(PKG + ".engine")
+    e = E.CddpmEngine(timesteps=10, max_batch=4, max_h=64, max_w=64, precision=16 if mode == "p16" else None)
+    out = {}
+    try:
+        for index, (name, spec) in enumerate(CASES.items()):
+            for suffix, d in run_case(e, index, spec).items():
+                out[name + suffix] = d
+    finally:
+        e.close()
+    if mode != "nb2":
+        out["unet forward 2x16x24"] = unet_digest(E, 16 if mode == "p16" else 32)
+    return out
+
+
+def digests_in_child(mode):
+    """the same in a process of its own (what a mode that is read once per process needs)"""
+    env = dict(os.environ)
+    env.pop("CDDPM_NB2", None)
+    if mode == "nb2":
+        env["CDDPM_NB2"] = "force"
+    o = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--json", "-"], env=env, capture_output=True, text=True, timeout=600)
+    if o.returncode != 0:
+        raise RuntimeError(f"conv_bits --mode {mode} failed (exit {o.returncode}):\n{o.stdout[-2000:]}\n{o.stderr[-2000:]}")
+    return json.loads(o.stdout.strip().splitlines()[-1])["modes"][mode]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--mode", default="default", choices=MODES + ("all",))
+    ap.add_argument("--json", default=None, help="write the digests to this file ('-': one line on stdout)")
+    ap.add_argument("--parent", default=None, help="commit hash to record (the build CDDPM_LIB points at)")
+    a = ap.parse_args()
+    if a.mode == "all":
+        modes = {}
+        for m in MODES:      # one process each; stop at the first that fails: nothing more is started on a device a child may have left faulted
+            modes[m] = digests_in_child(m)
+    else:
+        modes = {a.mode: digests(a.mode)}
+    rec = {"parent": a.parent, "seed": SEED, "lib": os.path.basename(os.environ.get("CDDPM_LIB", "libcddpm_hip.so")),
+           "cases": {k: list(v) for k, v in CASES.items()}, "unet": {k: list(v) if isinstance(v, tuple) else v for k, v in UNET.items()},
+           "modes": modes}
+    if a.json == "-":
+        print(json.dumps(rec))
+        return
+    for m, d in modes.items():
+        for name, v in d.items():
+            print(f"{m:8s} {name:32s} {v}")
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
