@@ -87,6 +87,9 @@ SYMBOLS = {
     "cddpm_op_conv": (_i, [_vp, _fp, _i, _fp, _i, _fp, _i, _i, _fp, _fp, _i, _i, _fp, _i, _fp, _i, _i, _i, _vp]),
     "cddpm_op_conv_skip": (_i, [_vp, _fp, _i, _fp, _i, _fp, _fp, _i, _fp, _i, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_conv_gn": (_i, [_vp, _fp, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _vp]),
+    "cddpm_conv_ksplit_plan": (_i, [_i, C.c_longlong, _i, _i, _i, C.POINTER(_i)]),
+    "cddpm_op_conv_planned": (_i, [_vp, _fp, _i, _fp, _i, _fp, _i, _i, _fp, _fp, _i, _i, _fp, _i, _fp, _i, _fp, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _i,
+                                   _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp]),
     "cddpm_op_gn_coef": (_i, [_vp, _fp, _i, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _vp]),
     "cddpm_op_attention": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
     "cddpm_op_attention_p16": (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),

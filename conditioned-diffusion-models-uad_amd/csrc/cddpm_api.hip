@@ -45,12 +45,18 @@ long long conv_workgroups_at_max(const cddpm_ctx* h, const ConvArgs& a) {
 // by S workgroups per tile (plane j of `kpart` each) and conv_reduce_kernel adds the planes in the order of j. S is a property of
 // the handle (max_batch, max_h, max_w and the layer), never of the call: a slice's bits do not depend on the batch it is in, as long
 // as it is computed on handles of the same maximum geometry (sharded runs: the same engine configuration on every rank).
-constexpr int KSPLIT_PLANE_FLOATS = 256 * 256 * 128;      // S * workgroups <= 256, a workgroup's tile <= 256 x 128 outputs
+// The arithmetic is ksplit_rule (below, outside this namespace: the host-only query cddpm_conv_ksplit_plan runs it too).
 int plan_ksplit(const cddpm_ctx* h, const ConvArgs& a, short* kbound) {
-    if (h->family != 2 || h->cur_H <= 0) return 1;
-    const long long nwg = conv_workgroups_at_max(h, a);
-    const int nch_main = (a.C0 + a.C1) / 32, nch_skip = (a.S0 + a.S1) / 32, nch = nch_main + nch_skip;
-    const int units = nch_main * a.taps + nch_skip;           // taps to multiply per tile
+    if (h->cur_H <= 0) return 1;
+    return ksplit_rule(h->family, conv_workgroups_at_max(h, a), a.C0 + a.C1, a.S0 + a.S1, a.taps, kbound);
+}
+
+}  // namespace
+
+int cddpm::ksplit_rule(int family, long long nwg, int Cin, int Cskip, int taps, short* kbound) {
+    if (family != 2) return 1;
+    const int nch_main = Cin / 32, nch_skip = Cskip / 32, nch = nch_main + nch_skip;
+    const int units = nch_main * taps + nch_skip;           // taps to multiply per tile
     int S = 1;
     while (S < CDDPM_MAX_KSPLIT && nwg * (S * 2) <= 256 && units / (S * 2) >= 9 && S * 2 <= nch) S *= 2;
     if (S == 1) return 1;
@@ -59,21 +65,25 @@ int plan_ksplit(const cddpm_ctx* h, const ConvArgs& a, short* kbound) {
     kbound[0] = 0;
     for (int j = 1; j < S; ++j) {
         const int target = (int)((long long)units * j / S);
-        while (c < nch - (S - j) && acc + (c < nch_main ? a.taps : 1) / 2 < target) { acc += (c < nch_main ? a.taps : 1); ++c; }
-        if (c <= kbound[j - 1]) { acc += (c < nch_main ? a.taps : 1); ++c; }
+        while (c < nch - (S - j) && acc + (c < nch_main ? taps : 1) / 2 < target) { acc += (c < nch_main ? taps : 1); ++c; }
+        if (c <= kbound[j - 1]) { acc += (c < nch_main ? taps : 1); ++c; }
         kbound[j] = (short)c;
     }
     kbound[S] = (short)nch;
     return S;
 }
 
-int conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s) {
+int cddpm::conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s, ConvPlanTaken* took) {
     auto it = h->stat.find(a.out);           // outputs that can feed a GroupNorm get their statistics for free
     StatBuf* sb = (it != h->stat.end()) ? &it->second : nullptr;
     a.stats = sb ? sb->records : nullptr;
     a.hi_only = (h->precision == 16) ? 1 : 0;      // plain fp16 operands on every convolution of a precision-16 handle, split-K included
     short kb[CDDPM_MAX_KSPLIT + 1] = {0};
     const int S = plan_ksplit(h, a, kb);
+    if (took) {
+        took->S = S; took->nb2 = 0;
+        for (int j = 0; j <= CDDPM_MAX_KSPLIT; ++j) took->kbound[j] = kb[j];
+    }
     if (S > 1) {
         if ((size_t)S * a.B * a.H * a.W * a.Cout > (size_t)KSPLIT_PLANE_FLOATS)
             return fail(h, "split-K planes of a %dx%dx%d conv output (B=%d, S=%d) exceed the workspace", a.H, a.W, a.Cout, a.B, S);
@@ -92,6 +102,7 @@ int conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s) {
         return 0;
     }
     conv_set_nb2(a, h, NB2_HANDLE_PLAN, conv_workgroups_at_max(h, a));      // the large-batch plan
+    if (took) took->nb2 = (a.nb2 && a.taps != 1) ? 1 : 0;      // the 1x1 loop has no 256-cout form (conv_x6.hip::launch_split)
     const int nrec = (a.taps == 4) ? conv_stat_records_up2(a.H, a.W) : conv_stat_records(a.H, a.W);
     if (sb) {
         // a statically sized buffer against a shape-derived count: refuse to launch rather than write past the end
@@ -107,6 +118,8 @@ int conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s) {
     if (sb) sb->valid_count = nrec;
     return 0;
 }
+
+namespace {
 
 template <typename T>
 int dev_alloc(cddpm_ctx* h, T** p, size_t count) {

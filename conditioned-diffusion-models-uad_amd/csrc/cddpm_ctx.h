@@ -298,6 +298,18 @@ inline void conv_set_nb2(ConvArgs& a, const cddpm_ctx* h, Nb2Policy policy, long
     a.nb2 = (wanted && conv_nb2_ok(a.Cout, workgroups, 1, h->family)) ? 1 : 0;
 }
 
+// The small-batch split-K rule as plain arithmetic (cddpm_api.hip; exported as cddpm_conv_ksplit_plan): `workgroups_at_max` of the
+// 128-cout form at the handle's maximum geometry, Cin main and Cskip skip-segment channels (multiples of 32), `taps` per main chunk.
+// Returns S; S > 1 fills kbound[0 .. S].
+int ksplit_rule(int family, long long workgroups_at_max, int Cin, int Cskip, int taps, short* kbound);
+constexpr int KSPLIT_PLANE_FLOATS = 256 * 256 * 128;      // floats of cddpm_ctx::kpart: S * workgroups <= 256, a workgroup's tile <= 256 x 128 outputs
+
+// One convolution of the reconstruction path as the handle plans it (cddpm_api.hip): statistics records when a.out has a StatBuf,
+// hi_only by the handle's precision, then split-K + combine or one launch in the 128- / 256-cout form. `took`: the plan, for
+// cddpm_op_conv_planned.
+struct ConvPlanTaken { int S; short kbound[CDDPM_MAX_KSPLIT + 1]; int nb2; };
+int conv_launch(cddpm_ctx* h, ConvArgs a, hipStream_t s, ConvPlanTaken* took = nullptr);
+
 // widest concatenated GroupNorm / convolution input of the kernels (see check_program in cddpm_api.hip)
 constexpr int MAX_CONCAT_CHANNELS = 1536;
 

@@ -196,6 +196,88 @@ int cddpm_op_conv_gn(cddpm_handle h, const float* src0, int C0, const float* w_h
     OP_EPILOGUE_SYNC()
 }
 
+// One convolution through conv_launch -- the plan of the handle, not of the call: for the duration of the call the handle is "inside a
+// forward at img_H x img_W" (cur_H / cur_W) on a step of accumulation plan t (nb2_now), and out_dev has a statistics buffer when the
+// GroupNorm coefficients are asked for, as every activation buffer of the forward program has. All of it is put back on every path.
+namespace {
+struct PlannedCallScope {
+    cddpm_ctx* h; int H, W, nb2; const float* stat_key;
+    ~PlannedCallScope() {
+        h->cur_H = H; h->cur_W = W; h->nb2_now = nb2;
+        if (stat_key) h->stat.erase(stat_key);
+    }
+};
+}
+int cddpm_op_conv_planned(cddpm_handle h, const float* src0, int C0, const float* src1, int C1, const float* coef_dev, int silu, int folded_up,
+                          const float* w_host, const float* bias_host, int Cout, int ksize, const float* res_dev, int res_upsample,
+                          const float* skip0_dev, int S0, const float* skip1_dev, int S1, const float* wskip_host, const float* gamma_host,
+                          const float* beta_host, float* coef_out_dev, float* out_dev, int B, int H, int W, int img_H, int img_W, int t,
+                          int* ksplit_out, int* kbound_out, int* nb2_out, int* scale_exp_out, void* stream) {
+    const int Cin = C0 + C1, taps = ksize * ksize;
+    const bool skip = skip0_dev != nullptr, gn = gamma_host || beta_host || coef_out_dev;
+    OP_CHECK(!((ksize != 1 && ksize != 3) || C0 <= 0 || C0 % 32 || C1 < 0 || C1 % 32 || Cin > MAX_CONCAT_CHANNELS || Cout <= 0 || Cout % 128 ||
+               Cout > 4096 || (C1 && !src1) || (folded_up && (ksize != 3 || C1 || H % 2 || W % 2 || skip)) ||
+               (skip && (ksize != 3 || S0 <= 0 || S0 % 32 || S1 < 0 || S1 % 32 || S0 + S1 > MAX_CONCAT_CHANNELS || !wskip_host ||
+                         (S1 > 0 && !skip1_dev) || res_dev)) ||
+               (res_upsample && (!res_dev || H % 2 || W % 2)) || (gn && (!gamma_host || !beta_host || !coef_out_dev || Cout > 1024))),
+             "cddpm_op_conv_planned: unsupported shape (k %d, C0 %d, C1 %d, Cout %d, S0 %d, S1 %d)", ksize, C0, C1, Cout, S0, S1)
+    OP_CHECK(B >= 1 && B <= h->d.max_batch && img_H >= 1 && img_H <= h->d.max_h && img_W >= 1 && img_W <= h->d.max_w && H >= 1 && H <= img_H &&
+                 W >= 1 && W <= img_W,
+             "cddpm_op_conv_planned: a %d x %d layer of a %d x %d x %d forward is outside the handle's geometry (%d x %d x %d)", H, W, B, img_H, img_W,
+             h->d.max_batch, h->d.max_h, h->d.max_w)
+    OP_CHECK(h->stat.find(out_dev) == h->stat.end(), "cddpm_op_conv_planned: out_dev is a buffer of the handle")
+    OP_PROLOGUE(PC_NONE, 0.0, 0.0, src0 && w_host && bias_host && out_dev, "cddpm_op_conv_planned: NULL argument")
+    // one pre-scale exponent for the main and the skip tensor, as cddpm_load_weights chooses it; the folded classes choose their own
+    const int fam = h->family;
+    std::vector<float> pk(folded_up ? 4 * packed_conv_floats(Cout, Cin, 4, fam) : 0), pks;
+    int wexp = folded_up ? pack_conv_weights_up2(w_host, Cout, Cin, pk.data(), fam) : conv_weight_exp(w_host, (size_t)Cout * Cin * taps, fam);
+    if (skip) wexp = std::min(wexp, conv_weight_exp(wskip_host, (size_t)Cout * (S0 + S1), fam));
+    if (!folded_up) pk = host_pack(h, w_host, Cout, Cin, taps, wexp);
+    if (skip) pks = host_pack(h, wskip_host, Cout, S0 + S1, 1, wexp);
+    // records of either epilogue: the convolution's own (per wave tile) or the combine's (per 64 consecutive pixels)
+    const int nrec_cap = std::max(conv_reduce_stat_records(H, W), folded_up ? conv_stat_records_up2(H, W) : conv_stat_records(H, W));
+    OpScratch sc(h, s, true);
+    ConvArgs a;
+    zero_conv_args(a, h);
+    a.src0 = src0; a.C0 = C0; a.src1 = C1 ? src1 : nullptr; a.C1 = C1;
+    a.srcH = folded_up ? H / 2 : H; a.srcW = folded_up ? W / 2 : W;
+    a.coef = coef_dev; a.silu = silu; a.res = res_dev; a.res_up = res_dev ? res_upsample : 0;
+    if (skip) {
+        a.skip0 = skip0_dev; a.S0 = S0; a.skip1 = S1 > 0 ? skip1_dev : nullptr; a.S1 = S1;
+        a.skip_wpk = sc.param(pks.data(), pks.size());
+    }
+    a.out = out_dev; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.taps = folded_up ? 4 : taps;
+    a.wpk = sc.param(pk.data(), pk.size());
+    a.bias = sc.param(bias_host, Cout);
+    a.wscale_inv = ldexpf(1.0f, -wexp);
+    const float *g = nullptr, *bt = nullptr;
+    float* rec = nullptr;
+    if (gn) {
+        g = sc.param(gamma_host, Cout);
+        bt = sc.param(beta_host, Cout);
+        rec = sc.n<float>((size_t)B * nrec_cap * Cout * CDDPM_STAT_FLOATS);
+    }
+    SCRATCH_CHECK(sc)
+    PlannedCallScope scope{h, h->cur_H, h->cur_W, h->nb2_now, nullptr};
+    h->cur_H = img_H; h->cur_W = img_W;
+    h->nb2_now = (t >= 0 && t >= h->nb2_tmin) ? 1 : 0;      // as step_once of cddpm_api.hip sets it; t < 0: a single forward
+    if (gn) {
+        h->stat[out_dev] = StatBuf{rec, (size_t)B * nrec_cap * Cout * CDDPM_STAT_FLOATS, STAT_NONE};
+        scope.stat_key = out_dev;
+    }
+    ConvPlanTaken took;
+    if (conv_launch(h, a, s, &took)) return -1;
+    if (ksplit_out) *ksplit_out = took.S;
+    if (kbound_out) {
+        if (took.S == 1) { took.kbound[0] = 0; took.kbound[1] = (short)((Cin + a.S0 + a.S1) / 32); }
+        for (int j = 0; j <= CDDPM_MAX_KSPLIT; ++j) kbound_out[j] = j <= took.S ? took.kbound[j] : 0;
+    }
+    if (nb2_out) *nb2_out = took.nb2;
+    if (scale_exp_out) *scale_exp_out = wexp;
+    if (gn) launch_gn_finalize(rec, Cout, h->stat[out_dev].valid_count, nullptr, 0, 0, B, H * W, g, bt, nullptr, nullptr, 0, 0, nullptr, nullptr, coef_out_dev, s);
+    OP_EPILOGUE_SYNC()
+}
+
 static void gn_coef_scratch(OpScratch& sc, int C0, bool two, int C1, int B, int HW, float*& rec0, float*& rec1) {
     const int ns = gn_nsplit(B, HW);
     rec0 = sc.n<float>((size_t)B * ns * C0 * 2);
@@ -784,6 +866,17 @@ int cddpm_stat_records(int H, int W, int kind) {
     if (kind == 1) return conv_stat_records_up2(H, W);
     if (kind == 2) return gn_nsplit(1, H * W);
     return -1;
+}
+
+int cddpm_conv_ksplit_plan(int family, long long workgroups_at_max, int Cin, int Cskip, int taps, int* kbound_out) {
+    if (!kbound_out || family < 0 || family > 2 || workgroups_at_max < 1 || Cin <= 0 || Cin % 32 || Cskip < 0 || Cskip % 32 ||
+        (Cin + Cskip) / 32 > 32767 || (taps != 1 && taps != 4 && taps != 9))
+        return -1;
+    short kb[CDDPM_MAX_KSPLIT + 1] = {0};
+    const int S = ksplit_rule(family, workgroups_at_max, Cin, Cskip, taps, kb);
+    if (S == 1) kb[1] = (short)((Cin + Cskip) / 32);      // unsplit: the one range is the whole K loop
+    for (int j = 0; j <= CDDPM_MAX_KSPLIT; ++j) kbound_out[j] = j <= S ? kb[j] : 0;
+    return S;
 }
 
 size_t cddpm_packed_conv_bytes(int Cout, int Cin, int taps) {

@@ -1036,6 +1036,37 @@ class CddpmEngine:
             _stream_ptr(self.device)), "cddpm_op_conv")
         return out
 
+    def op_conv_planned(self, src0, src1, coef, silu, upsample, weight, bias, res, res_upsample, ksize, *, img_hw, t=-1, skip0=None,
+                        skip1=None, wskip=None, gamma=None, beta=None, out=None):
+        """one fused conv on NHWC device tensors launched as this engine's HANDLE plans it (cddpm_op_conv_planned): the layer of a
+        forward at img_hw = (H, W) on reverse step t (t < 0: a single forward). upsample: 0 or 2 (the folded form). skip0 / skip1 / wskip:
+        the two-source 1x1 skip segment; gamma / beta: also return the output's GroupNorm coefficients [3,B,Cout]. out: a contiguous
+        [B,H,W,Cout] view to write into. -> (out, coef_out or None, plan) with plan = {'S', 'kbound' (S + 1 chunk bounds), 'nb2',
+        'scale_exp'}, what the library reports it took."""
+        if upsample not in (0, 2, False):
+            raise ValueError("op_conv_planned: upsample is 0 or 2 (the folded form the UNet uses)")
+        B, h, w, C0 = src0.shape
+        H, W = (2 * h, 2 * w) if upsample else (h, w)
+        f = lambda x: None if x is None else np.ascontiguousarray(x.detach().cpu().numpy(), dtype=np.float32)
+        hp = lambda a: None if a is None else a.ctypes.data
+        dp = lambda x: None if x is None else x.data_ptr()
+        wt, bs, ws, g, b = f(weight), f(bias), f(wskip), f(gamma), f(beta)
+        Cout = wt.shape[0]
+        if out is None:
+            out = torch.empty((B, H, W, Cout), dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != (B, H, W, Cout) or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError("op_conv_planned: out must be a contiguous float32 [B,H,W,Cout] tensor")
+        coef_out = torch.empty((3, B, Cout), dtype=torch.float32, device=self.device) if g is not None else None
+        S, nb2, e = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        kb = (C.c_int * 9)()
+        self._ck(self.lib.cddpm_op_conv_planned(
+            self._h, src0.data_ptr(), C0, dp(src1), src1.shape[-1] if src1 is not None else 0, dp(coef), int(silu), 1 if upsample else 0,
+            hp(wt), hp(bs), Cout, ksize, dp(res), int(res_upsample), dp(skip0), skip0.shape[-1] if skip0 is not None else 0, dp(skip1),
+            skip1.shape[-1] if skip1 is not None else 0, hp(ws), hp(g), hp(b), dp(coef_out), out.data_ptr(), B, H, W, int(img_hw[0]),
+            int(img_hw[1]), int(t), C.byref(S), kb, C.byref(nb2), C.byref(e), _stream_ptr(self.device)), "cddpm_op_conv_planned")
+        plan = {"S": S.value, "kbound": [int(kb[j]) for j in range(S.value + 1)], "nb2": bool(nb2.value), "scale_exp": e.value}
+        return out, coef_out, plan
+
     def op_conv_skip(self, src0, coef, silu, weight, bias, skip, wskip):
         """conv3x3(act(src0)) + conv1x1(skip) + bias on NHWC device tensors (cddpm_op_conv_skip)"""
         B, H, W, C0 = src0.shape

@@ -661,6 +661,39 @@ int cddpm_op_conv_gn(cddpm_handle h, const float* src0_dev, int C0, const float*
                      const float* gamma_host, const float* beta_host, float* out_dev, float* coef_dev, int B, int H, int W,
                      void* stream);
 
+/* host-only (no GPU): the split-K rule of the small-batch plan as a function of its inputs -- the convolution family (CDDPM_CONV_*),
+ * the layer's workgroup count of the 128-cout form at the HANDLE's maximum geometry (max_batch x [4 parity classes of the folded
+ * upsample] x ceil(w / 32) x ceil(h / 8) x Cout / 128, w x h the layer's extent at max_h x max_w, halved for the folded form), the
+ * channels of the main segment (Cin = C0 + C1) and of the 1x1 skip segment (Cskip = S0 + S1, or 0; multiples of 32) and the taps per
+ * main chunk (1, 9, or 4 = folded upsample). Returns S, the number of consecutive ranges the K loop's 32-channel chunks (main
+ * segment first, then skip) are cut into: a power of two <= CDDPM_MAX_KSPLIT with S * workgroups <= 256, 1 = not split and always 1
+ * outside CDDPM_CONV_H3. kbound_out [CDDPM_MAX_KSPLIT + 1]: range j is chunks kbound_out[j] .. kbound_out[j + 1] - 1, with
+ * kbound_out[0] = 0 and kbound_out[S] = (Cin + Cskip) / 32; entries beyond S are 0. -1 on bad arguments. The code every convolution of
+ * cddpm_unet_forward / cddpm_reverse is planned with. */
+#define CDDPM_MAX_KSPLIT 8
+int cddpm_conv_ksplit_plan(int family, long long workgroups_at_max, int Cin, int Cskip, int taps, int* kbound_out);
+
+/* one fused convolution launched as the HANDLE plans it inside its forward program -- the union of cddpm_op_conv, cddpm_op_conv_skip
+ * and cddpm_op_conv_gn, but through the planning path of cddpm_unet_forward / cddpm_reverse instead of a direct kernel launch: split-K
+ * ranges + the fixed-order combine (bias, residual and statistics records then come from the combine kernel) at small maximum
+ * geometries, the 128- or 256-cout workgroup form otherwise, plain fp16 operands on a handle at precision 16. Kernel tests.
+ *   out[B,H,W,Cout] = conv_k(act(cat[src0, src1])) + bias + (res | conv1x1(cat[skip0, skip1])),  k in {1, 3}
+ * folded_up: the folded nearest-x2-upsample form (sources [B,H/2,W/2,C0]; k = 3, single source, no skip segment). res_dev at the
+ * output's resolution, or half of it with res_upsample. The skip segment (k = 3 only, instead of a residual) reads two RAW tensors
+ * skip0_dev [B,H,W,S0] and skip1_dev [B,H,W,S1] (S1 = 0: one) under ONE weight tensor wskip_host [Cout, S0 + S1, 1, 1], packed with
+ * the main tensor's pre-scale exponent as cddpm_load_weights does. gamma_host / beta_host / coef_out_dev (all three or none; Cout <=
+ * 1024): coef_out_dev [3][B][Cout] = (mean, a, d) of GroupNorm32(out) from the statistics records of whichever epilogue the plan used.
+ * The plan is that of a layer of H x W inside a forward of B <= max_batch slices at img_H x img_W <= max_h x max_w; t >= 0: the
+ * accumulation plan of reverse step t (cddpm_set_accumulation_switch), t < 0: that of a single forward. The handle's state is
+ * restored before the call returns. The plan taken comes back through (each may be NULL) ksplit_out = S, kbound_out
+ * [CDDPM_MAX_KSPLIT + 1] as cddpm_conv_ksplit_plan fills it, nb2_out = 1 when 256-cout workgroups ran, scale_exp_out = the pre-scale
+ * exponent of the packed weights (0 outside CDDPM_CONV_H3). Synchronises the stream. */
+int cddpm_op_conv_planned(cddpm_handle h, const float* src0_dev, int C0, const float* src1_dev, int C1, const float* coef_dev, int silu,
+                          int folded_up, const float* w_host, const float* bias_host, int Cout, int ksize, const float* res_dev,
+                          int res_upsample, const float* skip0_dev, int S0, const float* skip1_dev, int S1, const float* wskip_host,
+                          const float* gamma_host, const float* beta_host, float* coef_out_dev, float* out_dev, int B, int H, int W,
+                          int img_H, int img_W, int t, int* ksplit_out, int* kbound_out, int* nb2_out, int* scale_exp_out, void* stream);
+
 /* standalone GroupNorm(32) statistics + coefficient kernel pair: coef_dev [3][B][C] (mean, a, d) with
  * a = rstd*gamma*(1+scale), d = beta*(1+scale)+shift; film_dev = [B][2C] (scale | shift) or NULL. */
 int cddpm_op_gn_coef(cddpm_handle h, const float* src0_dev, int C0, const float* src1_dev, int C1,

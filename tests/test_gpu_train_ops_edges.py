@@ -23,10 +23,11 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_pkg
+from conv_p16_reference import (U20, U24, U25, f16, f16_ulp, folded_classes, folded_conv, fused_act, near_f16_midpoint,  # noqa: F401
+                               p16_forward_ref, w16)
 
 gpu = pytest.mark.gpu
 
-U20, U24, U25 = 2.0 ** -20, 2.0 ** -24, 2.0 ** -25
 
 
 @pytest.fixture(scope="module")
@@ -60,40 +61,7 @@ def precision(eng, bits):
         eng.lib.cddpm_set_train_precision(32)
 
 
-# ---- float64 helpers -------------------------------------------------------------------------------------------------------------------
-def f16(x):
-    """fp16 value of an fp32 operand, as float64 (torch's .half(): RNE, gradual underflow, inf above 65504)"""
-    return x.float().half().double()
-
-
-def f16_ulp(v):
-    """spacing of the fp16 grid at |v| (2^-24 in the subnormal range)"""
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -14)))
-    return torch.exp2(e - 10)
-
-
-def near_f16_midpoint(v, scale):
-    """elements whose float64 value lies within `scale` of a rounding midpoint of the fp16 grid (there the device's fp32 value of the
-    same expression may round to the other neighbour)"""
-    u = f16_ulp(v)
-    r = torch.remainder(v.abs(), u)
-    return (r - u / 2).abs() <= scale
-
-
-def fused_act(x, coef, silu):
-    """float64 act(v) = silu?((v - mean) a + d) of the fp32 inputs, and the tolerance of the device's fp32 evaluation: the affine takes
-    three roundings, each <= 2^-24 of its operand; SiLU's exp2 / rcp form ~1.5 ulp -- 2^-20 of the largest intermediate covers them with
-    room (16 fp32 ulp)"""
-    v = x.double()
-    if coef is None:
-        return v, torch.zeros_like(v)
-    m, a, d = (coef[i].double()[:, :, None, None] for i in range(3))
-    t = (v - m) * a
-    u = t + d
-    tol = U20 * torch.maximum(torch.maximum(t.abs(), d.abs().expand_as(t)), (v - m).abs() * a.abs())
-    return (F.silu(u) if silu else u), tol
-
-
+# ---- float64 helpers: conv_p16_reference.py (shared with test_gpu_conv_planned.py) ---------------------------------------------------------
 def weight_exp(eng, w, mult=1.0):
     """the pre-scale exponent of a weight tensor: max |w| from cddpm_op_absmax, then the largest e in [0, 24] with mult max|w| 2^e < 2^14
     (mult 4: the folded-upsample class sums reach 4 max|w|)"""
@@ -118,42 +86,6 @@ def pack(eng, w, mode, e):
     wd = w.float().cuda().contiguous()
     _ck(eng, eng.lib.cddpm_op_pack_conv(eng._h, wd.data_ptr(), Cout, Cin, k, mode, e, dev.data_ptr(), None), "pack_conv")
     return dev
-
-
-def w16(w, e):
-    """the precision-16 weight operand of a forward / input-gradient image: fp16(w 2^e) 2^-e"""
-    return (w.float() * 2.0 ** e).half().double() * 2.0 ** -e
-
-
-def folded_classes(w, e=None):
-    """the four 2 x 2 class kernels of 'nearest x2 upsample -> conv3x3' (class (pa, pb) = output pixel (2 gy + pa, 2 gx + pb); tap (ty, tx)
-    reads the low-resolution pixel (gy + ty + pa - 1, gx + tx + pb - 1)), summed in float64 and rounded once to fp32 as the packer does;
-    e given: the precision-16 operand fp16(sum 2^e) 2^-e"""
-    w64 = w.double()
-    out = {}
-    for pa in (0, 1):
-        for pb in (0, 1):
-            rows = [(0, 0), (1, 2)] if pa == 0 else [(0, 1), (2, 2)]
-            cols = [(0, 0), (1, 2)] if pb == 0 else [(0, 1), (2, 2)]
-            k = torch.zeros(w.shape[0], w.shape[1], 2, 2, dtype=torch.float64)
-            for ty, (y0, y1) in enumerate(rows):
-                for tx, (x0, x1) in enumerate(cols):
-                    k[:, :, ty, tx] = w64[:, :, y0:y1 + 1, x0:x1 + 1].sum(dim=(2, 3)).float().double()
-            out[(pa, pb)] = k if e is None else w16(k, e)
-    return out
-
-
-def folded_conv(a, classes):
-    """out[2 gy + pa, 2 gx + pb] = sum over the class's 2 x 2 taps of the low-resolution input a [B, C, h, w]"""
-    B, _, h, w_ = a.shape
-    ap = F.pad(a, (1, 1, 1, 1))
-    out = None
-    for (pa, pb), k in classes.items():
-        o = F.conv2d(ap[:, :, pa:pa + h + 1, pb:pb + w_ + 1], k)
-        if out is None:
-            out = torch.zeros(B, o.shape[1], 2 * h, 2 * w_, dtype=torch.float64)
-        out[:, :, pa::2, pb::2] = o
-    return out
 
 
 def ratio_check(got, ref, lim, what):
@@ -231,32 +163,6 @@ def test_fp16_midpoint_helper():
 
 
 # ---- A: precision 16 by its definition ------------------------------------------------------------------------------------------------
-def p16_forward_ref(x, coef, silu, w, e, k, bias, folded=False, x1=None, skip=None, ws=None, res=None, res_up=False):
-    """float64 reference of a precision-16 cddpm_op_conv_packed call and its bound:
-    out = 2^-e sum fp16(act) fp16(w 2^e) (fp32 accumulation: 2^-20 sum |.||.|) + bias [+ res] (two fp32 adds in the epilogue: 2^-23 of the
-    larger of the sum and the addends); elements of the fused transform's output within a few fp32 ulp of an fp16 rounding midpoint may round
-    either way: one fp16 ulp on exactly those"""
-    xin = torch.cat([x, x1], 1) if x1 is not None else x
-    v, tol = fused_act(xin, coef, silu)
-    fa = f16(v)
-    slack = near_f16_midpoint(v, tol).double() * f16_ulp(v) if coef is not None else torch.zeros_like(v)
-    if folded:
-        cls = folded_classes(w, e)
-        s, sabs, sx = folded_conv(fa, cls), folded_conv(fa.abs(), {c: t.abs() for c, t in cls.items()}), folded_conv(slack, {c: t.abs() for c, t in cls.items()})
-    else:
-        fw = w16(w, e)
-        s, sabs, sx = F.conv2d(fa, fw, None, padding=k // 2), F.conv2d(fa.abs(), fw.abs(), None, padding=k // 2), F.conv2d(slack, fw.abs(), None, padding=k // 2)
-    if skip is not None:
-        fs, fws = f16(skip), w16(ws, e)
-        s, sabs = s + F.conv2d(fs, fws), sabs + F.conv2d(fs.abs(), fws.abs())
-    add = bias.double()[None, :, None, None].expand_as(s)
-    if res is not None:
-        add = add + (F.interpolate(res.double(), scale_factor=2, mode="nearest") if res_up else res.double())
-    ref = s + add
-    lim = U20 * sabs + sx + 2.0 ** -23 * (s.abs() + add.abs() + ref.abs()) + 1e-300
-    return ref, lim
-
-
 P16_CONV = [
     # name, B, C0, C1, Cout, k, H, W, coef, silu, folded, skip S0, S1, res
     ("3x3_act", 2, 128, 0, 128, 3, 12, 40, True, True, False, 0, 0, "same"),
