@@ -647,7 +647,58 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     // the epilogue handles 2 NB quarter-tiles q = 2 hb + nt (cout block hb of the workgroup, 32-cout half nt of the wave's 64): the
     // residual of quarter q sits in buffer q & 1, requested two quarters ahead (q = 0, 1 here, q + 2 when quarter q's registers are free)
     v4f rsd_all[2][2][4];
-    auto load_rsd = [&](int q) {
+    // Full tiles (every pixel of the workgroup's 8 x 32 tile inside the image: workgroup-uniform, from scalars) take an epilogue without
+    // per-lane predicates: residual requests and tile stores are straight-line code on a wave-uniform 64-bit base + a 32-bit lane offset
+    // (as load_act), so the compiler counts vmcnt across them instead of draining to zero in front of every exec-masked block, and the
+    // loads / stores issue back to back. Ragged tiles keep the masked code below. Same values, same stores, same order of the sums.
+    // (the lane offsets are 32-bit BYTE offsets inside the wave's rows: at most (2 W + 64) Cout floats; NB = 2 keeps the masked code for
+    // every tile: its 128 accumulator registers leave no room for the straight-line form, which spilled 250 B per lane)
+    const bool full = (NB == 1) && (y0 + ROWS <= gridH) && (x0 + 32 <= gridW) && ((unsigned long long)(2 * a.W + 64) * (unsigned)a.Cout < (1ull << 30));
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int wm_u = wave_u % (ROWS / 2), wn_u = wave_u / (ROWS / 2);
+    // the wave's two rows x 32 columns in a tensor of row width rw (pixels): lane pixel (hf, i) = row hf, column 8 i + (lane >> 3), at
+    // (lp + hf sh rw + i si) Cout floats from the wave's first pixel; the folded form writes every other pixel of every other row, a
+    // half-resolution residual of an unfolded launch is read at (y >> 1, x >> 1)
+    // (readfirstlane: the compiler then keeps the wave-uniform parts in scalar registers and addresses with base + 32-bit lane offset)
+    auto uni = [](unsigned v) -> unsigned { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); };
+    auto uni64 = [&](size_t v) -> size_t { return ((size_t)uni((unsigned)(v >> 32)) << 32) | uni((unsigned)v); };
+    auto load_rsd_full = [&](int q0, int nq) {      // quarters q0 .. q0 + nq - 1, back to back
+        const int cq = lane & 7, prow = lane >> 3;
+        if (!a.res) {
+#pragma unroll
+            for (int q = q0; q < q0 + nq; ++q)
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) rsd_all[q & 1][hf][i] = v4f{0.f, 0.f, 0.f, 0.f};
+            return;
+        }
+        const int gy0 = y0 + 2 * wm_u;
+        const int rH = a.res_up ? (a.H >> 1) : a.H, rW = a.res_up ? (a.W >> 1) : a.W;
+        int ry0 = gy0, rx0 = x0;
+        unsigned lp = (unsigned)prow, si = 8u, sh = 1u;
+        if (UP2 && !a.res_up) { ry0 = 2 * gy0 + pa; rx0 = 2 * x0 + pb; lp = 2u * prow; si = 16u; sh = 2u; }
+        else if (!UP2 && a.res_up) { ry0 = gy0 >> 1; rx0 = x0 >> 1; lp = (unsigned)prow >> 1; si = 4u; sh = 0u; }
+        const unsigned l0 = lp * (unsigned)a.Cout + 4u * cq, sI = uni(si * (unsigned)a.Cout), sH = uni(sh * (unsigned)rW * (unsigned)a.Cout);
+#pragma unroll
+        for (int q = q0; q < q0 + nq; ++q) {
+            const int cob = (NB * cb + (q >> 1)) * 128 + 64 * wn_u + 32 * (q & 1);
+            const float* rb = a.res + uni64(((size_t)(b * rH + ry0) * rW + rx0) * a.Cout + cob);
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    rsd_all[q & 1][hf][i] = *reinterpret_cast<const v4f*>(reinterpret_cast<const char*>(rb) + 4u * (l0 + hf * sH + i * sI));
+        }
+    };
+    // ... and their bias with the residual requests: requested behind the previous quarter's stores (where the masked path loads it),
+    // waiting for it would wait for those stores' acknowledgements
+    v4f bias_all[2];
+    auto load_bias_full = [&](int q) {
+        const int co = (NB * cb + (q >> 1)) * 128 + 64 * wn_u + 32 * (q & 1) + 4 * (lane & 7);
+        bias_all[q & 1] = a.bias ? *reinterpret_cast<const v4f*>(a.bias + co) : v4f{0.f, 0.f, 0.f, 0.f};
+    };
+    auto load_rsd_masked = [&](int q) {
         const int cq = lane & 7, prow = lane >> 3;
         const int hb = q >> 1, nt = q & 1;
 #pragma unroll
@@ -667,12 +718,16 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 rsd_all[q & 1][hf][i] = r;
             }
     };
-    load_rsd(0);
-    load_rsd(1);
+    if (full) { load_rsd_full(0, 2); load_bias_full(0); load_bias_full(1); }
+    else { load_rsd_masked(0); load_rsd_masked(1); }
     __syncthreads();   // every wave is done with the patch / weight buffers before they become transpose space
     // ---- epilogue: as conv_mfma.hip -- each wave transposes its 64 x 64 tile through a private 8-KB LDS region so
     //      that every lane moves 16 B; bias, residual and the GroupNorm statistics of the output are applied here.
-    {
+    auto epilogue = [&](auto fullc) {
+        auto fma4 = [](v4f x, v4f y, v4f z) -> v4f {
+            return v4f{__builtin_fmaf(x.x, y.x, z.x), __builtin_fmaf(x.y, y.y, z.y), __builtin_fmaf(x.z, y.z, z.z), __builtin_fmaf(x.w, y.w, z.w)};
+        };
+        constexpr bool FULL = decltype(fullc)::value;    // its own copy of the quarter loop: no wait of the masked path leaks into the full one
         constexpr int TRS = M16 ? 36 : 32;                            // row stride of the transpose region (36: conflict-free for the 16 x 16 C layout)
         // column fragments: a wave's accumulators are 8 rows x 8 columns of the tile, but outputs, residual adds and the statistics records
         // are formed over 2 rows x 32 columns per wave as ever (the fp32 record sums depend on that order). Each wave therefore writes into
@@ -685,7 +740,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         const int cq = lane & 7;
         const int prow = lane >> 3;
         const int tilesY4 = (gridH + 3) >> 2;                         // statistics records are per 4-row band (kernels.h)
-        const int ty4 = (y0 >> 2) + (wm >> 1);
+        const int ty4 = (y0 >> 2) + (wm_u >> 1);                      // (wave-uniform: the record test below is a scalar branch)
 #pragma unroll
         for (int q = 0; q < 2 * NB; ++q) {
             const int hb = q >> 1, nt = q & 1;
@@ -718,9 +773,36 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             }
             if constexpr (COLF) __syncthreads();
             else __builtin_amdgcn_wave_barrier();
-            const v4f bias = a.bias ? *reinterpret_cast<const v4f*>(a.bias + co) : v4f{0.f, 0.f, 0.f, 0.f};
+            v4f bias;
+            if constexpr (FULL) bias = bias_all[q & 1];
+            else bias = a.bias ? *reinterpret_cast<const v4f*>(a.bias + co) : v4f{0.f, 0.f, 0.f, 0.f};
             const float wsc = (NS == 2) ? a.wscale_inv : 1.0f;      // fp16 weights were pre-scaled by a power of two
             v4f ssum = v4f{0.f, 0.f, 0.f, 0.f}, ssq = ssum;
+            if constexpr (FULL) {
+                const int gy0 = y0 + 2 * wm_u;
+                const int oy0 = UP2 ? (2 * gy0 + pa) : gy0, ox0 = UP2 ? (2 * x0 + pb) : x0;
+                float* ob = a.out + uni64(((size_t)((ks * a.B + b) * a.H + oy0) * a.W + ox0) * a.Cout + ((NB * cb + hb) * 128 + 64 * wn_u + 32 * nt));
+                const unsigned l0 = (UP2 ? 2u : 1u) * prow * (unsigned)a.Cout + 4u * cq, sI = uni((UP2 ? 16u : 8u) * (unsigned)a.Cout),
+                               sH = uni((UP2 ? 2u : 1u) * (unsigned)a.W * (unsigned)a.Cout);
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    v4f o[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int p = 8 * (4 * hf + i) + prow;
+                        // the roundings of the masked code, spelled out (left to the compiler's contraction, straight-line code fused
+                        // o0 o0 + o1 o1 the other way round): fma(val, wsc, bias) + residual; sum of squares = fma chain from o0 o0
+                        o[i] = fma4(*reinterpret_cast<const v4f*>(tr + p * TRS + 4 * cq), v4f{wsc, wsc, wsc, wsc}, bias) + rsd_all[q & 1][hf][i];
+                        ssum += o[i];
+                        ssq = (hf == 0 && i == 0) ? o[i] * o[i] : fma4(o[i], o[i], ssq);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) *reinterpret_cast<v4f*>(reinterpret_cast<char*>(ob) + 4u * (l0 + hf * sH + i * sI)) = o[i];
+                }
+                // this quarter's bias and residual registers are free: request those of the quarter after next. vmcnt completes in order,
+                // so waiting for them two quarters on leaves the NEXT quarter's stores in flight.
+                if (q + 2 < 2 * NB) { load_rsd_full(q + 2, 1); load_bias_full(q + 2); }
+            } else {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 v4f val[4];
@@ -744,7 +826,8 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                         ssq += o * o;
                     }
             }
-            if (q + 2 < 2 * NB) load_rsd(q + 2);       // this quarter's residual registers are free: request the one after next
+            if (q + 2 < 2 * NB) load_rsd_masked(q + 2);       // this quarter's residual registers are free: request the one after next
+            }
             if (a.stats) {
 #pragma unroll
                 for (int m = 8; m < 64; m <<= 1) {
@@ -753,9 +836,9 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     ssq.x += __shfl_xor(ssq.x, m, 64); ssq.y += __shfl_xor(ssq.y, m, 64);
                     ssq.z += __shfl_xor(ssq.z, m, 64); ssq.w += __shfl_xor(ssq.w, m, 64);
                 }
-                if (prow == 0 && ty4 < tilesY4) {
+                if ((FULL || ty4 < tilesY4) && prow == 0) {      // (a full tile's two bands are inside the image)
                     const int nrec = (UP2 ? 8 : 2) * tilesX * tilesY4;
-                    const int rec = 2 * ((cls * tilesY4 + ty4) * tilesX + tx) + (wm & 1);
+                    const int rec = 2 * ((cls * tilesY4 + ty4) * tilesX + tx) + (wm_u & 1);
                     float* o = a.stats + (((size_t)b * nrec + rec) * a.Cout + co) * 2;
                     *reinterpret_cast<v4f*>(o) = v4f{ssum.x, ssq.x, ssum.y, ssq.y};
                     *reinterpret_cast<v4f*>(o + 4) = v4f{ssum.z, ssq.z, ssum.w, ssq.w};
@@ -764,7 +847,9 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             if constexpr (COLF) { if (q + 1 < 2 * NB) __syncthreads(); }      // every wave has read its region before the next quarter lands in it
             else __builtin_amdgcn_wave_barrier();
         }
-    }
+    };
+    if (full) epilogue(std::true_type{});
+    else epilogue(std::false_type{});
 }
 
 int conv_mode() {

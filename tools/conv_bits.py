@@ -2,7 +2,7 @@
 """md5 of the fused convolution's output bytes on fixed inputs, per library build (CDDPM_LIB): two builds that claim the same arithmetic
 in the same order must print the same digests.
 
-    CDDPM_LIB=<so> python tools/conv_bits.py [--mode default|nb2|p16|all] [--json FILE] [--parent COMMIT]
+    CDDPM_LIB=<so> python tools/conv_bits.py [--set fragments|epilogue] [--mode default|nb2|p16|x6|all] [--json FILE] [--parent COMMIT]
 
 Inputs come from numpy.random.default_rng(SEED) on the host (one generator per case, keyed by the case's position) and are copied to the
 device: no device generator is involved. The cases are the smallest shapes at which the wave -> pixel mapping of the 16 x 16 form can go
@@ -14,7 +14,13 @@ coefficients that op_conv_gn returns), and three larger layers. Modes:
              mode wants a process of its own: `all` starts one)
     p16      a precision-16 handle: the operators again, and a small UNet forward (plain-fp16 convolutions: the hi-only kernels)
 `default` and `p16` also digest that UNet forward. --json writes {parent, seed, cases, modes: {mode: {case: md5}}} (tests/golden/
-conv_bits_parent.json is this file, written once with CDDPM_LIB set to a build of the parent commit)."""
+conv_bits_parent.json is this file, written once with CDDPM_LIB set to a build of the parent commit).
+
+--set epilogue: the shapes at which the epilogue's two paths occur (csrc/conv_x6.hip: a workgroup whose 8 x 32 tile lies inside the image
+stores without per-lane predicates, a ragged one keeps them) -- EPILOGUE_SHAPES x EPILOGUE_OPS below, B = 2, 128 channels: 3x3 with and
+without residual, the statistics records, the folded upsample with a half-resolution residual, 1x1, a 256-cout layer (256-cout workgroups
+in mode nb2) and the layer as a small handle plans it (split-K: plane stores and the combine). Mode x6: an exact-bf16-family handle.
+tests/golden/conv_bits_epilogue_parent.json is that output for the commit before the full-tile path."""
 import argparse
 import hashlib
 import importlib
@@ -31,6 +37,7 @@ sys.path.insert(0, ROOT)
 PKG = "conditioned-diffusion-models-uad_amd"
 SEED = 20261021
 MODES = ("default", "nb2", "p16")
+EPILOGUE_MODES = MODES + ("x6",)
 
 # name: (op, B, C0, C1, Cout, H, W of the SOURCE, coef, silu, res, skipC)     op: conv | up2 (folded upsample, output 2H x 2W, res_upsample)
 CASES = {
@@ -46,6 +53,11 @@ CASES = {
     "conv 128>128 64x64": ("conv", 3, 128, 0, 128, 64, 64, 1, 1, 0, 0),
     "cat 256+128>256 32x40 +res": ("conv", 3, 256, 128, 256, 32, 40, 1, 1, 1, 0),
 }
+# epilogue set: H x W of the OUTPUT grid the tiles cover (the folded case's source; its output is 2H x 2W)
+EPILOGUE_SHAPES = {"8x32": (8, 32), "16x40": (16, 40), "12x20": (12, 20), "16x64": (16, 64)}
+# op: (kind, Cout, res)      kind: conv | gn | up2 | 1x1 | planned (a handle of max_batch 2 at the layer's own size: K is split)
+EPILOGUE_OPS = {"3x3": ("conv", 128, 0), "3x3 +res": ("conv", 128, 1), "3x3 gn": ("gn", 128, 0), "up2 +res_up": ("up2", 128, 1),
+                "1x1 +res": ("1x1", 128, 1), "3x3 >256 +res": ("conv", 256, 1), "planned +res": ("planned", 128, 1)}
 UNET = dict(model_channels=128, channel_mult=(1, 2), num_res_blocks=1, attention_resolutions=(3, 6, 12))      # + geometry (2, 16, 24), t = (123, 877)
 
 
@@ -75,6 +87,56 @@ def run_case(e, index, spec):
         return {"": md5(e.op_conv_skip(x0, cf, silu, w, bias, skip, wskip))}
     out, co = e.op_conv_gn(x0, w, bias, 1 + n(Cout, scale=0.1), n(Cout, scale=0.1))
     return {"": md5(out), " coef": md5(co)}
+
+
+def run_epilogue_case(E, e, index, shape, op, mode):
+    """{suffix: md5} of one (shape, op) of the epilogue set on engine e"""
+    kind, Cout, res = op
+    H, W = shape
+    B, Cin = 2, 128
+    rng = np.random.default_rng([SEED, 100 + index])
+    n = lambda *shp, scale=1.0: torch.from_numpy((rng.standard_normal(shp, dtype=np.float32) * np.float32(scale)))
+    k = 1 if kind == "1x1" else 3
+    x0 = n(B, H, W, Cin).cuda()
+    cf = torch.stack([n(B, Cin, scale=0.2), 1 + n(B, Cin, scale=0.2), n(B, Cin, scale=0.2)]).contiguous().cuda()
+    w = n(Cout, Cin, k, k, scale=1.0 / (Cin * k * k) ** 0.5)
+    bias = n(Cout, scale=0.1)
+    r = n(B, H, W, Cout).cuda() if res else None
+    if kind in ("conv", "1x1"):
+        return {"": md5(e.op_conv(x0, None, cf, 1, 0, w, bias, r, False, k))}
+    if kind == "up2":
+        return {"": md5(e.op_conv(x0, None, cf, 1, 2, w, bias, r, True, 3))}
+    if kind == "gn":
+        out, co = e.op_conv_gn(x0, w, bias, 1 + n(Cout, scale=0.1), n(Cout, scale=0.1))
+        return {"": md5(out), " coef": md5(co)}
+    small = E.CddpmEngine(timesteps=10, max_batch=B, max_h=H, max_w=W, precision=16 if mode == "p16" else None,
+                          **({"conv_family": "x6"} if mode == "x6" else {}))
+    try:
+        out, co, plan = small.op_conv_planned(x0, None, cf, 1, 0, w, bias, r, False, 3, img_hw=(H, W), gamma=1 + n(Cout, scale=0.1),
+                                              beta=n(Cout, scale=0.1))
+        return {f" S{plan['S']}": md5(out), f" S{plan['S']} coef": md5(co)}
+    finally:
+        small.close()
+
+
+def epilogue_digests(mode):
+    """{case: md5} of the epilogue set in one mode, in this process"""
+    assert mode in EPILOGUE_MODES, mode
+    assert (os.environ.get("CDDPM_NB2") == "force") == (mode == "nb2"), "nb2 <=> CDDPM_NB2=force, per process"
+    E = importlib.import_module(PKG + ".engine")
+    e = E.CddpmEngine(timesteps=10, max_batch=4, max_h=64, max_w=128, precision=16 if mode == "p16" else None,
+                      **({"conv_family": "x6"} if mode == "x6" else {}))
+    out = {}
+    try:
+        index = 0
+        for sname, shape in EPILOGUE_SHAPES.items():
+            for oname, op in EPILOGUE_OPS.items():
+                for suffix, d in run_epilogue_case(E, e, index, shape, op, mode).items():
+                    out[f"{oname} {sname}{suffix}"] = d
+                index += 1
+    finally:
+        e.close()
+    return out
 
 
 def unet_digest(E, precision):
@@ -110,13 +172,14 @@ def digests(mode):
     return out
 
 
-def digests_in_child(mode):
+def digests_in_child(mode, which="fragments"):
     """the same in a process of its own (what a mode that is read once per process needs)"""
     env = dict(os.environ)
     env.pop("CDDPM_NB2", None)
     if mode == "nb2":
         env["CDDPM_NB2"] = "force"
-    o = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--json", "-"], env=env, capture_output=True, text=True, timeout=600)
+    o = subprocess.run([sys.executable, os.path.abspath(__file__), "--set", which, "--mode", mode, "--json", "-"], env=env, capture_output=True,
+                       text=True, timeout=600)
     if o.returncode != 0:
         raise RuntimeError(f"conv_bits --mode {mode} failed (exit {o.returncode}):\n{o.stdout[-2000:]}\n{o.stderr[-2000:]}")
     return json.loads(o.stdout.strip().splitlines()[-1])["modes"][mode]
@@ -124,19 +187,24 @@ def digests_in_child(mode):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--mode", default="default", choices=MODES + ("all",))
+    ap.add_argument("--set", default="fragments", choices=("fragments", "epilogue"), dest="which")
+    ap.add_argument("--mode", default="default", choices=EPILOGUE_MODES + ("all",))
     ap.add_argument("--json", default=None, help="write the digests to this file ('-': one line on stdout)")
     ap.add_argument("--parent", default=None, help="commit hash to record (the build CDDPM_LIB points at)")
     a = ap.parse_args()
+    epi = a.which == "epilogue"
     if a.mode == "all":
         modes = {}
-        for m in MODES:      # one process each; stop at the first that fails: nothing more is started on a device a child may have left faulted
-            modes[m] = digests_in_child(m)
+        for m in (EPILOGUE_MODES if epi else MODES):      # one process each; stop at the first that fails: nothing more is started on a device a child may have left faulted
+            modes[m] = digests_in_child(m, a.which)
     else:
-        modes = {a.mode: digests(a.mode)}
-    rec = {"parent": a.parent, "seed": SEED, "lib": os.path.basename(os.environ.get("CDDPM_LIB", "libcddpm_hip.so")),
-           "cases": {k: list(v) for k, v in CASES.items()}, "unet": {k: list(v) if isinstance(v, tuple) else v for k, v in UNET.items()},
-           "modes": modes}
+        modes = {a.mode: epilogue_digests(a.mode) if epi else digests(a.mode)}
+    rec = {"parent": a.parent, "seed": SEED, "lib": os.path.basename(os.environ.get("CDDPM_LIB", "libcddpm_hip.so"))}
+    if epi:
+        rec.update(shapes={k: list(v) for k, v in EPILOGUE_SHAPES.items()}, ops={k: list(v) for k, v in EPILOGUE_OPS.items()}, modes=modes)
+    else:
+        rec.update(cases={k: list(v) for k, v in CASES.items()}, unet={k: list(v) if isinstance(v, tuple) else v for k, v in UNET.items()},
+                   modes=modes)
     if a.json == "-":
         print(json.dumps(rec))
         return
