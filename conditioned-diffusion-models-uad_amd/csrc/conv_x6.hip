@@ -28,7 +28,7 @@
 //   2 x 2 MFMA tiles of 32 x 32 (bf16 form) or 4 x 4 tiles of 16 x 16 (fp16 form). Which 64 pixels:
 //     row fragments (bf16 form; fp16 form: 1x1 taps and the 256-cout workgroups): tile rows 2 wm, 2 wm + 1, all 32 columns; an A fragment
 //       is 16 (32) consecutive columns of one row;
-//     column fragments (fp16 form, 3x3 and folded 2x2 taps, 128-cout workgroups -- conv_colfrag): tile columns 4 wm .. 4 wm + 3 and
+//     column fragments (fp16 form, 3x3 and folded 2x2 taps, 128-cout workgroups -- ConvTile::COLF): tile columns 4 wm .. 4 wm + 3 and
 //       16 + 4 wm .. 16 + 4 wm + 3, all 8 rows; an A fragment is the 8 rows of one column and of the column 16 further right. A weight stage
 //       is one ROW of taps (ky fixed, kx = 0, 1, 2), and fragment j + 1 of tap kx is fragment j of tap kx + 1: the stage keeps a ring of four
 //       column fragments per term and reads 4 + 1 + 1 columns (12 ds_read_b128 with both terms) where row fragments read 3 x 4 (24); with the
@@ -39,7 +39,7 @@
 // LDS (one workgroup per CU): per pixel / per cout row SP = 4 NS slots of 16 B (slot = split s, u = channel / 8):
 //   weights, and the patch of the bf16 form:  NS = 3: stride 12 slots, slot (s, u) at 4 s + (u ^ ((row >> 2) & 3));  NS = 2: stride 8,
 //   (4 s + u) ^ ((row >> 1) & 7) -> 16 consecutive rows x one slot cover all 16 four-bank groups: ds_read_b128 of a fragment is conflict free.
-//   patch of the fp16 form, row fragments: stride 8, slot bits 1, 2 swizzled by the pixel's column (swz16 below);
+//   patch of the fp16 form, row fragments: stride 8, slot bits 1, 2 swizzled by the pixel's column (conv_swz16, conv_split.h);
 //   column fragments: patch row pitch PW * 8 + 2 slots (2 mod 16 times an odd number), pixel (pr, pc) at pr * pitch + 8 pc, slot
 //   (4 s + u) ^ 4 (pc & 1) inside it: the 16 lanes one LDS cycle serves are the 8 rows of a column at u and of the column 16 further at u ^ 1,
 //   8 even slot offsets x 2 -> all 16 four-bank groups, for every tap (a tap's row adds a multiple of the pitch, its column a constant);
@@ -52,6 +52,7 @@
 #include "kernels.h"
 #include "conv_split.h"
 #include <algorithm>
+#include <cassert>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -70,60 +71,32 @@ namespace cddpm {
 // registers `acc` and `tot` take at NB = 1, so the three-level accumulation becomes two-level: every MFMA accumulates into the output's
 // one long-lived chain (rounding noise of a K = 4608 dot product 7.6e-7 of rms(C) instead of 1.9e-7; the reference's CPU fmaf chain:
 // 1.2e-6 -- tools/ubench/bf16_split_accuracy.hip, rows "h3" / "h3 fold96" / "cpu fma32").
-static constexpr int ROWS = 8;      // image rows of a workgroup's pixel tile (x 32 columns), two per wave
-// 16 x 16 form: which instantiations hold COLUMN fragments (a fragment = the 8 rows of one patch column and of the column 16 further
-// right, so that the A operand of tap kx + 1 is the A operand of tap kx one fragment on: a row of taps reads each column once).
-// Results are identical either way; the 1x1 form has one tap and nothing to reuse, and the 256-cout workgroups (NB = 2: 128 accumulator
-// registers in one chain, 253 VGPRs as they are) spill with the ring (3x3: 129 VGPRs, 176 B of scratch per lane), so they keep row
-// fragments. Kernel and launcher (LDS size) both ask here.
-static constexpr bool conv_colfrag(int ns, int taps, bool hi1, int nb) { return ns == 2 && taps != 1 && nb == 1; }
-static constexpr int conv_colfrag_pitch(int pw) { return pw * 8 + 2; }      // 16-B slots per patch row: 2 mod 16 x odd -> the 8 rows of a column start in 8 different even slots
-static constexpr int conv_colfrag_slots(int pw, int ph) { return (ph * conv_colfrag_pitch(pw) + 15) & ~15; }
+// The tile's constants, its LDS layout and the slot functions (swizzles) are stated once, in conv_split.h: ConvTile<TAPS, NS, HI1, NB> (T
+// below), conv_wslot (weight image), conv_slot_a / conv_swz16 / conv_colfrag_pitch (patch).
+// (Why the stages are still lambdas of one function: DESIGN.md section 4, "Where the kernel's pieces are stated".)
 template <int TAPS, int NS, bool HI1 = false, int NB = 1>
-__global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a) {
-    static_assert(NB == 1 || (NB == 2 && NS == 2 && TAPS != 1), "two cout blocks per workgroup: 16 x 16 fp16 form, LDS-DMA loop (3x3 and folded 2x2) only");
+__global__ __launch_bounds__(512) void conv_split_kernel(const ConvArgs a) {
+    typedef ConvTile<TAPS, NS, HI1, NB> T;
+    static_assert(T::THREADS == 512, "launch bounds");
     typedef typename SplitT<NS>::v8 frag;
-    constexpr int SP = 4 * NS;                          // 16-B slots per pixel / per cout row
-    constexpr int THREADS = 64 * ROWS;
-    // TAPS == 4: folded "nearest x2 upsample -> 3x3 conv", one parity class of the output per tile (see conv_mfma.hip)
-    constexpr bool UP2 = (TAPS == 4);
-    constexpr int PAD = (TAPS == 9) ? 1 : 0;
-    constexpr int PW = UP2 ? 33 : 32 + 2 * PAD;         // patch width  (pixels)
-    constexpr int PH = UP2 ? ROWS + 1 : ROWS + 2 * PAD; // patch height (pixels)
-    constexpr int NPIX = PW * PH;                       // 340 | 256 | 297 at ROWS = 8
-    constexpr int NK = (NPIX * 8 + THREADS - 1) / THREADS;   // 16-B (4-channel) patch entries per thread: 6 | 4 | 5
-    constexpr int FOLD = (TAPS == 9) ? 3 : (TAPS == 4 ? 2 : 1);   // taps per accumulation group: one row of taps
-    constexpr int WSLOTS = 128 * SP;                    // 16-B slots of a weight slab
-    // taps per weight stage: the fp16 form stages a whole row of taps (3 of the 3x3, 2 of the folded 2x2) per workgroup
-    // barrier -- one barrier (and one burst of fragment reads behind it) per 72 MFMAs of a wave instead of per 24, and the
-    // stage is exactly one accumulation group (FOLD taps). The bf16 form's slabs are 1.5x larger: one tap per stage.
-    constexpr int TPS = (NS == 2) ? FOLD : 1;
-    constexpr int WSTAGE = TPS * WSLOTS;                // 16-B slots of one weight stage
-    constexpr int WK = WSLOTS / THREADS;                // 16-B pieces of ONE slab per thread: 3 | 2
-    static_assert(WSLOTS % THREADS == 0, "weight slab must divide evenly");
-
-    constexpr bool COLF = conv_colfrag(NS, TAPS, HI1, NB);      // column fragments (16 x 16 form)
-    constexpr int CPITCH = conv_colfrag_pitch(PW);              // ... their patch row pitch in slots
-    constexpr int ASLOTS = COLF ? conv_colfrag_slots(PW, PH) : NPIX * SP;
-
     extern __shared__ v4f lds[];
-    v4f* ldsA = lds;                    // ASLOTS slots
-    v4f* ldsW = lds + ASLOTS;           // 2 * WSTAGE
-    v4f* ldsC = ldsW + 2 * WSTAGE;      // GroupNorm/FiLM coefficients of this sample (3 x Cin floats)
+    v4f* ldsA = lds + T::LDS_A;         // the patch
+    v4f* ldsW = lds + T::LDS_W;         // two weight stages
+    v4f* ldsC = lds + T::LDS_C;         // GroupNorm/FiLM coefficients of this sample (3 x Cin floats)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int li = lane & 31;
     const int lh = lane >> 5;
-    const int wm = wave % (ROWS / 2);   // pixel rows {2 wm, 2 wm + 1} of the tile
-    const int wn = wave / (ROWS / 2);   // cout half
+    const int wm = wave % (T::ROWS / 2);   // pixel rows {2 wm, 2 wm + 1} of the tile
+    const int wn = wave / (T::ROWS / 2);   // cout half
 
     const int ncb = a.Cout >> 7;              // cout blocks of the weight image
     const int ncbw = ncb / NB;                // ... per workgroup column: this workgroup multiplies blocks NB cb .. NB cb + NB - 1
-    const int gridH = UP2 ? (a.H >> 1) : a.H, gridW = UP2 ? (a.W >> 1) : a.W;
+    const int gridH = T::UP2 ? (a.H >> 1) : a.H, gridW = T::UP2 ? (a.W >> 1) : a.W;
     const int tilesX = (gridW + 31) >> 5;
-    const int tilesY = (gridH + ROWS - 1) / ROWS;
+    const int tilesY = (gridH + T::ROWS - 1) / T::ROWS;
     // Workgroups go to the 8 XCDs round-robin (blockIdx % 8), each with its own L2. Give every XCD a CONTIGUOUS range of
     // tiles instead: the cout blocks of one tile and the tiles above / below it (shared halo rows) then run on one XCD at
     // about the same time, and the second reader of a patch row finds it in that L2.
@@ -140,31 +113,10 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     bid /= tilesX;
     const int ty = bid % tilesY;
     bid /= tilesY;
-    const int cls = UP2 ? (bid & 3) : 0;
-    const int b = UP2 ? (bid >> 2) : bid;
+    const int cls = T::UP2 ? (bid & 3) : 0;
+    const int b = T::UP2 ? (bid >> 2) : bid;
     const int pa = cls >> 1, pb = cls & 1;
-    const int y0 = ty * ROWS, x0 = tx * 32;
-
-    // 16-B slot of (row = pixel or cout row, split s, u = channel / 8)
-    auto slot_of = [](int row, int sp, int u) -> int {
-        return (NS == 3) ? (row * 12 + 4 * sp + (u ^ ((row >> 2) & 3))) : (row * 8 + ((4 * sp + u) ^ ((row >> 1) & 7)));
-    };
-    // ... of the patch in the fp16 form. The weight image above is fixed by the host packer; the patch is written here, so
-    // its swizzle follows the reads: a ds_read_b128 is served in four groups of 16 lanes ({0-3,12-15,20-27}, {4-11,16-19,
-    // 28-31}, +32) over 64 banks of 4 B, a ds_write_b64 in 16 consecutive lanes over 32 banks (MI355X_MICROARCH.md, LDS).
-    //   32x32x16: a group reads 16 consecutive pixels at one u  -> pixel bits 1..3 into the slot (as the weights), and pixel
-    //             bit 0 flips the split half so that the two pixels one store instruction covers do not share banks;
-    //   16x16x32: a group reads 8 + 8 pixels at u and u ^ 1, from ANY start pixel (tap shifts) -> slot bit 0 must stay u's,
-    //             so only bits 1, 2 are swizzled -- by the pixel's COLUMN in the patch (bits 1, 2 -> slot bit 1, 2; bit 0 ->
-    //             slot bit 2; the patch width is even, so column and pixel parity agree): a tap's row shift ky is then a
-    //             plain address offset and the fragment addresses are computed once per kernel, not once per tap.
-    // Both are conflict-free for every tap; with the weights' swizzle the 16x16 reads took 7 LDS cycles instead of 4.
-    constexpr bool M16 = (NS == 2);      // the 16 x 16 form
-    auto swz16 = [](int pc) -> int { return (2 * ((pc >> 1) & 3)) ^ (4 * (pc & 1)); };
-    auto slot_a = [](int row, int sp, int u) -> int {      // (not the 16x16 form)
-        if (NS == 3) return row * 12 + 4 * sp + (u ^ ((row >> 2) & 3));
-        return row * 8 + ((4 * sp + u) ^ ((row >> 1) & 7) ^ (4 * (row & 1)));
-    };
+    const int y0 = ty * T::ROWS, x0 = tx * 32;
 
     const int Cin = a.C0 + a.C1;
     const int nch_main = Cin >> 5;
@@ -175,34 +127,34 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
 
     // ---- per-thread patch entries: channel quad c4 is fixed per thread, pixel q = (tid>>3) + (THREADS/8) k
     const int c4 = tid & 7;
-    int psrc[NK];
+    int psrc[T::NK];
     unsigned centre = 0;
-    unsigned colswz = 0;                 // 16x16 form: swz16(column) of entry k in bits 3k .. 3k+2 (column fragments: patch row | column parity << 4 in bits 5k .. 5k+4)
+    unsigned colswz = 0;                 // 16x16 form: conv_swz16(column) of entry k in bits 3k .. 3k+2 (column fragments: patch row | column parity << 4 in bits 5k .. 5k+4)
 #pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        const int q = (tid >> 3) + (THREADS / 8) * k;
-        const int pr = q / PW, pc = q - pr * PW;
-        if constexpr (COLF) colswz |= (unsigned)(pr | ((pc & 1) << 4)) << (5 * k);
-        else if constexpr (M16) colswz |= (unsigned)swz16(pc) << (3 * k);
-        const int y = UP2 ? (y0 + pr + pa - 1) : (y0 + pr - PAD), x = UP2 ? (x0 + pc + pb - 1) : (x0 + pc - PAD);
-        const bool valid = (q < NPIX) && (y >= 0) && (y < gridH) && (x >= 0) && (x < gridW);
-        const int sy = (!UP2 && a.upsample) ? (y >> 1) : y, sx = (!UP2 && a.upsample) ? (x >> 1) : x;
+    for (int k = 0; k < T::NK; ++k) {
+        const int q = (tid >> 3) + (T::THREADS / 8) * k;
+        const int pr = q / T::PW, pc = q - pr * T::PW;
+        if constexpr (T::COLF) colswz |= (unsigned)(pr | ((pc & 1) << 4)) << (5 * k);
+        else if constexpr (T::M16) colswz |= (unsigned)conv_swz16(pc) << (3 * k);
+        const int y = T::UP2 ? (y0 + pr + pa - 1) : (y0 + pr - T::PAD), x = T::UP2 ? (x0 + pc + pb - 1) : (x0 + pc - T::PAD);
+        const bool valid = (q < T::NPIX) && (y >= 0) && (y < gridH) && (x >= 0) && (x < gridW);
+        const int sy = (!T::UP2 && a.upsample) ? (y >> 1) : y, sx = (!T::UP2 && a.upsample) ? (x >> 1) : x;
         psrc[k] = valid ? (sy * a.srcW + sx) : -1;           // pixel index inside sample b (< 2^24)
-        if (valid && (pr >= PAD) && (pr < PH - PAD) && (pc >= PAD) && (pc < PW - PAD)) centre |= 1u << k;
+        if (valid && (pr >= T::PAD) && (pr < T::PH - T::PAD) && (pc >= T::PAD) && (pc < T::PW - T::PAD)) centre |= 1u << k;
     }
 
-    const v4f* wmain = reinterpret_cast<const v4f*>(a.wpk) + (size_t)(cls * ncb + NB * cb) * nch_main * TAPS * WSLOTS;
-    const v4f* wskip = reinterpret_cast<const v4f*>(a.skip_wpk) + (size_t)(NB * cb) * nch_skip * WSLOTS;
-    const size_t wmain_blk = (size_t)nch_main * TAPS * WSLOTS, wskip_blk = (size_t)nch_skip * WSLOTS;    // next cout block of the image
+    const v4f* wmain = reinterpret_cast<const v4f*>(a.wpk) + (size_t)(cls * ncb + NB * cb) * nch_main * TAPS * T::WSLOTS;
+    const v4f* wskip = reinterpret_cast<const v4f*>(a.skip_wpk) + (size_t)(NB * cb) * nch_skip * T::WSLOTS;
+    const size_t wmain_blk = (size_t)nch_main * TAPS * T::WSLOTS, wskip_blk = (size_t)nch_skip * T::WSLOTS;    // next cout block of the image
 
-    v4f wreg[WK];                       // (TPS == 1 loop) the next weight slab
-    v4f areg[NK];
+    v4f wreg[T::WK];                       // (TPS == 1 loop) the next weight slab
+    v4f areg[T::NK];
     const bool have_coef = (a.coef != nullptr);
 
     auto wslab = [&](int chunk, int tap) -> const v4f* {
         if (chunk >= nch) { chunk = 0; tap = 0; }      // past the end: wrap, so the prefetch stays unconditional
-        return (chunk < nch_main) ? (wmain + ((size_t)chunk * TAPS + tap) * WSLOTS)
-                                  : (wskip + (size_t)(chunk - nch_main) * WSLOTS);
+        return (chunk < nch_main) ? (wmain + ((size_t)chunk * TAPS + tap) * T::WSLOTS)
+                                  : (wskip + (size_t)(chunk - nch_main) * T::WSLOTS);
     };
     auto load_act = [&](int chunk) {
         const float* base;
@@ -219,7 +171,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         }
         const float* ubase = base + ((size_t)b * a.srcH * a.srcW * Cs + c0);
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
+        for (int k = 0; k < T::NK; ++k) {
             const int p = (main_seg || ((centre >> k) & 1u)) ? psrc[k] : -1;
             v4f v = v4f{0.f, 0.f, 0.f, 0.f};
             // wave-uniform 64-bit base (sample, channel chunk) + a 32-bit per-lane offset: one v_mad_u32_u24 per entry
@@ -232,7 +184,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     // coefficient cache is read-only), write_act stores them to the patch once every wave is done reading the previous one.
     // A wave that finishes its MFMAs early (the older wave of a SIMD wins the matrix pipe) transforms while its partner still
     // multiplies, instead of waiting at the barrier and transforming afterwards.
-    typename SplitT<NS>::v4 sreg[NK][NS];
+    typename SplitT<NS>::v4 sreg[T::NK][NS];
     auto transform_act = [&](int chunk) {
         const bool main_seg = chunk < nch_main;
         const bool do_silu = main_seg && a.silu;
@@ -245,7 +197,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             cd = ldsC[2 * (Cin >> 2) + ci];
         }
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
+        for (int k = 0; k < T::NK; ++k) {
             v4f v = areg[k];
             const int p = (main_seg || ((centre >> k) & 1u)) ? psrc[k] : -1;
             if (p >= 0) {   // zero padding stays exactly zero: the conv pads AFTER the activation
@@ -261,15 +213,15 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     auto write_act = [&]() {
         v2f* dst = reinterpret_cast<v2f*>(ldsA);       // 8-B units
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const int q = (tid >> 3) + (THREADS / 8) * k;
-            if (q < NPIX) {
+        for (int k = 0; k < T::NK; ++k) {
+            const int q = (tid >> 3) + (T::THREADS / 8) * k;
+            if (q < T::NPIX) {
                 // 4 channels = half a slot: slot u = c4 >> 1 of each split, half c4 & 1
 #pragma unroll
                 for (int sp = 0; sp < (HI1 ? 1 : NS); ++sp) {        // (hi-only products never read the mid plane: it is neither computed nor stored)
                     // column fragments: pixel (pr, pc) at pr * CPITCH + 8 pc = 8 q + 2 pr, odd columns with hi and mid exchanged
-                    const int sl = COLF ? (q * 8 + 2 * (int)((colswz >> (5 * k)) & 15u) + ((4 * sp + (c4 >> 1)) ^ (4 * (int)((colswz >> (5 * k + 4)) & 1u))))
-                                 : M16 ? (q * 8 + ((4 * sp + (c4 >> 1)) ^ (int)((colswz >> (3 * k)) & 7u))) : slot_a(q, sp, c4 >> 1);
+                    const int sl = T::COLF ? (q * 8 + 2 * (int)((colswz >> (5 * k)) & 15u) + ((4 * sp + (c4 >> 1)) ^ (4 * (int)((colswz >> (5 * k + 4)) & 1u))))
+                                 : T::M16 ? (q * 8 + ((4 * sp + (c4 >> 1)) ^ (int)((colswz >> (3 * k)) & 7u))) : conv_slot_a(q, sp, c4 >> 1);
                     dst[sl * 2 + (c4 & 1)] = __builtin_bit_cast(v2f, sreg[k][sp]);
                 }
             }
@@ -280,7 +232,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x16 acc[2][2], tot[2][2];            // 32 x 32 form: [pixel row][cout 32-tile]
     f32x4 acc16[NB][4][4], tot16[4][4];     // 16 x 16 form: [cout block][pixel 16-group][cout 16-group]  (only one of the two sets is live; NB = 2: no tot16)
-    if constexpr (M16) {
+    if constexpr (T::M16) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -300,7 +252,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     auto fold_acc = [&]() {
         if constexpr (NB == 2) {
             // two-level accumulation: the MFMAs chain into acc16[h] from the first chunk to the last, nothing to fold
-        } else if constexpr (M16) {
+        } else if constexpr (T::M16) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -323,22 +275,20 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     // so the four pixel groups (two rows x two 16-column halves) and the four cout groups of a wave sit at CONSTANT slot
     // offsets from the first one: one hi-term and one mid-term base (4 slots away under XOR) per column shift kx and one
     // pair for the weights; everything else is an instruction offset. A tap's ky adds ky * PW * 8 slots.
-    constexpr int NKX = (TAPS == 9) ? 3 : (UP2 ? 2 : 1);
-    static_assert(!M16 || TPS == NKX, "16x16 form: a weight stage is one row of taps, so the column shift is the unrolled index");
-    int a_hi[NKX], a_mid[NKX], b_hi = 0, b_mid = 0, a_col = 0;
-    if constexpr (M16) {
+    int a_hi[T::NKX], a_mid[T::NKX], b_hi = 0, b_mid = 0, a_col = 0;
+    if constexpr (T::M16) {
         const int r16 = lane & 15, g = lane >> 4;
         // column fragments: wave wm owns the patch columns 4 wm + c and 16 + 4 wm + c (c = fragment j + tap kx: 0 .. 3 + NKX - 1), MFMA row
         // r16 = patch row r16 & 7 of the left (r16 < 8) or right column. ONE base: the column c (8 c slots, hi / mid at 4 (c & 1) and its
         // complement), the tap row ky and the term are offsets from it.
-        a_col = (r16 & 7) * CPITCH + (4 * wm + 16 * (r16 >> 3)) * 8 + g;
+        a_col = (r16 & 7) * T::CPITCH + (4 * wm + 16 * (r16 >> 3)) * 8 + g;
 #pragma unroll
-        for (int kx = 0; kx < NKX; ++kx) {
+        for (int kx = 0; kx < T::NKX; ++kx) {
             const int pc = r16 + kx;
-            a_hi[kx] = ((2 * wm) * PW + pc) * 8 + (g ^ swz16(pc));
+            a_hi[kx] = ((2 * wm) * T::PW + pc) * 8 + (g ^ conv_swz16(pc));
             a_mid[kx] = a_hi[kx] ^ 4;
         }
-        b_hi = slot_of(64 * wn + r16, 0, g);
+        b_hi = conv_wslot(NS, 64 * wn + r16, 0, g);
         b_mid = b_hi ^ 4;
     }
 
@@ -348,18 +298,18 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     auto compute = [&](auto hc, int tap, int kxc, bool skip, const v4f* wb, bool first) {
         constexpr int HB = decltype(hc)::value;      // cout block of this pass (selects the accumulator registers)
         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int ky = (TAPS == 9) ? (tap / 3) : (UP2 ? (tap >> 1) : 0);
-        const int kx = (TAPS == 9) ? (tap - 3 * ky) : (UP2 ? (tap & 1) : 0);
-        if constexpr (M16) {
+        const int ky = (TAPS == 9) ? (tap / 3) : (T::UP2 ? (tap >> 1) : 0);
+        const int kx = (TAPS == 9) ? (tap - 3 * ky) : (T::UP2 ? (tap & 1) : 0);
+        if constexpr (T::M16) {
             const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
             f16x8 fa[2][4];
-            const v4f* ah = ldsA + (((TAPS == 9 && skip) ? a_hi[NKX / 2] : a_hi[kxc]) + ky * (PW * 8));
-            const v4f* am = ldsA + (((TAPS == 9 && skip) ? a_mid[NKX / 2] : a_mid[kxc]) + ky * (PW * 8));
+            const v4f* ah = ldsA + (((TAPS == 9 && skip) ? a_hi[T::NKX / 2] : a_hi[kxc]) + ky * (T::PW * 8));
+            const v4f* am = ldsA + (((TAPS == 9 && skip) ? a_mid[T::NKX / 2] : a_mid[kxc]) + ky * (T::PW * 8));
             const v4f* bh = wb + b_hi;
             const v4f* bm = wb + b_mid;
 #pragma unroll
             for (int t16 = 0; t16 < 4; ++t16) {
-                const int off = ((t16 >> 1) * PW + (t16 & 1) * 16) * 8;      // compile-time: an instruction offset
+                const int off = ((t16 >> 1) * T::PW + (t16 & 1) * 16) * 8;      // compile-time: an instruction offset
                 fa[0][t16] = __builtin_bit_cast(f16x8, ah[off]);
                 fa[1][t16] = __builtin_bit_cast(f16x8, am[off]);
             }
@@ -394,7 +344,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         }
         int arow[2];
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) arow[mt] = (2 * wm + mt + ky) * PW + li + kx;
+        for (int mt = 0; mt < 2; ++mt) arow[mt] = (2 * wm + mt + ky) * T::PW + li + kx;
         // products kept, smallest first: NS = 3: lh hl mm mh hm hh;  NS = 2: mh hm hh
         constexpr int NP = (NS == 3) ? 6 : 3;
         constexpr int PA[6] = {NS == 3 ? 2 : 1, 0, 1, 1, 0, 0};      // split index of the A term
@@ -407,8 +357,8 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             for (int sp = 0; sp < NS; ++sp)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    fa[sp][i] = __builtin_bit_cast(frag, ldsA[slot_a(arow[i], sp, u)]);
-                    fb[sp][i] = __builtin_bit_cast(frag, wb[slot_of(brow[i], sp, u)]);
+                    fa[sp][i] = __builtin_bit_cast(frag, ldsA[conv_slot_a(arow[i], sp, u)]);
+                    fb[sp][i] = __builtin_bit_cast(frag, wb[conv_wslot(NS, brow[i], sp, u)]);
                 }
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
@@ -437,7 +387,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     auto compute_cols = [&](auto hc, auto kx0c, auto ntc, int ky, const v4f* wb) {
         constexpr int HB = decltype(hc)::value, KX0 = decltype(kx0c)::value, NT = decltype(ntc)::value;
         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-        const v4f* ap = ldsA + (a_col + ky * CPITCH);
+        const v4f* ap = ldsA + (a_col + ky * T::CPITCH);
         const v4f* bh = wb + b_hi;
         const v4f* bm = wb + b_mid;
         f16x8 fa[2][NT + 3];
@@ -459,8 +409,8 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 f16x8 fb[2][2];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    fb[0][j] = __builtin_bit_cast(f16x8, bh[tt * WSLOTS + 128 * (2 * nh + j)]);
-                    if constexpr (!HI1) fb[1][j] = __builtin_bit_cast(f16x8, bm[tt * WSLOTS + 128 * (2 * nh + j)]);
+                    fb[0][j] = __builtin_bit_cast(f16x8, bh[tt * T::WSLOTS + 128 * (2 * nh + j)]);
+                    if constexpr (!HI1) fb[1][j] = __builtin_bit_cast(f16x8, bm[tt * T::WSLOTS + 128 * (2 * nh + j)]);
                 }
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {       // mid*hi, hi*mid, hi*hi
@@ -476,9 +426,21 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             }
         }
     };
-    constexpr int SKY = (TAPS == 1) ? 0 : 1, SKX = (TAPS == 9) ? 1 : 0;      // the skip segment's (centre) tap
 
-    if constexpr (TPS == 1) {
+    // the sample's GroupNorm/FiLM coefficients (3 x Cin floats) -> the coefficient cache ldsC. transform_act reads it: a workgroup barrier
+    // lies between (the register pipeline's first chunk barrier; the LDS-DMA pipeline has one of its own in front of the chunk loop)
+    auto load_coef = [&]() {
+        if (have_coef) {
+            const int nq = Cin >> 2;
+            const size_t plane = (size_t)a.B * Cin;
+            for (int i = tid; i < 3 * nq; i += T::THREADS) {
+                const int pl = i / nq, cq = i - pl * nq;
+                ldsC[i] = *reinterpret_cast<const v4f*>(a.coef + pl * plane + (size_t)b * Cin + 4 * cq);
+            }
+        }
+    };
+
+    if constexpr (T::TPS == 1) {
     // ---- main loop: weights double-buffered in LDS and prefetched through registers one stage ahead;
     //      the next chunk's patch is fetched into registers behind the last tap's MFMAs.
     //      Like the LDS-DMA loop below it runs over this workgroup's split-K range [kc0, kc1) (all chunks when the layer is not split):
@@ -486,17 +448,10 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     {
         const v4f* p0 = wslab(kc0, 0);
 #pragma unroll
-        for (int i = 0; i < WK; ++i) wreg[i] = p0[tid + THREADS * i];
+        for (int i = 0; i < T::WK; ++i) wreg[i] = p0[tid + T::THREADS * i];
     }
     load_act(kc0);
-    if (have_coef) {
-        const int nq = Cin >> 2;
-        const size_t plane = (size_t)a.B * Cin;
-        for (int i = tid; i < 3 * nq; i += THREADS) {
-            const int pl = i / nq, cq = i - pl * nq;
-            ldsC[i] = *reinterpret_cast<const v4f*>(a.coef + pl * plane + (size_t)b * Cin + 4 * cq);
-        }
-    }
+    load_coef();
     int buf = 0;
     for (int chunk = kc0; chunk < kc1; ++chunk) {
         const bool main_seg = chunk < nch_main;
@@ -505,20 +460,20 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         store_act(chunk);
         for (int t = 0; t < ntap; ++t) {
 #pragma unroll
-            for (int i = 0; i < WK; ++i) ldsW[buf * WSLOTS + tid + THREADS * i] = wreg[i];
+            for (int i = 0; i < T::WK; ++i) ldsW[buf * T::WSLOTS + tid + T::THREADS * i] = wreg[i];
             const bool last_tap = (t == ntap - 1);
             const v4f* pn = last_tap ? wslab(chunk + 1, 0) : wslab(chunk, t + 1);
 #pragma unroll
-            for (int i = 0; i < WK; ++i) wreg[i] = pn[tid + THREADS * i];
+            for (int i = 0; i < T::WK; ++i) wreg[i] = pn[tid + T::THREADS * i];
             if (last_tap && chunk + 1 < kc1) load_act(chunk + 1);
             __syncthreads();
             // accumulation in three levels: an MFMA sums 16 products, `acc` collects FOLD taps of a 32-channel chunk
             // (<= 96 products per chain), `tot` sums those groups. The rounding noise of an fp32 chain grows with the
             // magnitude of its partial sums, so short chains folded into a long-lived total keep it near the
             // storage-rounding level (tools/ubench/bf16_split_accuracy.hip, tools/chain_noise.py).
-            compute(std::integral_constant<int, 0>{}, main_seg ? t : (TAPS / 2), 0, !main_seg, ldsW + buf * WSLOTS, (t % FOLD) == 0);   // skip segment: centre tap (16x16 form: 1x1 convolutions only get here)
+            compute(std::integral_constant<int, 0>{}, main_seg ? t : (TAPS / 2), 0, !main_seg, ldsW + buf * T::WSLOTS, (t % T::FOLD) == 0);   // skip segment: centre tap (16x16 form: 1x1 convolutions only get here)
             buf ^= 1;
-            if ((t % FOLD) == FOLD - 1 || last_tap) fold_acc();
+            if ((t % T::FOLD) == T::FOLD - 1 || last_tap) fold_acc();
         }
     }
 
@@ -529,21 +484,20 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
     auto wstage = [&](int chunk, int hb, int st, int& nsl) -> const v4f* {
-        if (chunk < nch_main) { nsl = TPS; return wmain + hb * wmain_blk + ((size_t)chunk * TAPS + st * TPS) * WSLOTS; }
+        if (chunk < nch_main) { nsl = T::TPS; return wmain + hb * wmain_blk + ((size_t)chunk * TAPS + st * T::TPS) * T::WSLOTS; }
         nsl = 1;
-        return wskip + hb * wskip_blk + (size_t)(chunk - nch_main) * WSLOTS;
+        return wskip + hb * wskip_blk + (size_t)(chunk - nch_main) * T::WSLOTS;
     };
     // Each wave copies one contiguous eighth of a slab (2 KB = two 1-KB wave-instructions) per slab of the stage. The pieces of
     // a slab share one address pair: the instruction's immediate offset advances the global and the LDS address alike.
-    static_assert(THREADS == 512 && WSLOTS == 1024, "one slab = 8 waves x 2 KB");
     auto dma_stage = [&](const v4f* p, int nsl, int buf) {
         const v4f* g0 = p + wave * 128 + lane;
-        v4f* d0 = ldsW + buf * WSTAGE + wave * 128;          // wave-uniform; lane l lands 16 l bytes further
+        v4f* d0 = ldsW + buf * T::WSTAGE + wave * 128;          // wave-uniform; lane l lands 16 l bytes further
 #pragma unroll
-        for (int sl = 0; sl < TPS; ++sl)
+        for (int sl = 0; sl < T::TPS; ++sl)
             if (sl < nsl) {
-                __builtin_amdgcn_global_load_lds((gptr_t)(g0 + sl * WSLOTS), (lptr_t)(d0 + sl * WSLOTS), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((gptr_t)(g0 + sl * WSLOTS), (lptr_t)(d0 + sl * WSLOTS), 16, 1024, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(g0 + sl * T::WSLOTS), (lptr_t)(d0 + sl * T::WSLOTS), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(g0 + sl * T::WSLOTS), (lptr_t)(d0 + sl * T::WSLOTS), 16, 1024, 0);
             }
     };
     int nsl_cur = 0;
@@ -552,24 +506,21 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         dma_stage(p0, nsl_cur, 0);
     }
     load_act(kc0);
-    if (have_coef) {
-        const int nq = Cin >> 2;
-        const size_t plane = (size_t)a.B * Cin;
-        for (int i = tid; i < 3 * nq; i += THREADS) {
-            const int pl = i / nq, cq = i - pl * nq;
-            ldsC[i] = *reinterpret_cast<const v4f*>(a.coef + pl * plane + (size_t)b * Cin + 4 * cq);
-        }
-    }
+    load_coef();
     if (have_coef) __syncthreads();     // the coefficient cache is read by transform_act in FRONT of the first chunk barrier
     int buf = 0;
     for (int chunk = kc0; chunk < kc1; ++chunk) {
         const bool main_seg = chunk < nch_main;
-        const int nst = main_seg ? TAPS / TPS : 1;       // stages of this chunk
+        const int nst = main_seg ? TAPS / T::TPS : 1;       // stages of this chunk
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this chunk's first weight stage (and its patch registers) have landed
         transform_act(chunk);   // registers only: in front of the barrier, where the early waves would otherwise wait
         __syncthreads();   // the stage has landed in every wave, and every wave is done reading the previous patch
         write_act();
         __syncthreads();
+        // (NB == 1 keeps its own copy of the stage loop, which is run_block below at HB = 0, NB = 1. Deleting it compiles without spills
+        // but changes the epilogue's wait rows of <4,2,false,1> and <4,2,true,1> (tools/conv_epilogue_counts.py), which must stay the
+        // parent's -- that alone keeps the copy -- and moves <9,2,false,1> from 251 to 256 VGPRs (4 s_waitcnt more), <4,2,false,1> from
+        // 242 to 244, <4,2,true,1> from 222 to 226. Compile results; that build was not timed.)
         if constexpr (NB == 1) {
         for (int st = 0; st < nst; ++st) {
             const int ntaps = nsl_cur;                    // taps of this stage
@@ -581,19 +532,19 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 const v4f* pn = last_st ? wstage(chunk + 1, 0, 0, nsl_next) : wstage(chunk, 0, st + 1, nsl_next);
                 dma_stage(pn, nsl_next, buf ^ 1);
             }
-            if constexpr (COLF) {      // (a main stage is tap row ky = st)
-                if (main_seg) compute_cols(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, TPS>{}, st, ldsW + buf * WSTAGE);
-                else compute_cols(std::integral_constant<int, 0>{}, std::integral_constant<int, SKX>{}, std::integral_constant<int, 1>{}, SKY, ldsW + buf * WSTAGE);
+            if constexpr (T::COLF) {      // (a main stage is tap row ky = st)
+                if (main_seg) compute_cols(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, T::TPS>{}, st, ldsW + buf * T::WSTAGE);
+                else compute_cols(std::integral_constant<int, 0>{}, std::integral_constant<int, T::SKX>{}, std::integral_constant<int, 1>{}, T::SKY, ldsW + buf * T::WSTAGE);
             } else
 #pragma unroll
-            for (int tt = 0; tt < TPS; ++tt)
+            for (int tt = 0; tt < T::TPS; ++tt)
                 if (tt < ntaps) {
-                    const int t = st * TPS + tt;                                  // tap index inside the chunk
-                    compute(std::integral_constant<int, 0>{}, main_seg ? t : (TAPS / 2), tt, !main_seg, ldsW + buf * WSTAGE + tt * WSLOTS, (t % FOLD) == 0);   // skip segment: centre tap
+                    const int t = st * T::TPS + tt;                                  // tap index inside the chunk
+                    compute(std::integral_constant<int, 0>{}, main_seg ? t : (TAPS / 2), tt, !main_seg, ldsW + buf * T::WSTAGE + tt * T::WSLOTS, (t % T::FOLD) == 0);   // skip segment: centre tap
                 }
             buf ^= 1;
             nsl_cur = nsl_next;
-            if (((st + 1) * TPS) % FOLD == 0 || last_st) fold_acc();
+            if (((st + 1) * T::TPS) % T::FOLD == 0 || last_st) fold_acc();
             if (!last_st) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();   // the next stage has landed in every wave; this stage's buffer is free
@@ -614,20 +565,20 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                                             : (st == nst - 1 ? wstage(chunk, HB + 1, 0, nsl_next) : wstage(chunk, HB, st + 1, nsl_next));
                     dma_stage(pn, nsl_next, buf ^ 1);
                 }
-                if constexpr (COLF) {
-                    if (main_seg) compute_cols(hc, std::integral_constant<int, 0>{}, std::integral_constant<int, TPS>{}, st, ldsW + buf * WSTAGE);
-                    else compute_cols(hc, std::integral_constant<int, SKX>{}, std::integral_constant<int, 1>{}, SKY, ldsW + buf * WSTAGE);
+                if constexpr (T::COLF) {
+                    if (main_seg) compute_cols(hc, std::integral_constant<int, 0>{}, std::integral_constant<int, T::TPS>{}, st, ldsW + buf * T::WSTAGE);
+                    else compute_cols(hc, std::integral_constant<int, T::SKX>{}, std::integral_constant<int, 1>{}, T::SKY, ldsW + buf * T::WSTAGE);
                 } else
 #pragma unroll
-                for (int tt = 0; tt < TPS; ++tt)
+                for (int tt = 0; tt < T::TPS; ++tt)
                     if (tt < ntaps) {
-                        const int t = st * TPS + tt;                                  // tap index inside the chunk
-                        compute(hc, main_seg ? t : (TAPS / 2), tt, !main_seg, ldsW + buf * WSTAGE + tt * WSLOTS,
-                                (NB == 1) && (t % FOLD) == 0);   // skip segment: centre tap; NB = 2: one chain from the zeroed registers
+                        const int t = st * T::TPS + tt;                                  // tap index inside the chunk
+                        compute(hc, main_seg ? t : (TAPS / 2), tt, !main_seg, ldsW + buf * T::WSTAGE + tt * T::WSLOTS,
+                                (NB == 1) && (t % T::FOLD) == 0);   // skip segment: centre tap; NB = 2: one chain from the zeroed registers
                     }
                 buf ^= 1;
                 nsl_cur = nsl_next;
-                if (((st + 1) * TPS) % FOLD == 0 || st == nst - 1) fold_acc();
+                if (((st + 1) * T::TPS) % T::FOLD == 0 || st == nst - 1) fold_acc();
                 if (!last_st) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __syncthreads();   // the next stage has landed in every wave; this stage's buffer is free
@@ -653,9 +604,9 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
     // loads / stores issue back to back. Ragged tiles keep the masked code below. Same values, same stores, same order of the sums.
     // (the lane offsets are 32-bit BYTE offsets inside the wave's rows: at most (2 W + 64) Cout floats; NB = 2 keeps the masked code for
     // every tile: its 128 accumulator registers leave no room for the straight-line form, which spilled 250 B per lane)
-    const bool full = (NB == 1) && (y0 + ROWS <= gridH) && (x0 + 32 <= gridW) && ((unsigned long long)(2 * a.W + 64) * (unsigned)a.Cout < (1ull << 30));
+    const bool full = (NB == 1) && (y0 + T::ROWS <= gridH) && (x0 + 32 <= gridW) && ((unsigned long long)(2 * a.W + 64) * (unsigned)a.Cout < (1ull << 30));
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int wm_u = wave_u % (ROWS / 2), wn_u = wave_u / (ROWS / 2);
+    const int wm_u = wave_u % (T::ROWS / 2), wn_u = wave_u / (T::ROWS / 2);
     // the wave's two rows x 32 columns in a tensor of row width rw (pixels): lane pixel (hf, i) = row hf, column 8 i + (lane >> 3), at
     // (lp + hf sh rw + i si) Cout floats from the wave's first pixel; the folded form writes every other pixel of every other row, a
     // half-resolution residual of an unfolded launch is read at (y >> 1, x >> 1)
@@ -677,8 +628,8 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         const int rH = a.res_up ? (a.H >> 1) : a.H, rW = a.res_up ? (a.W >> 1) : a.W;
         int ry0 = gy0, rx0 = x0;
         unsigned lp = (unsigned)prow, si = 8u, sh = 1u;
-        if (UP2 && !a.res_up) { ry0 = 2 * gy0 + pa; rx0 = 2 * x0 + pb; lp = 2u * prow; si = 16u; sh = 2u; }
-        else if (!UP2 && a.res_up) { ry0 = gy0 >> 1; rx0 = x0 >> 1; lp = (unsigned)prow >> 1; si = 4u; sh = 0u; }
+        if (T::UP2 && !a.res_up) { ry0 = 2 * gy0 + pa; rx0 = 2 * x0 + pb; lp = 2u * prow; si = 16u; sh = 2u; }
+        else if (!T::UP2 && a.res_up) { ry0 = gy0 >> 1; rx0 = x0 >> 1; lp = (unsigned)prow >> 1; si = 4u; sh = 0u; }
         const unsigned l0 = lp * (unsigned)a.Cout + 4u * cq, sI = uni(si * (unsigned)a.Cout), sH = uni(sh * (unsigned)rW * (unsigned)a.Cout);
 #pragma unroll
         for (int q = q0; q < q0 + nq; ++q) {
@@ -708,7 +659,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                 const int co = (NB * cb + hb) * 128 + 64 * wn + 32 * nt + 4 * cq;
                 const int p = 8 * (4 * hf + i) + prow;
                 const int gy = y0 + 2 * wm + (p >> 5), gx = x0 + (p & 31);
-                const int y = UP2 ? (2 * gy + pa) : gy, x = UP2 ? (2 * gx + pb) : gx;
+                const int y = T::UP2 ? (2 * gy + pa) : gy, x = T::UP2 ? (2 * gx + pb) : gx;
                 v4f r = v4f{0.f, 0.f, 0.f, 0.f};
                 if (a.res && (gy < gridH) && (gx < gridW)) {
                     const size_t rp = a.res_up ? ((size_t)(b * (a.H >> 1) + (y >> 1)) * (a.W >> 1) + (x >> 1))
@@ -728,15 +679,13 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             return v4f{__builtin_fmaf(x.x, y.x, z.x), __builtin_fmaf(x.y, y.y, z.y), __builtin_fmaf(x.z, y.z, z.z), __builtin_fmaf(x.w, y.w, z.w)};
         };
         constexpr bool FULL = decltype(fullc)::value;    // its own copy of the quarter loop: no wait of the masked path leaks into the full one
-        constexpr int TRS = M16 ? 36 : 32;                            // row stride of the transpose region (36: conflict-free for the 16 x 16 C layout)
         // column fragments: a wave's accumulators are 8 rows x 8 columns of the tile, but outputs, residual adds and the statistics records
         // are formed over 2 rows x 32 columns per wave as ever (the fp32 record sums depend on that order). Each wave therefore writes into
         // the regions of the four waves of its cout half, at the pixel index the row partition gives, behind workgroup barriers; the
-        // regions sit 8 floats further apart so that the two row quads a store instruction covers do not share banks.
-        constexpr int TRW = 64 * TRS + (COLF ? 8 : 0);
-        float* tr = reinterpret_cast<float*>(lds) + wave * TRW;          // [64 pixels][32 channels]
+        // regions sit 8 floats further apart (ConvTile::TRW) so that the two row quads a store instruction covers do not share banks.
+        float* tr = reinterpret_cast<float*>(lds) + wave * T::TRW;          // [64 pixels][32 channels]
         // lane l, register r of column fragment j: MFMA row 4 (l >> 4) + r = tile row 4 ((l >> 4) & 1) + r, column 4 wm + j + 16 (l >> 5)
-        float* trx = reinterpret_cast<float*>(lds) + (4 * wn + 2 * ((lane >> 4) & 1)) * TRW + (4 * wm + 16 * (lane >> 5)) * TRS + (lane & 15);
+        float* trx = reinterpret_cast<float*>(lds) + (4 * wn + 2 * ((lane >> 4) & 1)) * T::TRW + (4 * wm + 16 * (lane >> 5)) * T::TRS + (lane & 15);
         const int cq = lane & 7;
         const int prow = lane >> 3;
         const int tilesY4 = (gridH + 3) >> 2;                         // statistics records are per 4-row band (kernels.h)
@@ -745,16 +694,16 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
         for (int q = 0; q < 2 * NB; ++q) {
             const int hb = q >> 1, nt = q & 1;
             const int co = (NB * cb + hb) * 128 + 64 * wn + 32 * nt + 4 * cq;
-            if constexpr (COLF) {
+            if constexpr (T::COLF) {
 #pragma unroll
                 for (int t16 = 0; t16 < 4; ++t16)
 #pragma unroll
                     for (int n2 = 0; n2 < 2; ++n2)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)      // row r of the quad: wave 2 (..) + (r >> 1) of the row partition, its row r & 1
-                            trx[(r >> 1) * TRW + (32 * (r & 1) + t16) * TRS + 16 * n2] =
+                            trx[(r >> 1) * T::TRW + (32 * (r & 1) + t16) * T::TRS + 16 * n2] =
                                 (NB == 2) ? acc16[hb][t16][2 * nt + n2][r] : tot16[t16][2 * nt + n2][r];
-            } else if constexpr (M16) {
+            } else if constexpr (T::M16) {
                 // C tile layout of the 16 x 16 form: register r of lane l = row 4 (l >> 4) + r (pixel), column l & 15 (cout)
 #pragma unroll
                 for (int t16 = 0; t16 < 4; ++t16)
@@ -762,7 +711,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     for (int n2 = 0; n2 < 2; ++n2)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            tr[(16 * t16 + 4 * (lane >> 4) + r) * TRS + 16 * n2 + (lane & 15)] =
+                            tr[(16 * t16 + 4 * (lane >> 4) + r) * T::TRS + 16 * n2 + (lane & 15)] =
                                 (NB == 2) ? acc16[hb][t16][2 * nt + n2][r] : tot16[t16][2 * nt + n2][r];
             } else {
 #pragma unroll
@@ -771,7 +720,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     for (int r = 0; r < 16; ++r)
                         tr[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + li] = tot[mt][nt][r];
             }
-            if constexpr (COLF) __syncthreads();
+            if constexpr (T::COLF) __syncthreads();
             else __builtin_amdgcn_wave_barrier();
             v4f bias;
             if constexpr (FULL) bias = bias_all[q & 1];
@@ -780,10 +729,10 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
             v4f ssum = v4f{0.f, 0.f, 0.f, 0.f}, ssq = ssum;
             if constexpr (FULL) {
                 const int gy0 = y0 + 2 * wm_u;
-                const int oy0 = UP2 ? (2 * gy0 + pa) : gy0, ox0 = UP2 ? (2 * x0 + pb) : x0;
+                const int oy0 = T::UP2 ? (2 * gy0 + pa) : gy0, ox0 = T::UP2 ? (2 * x0 + pb) : x0;
                 float* ob = a.out + uni64(((size_t)((ks * a.B + b) * a.H + oy0) * a.W + ox0) * a.Cout + ((NB * cb + hb) * 128 + 64 * wn_u + 32 * nt));
-                const unsigned l0 = (UP2 ? 2u : 1u) * prow * (unsigned)a.Cout + 4u * cq, sI = uni((UP2 ? 16u : 8u) * (unsigned)a.Cout),
-                               sH = uni((UP2 ? 2u : 1u) * (unsigned)a.W * (unsigned)a.Cout);
+                const unsigned l0 = (T::UP2 ? 2u : 1u) * prow * (unsigned)a.Cout + 4u * cq, sI = uni((T::UP2 ? 16u : 8u) * (unsigned)a.Cout),
+                               sH = uni((T::UP2 ? 2u : 1u) * (unsigned)a.W * (unsigned)a.Cout);
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {
                     v4f o[4];
@@ -792,7 +741,7 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                         const int p = 8 * (4 * hf + i) + prow;
                         // the roundings of the masked code, spelled out (left to the compiler's contraction, straight-line code fused
                         // o0 o0 + o1 o1 the other way round): fma(val, wsc, bias) + residual; sum of squares = fma chain from o0 o0
-                        o[i] = fma4(*reinterpret_cast<const v4f*>(tr + p * TRS + 4 * cq), v4f{wsc, wsc, wsc, wsc}, bias) + rsd_all[q & 1][hf][i];
+                        o[i] = fma4(*reinterpret_cast<const v4f*>(tr + p * T::TRS + 4 * cq), v4f{wsc, wsc, wsc, wsc}, bias) + rsd_all[q & 1][hf][i];
                         ssum += o[i];
                         ssq = (hf == 0 && i == 0) ? o[i] * o[i] : fma4(o[i], o[i], ssq);
                     }
@@ -813,9 +762,9 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     const int p = 8 * (4 * hf + i) + prow;
                     const int gy = y0 + 2 * wm + (p >> 5), gx = x0 + (p & 31);
                     ok[i] = (gy < gridH) && (gx < gridW);
-                    const int y = UP2 ? (2 * gy + pa) : gy, x = UP2 ? (2 * gx + pb) : gx;
+                    const int y = T::UP2 ? (2 * gy + pa) : gy, x = T::UP2 ? (2 * gx + pb) : gx;
                     oidx[i] = ((size_t)((ks * a.B + b) * a.H + y) * a.W + x) * a.Cout + co;
-                    val[i] = *reinterpret_cast<const v4f*>(tr + p * TRS + 4 * cq);
+                    val[i] = *reinterpret_cast<const v4f*>(tr + p * T::TRS + 4 * cq);
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -837,14 +786,14 @@ __global__ __launch_bounds__(64 * ROWS) void conv_split_kernel(const ConvArgs a)
                     ssq.z += __shfl_xor(ssq.z, m, 64); ssq.w += __shfl_xor(ssq.w, m, 64);
                 }
                 if ((FULL || ty4 < tilesY4) && prow == 0) {      // (a full tile's two bands are inside the image)
-                    const int nrec = (UP2 ? 8 : 2) * tilesX * tilesY4;
+                    const int nrec = (T::UP2 ? 8 : 2) * tilesX * tilesY4;
                     const int rec = 2 * ((cls * tilesY4 + ty4) * tilesX + tx) + (wm_u & 1);
                     float* o = a.stats + (((size_t)b * nrec + rec) * a.Cout + co) * 2;
                     *reinterpret_cast<v4f*>(o) = v4f{ssum.x, ssq.x, ssum.y, ssq.y};
                     *reinterpret_cast<v4f*>(o + 4) = v4f{ssum.z, ssq.z, ssum.w, ssq.w};
                 }
             }
-            if constexpr (COLF) { if (q + 1 < 2 * NB) __syncthreads(); }      // every wave has read its region before the next quarter lands in it
+            if constexpr (T::COLF) { if (q + 1 < 2 * NB) __syncthreads(); }      // every wave has read its region before the next quarter lands in it
             else __builtin_amdgcn_wave_barrier();
         }
     };
@@ -862,57 +811,40 @@ int conv_mode() {
     return mode;
 }
 
+// One instantiation: the dynamic-LDS limit is raised once, at its first launch. (The bf16 family has the three plain kernels only.)
+template <int TAPS, int NS, bool HI1, int NB>
+static void launch_inst(const ConvArgs& a, unsigned grid, hipStream_t stream) {
+    if constexpr (NS == 2 || (!HI1 && NB == 1)) {
+        typedef ConvTile<TAPS, NS, HI1, NB> T;
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<TAPS, NS, HI1, NB>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)attr;
+        hipLaunchKernelGGL((conv_split_kernel<TAPS, NS, HI1, NB>), dim3(grid), dim3(T::THREADS), T::lds_bytes(a.coef ? (size_t)3 * (a.C0 + a.C1) : 0), stream, a);
+    }
+}
 template <int NS>
 static void launch_split(const ConvArgs& a, hipStream_t stream) {
+    typedef ConvTile<9, NS> T;
     const bool up2 = (a.taps == 4);
     const int gh = up2 ? a.H / 2 : a.H, gw = up2 ? a.W / 2 : a.W;
-    const int tilesX = (gw + 31) / 32, tilesY = (gh + ROWS - 1) / ROWS;
+    const int tilesX = (gw + 31) / 32, tilesY = (gh + T::ROWS - 1) / T::ROWS;
     // a.nb2 (set by the caller's plan: conv_nb2_ok): 256 couts per workgroup, the chunk's patch produced once for both cout blocks
     const bool nb2 = (NS == 2) && a.nb2 && a.ksplit <= 1 && (a.Cout % 256) == 0 && a.taps != 1;
+    const bool hi1 = (NS == 2) && a.hi_only;       // plain fp16 operands (the training operators under precision 16)
     const unsigned grid = (unsigned)(a.B * (up2 ? 4 : 1) * tilesX * tilesY * (a.Cout / (nb2 ? 256 : 128)) * (a.ksplit > 1 ? a.ksplit : 1));
-    const size_t coef_lds = a.coef ? (size_t)3 * (a.C0 + a.C1) * sizeof(float) : 0;
-    const int npix = (a.taps == 9) ? (ROWS + 2) * 34 : (up2 ? (ROWS + 1) * 33 : ROWS * 32);     // patch pixels (kernel: NPIX)
-    const int tps = (NS == 2) ? (a.taps == 9 ? 3 : (up2 ? 2 : 1)) : 1;                             // taps per weight stage (kernel: TPS)
-    const bool colf = conv_colfrag(NS, a.taps, a.hi_only, nb2 ? 2 : 1);    const int aslots = colf ? (a.taps == 9 ? conv_colfrag_slots(34, ROWS + 2) : conv_colfrag_slots(33, ROWS + 1)) : npix * 4 * NS;      // patch slots (kernel: ASLOTS)
-    const size_t main = (size_t)(aslots + 2 * tps * 128 * 4 * NS) * 16 + coef_lds;
-    const size_t tr = (size_t)ROWS * (64 * 36 + 8) * sizeof(float);   // epilogue transpose regions alias the buffers (stride <= 36, + 8 between regions)
-    const size_t lds = main > tr ? main : tr;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<1, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if constexpr (NS == 2) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<1, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<9, NS, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<4, NS, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        }
-        attr = true;
+    switch ((a.taps == 9 ? 0 : a.taps == 1 ? 1 : 2) + 3 * (int)hi1 + 6 * (int)nb2) {      // (taps: 9 | 1 | else the folded 4) + 3 hi_only + 6 nb2
+        case 0: return launch_inst<9, NS, false, 1>(a, grid, stream);
+        case 1: return launch_inst<1, NS, false, 1>(a, grid, stream);
+        case 2: return launch_inst<4, NS, false, 1>(a, grid, stream);
+        case 3: return launch_inst<9, NS, true, 1>(a, grid, stream);
+        case 4: return launch_inst<1, NS, true, 1>(a, grid, stream);
+        case 5: return launch_inst<4, NS, true, 1>(a, grid, stream);
+        case 6: return launch_inst<9, NS, false, 2>(a, grid, stream);
+        case 8: return launch_inst<4, NS, false, 2>(a, grid, stream);
+        case 9: return launch_inst<9, NS, true, 2>(a, grid, stream);
+        case 11: return launch_inst<4, NS, true, 2>(a, grid, stream);
+        default: assert(false && "1x1 taps have no 256-cout form: nb2 requires taps != 1");
     }
-    const dim3 g(grid), blk(64 * ROWS);
-    if constexpr (NS == 2) {
-        if (nb2) {
-            if (a.hi_only) {       // plain fp16 operands (the training operators under precision 16)
-                if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS, true, 2>), g, blk, lds, stream, a);
-                else hipLaunchKernelGGL((conv_split_kernel<4, NS, true, 2>), g, blk, lds, stream, a);
-            } else if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS, false, 2>), g, blk, lds, stream, a);
-            else hipLaunchKernelGGL((conv_split_kernel<4, NS, false, 2>), g, blk, lds, stream, a);
-            return;
-        }
-        if (a.hi_only) {
-            if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS, true>), g, blk, lds, stream, a);
-            else if (a.taps == 1) hipLaunchKernelGGL((conv_split_kernel<1, NS, true>), g, blk, lds, stream, a);
-            else hipLaunchKernelGGL((conv_split_kernel<4, NS, true>), g, blk, lds, stream, a);
-            return;
-        }
-    }
-    if (a.taps == 9) hipLaunchKernelGGL((conv_split_kernel<9, NS>), g, blk, lds, stream, a);
-    else if (a.taps == 1) hipLaunchKernelGGL((conv_split_kernel<1, NS>), g, blk, lds, stream, a);
-    else hipLaunchKernelGGL((conv_split_kernel<4, NS>), g, blk, lds, stream, a);
 }
 
 // May a launch use 256-cout workgroups (ConvArgs::nb2)? Feasibility only -- WHEN it is used is the caller's plan (cddpm_api.hip: the
@@ -963,8 +895,8 @@ int conv_weight_exp(const float* w, size_t n, int family) {
 }
 
 // w: PyTorch [Cout][Cin][k][k] (taps = k*k) -> [Cout/128][Cin/32][taps][128 rows][4 NS slots][8 x 16 bit]
-//   NS = 3 (bf16): slot (split s, u = channel/8 in the chunk) of row j at 4 s + (u ^ ((j>>2)&3)); 6 bytes per weight
-//   NS = 2 (fp16): w * 2^wexp is split; slot at (4 s + u) ^ ((j>>1)&7); 4 bytes per weight
+//   slot (split s, u = channel/8 in the chunk) of row j: conv_wslot (conv_split.h).  NS = 3 (bf16): 6 bytes per weight;
+//   NS = 2 (fp16): w * 2^wexp is split; 4 bytes per weight
 void pack_conv_weights_split(const float* w, int Cout, int Cin, int taps, void* dst_, int wexp, int family) {
     uint16_t* dst = static_cast<uint16_t*>(dst_);
     const int ncb = Cout / 128, nch = Cin / 32;
@@ -982,14 +914,14 @@ void pack_conv_weights_split(const float* w, int Cout, int Cin, int taps, void* 
                                 for (int s3 = 0; s3 < 3; ++s3) {
                                     const uint16_t q = bf16_rne(r);
                                     r -= bf16_to_f(q);
-                                    img[(size_t)(j * 12 + 4 * s3 + (u ^ ((j >> 2) & 3))) * 8 + e] = q;
+                                    img[(size_t)conv_wslot(3, j, s3, u) * 8 + e] = q;
                                 }
                             } else {
                                 r = ldexpf(r, wexp);
                                 for (int s2 = 0; s2 < 2; ++s2) {
                                     const uint16_t q = f16_rne(r);
                                     r -= f16_to_f(q);
-                                    img[(size_t)(j * 8 + ((4 * s2 + u) ^ ((j >> 1) & 7))) * 8 + e] = q;
+                                    img[(size_t)conv_wslot(2, j, s2, u) * 8 + e] = q;
                                 }
                             }
                         }
@@ -1036,9 +968,8 @@ __device__ __forceinline__ void pack_split_unit(const float* __restrict__ w, int
         hi.q[e] = __builtin_bit_cast(uint16_t, h);
         mid.q[e] = __builtin_bit_cast(uint16_t, m);
     }
-    const int sw = (j >> 1) & 7;
-    *reinterpret_cast<uint4*>(img + (size_t)(j * 8 + ((0 + u) ^ sw)) * 8) = hi.v;
-    *reinterpret_cast<uint4*>(img + (size_t)(j * 8 + ((4 + u) ^ sw)) * 8) = mid.v;
+    *reinterpret_cast<uint4*>(img + (size_t)conv_wslot(2, j, 0, u) * 8) = hi.v;
+    *reinterpret_cast<uint4*>(img + (size_t)conv_wslot(2, j, 1, u) * 8) = mid.v;
 }
 __global__ __launch_bounds__(256) void pack_split_kernel(const float* __restrict__ w, int O, int I, int taps, int mode, int wexp,
                                                          uint16_t* __restrict__ dst) {

@@ -56,3 +56,17 @@ def test_conv_bits_equal_parent(tool, parent, mode, monkeypatch):
 
 def test_conv_bits_equal_parent_256_cout_plan(tool, parent):
     _compare(tool.digests_in_child("nb2"), parent["modes"]["nb2"])
+
+
+def test_conv_bits_equal_parent_p16_256_cout_plan(tool, parent):
+    """the hi-only 256-cout kernels <9,2,true,2> and <4,2,true,2>, which the three modes above do not reach (the operator entry points do
+    not take the handle's precision): the set's 256-cout cases launched as a precision-16 handle plans them (op_conv_planned) under
+    CDDPM_NB2=force. tests/golden/conv_bits_p16nb2_parent.json is `conv_bits.py --mode p16nb2` with CDDPM_LIB pointing at a build of the
+    commit before conv_split_kernel took its constants and slot functions from conv_split.h. The mode asserts that the plan taken is one
+    unsplit launch of 256-cout workgroups; that the operands were hi-only shows in digests that differ from the `nb2` mode's."""
+    with open(os.path.join(GOLD, "conv_bits_p16nb2_parent.json")) as f:
+        rec = json.load(f)
+    assert rec["seed"] == tool.SEED and rec["cases"] == {k: list(tool.CASES[k]) for k in tool.P16NB2_CASES}
+    want = rec["modes"]["p16nb2"]
+    assert all(want[k] != parent["modes"]["nb2"][k] for k in want), "the recorded digests are those of the two-term kernels"
+    _compare(tool.digests_in_child("p16nb2"), want)
