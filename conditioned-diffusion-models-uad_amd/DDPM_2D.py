@@ -261,6 +261,9 @@ class DDPM_2D(HipMirror, _Base):
             self._hip_enc_trainer = EncoderTrainer(sd, self.hip_trainer(device), drop_path_rate=(dp if dp != 0 else 0.05) if spark else 0.0,
                                                    precision=_cfg_get(self.cfg, "train_encoder_precision", 32))
             self.__dict__["_enc_core"] = core          # NOT a registered submodule: state_dict() must keep the reference's key set
+            # the inference encoder re-reads the weights and running statistics after every write of the trainer's kernels, whoever
+            # drives the trainer (this module's training_step or training.training_step called directly)
+            self._hip_enc_trainer.on_write = core.invalidate
             self._alias_encoder()
             self._load_pending_optimizer_state()
         return self._hip_enc_trainer
@@ -319,7 +322,6 @@ class DDPM_2D(HipMirror, _Base):
         if trainer.loss_scaling:
             self._watch_loss_scale(trainer)
         if enc_trainer is not None:
-            self._enc_core._key = None                    # the inference encoder re-reads the updated weights and running statistics
             for name, buf in self._enc_core.named_buffers():
                 if name.endswith("num_batches_tracked"):  # BatchNorm's forward counter in training mode (torch: += 1 per forward)
                     buf += 1

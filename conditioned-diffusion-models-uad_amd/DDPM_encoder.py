@@ -83,6 +83,11 @@ class ResNet50Encoder(nn.Module):
         self._h, self._key = h, key
         return lib, h
 
+    def invalidate(self):
+        """the parameters or running statistics were written outside torch's version counters (the training kernels write them in
+        place): the next forward re-reads them"""
+        self._key = None
+
     def close(self):
         if self._h is not None:
             _lib.load_library().cddpm_encoder_destroy(self._h)

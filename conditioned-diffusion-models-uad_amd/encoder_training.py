@@ -133,6 +133,9 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
         self.ops = ops
         # whose control block and loss scaler a guarded adam_step runs under: the trainer the encoder is trained jointly with
         self.optimizer = ops
+        # called after the kernels wrote parameters or running statistics in place, which torch's version counters do not see: whoever
+        # aliases these tensors (DDPM_2D: the inference encoder) sets it to drop what it derived from them
+        self.on_write = None
         train_names = [k for k in params if not (k.endswith("running_mean") or k.endswith("running_var") or k.endswith("num_batches_tracked"))]
         super().__init__(params, train_names, ops.dev)      # flat, gflat, p, g, state, and a control block for a step of its own
         self.buf = {k: params[k].detach().to(self.dev, torch.float32).clone() for k in params
@@ -303,7 +306,13 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
             r.update(mr3=mr3, out=out)
             sv[n] = r
             cur = out
+        if training:
+            self._wrote()                   # every BatchNorm moved its running statistics
         return sv, cur
+
+    def _wrote(self):
+        if self.on_write is not None:
+            self.on_write()
 
     def _block_backward(self, bk, r, d, mask=None):
         """d = dL/d(the block's output) -> dL/d(its input); the gradients of its parameters land in g"""
@@ -448,6 +457,7 @@ class EncoderTrainer(_optimizer.FlatOptimizer):
         else:
             _optimizer.update(opt, self, lr, betas, eps, unscale=1.0 / (grad_scale if grad_scale is not None else 1.0))
         self.repack()
+        self._wrote()
 
     def optimizer_state(self) -> Dict[str, torch.Tensor]:
         m, v = _optimizer.moments(self)
